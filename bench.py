@@ -15,7 +15,8 @@ gathered onto rank 0 over RCCL (one collective per output = per step, sunvolumer
 tone-maps the assembled frame (svr_hdr_to_ldr_frame), all inside the timed region; the ranks skip the tone map of their own
 strips (SVR_OPT_SKIP_TONEMAP), whose result nobody would read.
 
-One JSON line on rank 0 (the task contract's fields) plus
+A plain run sets up, warms up, times `--steps` steps and prints one JSON line on rank 0: the task contract's fields
+(`ms_per_step` = milliseconds of one timed step) plus `config` and
   roofline      what bounds the dominant kernel (k_trace_tile).  The counters say vector-instruction issue, not HBM
                 (profiles/): `bound` = "valu_issue", `achieved` = wave64 VALU instructions per second (instructions
                 per launch from the committed rocprofv3 --pmc SQ_INSTS_VALU pass of the same workload / the HIP-event
@@ -23,7 +24,9 @@ One JSON line on rank 0 (the task contract's fields) plus
                 instruction (MI355X_MICROARCH.md).  The SURVEY 8(d) byte figure (16 B per volume tap of the REFERENCE
                 algorithm + 24 B per pixel per launch) is kept as `algorithmic_*`; on the headline scene 95 % of those
                 taps are proven transparent and never fetched, so `algorithmic_demand_frac` can exceed 1 and is not a
-                fraction of anything -- `hbm_traffic_bytes` is what HBM really moved.
+                fraction of anything -- `hbm_traffic_bytes` is what HBM really moved.  The `algorithmic_*` / `executed_*`
+                figures need the tap-counting pass (`counters`), which only --full runs.
+`--full` also measures, after the headline:
   workloads     the same measurement on the scenes where nothing can be skipped and algorithmic bytes = executed
                 bytes: c3 with noisy, non-zero air (`c3n`), and c3 with empty-space skipping switched off; the headline
                 scene in the opt-in fast-math mode, and at trace depth 2 and 4.
@@ -31,7 +34,11 @@ One JSON line on rank 0 (the task contract's fields) plus
                 off, depth 2 / 4, the opt-in fast-math mode, and the OPT-IN local-majorant mode (SVR_OPT_LOCAL_MAJORANT,
                 "Woodcock max-density acceleration": not bit-identical, converged images agree) on c3, c3n and c5.
   cpu_baseline  the CPU oracle (a plain-C port of the reference's arithmetic, OpenMP) on a bounded sample: on the box's CPU
-                share of one GPU (16 threads) and on all host cores (`value_all`, `cores_all`).
+                share of one GPU (16 threads) and on all host cores (`value_all`, `cores_all`); null without --full.
+
+`--dump-outputs DIR` writes what the last timed step computed (on N GPUs: the assembled frame on rank 0) as DIR/hdr.npy,
+DIR/hdr_nonfinite.npy and DIR/image.npy (see dump_outputs); the scenes are generated from fixed seeds, so the same arguments
+give the same inputs.
 """
 from __future__ import annotations
 
@@ -68,9 +75,14 @@ def parse_args():
     ap.add_argument("--blocks-per-cu", type=int, default=0)
     ap.add_argument("--strip-rows", type=int, default=16, help="rows per interleaved strip under row sharding (16: max/mean rank time 1.02 at 8 ranks on c3, 32: 1.08)")
     ap.add_argument("--assemble", default="gather", choices=["gather", "reduce"], help="collective that assembles the frame on rank 0")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline budget (0 = skip)")
-    ap.add_argument("--no-count", action="store_true", help="skip the tap-counting pass (algorithmic_* = null)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads (noisy air, skipping off, fast math, depth 2 / 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the tap-counting pass, the secondary workloads and the CPU baseline "
+                         "(a plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0: the whole frame) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline budget under --full (0 = skip)")
+    ap.add_argument("--no-count", action="store_true", help="under --full: skip the tap-counting pass (algorithmic_* = null)")
+    ap.add_argument("--no-extra", action="store_true", help="under --full: skip the secondary workloads (noisy air, skipping off, fast math, depth 2 / 4)")
     ap.add_argument("--extra-steps", type=int, default=2)
     ap.add_argument("--empty-skip", type=int, default=1)
     ap.add_argument("--fast-math", type=int, default=0)
@@ -301,6 +313,32 @@ def compact_first(out: dict) -> dict:
     return head
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, hdr, img, H, W):
+    """--dump-outputs: what a caller of the timed path holds after the last step, as finite float32 arrays: `hdr.npy` = the HDR
+    accumulator [H][W][3], `image.npy` = the tone-mapped RGBA8 frame [H][W][4] (channel values 0..255).  The accumulator keeps
+    the reference's rare non-finite samples for good (SVR_OPT_NAN_GUARD is off): such elements are 0 in `hdr.npy` and
+    `hdr_nonfinite.npy` [H][W][3] says which they are (0 finite, 1 NaN, 2 +inf, 3 -inf).  Beyond 64 MB in all, every k-th row
+    only (the same rows in every run of a configuration), listed in `rows.npy`."""
+    import numpy as np
+
+    hdr = hdr.reshape(H, W, 3).cpu().numpy()
+    img = img.cpu().numpy().view(np.uint8).reshape(H, W, 4).astype(np.float32)
+    stride = -(-(2 * hdr.nbytes + img.nbytes) // DUMP_BUDGET_BYTES)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    if stride > 1:
+        rows = np.arange(0, H, stride)
+        hdr, img = hdr[rows], img[rows]
+        np.save(out / "rows.npy", rows.astype(np.float64))
+    kind = np.select([np.isnan(hdr), hdr == np.inf, hdr == -np.inf], [1, 2, 3], 0).astype(np.float32)
+    np.save(out / "hdr.npy", np.where(kind == 0, hdr, np.float32(0)).astype(np.float32))
+    np.save(out / "hdr_nonfinite.npy", kind)
+    np.save(out / "image.npy", np.ascontiguousarray(img))
+
+
 def main():
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -376,16 +414,19 @@ def main():
             dev.check(dev.lib.svr_hdr_to_ldr_frame(C.c_void_p(frame_img.data_ptr()), C.c_void_p(frame.data_ptr()), W, H))
         return frame
 
-    # ---- tap-counting pass (untimed): exact algorithmic bytes of the frames about to be timed ----
-    counters = None if args.no_count else wl.count(args.steps, S)
+    # ---- tap-counting pass (untimed, --full only): exact algorithmic bytes of the frames about to be timed ----
+    counters = wl.count(args.steps, S) if args.full and not args.no_count else None
 
     # ---- warm-up (includes one assembly, so that its staging buffers and the RCCL channels exist) ----
     def full_step():
         """One step = S more samples for every pixel AND the output a one-GPU step ends in: a tone-mapped image of the whole
-        frame (on one GPU the library's own tone map behind the last launch; on N GPUs gather + tone map on rank 0)."""
+        frame (on one GPU the library's own tone map behind the last launch; on N GPUs gather + tone map on rank 0).
+        Returns what the caller holds afterwards: (HDR frame, RGBA8 image) on rank 0, None on the other ranks."""
         wl.step(S)
-        if world > 1:
-            assemble_and_tonemap(wl.hdr)
+        if world == 1:
+            return wl.hdr, wl.img
+        frame = assemble_and_tonemap(wl.hdr)
+        return (frame, frame_img) if rank == 0 else None
 
     canvas.ReStartRender()
     for _ in range(max(args.warmup, 1 if world > 1 else 0)):     # (N > 1: at least one, so that the staging buffers and the RCCL channels exist)
@@ -396,12 +437,15 @@ def main():
     dev.check(dev.lib.svr_reset_kernel_time())
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        full_step()
+        last = full_step()
     barrier()
     elapsed = time.perf_counter() - t0
     dev.set_option(abi.OPT_TIMING, 0)
     k_ms, k_n = dev.kernel_time()
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, *last, H, W)
 
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
     if world > 1:
@@ -453,8 +497,8 @@ def main():
         if cnt is not None:
             out["counters"] = cnt
 
-    # ---- secondary workloads (one GPU only) ----
-    if world == 1 and not args.no_extra and args.scene == "c3" and args.kernel in (0, 2):
+    # ---- secondary workloads (--full, one GPU only) ----
+    if args.full and world == 1 and not args.no_extra and args.scene == "c3" and args.kernel in (0, 2):
         extra = {}
         # the reference's own host protocol (gui/canvas.cpp:96-116): ONE render_pathtracer call + ONE device synchronisation per frame, frameNo++ --
         # what an unmodified host does.  Frames are traced ahead in batches (1, 2, 4 ... 64) on the library's streams and a call folds its frame;
@@ -547,7 +591,7 @@ def main():
         out["workloads"] = extra
 
     if rank == 0:
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(scene, args.trace_depth, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None

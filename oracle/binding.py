@@ -52,6 +52,16 @@ _lib = None
 
 
 REFERENCE = Path("/root/reference")
+
+
+def _have_ref(rel: str) -> bool:
+    """True if the reference checkout has `rel` and this user may read it (an unreadable directory is absent, not an error)."""
+    try:
+        return (REFERENCE / rel).exists()
+    except OSError:
+        return False
+
+
 STB_REF = ORACLE_DIR / "_ref" / "libstb_ref.so"
 
 
@@ -68,7 +78,7 @@ def build(force: bool = False) -> Path:
 def build_ref(force: bool = False):
     """oracle/_ref/libstb_ref.so: the reference's vendored stb headers compiled where they lie.  Only possible
     where /root/reference exists (this container); the GPU box uses the prebuilt file."""
-    if (REFERENCE / "utils" / "stb_image.h").exists() and (force or not STB_REF.exists()
+    if _have_ref("utils/stb_image.h") and (force or not STB_REF.exists()
                                                          or STB_REF.stat().st_mtime < (ORACLE_DIR / "stb_ref.c").stat().st_mtime):
         subprocess.run(["make", "-C", str(ORACLE_DIR), "-B", "_ref/libstb_ref.so"], check=True, capture_output=True)
     return STB_REF if STB_REF.exists() else None
@@ -94,7 +104,7 @@ def _cuda_include_dir():
 def build_fresnel_ref(force: bool = False):
     """oracle/_ref/libref_fresnel.so: the reference's own schlick_fresnel (core/bsdf/fresnel.h) compiled where it lies."""
     inc = _cuda_include_dir()
-    if (REFERENCE / "core" / "bsdf" / "fresnel.h").exists() and inc is not None and (
+    if _have_ref("core/bsdf/fresnel.h") and inc is not None and (
             force or not FRESNEL_REF.exists() or FRESNEL_REF.stat().st_mtime < (ORACLE_DIR / "ref_fresnel.cpp").stat().st_mtime):
         subprocess.run(["make", "-C", str(ORACLE_DIR), "-B", "_ref/libref_fresnel.so", f"CUDA_INC={inc}"], check=True, capture_output=True)
     return FRESNEL_REF if FRESNEL_REF.exists() else None
@@ -107,7 +117,7 @@ def build_wanghash_ref(force: bool = False):
     """oracle/_ref/libref_wanghash.so: the reference's own wangHash (pathtracer.cu:70-79), cut out of the file where it lies at
     build time (oracle/ref_wanghash.cpp, oracle/Makefile)."""
     inc = _cuda_include_dir()
-    if (REFERENCE / "pathtracer.cu").exists() and inc is not None and (
+    if _have_ref("pathtracer.cu") and inc is not None and (
             force or not WANGHASH_REF.exists() or WANGHASH_REF.stat().st_mtime < (ORACLE_DIR / "ref_wanghash.cpp").stat().st_mtime):
         subprocess.run(["make", "-C", str(ORACLE_DIR), "-B", "_ref/libref_wanghash.so", f"CUDA_INC={inc}"], check=True, capture_output=True)
     return WANGHASH_REF if WANGHASH_REF.exists() else None

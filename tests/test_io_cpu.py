@@ -201,33 +201,49 @@ def _hdr_cases(tmp_path):
     return cases
 
 
-def test_hdr_loader_matches_the_reference_stb(lib, tmp_path):
-    """The files are decoded by the reference's own stb_image.h v2.12 (stbi_loadf, lights.cpp:34) and by
-    svr_hdr_load; the float4 expansion is lights.cpp:45-53."""
-    if binding.stb_ref() is None:
-        pytest.skip("oracle/_ref/libstb_ref.so not built (no /root/reference here); the golden test covers this row")
-    cases = _hdr_cases(tmp_path)
-    # also a file written by the reference's stb_image_write (its RLE encoder)
+def _stb_written_img():
+    """The image the reference's stbi_write_hdr writes (its RLE encoder) for the .hdr comparison."""
     rs = np.random.RandomState(5)
     img = (rs.uniform(0, 4, (6, 40, 3))).astype(np.float32)
     img[:, 10:30] = img[:, 10:11]
-    binding.ref_write_hdr(tmp_path / "stbw.hdr", img)
+    return img
+
+
+# files stb rejects (the record generator checks that the reference's stbi_loadf returns NULL for each)
+BAD_HDR_FILES = {"magic.hdr": b"#?RGBE\nFORMAT=32-bit_rle_rgbe\n\n-Y 1 +X 1\n\x01\x02\x03\x80",
+                 "format.hdr": b"#?RADIANCE\nFORMAT=32-bit_rle_xyze\n\n-Y 1 +X 1\n\x01\x02\x03\x80",
+                 "layout.hdr": b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n+Y 1 +X 1\n\x01\x02\x03\x80"}
+
+
+def test_hdr_loader_matches_the_reference_stb(lib, tmp_path):
+    """The files are decoded by the reference's own stb_image.h v2.12 (stbi_loadf, lights.cpp:34) and by
+    svr_hdr_load; the float4 expansion is lights.cpp:45-53.  The reference's results are the record in
+    tests/golden/stb_ref_golden.npz; where oracle/_ref/libstb_ref.so is built, the live library is checked against it too."""
+    g = np.load(GOLD / "stb_ref_golden.npz")
+    live = binding.stb_ref() is not None
+    cases = _hdr_cases(tmp_path)
+    # also a file written by the reference's stb_image_write (its RLE encoder)
+    if live:
+        binding.ref_write_hdr(tmp_path / "stbw.hdr", _stb_written_img())
+    else:
+        (tmp_path / "stbw.hdr").write_bytes(g["hdr_stb_written_file"].tobytes())
     cases["stb_written"] = tmp_path / "stbw.hdr"
     for name, path in cases.items():
-        ref = binding.ref_loadf(path)
-        assert ref is not None and ref.shape[2] == 3, name
+        assert path.read_bytes() == g[f"hdr_{name}_file"].tobytes(), name
+        ref = g[f"hdr_{name}_rgb"]
+        assert ref.shape[2] == 3, name
+        if live:
+            assert np.array_equal(binding.ref_loadf(path).view(np.uint32), ref.view(np.uint32)), name
         got = _hdr_load(lib, path)
         assert got is not None, (name, _err(lib))
         assert got.shape[:2] == ref.shape[:2], name
         assert np.array_equal(got[..., :3].view(np.uint32), ref.view(np.uint32)), name
         assert np.all(got[..., 3] == 0.0)
     # files stb rejects are rejected here too
-    bad = {"magic.hdr": b"#?RGBE\nFORMAT=32-bit_rle_rgbe\n\n-Y 1 +X 1\n\x01\x02\x03\x80",
-           "format.hdr": b"#?RADIANCE\nFORMAT=32-bit_rle_xyze\n\n-Y 1 +X 1\n\x01\x02\x03\x80",
-           "layout.hdr": b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n+Y 1 +X 1\n\x01\x02\x03\x80"}
-    for name, data in bad.items():
+    for name, data in BAD_HDR_FILES.items():
         (tmp_path / name).write_bytes(data)
-        assert binding.ref_loadf(tmp_path / name) is None, name
+        if live:
+            assert binding.ref_loadf(tmp_path / name) is None, name
         assert _hdr_load(lib, tmp_path / name) is None, name
         lib.svr_clear_error()
 
@@ -266,11 +282,15 @@ def _tga_images():
 
 def test_tga_writer_matches_the_reference_stb(lib, tmp_path):
     """Byte-for-byte the file stbi_write_tga(name, W, H, 4, data) of the reference's stb_image_write.h v1.02
-    writes (canvas.cpp:102), RLE packets included."""
-    if binding.stb_ref() is None:
-        pytest.skip("oracle/_ref/libstb_ref.so not built; the golden test covers this row")
+    writes (canvas.cpp:102), RLE packets included.  The reference's files are the record in tests/golden/io_golden.npz;
+    where oracle/_ref/libstb_ref.so is built, the live library is checked against it too."""
+    g = np.load(GOLD / "io_golden.npz")
+    live = binding.stb_ref() is not None
     for name, img in _tga_images().items():
-        ref = binding.ref_write_tga(tmp_path / f"ref_{name}.tga", img)
+        assert np.array_equal(img, g[f"tga_{name}_img"]), name
+        ref = g[f"tga_{name}_file"].tobytes()
+        if live:
+            assert binding.ref_write_tga(tmp_path / f"ref_{name}.tga", img) == ref, name
         assert lib.svr_tga_write(str(tmp_path / f"{name}.tga").encode(), img.shape[1], img.shape[0], img.ctypes.data_as(C.c_void_p)) == 0, _err(lib)
         assert (tmp_path / f"{name}.tga").read_bytes() == ref, name
     # decode check independent of stb: header fields and bottom-up BGRA order of a 1x1 image

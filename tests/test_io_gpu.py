@@ -169,15 +169,22 @@ def test_load_mhd_end_to_end(hip_dev, tmp_path, style):
         canvas.close()
 
 
-def test_env_map_file(hip_dev, tmp_path):
-    """Lights::SetEnvironmentLight(filename) (lights.cpp:31-75): the .hdr decoded by the library lights the scene
-    exactly as the same pixels given as a table."""
+def _sky_hdr(path):
     rs = np.random.RandomState(4)
     img = (rs.uniform(0, 1, (16, 32, 3)) ** 3 * 20).astype(np.float32)
     img[:, 8:20] = img[:, 8:9]
-    path = write_hdr(tmp_path / "sky.hdr", float_to_rgbe(img))
+    return write_hdr(path, float_to_rgbe(img))
+
+
+def test_env_map_file(hip_dev, tmp_path):
+    """Lights::SetEnvironmentLight(filename) (lights.cpp:31-75): the .hdr decoded by the library lights the scene
+    exactly as the same pixels given as a table.  The decode is the reference stb's (tests/golden/stb_ref_golden.npz)."""
+    path = _sky_hdr(tmp_path / "sky.hdr")
+    g = np.load(Path(__file__).parent / "golden" / "stb_ref_golden.npz")
+    assert path.read_bytes() == g["hdr_sky_file"].tobytes()
     table = io.hdr_load(hip_dev, str(path))
     assert table.shape == (16, 32, 4) and np.all(table[..., 3] == 0)
+    assert np.array_equal(table[..., :3], g["hdr_sky_rgb"])
     if binding.stb_ref() is not None:
         assert np.array_equal(table[..., :3], binding.ref_loadf(path))
     sc = dataclasses.replace(scenes.make_scene("tiny_head", trace_depth=2), env_map=table, env_on_escape=True, env_offset=(0.2, 0.05))
