@@ -2,7 +2,7 @@
 // without the GUI: load a MetaImage volume, the GUI-default (or a saved .tf) transfer function, one area light, an
 // optional .hdr environment map; render N progressive frames; write the image as TGA.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-o out.tga]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,9 +12,10 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
+    int denoisePreview = 0;
     bool raycast = false;
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
@@ -23,6 +24,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-depth") && i + 1 < argc) depth = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-size") && i + 2 < argc) { W = atoi(argv[i + 1]); H = atoi(argv[i + 2]); i += 2; }
         else if (!strcmp(argv[i], "-raycast")) raycast = true;
+        else if (!strcmp(argv[i], "-denoise-preview") && i + 1 < argc) denoisePreview = atoi(argv[++i]);   // denoised image up to N spp
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -65,6 +67,7 @@ int main(int argc, char** argv)
         }
         canvas.SetScatterTimes(depth);
         canvas.SetRenderMode(raycast ? RENDER_MODE_RAYCASTING : RENDER_MODE_PATHTRACER);
+        canvas.SetDenoisePreview(denoisePreview);
 
         for (int f = 0; f < (raycast ? 1 : frames); ++f) canvas.paintGL();
         if (!canvas.SaveImage(out)) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }

@@ -265,6 +265,10 @@ public:
     void SetFocalLength(float f) { focalLength = f; UpdateCamera(); ReStartRender(); }
     void SetExposure(float e) { exposure = e; UpdateCamera(); ReStartRender(); }
 
+    // extension: edge-aware denoised image while a restarted render has at most `frames` samples per pixel (SVR_OPT_DENOISE_PREVIEW;
+    // 0 = off).  Changes only the RGBA8 image, never the accumulator
+    void SetDenoisePreview(int frames) { svr_set_option(SVR_OPT_DENOISE_PREVIEW, frames); }
+
     // clip planes, canvas.h:165-184
     void SetXClipPlane(double mn, double mx) { deviceVolume.SetXClipPlane(glm::vec2(float(mn), float(mx))); setup_volume(deviceVolume); ReStartRender(); }
     void SetYClipPlane(double mn, double mx) { deviceVolume.SetYClipPlane(glm::vec2(float(mn), float(mx))); setup_volume(deviceVolume); ReStartRender(); }

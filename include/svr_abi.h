@@ -300,6 +300,12 @@ int svr_assemble_frame(void* nccl_comm, void* frame_on_root, const void* hdr_loc
                                      * kernel) look the fetch bound of an iteration up from the ray parameter -- one fma per axis into a byte table whose cells cover one more
                                      * voxel per side, compared with the top 8 bits of the accept draw's random word (csrc/svr_accel.hip k_bound8) -- instead of from the exact
                                      * trilinear cell and a class threshold.  Any valid bound culls correctly: results unchanged (bit-exact); c3n +17 %, c3n at depth 2 / 4 +32 % / +31 % (same box).  Needs the clipped box inside the volume and the camera within 2^21 / (16 N) volume extents (else, and with 0: the exact cell) */
+#define SVR_OPT_DENOISE_PREVIEW 36    /* default 0 = off.  N > 0: render_pathtracer and svr_render_pathtracer_frames write an edge-aware DENOISED tone map to img
+                                     * while the frame shown has at most N samples per pixel (frameNo + nframes <= N), the ordinary one after that
+                                     * (svr_denoise_to_ldr with the parameters of svr_set_denoise_params; csrc/svr_denoise.hip).  Only the RGBA8 image changes:
+                                     * the accumulator (hdrBuffer) is never written by the filter, so convergence and bit-exactness are untouched.  Inert
+                                     * under a row shard, a render window or SVR_OPT_SKIP_TONEMAP.  If the guide / scratch memory cannot be allocated the
+                                     * frame gets the ordinary tone map and svr_last_error() says so (no error code: the render does not fail) */
 #define SVR_OPT_FRAME_AHEAD 13           /* render_pathtracer traces frames ahead of the calls that ask for them (batches of 1, 2, 4 ... 32 frames; results unchanged); default 1 */
 #define SVR_OPT_RAYCAST_LANES_LOG2 12   /* ray caster: 1 << v adjacent lanes share one ray (samples of a chunk in parallel, composited in order); 0..5, default 3 */
 #define SVR_OPT_FRAMES_PER_WAVE_LOG2 11 /* tile kernel: a wave traces (64 >> f) pixels x (1 << f) frames of a group; -1 (default) = up to 8 frames */
@@ -344,6 +350,46 @@ int svr_selftest_math(int fn, const float* in, uint32_t in_stride, float* out, u
  * accept test forms there (exact cell, fetch, alpha, invSigmaMax).  out[i] = 1 tested | 2 VIOLATION (a draw the byte culls could be accepted)
  * | 4 index outside the table | byte << 8; 0 = the ray misses the box.  Fails (-3) when the look-up is not in use for the scene */
 int svr_selftest_bound8(const float* rays, uint32_t n, uint32_t* out);
+/* ---- denoised preview (SVR_OPT_DENOISE_PREVIEW; csrc/svr_denoise.hip) ----
+ * GUIDES: one deterministic ray per pixel (the pinhole centre ray, cuda_camera.h:85-95) is marched through the clipped box
+ * (the path tracer's interval, tNear < 0 -> 1e-6) at a fixed step h with the path tracer's extinction sigma = TF alpha of
+ * volume(p): first-collision weight w_i = T_i (1 - exp(-sigma_i h)), T_{i+1} = T_i exp(-sigma_i h), T_0 = 1, until T < 2^-10.
+ * Per pixel 8 floats, two float4: [0] = (N.x, N.y, N.z, D), [1] = (A.r, A.g, A.b, O) with opacity O = sum w, expected depth
+ * D = sum w t / O, albedo A = sum w rgb_TF / O, normal N = normalize(sum w grad) (the central-difference gradient,
+ * cuda_volume.h:54-61; 0 if the sum is 0).  O == 0 (the ray misses the box or sees only exactly transparent medium):
+ * D = -1, N = 0, A = 1.  Cached; recomputed only when the scene PODs (volume, transfer function, camera, image size), the
+ * transfer function's contents, the march step or SVR_OPT_EMPTY_SKIP change -- not for lights or the environment.
+ * FILTER: edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) over c = hdr / max(A, 1e-3), `passes` passes at steps
+ * 1, 2, 4 ..., 5 x 5 B3-spline taps (1/16, 1/4, 3/8, 1/4, 1/16), weights normalised per pixel.  Weight of q for p (q != p):
+ *   h(q) exp(-( |D_p - D_q| / (sigma_depth step D_p f) + |A_p - A_q|^2 / sigma_albedo^2 + |O_p - O_q| / sigma_opacity
+ *              + (lum(c_p) - lum(c_q))^2 / (sigma_color^2 2^-k) )) max(0, N_p . N_q)^sigma_normal
+ * on pass k (step = 2^k), f = 2 tanFovxOverTwo / (H - 1) (pixel footprint per unit depth), lum = 0.2126 r + 0.7152 g + 0.0722 b;
+ * a sigma of 0 switches its term off.  Neighbours outside the image, with O == 0 or a non-finite colour get weight 0; the centre
+ * has weight h(p).  A pixel with O == 0 passes through untouched.  The result is remodulated by max(A, 1e-3) and tone-mapped
+ * like svr_hdr_to_ldr. */
+typedef struct svr_denoise_params {
+    int32_t passes;            /* 1..10; default 5 (steps 1, 2, 4, 8, 16) */
+    float sigma_depth;         /* default 0.5 */
+    float sigma_normal;        /* exponent; default 32 */
+    float sigma_albedo;        /* default 0.4 */
+    float sigma_opacity;       /* default 0.8 */
+    float sigma_color;         /* 0 (default) = off: at 1-4 spp a colour term mostly stops the filter from removing noise */
+    float step;                /* march step of the guides in world units; 0 (default) = half the smallest voxel edge */
+} svr_denoise_params;
+int svr_denoise_params_default(svr_denoise_params* p);
+int svr_set_denoise_params(const svr_denoise_params* p);     /* the parameters of SVR_OPT_DENOISE_PREVIEW and of p == NULL below */
+int svr_get_denoise_params(svr_denoise_params* p);
+/* the W x H x 8-float guide buffer of the current setup_* scene into a device buffer (on the library's stream) */
+int svr_render_guides(void* guides);
+/* denoise a WHOLE w x h accumulator (device, packed float3; read only) with the current scene's guides and tone-map it into img (device,
+ * RGBA8); w x h must be the camera's image size.  Ignores any row shard or window, like svr_hdr_to_ldr_frame: the call rank 0 makes
+ * after svr_assemble_frame.  p == NULL: the current parameters */
+int svr_denoise_to_ldr(void* img, const void* hdr, uint32_t w, uint32_t h, const svr_denoise_params* p);
+/* the same filter, HDR result (remodulated, not tone-mapped) into out (device, w x h packed float3) */
+int svr_denoise_hdr(void* out, const void* hdr, uint32_t w, uint32_t h, const svr_denoise_params* p);
+/* number of times the guides have been computed (cache test hook) */
+uint64_t svr_guide_builds(void);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

@@ -112,6 +112,24 @@ class Counters(C.Structure):  # svr_counters
         return {n: int(getattr(self, n)) for n, _ in self._fields_ }
 
 
+class DenoiseParams(C.Structure):  # svr_denoise_params
+    _fields_ = [
+        ("passes", C.c_int32),
+        ("sigma_depth", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_albedo", C.c_float),
+        ("sigma_opacity", C.c_float),
+        ("sigma_color", C.c_float),
+        ("step", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+svr_denoise_params = DenoiseParams
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -123,6 +141,7 @@ EXPECTED_SIZES = {
     cudaEnvironmentLight: 32,
     RenderParams: 16,
     Counters: 96,
+    DenoiseParams: 28,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -156,6 +175,7 @@ OPT_MACRO_SHIFT_MIN = 32
 OPT_SPLIT = 33
 OPT_ENV_NEE = 34
 OPT_FAST_BOUND = 35
+OPT_DENOISE_PREVIEW = 36
 KERNEL_AUTO, KERNEL_PIXEL, KERNEL_TILE, KERNEL_ULOOP, KERNEL_WAVEFRONT = 0, 1, 2, 3, 4
 
 ELEM_I8, ELEM_U8, ELEM_I16, ELEM_U16, ELEM_I32, ELEM_U32, ELEM_F32, ELEM_F64 = range(8)
@@ -224,6 +244,13 @@ PROTOTYPES = {
     "svr_selftest_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "svr_selftest_math": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "svr_selftest_bound8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "svr_denoise_params_default": (C.c_int, [_P(DenoiseParams)]),
+    "svr_set_denoise_params": (C.c_int, [_P(DenoiseParams)]),
+    "svr_get_denoise_params": (C.c_int, [_P(DenoiseParams)]),
+    "svr_render_guides": (C.c_int, [C.c_void_p]),
+    "svr_denoise_to_ldr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(DenoiseParams)]),
+    "svr_denoise_hdr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(DenoiseParams)]),
+    "svr_guide_builds": (C.c_uint64, []),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

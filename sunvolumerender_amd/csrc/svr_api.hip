@@ -6,6 +6,7 @@
 // entry point either launches HIP work or reports an error.
 #include "../../include/svr_abi.h"
 #include "svr_kernels.hpp"
+#include "svr_denoise.hpp"
 #include "svr_device.hpp"   // wang_hash (host)
 
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@ static_assert(sizeof(svr_environment_light) == 32 && offsetof(svr_environment_li
               offsetof(svr_environment_light, intensity) == 20 && offsetof(svr_environment_light, offset) == 24, "cudaEnvironmentLight layout");
 static_assert(sizeof(svr_render_params) == 16 && offsetof(svr_render_params, hdrBuffer) == 8, "RenderParams layout");
 static_assert(sizeof(svr_counters) == 8 * svr::CNT_N, "counter block");
+static_assert(sizeof(svr_denoise_params) == 28 && offsetof(svr_denoise_params, step) == 24, "svr_denoise_params layout");
 
 namespace svr_fast { hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st); }   // svr_trace_tile_fast.hip
 
@@ -64,6 +66,9 @@ struct Texture {
     uint64_t version = 0;
 };
 constexpr uint32_t TEX_MAGIC = 0x53565254u;   // "SVRT"
+// defaults of the denoised preview (include/svr_abi.h, svr_denoise_params): the setting of the sweep over small_head, c3 and c2 at 1 and 4 spp
+// (tools/denoise_sweep.py, profiles/denoise_sweep.txt) with the smallest worst-case drift of the mean luminance whose RMSE ratios all stay below 0.6
+constexpr svr_denoise_params DN_DEFAULT = {5, 0.5f, 32.f, 0.4f, 0.8f, 0.f, 0.f};
 
 struct Context {
     bool inited = false;
@@ -145,6 +150,21 @@ struct Context {
     uint32_t mask_ds_bits = 0, mask_sigma_bits = 0;
     bool mask_cull_useful = false, mask_has_empty = true;
     uint32_t mask_words = 0;
+    // denoised preview (SVR_OPT_DENOISE_PREVIEW, svr_denoise.hip): the guides of the current scene, cached under what they depend on -- the
+    // scene PODs of build_scene (volume, transfer function, camera, image size; not lights, not the env map), the transfer function's edit
+    // counter, the march step and the skipping mode -- and the filter's ping-pong scratch
+    int opt_denoise_preview = 0;
+    svr_denoise_params dn = DN_DEFAULT;
+    float4* d_guides = nullptr;
+    size_t guides_px = 0;
+    bool guides_valid = false;
+    svr::DevScene guides_key{};
+    uint64_t guides_vol = 0, guides_tf = 0, guides_tf_version = 0;
+    float guides_h = 0.f;
+    int guides_skip = -1;
+    uint64_t guide_builds = 0;
+    float4* d_dn_scratch = nullptr;
+    size_t dn_scratch_px = 0;
     // ring of HIP event pairs around the path-tracing kernel (SVR_OPT_TIMING); drained lazily so the
     // timed launches never synchronise with the host
     static constexpr int EV_RING = 512;
@@ -669,7 +689,7 @@ int ensure_queues(uint32_t W, uint32_t H)
     return 0;
 }
 
-int render_frames(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
+int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
 {
     if (ensure_init()) return g.err_code;
     if (!rp) return fail(-4, "render_pathtracer: renderParams is null");
@@ -980,6 +1000,123 @@ int render_frames(void* img, const svr_render_params* rp, uint32_t nframes, bool
     return 0;
 }
 
+// ---------------- denoised preview (svr_denoise.hip) ----------------
+
+int check_denoise_params(const svr_denoise_params& p)
+{
+    if (p.passes < 1 || p.passes > 10) return fail(-6, "svr_denoise_params.passes must be 1..10 (got %d)", p.passes);
+    const float v[6] = {p.sigma_depth, p.sigma_normal, p.sigma_albedo, p.sigma_opacity, p.sigma_color, p.step};
+    for (float x : v)
+        if (!std::isfinite(x) || x < 0.f) return fail(-6, "svr_denoise_params: sigmas and step must be finite and >= 0");
+    return 0;
+}
+
+// march step of the guides: p.step, or half the smallest voxel edge of the volume in world units
+float guide_step(const svr::DevScene& s, const svr_denoise_params& p)
+{
+    if (p.step > 0.f) return p.step;
+    double e = 1e30;
+    const double n[3] = {s.fnx, s.fny, s.fnz};
+    for (int a = 0; a < 3; ++a) {
+        const double edge = 1.0 / ((double)s.invSize[a] * n[a]);
+        if (edge > 0.0 && edge < e) e = edge;
+    }
+    return (float)(0.5 * e);
+}
+
+// device memory of the preview; soft: an allocation failure is recorded in svr_last_error() without an error code and
+// reported as `ok` = false (the caller falls back to the ordinary tone map)
+int ensure_denoise_memory(size_t px, bool soft, bool& ok)
+{
+    ok = true;
+    auto grow = [&](float4*& buf, size_t& have, size_t want) -> int {
+        if (have >= want && buf) return 0;
+        if (buf) HIP_TRY(hipFree(buf));
+        buf = nullptr; have = 0;
+        const hipError_t e = hipMalloc((void**)&buf, want * sizeof(float4));
+        if (e == hipSuccess) { have = want; return 0; }
+        buf = nullptr;
+        (void)hipGetLastError();
+        if (!soft) return fail((int)e, "denoise: hipMalloc of %zu bytes failed: %s", want * sizeof(float4), hipGetErrorName(e));
+        g.err_msg = std::string("denoise preview: device memory unavailable (") + hipGetErrorName(e) + "), fell back to the ordinary tone map";
+        ok = false;
+        return 0;
+    };
+    if (g.guides_px < px) g.guides_valid = false;
+    if (grow(g.d_guides, g.guides_px, 2 * px)) return g.err_code;
+    if (!ok) return 0;
+    if (grow(g.d_dn_scratch, g.dn_scratch_px, 2 * px)) return g.err_code;
+    return 0;
+}
+
+// the guides of the current scene in g.d_guides, recomputed on the caller's stream only when something they depend on changed
+int ensure_guides(const svr_denoise_params& p, bool soft, bool& ok)
+{
+    svr::DevScene s;
+    if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
+    const size_t px = (size_t)s.imageW * s.imageH;
+    if (ensure_denoise_memory(px, soft, ok) || !ok) return g.err_code;
+    const float h = guide_step(s, p);
+    Texture* tt = find_tex(g.tf.tex, TEX_TF);
+    const uint64_t tf_version = tt ? tt->version : 0;
+    if (g.guides_valid && memcmp(&g.guides_key, &s, sizeof s) == 0 && g.guides_vol == g.vol.tex && g.guides_tf == g.tf.tex &&
+        g.guides_tf_version == tf_version && g.guides_h == h && g.guides_skip == g.opt_empty_skip)
+        return 0;
+    const svr::DevScene key = s;
+    if (ensure_mask(s, g.vol, g.tf)) return g.err_code;       // empty-space skipping (same guides without it)
+    HIP_TRY(svr::launch_guides(s, g.d_guides, h, g.stream));
+    g.guides_valid = true;
+    g.guides_key = key;
+    g.guides_vol = g.vol.tex; g.guides_tf = g.tf.tex; g.guides_tf_version = tf_version;
+    g.guides_h = h;
+    g.guides_skip = g.opt_empty_skip;
+    g.guide_builds++;
+    return 0;
+}
+
+// filter a whole W x H accumulator with the current scene's guides: tone-mapped into img, or (img null) into hdr_out
+int denoise_frame(void* img, float* hdr_out, const void* hdr, uint32_t W, uint32_t H, const svr_denoise_params& p, bool soft, bool& ok)
+{
+    ok = true;
+    if (W != g.cam.imageW || H != g.cam.imageH)
+        return fail(-4, "denoise: the frame (%u x %u) must have the image size of the current camera (%u x %u)", W, H, g.cam.imageW, g.cam.imageH);
+    if (ensure_guides(p, soft, ok) || !ok) return g.err_code;
+    svr::DenoiseArgs a;
+    a.W = W; a.H = H;
+    a.passes = p.passes;
+    a.sigma_depth = p.sigma_depth; a.sigma_normal = p.sigma_normal; a.sigma_albedo = p.sigma_albedo;
+    a.sigma_opacity = p.sigma_opacity; a.sigma_color = p.sigma_color;
+    a.pix_scale = H > 1 ? 2.f * g.cam.tanFovxOverTwo / (float)(H - 1) : 2.f * g.cam.tanFovxOverTwo;
+    a.exposure = g.cam.exposure;
+    HIP_TRY(svr::launch_denoise((const float*)hdr, g.d_guides, g.d_dn_scratch, (uint8_t*)img, hdr_out, a, g.stream));
+    return 0;
+}
+
+// render_pathtracer / svr_render_pathtracer_frames.  SVR_OPT_DENOISE_PREVIEW = N > 0: while the frame shown has at most N samples per
+// pixel the traced frames are resolved WITHOUT their tone map, and guides (if stale) + filter + tone map follow on the caller's stream --
+// behind the resolve or fold that writes the accumulator, so svr_device_synchronize still waits for the shown image.  Inert under a row
+// shard, a render window or SVR_OPT_SKIP_TONEMAP.
+int render_frames(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
+{
+    if (ensure_init()) return g.err_code;
+    const bool preview = rp && img && nframes > 0 && tonemap && !g.opt_skip_tonemap && g.opt_denoise_preview > 0 && g.have_vol && g.have_tf && g.have_cam &&
+                         (uint64_t)rp->frameNo + nframes <= (uint64_t)g.opt_denoise_preview && !partial_frame(g.cam.imageW, g.cam.imageH);
+    if (render_frames_traced(img, rp, nframes, tonemap && !preview)) return g.err_code;
+    if (!preview) return 0;
+    bool ok = true;
+    if (denoise_frame(img, nullptr, rp->hdrBuffer, g.cam.imageW, g.cam.imageH, g.dn, true, ok)) return g.err_code;
+    if (!ok) {
+        svr::DevScene s;
+        if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
+        svr::DevWork w;
+        fill_work_full(w, s.imageW, s.imageH);
+        w.hdr = (float*)rp->hdrBuffer;
+        w.img = (uint8_t*)img;
+        HIP_TRY(svr::launch_tonemap(s, w, g.stream));
+    }
+    return 0;
+}
+
 } // namespace
 
 // hooks for the other translation units of the library (svr_internal.hpp)
@@ -1037,6 +1174,8 @@ void svr_shutdown(void)
     if (g.d_pend) hipFree(g.d_pend);
     if (g.queue_done) hipEventDestroy(g.queue_done);
     if (g.d_split_pool) hipFree(g.d_split_pool);
+    if (g.d_guides) hipFree(g.d_guides);
+    if (g.d_dn_scratch) hipFree(g.d_dn_scratch);
     if (g_stage) { hipFree(g_stage); g_stage = nullptr; g_stage_floats = 0; }
     for (int i = 0; i < Context::EV_RING; ++i) {
         if (g.ev0[i]) hipEventDestroy(g.ev0[i]);
@@ -1273,6 +1412,7 @@ int svr_destroy_texture(uint64_t handle)
     if (t->zero_prefix) hipFree(t->zero_prefix);
     if (t->env_cdf) hipFree(t->env_cdf);
     if (g.mask_vol == handle || g.mask_tf == handle) g.mask_valid = false;
+    if (g.guides_vol == handle || g.guides_tf == handle) g.guides_valid = false;
     t->magic = 0;
     delete t;
     g.textures.erase(it);
@@ -1393,6 +1533,65 @@ int svr_hdr_to_ldr_frame(void* img, const void* hdr, uint32_t w_, uint32_t h_)
     w.img = (uint8_t*)img;
     HIP_TRY(svr::launch_tonemap(s, w, g.stream));
     return 0;
+}
+
+// ---------------- denoised preview ----------------
+int svr_denoise_params_default(svr_denoise_params* p)
+{
+    if (!p) return fail(-4, "svr_denoise_params_default: null argument");
+    *p = DN_DEFAULT;
+    return 0;
+}
+
+int svr_set_denoise_params(const svr_denoise_params* p)
+{
+    if (!p) return fail(-4, "svr_set_denoise_params: null argument");
+    if (check_denoise_params(*p)) return g.err_code;
+    g.dn = *p;
+    return 0;
+}
+
+int svr_get_denoise_params(svr_denoise_params* p)
+{
+    if (!p) return fail(-4, "svr_get_denoise_params: null argument");
+    *p = g.dn;
+    return 0;
+}
+
+int svr_render_guides(void* guides)
+{
+    if (ensure_init()) return g.err_code;
+    if (!guides) return fail(-4, "svr_render_guides: null argument");
+    if (!g.have_vol || !g.have_tf || !g.have_cam) return fail(-4, "svr_render_guides before setup_volume/setup_transferfunction/setup_camera");
+    bool ok = true;
+    if (ensure_guides(g.dn, false, ok)) return g.err_code;
+    HIP_TRY(hipMemcpyAsync(guides, g.d_guides, (size_t)g.cam.imageW * g.cam.imageH * 2 * sizeof(float4), hipMemcpyDeviceToDevice, g.stream));
+    return 0;
+}
+
+uint64_t svr_guide_builds(void) { return g.guide_builds; }
+
+static int denoise_call(void* img, void* hdr_out, const void* hdr, uint32_t w, uint32_t h, const svr_denoise_params* p, const char* who)
+{
+    if (ensure_init()) return g.err_code;
+    if (!hdr || (!img && !hdr_out) || w == 0 || h == 0) return fail(-4, "%s: bad argument", who);
+    if (!g.have_vol || !g.have_tf || !g.have_cam) return fail(-4, "%s before setup_volume/setup_transferfunction/setup_camera", who);
+    const svr_denoise_params prm = p ? *p : g.dn;
+    if (check_denoise_params(prm)) return g.err_code;
+    bool ok = true;
+    return denoise_frame(img, (float*)hdr_out, hdr, w, h, prm, false, ok);
+}
+
+int svr_denoise_to_ldr(void* img, const void* hdr, uint32_t w, uint32_t h, const svr_denoise_params* p)
+{
+    if (!img) { ensure_init(); return fail(-4, "svr_denoise_to_ldr: img is null"); }
+    return denoise_call(img, nullptr, hdr, w, h, p, "svr_denoise_to_ldr");
+}
+
+int svr_denoise_hdr(void* out, const void* hdr, uint32_t w, uint32_t h, const svr_denoise_params* p)
+{
+    if (!out) { ensure_init(); return fail(-4, "svr_denoise_hdr: out is null"); }
+    return denoise_call(nullptr, out, hdr, w, h, p, "svr_denoise_hdr");
 }
 
 void render_raycasting(void* img, svr_volume* volume, svr_transfer_function* transferFunction, svr_camera* camera, float stepSize)
@@ -1556,6 +1755,9 @@ int svr_set_option(int key, int value)
     case SVR_OPT_COUNT: g.opt_count = value ? 1 : 0; return 0;
     case SVR_OPT_TIMING: g.opt_timing = value ? 1 : 0; return 0;
     case SVR_OPT_SKIP_TONEMAP: g.opt_skip_tonemap = value ? 1 : 0; return 0;
+    case SVR_OPT_DENOISE_PREVIEW:
+        if (value < 0) return fail(-6, "SVR_OPT_DENOISE_PREVIEW: bad value %d (0 = off, N > 0 = frames)", value);
+        g.opt_denoise_preview = value; return 0;
     case SVR_OPT_BLOCKS_PER_CU:
         if (value < 0 || value > 8) return fail(-6, "SVR_OPT_BLOCKS_PER_CU: bad value %d", value);
         g.opt_blocks_per_cu = value; return 0;
@@ -1638,6 +1840,7 @@ int svr_get_option(int key)
     case SVR_OPT_COUNT: return g.opt_count;
     case SVR_OPT_TIMING: return g.opt_timing;
     case SVR_OPT_SKIP_TONEMAP: return g.opt_skip_tonemap;
+    case SVR_OPT_DENOISE_PREVIEW: return g.opt_denoise_preview;
     case SVR_OPT_BLOCKS_PER_CU: return g.opt_blocks_per_cu;
     case SVR_OPT_PIPELINE: return g.opt_pipeline;
     case SVR_OPT_EMPTY_SKIP: return g.opt_empty_skip;

@@ -229,6 +229,41 @@ class Device:
         self.check(self.lib.svr_get_kernel_time(C.byref(ms), C.byref(n)))
         return ms.value, int(n.value)
 
+    # ---- denoised preview (SVR_OPT_DENOISE_PREVIEW, svr_denoise_to_ldr) ----
+    def denoise_params(self, **overrides) -> abi.DenoiseParams:
+        """The library's default svr_denoise_params with the named fields replaced."""
+        p = abi.DenoiseParams()
+        self.check(self.lib.svr_denoise_params_default(C.byref(p)))
+        for k, v in overrides.items():
+            if k not in dict(abi.DenoiseParams._fields_):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+    def set_denoise_params(self, params: Optional[abi.DenoiseParams] = None, **overrides):
+        """svr_set_denoise_params(params or the defaults with `overrides`)."""
+        p = params if params is not None else self.denoise_params(**overrides)
+        self.check(self.lib.svr_set_denoise_params(C.byref(p)))
+
+    def get_denoise_params(self) -> abi.DenoiseParams:
+        p = abi.DenoiseParams()
+        self.check(self.lib.svr_get_denoise_params(C.byref(p)))
+        return p
+
+    def denoise_to_ldr(self, img_ptr: int, hdr_ptr: int, width: int, height: int, params: Optional[abi.DenoiseParams] = None):
+        """svr_denoise_to_ldr: the whole width x height accumulator at hdr_ptr, denoised with the current scene's guides and tone-mapped
+        into img_ptr (device pointers).  params None = the current parameters."""
+        self.check(self.lib.svr_denoise_to_ldr(C.c_void_p(img_ptr), C.c_void_p(hdr_ptr), int(width), int(height),
+                                               C.byref(params) if params is not None else None))
+
+    def denoise_hdr(self, out_ptr: int, hdr_ptr: int, width: int, height: int, params: Optional[abi.DenoiseParams] = None):
+        """svr_denoise_hdr: the same filter, HDR result (packed float3) into out_ptr."""
+        self.check(self.lib.svr_denoise_hdr(C.c_void_p(out_ptr), C.c_void_p(hdr_ptr), int(width), int(height),
+                                            C.byref(params) if params is not None else None))
+
+    def guide_builds(self) -> int:
+        return int(self.lib.svr_guide_builds())
+
 
 class Canvas:
     """Headless replay of the reference's Qt `Canvas` render protocol (gui/canvas.{h,cpp}).
@@ -447,6 +482,23 @@ class Canvas:
         if sync:
             self.dev.synchronize()
         self.renderParams.frameNo += int(nframes)
+
+    # ---- extension: denoised preview of the first frames after a restart ----
+    def SetDenoisePreview(self, frames: int, params: Optional[abi.DenoiseParams] = None):
+        """SVR_OPT_DENOISE_PREVIEW = frames (0 = off): the image of a frame with at most `frames` samples per pixel is the
+        edge-aware denoised tone map; params (svr_denoise_params) replace the current filter parameters if given."""
+        if params is not None:
+            self.dev.set_denoise_params(params)
+        self.dev.set_option(abi.OPT_DENOISE_PREVIEW, int(frames))
+
+    def read_guides(self) -> np.ndarray:
+        """The guide buffer of the current scene (svr_render_guides): (H, W, 8) float32 = N.xyz, D, A.rgb, O."""
+        buf = self.dev.malloc(self.W * self.H * 32)
+        try:
+            self.dev.check(self.lib.svr_render_guides(C.c_void_p(buf)))
+            return self.dev.to_host(buf, (self.H, self.W, 8), np.float32)
+        finally:
+            self.dev.free(buf)
 
     def read_hdr(self) -> np.ndarray:
         return self.dev.to_host(int(self.renderParams.hdrBuffer), (self.H, self.W, 3), np.float32)
