@@ -1,8 +1,10 @@
 // render_mhd.cpp -- the reference application's start-up sequence (main.cpp / gui/mainwindow.cpp:22-62, 229-238)
 // without the GUI: load a MetaImage volume, the GUI-default (or a saved .tf) transfer function, one area light, an
-// optional .hdr environment map; render N progressive frames; write the image as TGA.
+// optional .hdr environment map; render N progressive frames (or, with -noise T, until the predicted RMSE of the tone-mapped
+// image is <= T, at most N frames); write the image as TGA.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-o out.tga]
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,10 +14,11 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
+    float noiseTarget = 0.f;                                        // 0: render exactly -frames frames
     bool raycast = false;
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
@@ -25,6 +28,11 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-size") && i + 2 < argc) { W = atoi(argv[i + 1]); H = atoi(argv[i + 2]); i += 2; }
         else if (!strcmp(argv[i], "-raycast")) raycast = true;
         else if (!strcmp(argv[i], "-denoise-preview") && i + 1 < argc) denoisePreview = atoi(argv[++i]);   // denoised image up to N spp
+        else if (!strcmp(argv[i], "-noise") && i + 1 < argc) {                                          // render until converged
+            char* end = nullptr;
+            noiseTarget = strtof(argv[++i], &end);
+            if (end == argv[i] || *end != '\0' || !(noiseTarget > 0.f)) { fprintf(stderr, "-noise needs a target RMSE > 0 (got %s)\n", argv[i]); return 2; }
+        }
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -69,7 +77,17 @@ int main(int argc, char** argv)
         canvas.SetRenderMode(raycast ? RENDER_MODE_RAYCASTING : RENDER_MODE_PATHTRACER);
         canvas.SetDenoisePreview(denoisePreview);
 
-        for (int f = 0; f < (raycast ? 1 : frames); ++f) canvas.paintGL();
+        if (noiseTarget > 0.f && !raycast) {
+            const auto t0 = std::chrono::steady_clock::now();
+            const uint32_t used = canvas.RenderUntil(noiseTarget, 0.f, frames > 0 ? (uint32_t)frames : 1u);
+            svr_device_synchronize();
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            const svr_noise_estimate e = canvas.GetNoiseEstimate();
+            if (svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            printf("noise target %g: %u frames in %.1f ms; estimate at %u frames (against %u): rmse %.5f, largest tile %.5f, %llu pixels, %llu non-finite\n",
+                   noiseTarget, used, ms, e.frames, e.frames_ref, e.rmse, e.tile_max, (unsigned long long)e.pixels, (unsigned long long)e.nonfinite);
+        } else
+            for (int f = 0; f < (raycast ? 1 : frames); ++f) canvas.paintGL();
         if (!canvas.SaveImage(out)) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%u frame(s) on %s -> %s\n", canvas.FrameNo(), svr_device_info(), out.c_str());
     }

@@ -268,6 +268,15 @@ public:
     // extension: edge-aware denoised image while a restarted render has at most `frames` samples per pixel (SVR_OPT_DENOISE_PREVIEW;
     // 0 = off).  Changes only the RGBA8 image, never the accumulator
     void SetDenoisePreview(int frames) { svr_set_option(SVR_OPT_DENOISE_PREVIEW, frames); }
+    // extension: follow the render and estimate its remaining noise (SVR_OPT_NOISE_ESTIMATE); the latest estimate (frames == 0: none yet)
+    void SetNoiseEstimate(bool on) { svr_set_option(SVR_OPT_NOISE_ESTIMATE, on ? 1 : 0); }
+    // (the library keeps one estimate per process, of the render it last followed: one with another tile grid is another canvas's)
+    svr_noise_estimate GetNoiseEstimate() const
+    {
+        svr_noise_estimate e = {};
+        if (svr_get_noise_estimate(&e, nullptr) != 0 || e.tiles_x != (WIDTH + 15u) / 16u || e.tiles_y != (HEIGHT + 15u) / 16u) e = svr_noise_estimate{};
+        return e;
+    }
 
     // clip planes, canvas.h:165-184
     void SetXClipPlane(double mn, double mx) { deviceVolume.SetXClipPlane(glm::vec2(float(mn), float(mx))); setup_volume(deviceVolume); ReStartRender(); }
@@ -309,6 +318,16 @@ public:
         if (!ready || renderMode != RENDER_MODE_PATHTRACER) return;
         svr_render_pathtracer_frames(img, &renderParams, n);
         renderParams.frameNo += n;
+    }
+
+    // extension: render until the predicted RMSE of the tone-mapped image is <= targetRmse (and every 16 x 16 tile's <= targetTileRmse; 0 =
+    // unchecked) or maxFrames frames were traced (svr_render_pathtracer_until); frameNo advances by the frames traced, which are returned
+    uint32_t RenderUntil(float targetRmse, float targetTileRmse, uint32_t maxFrames)
+    {
+        if (!ready || renderMode != RENDER_MODE_PATHTRACER) return 0;
+        uint32_t done = 0;
+        svr_render_pathtracer_until(img, &renderParams, targetRmse, targetTileRmse, maxFrames, &done);
+        return done;
     }
 
     bool SaveImage(const std::string& filename)

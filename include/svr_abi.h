@@ -306,6 +306,14 @@ int svr_assemble_frame(void* nccl_comm, void* frame_on_root, const void* hdr_loc
                                      * the accumulator (hdrBuffer) is never written by the filter, so convergence and bit-exactness are untouched.  Inert
                                      * under a row shard, a render window or SVR_OPT_SKIP_TONEMAP.  If the guide / scratch memory cannot be allocated the
                                      * frame gets the ordinary tone map and svr_last_error() says so (no error code: the render does not fail) */
+#define SVR_OPT_NOISE_ESTIMATE 37      /* 0 (default) = off (no memory, no launch, no state change); 1: render_pathtracer and svr_render_pathtracer_frames follow the
+                                     * render and estimate its remaining noise from the accumulator alone (csrc/svr_noise.hip; see svr_noise_estimate below).
+                                     * A call with frameNo 0, a frameNo that is not the previous call's end, or another hdrBuffer / image size / window /
+                                     * shard / trace depth starts a new render; the first call that ends at n >= 4 frames takes a snapshot A(m) = A(n)
+                                     * (12 B per pixel, allocated once), every later call that ends at n >= 2m estimates A(n) against it and takes
+                                     * the snapshot A(n), m = n: estimates at 8, 16, 32 ... frames for one frame per call.  Everything runs on the
+                                     * library's stream behind the call; the accumulator and the image are unchanged.  If the memory cannot be
+                                     * allocated there is no estimate and svr_last_error() says so (no error code: the render does not fail) */
 #define SVR_OPT_FRAME_AHEAD 13           /* render_pathtracer traces frames ahead of the calls that ask for them (batches of 1, 2, 4 ... 32 frames; results unchanged); default 1 */
 #define SVR_OPT_RAYCAST_LANES_LOG2 12   /* ray caster: 1 << v adjacent lanes share one ray (samples of a chunk in parallel, composited in order); 0..5, default 3 */
 #define SVR_OPT_FRAMES_PER_WAVE_LOG2 11 /* tile kernel: a wave traces (64 >> f) pixels x (1 << f) frames of a group; -1 (default) = up to 8 frames */
@@ -389,6 +397,42 @@ int svr_denoise_to_ldr(void* img, const void* hdr, uint32_t w, uint32_t h, const
 int svr_denoise_hdr(void* out, const void* hdr, uint32_t w, uint32_t h, const svr_denoise_params* p);
 /* number of times the guides have been computed (cache test hook) */
 uint64_t svr_guide_builds(void);
+
+/* ---- noise estimate of a progressive render (SVR_OPT_NOISE_ESTIMATE; csrc/svr_noise.hip) ----
+ * A(k) = the accumulator after k frames.  From A(m) and A(n), m < n: B = (n A(n) - m A(m)) / (n - m), the mean of frames m+1 .. n (independent
+ * of A(m)); with the tone curve before quantisation T(L) = (1 - e^(-16 exposure max(L, 0)))^2.2 per channel,
+ *   d^2_p = mean over the 3 channels of (T(A(m)) - T(B))^2,   e^2_p = d^2_p m (n - m) / n^2
+ * is the predicted squared error of T(A(n)) in [0, 1] tone-mapped units (delta method; e^2 = d^2 / 4 at n = 2m).  A pixel counts when all 6
+ * values are finite and the process owns it (row shard, window); owned pixels with a non-finite value are counted in `nonfinite`.  Tiles:
+ * 16 x 16 pixels aligned to the image.  The estimate applies to n frames; for n' > n frames of the same render it scales by sqrt(n / n'). */
+typedef struct svr_noise_estimate {
+    uint32_t frames;           /* n; 0 = no estimate (yet) */
+    uint32_t frames_ref;       /* m */
+    float rmse;                /* sqrt(sse / pixels); NaN if no pixel counted */
+    float tile_max;            /* largest tile RMSE sqrt(mean e^2 over the tile's counted pixels); NaN if no tile has one */
+    uint32_t tiles_x, tiles_y; /* ceil(W / 16), ceil(H / 16): the tile map, row-major */
+    uint64_t pixels;           /* counted pixels */
+    uint64_t nonfinite;        /* owned pixels left out for a non-finite value */
+    double sse;                /* sum of e^2 over the counted pixels: add the sse and pixels of the ranks of a row shard for the frame's rmse */
+} svr_noise_estimate;
+/* the latest estimate of the render SVR_OPT_NOISE_ESTIMATE (or svr_render_pathtracer_until) follows; frames = 0 if there is none.  Like the scene, the
+ * estimate is per process: it belongs to the render the library last followed, whichever accumulator that was (a host with several
+ * canvases checks tiles_x / tiles_y, or calls with tile_rmse_device = NULL first).  tile_rmse_device (may be NULL): receives tiles_x * tiles_y
+ * floats, NaN for tiles without a counted pixel; an error if it is not a device allocation that large.  Synchronises the library's stream */
+int svr_get_noise_estimate(svr_noise_estimate* out, float* tile_rmse_device);
+/* stateless: the estimate of A(n) = hdr_n against A(m) = hdr_m (device, w x h packed float3 each; 0 < m < n) over the WHOLE frame, whatever
+ * shard or window is set (the call rank 0 makes after svr_assemble_frame; hosts that keep their own copies), with the exposure of the last
+ * setup_camera.  tile_rmse_device may be NULL.  Synchronises the library's stream */
+int svr_estimate_noise(const void* hdr_m, uint32_t m, const void* hdr_n, uint32_t n, uint32_t w, uint32_t h, float* tile_rmse_device,
+                       svr_noise_estimate* out);
+/* render from renderParams->frameNo until the predicted noise meets the targets: frames go in folding many-frame launches that end at the
+ * checkpoints of SVR_OPT_NOISE_ESTIMATE (the snapshot, then doubling frame counts), one stream synchronisation per estimate; the call stops at
+ * the first estimate with rmse <= target_rmse and tile_max <= target_tile_rmse (a target of 0 is not checked; both 0: exactly max_frames), or
+ * after max_frames frames.  Works with the option off (the estimator runs for the call's duration).  The accumulator is bit-identical to
+ * *frames_done calls of render_pathtracer; renderParams->frameNo advances by *frames_done (frames_done may be NULL) and img holds the tone map
+ * of the last frame (SVR_OPT_DENOISE_PREVIEW / SVR_OPT_SKIP_TONEMAP as for any call) */
+int svr_render_pathtracer_until(void* img, svr_render_params* renderParams, float target_rmse, float target_tile_rmse, uint32_t max_frames,
+                                uint32_t* frames_done);
 
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);

@@ -130,6 +130,26 @@ class DenoiseParams(C.Structure):  # svr_denoise_params
 svr_denoise_params = DenoiseParams
 
 
+class NoiseEstimate(C.Structure):  # svr_noise_estimate
+    _fields_ = [
+        ("frames", C.c_uint32),
+        ("frames_ref", C.c_uint32),
+        ("rmse", C.c_float),
+        ("tile_max", C.c_float),
+        ("tiles_x", C.c_uint32),
+        ("tiles_y", C.c_uint32),
+        ("pixels", C.c_uint64),
+        ("nonfinite", C.c_uint64),
+        ("sse", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+svr_noise_estimate = NoiseEstimate
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -142,6 +162,7 @@ EXPECTED_SIZES = {
     RenderParams: 16,
     Counters: 96,
     DenoiseParams: 28,
+    NoiseEstimate: 48,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -176,6 +197,7 @@ OPT_SPLIT = 33
 OPT_ENV_NEE = 34
 OPT_FAST_BOUND = 35
 OPT_DENOISE_PREVIEW = 36
+OPT_NOISE_ESTIMATE = 37
 KERNEL_AUTO, KERNEL_PIXEL, KERNEL_TILE, KERNEL_ULOOP, KERNEL_WAVEFRONT = 0, 1, 2, 3, 4
 
 ELEM_I8, ELEM_U8, ELEM_I16, ELEM_U16, ELEM_I32, ELEM_U32, ELEM_F32, ELEM_F64 = range(8)
@@ -251,6 +273,9 @@ PROTOTYPES = {
     "svr_denoise_to_ldr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(DenoiseParams)]),
     "svr_denoise_hdr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(DenoiseParams)]),
     "svr_guide_builds": (C.c_uint64, []),
+    "svr_get_noise_estimate": (C.c_int, [_P(NoiseEstimate), C.c_void_p]),
+    "svr_estimate_noise": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _P(NoiseEstimate)]),
+    "svr_render_pathtracer_until": (C.c_int, [C.c_void_p, _P(RenderParams), C.c_float, C.c_float, C.c_uint32, _P(C.c_uint32)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

@@ -7,9 +7,11 @@
 #include "../../include/svr_abi.h"
 #include "svr_kernels.hpp"
 #include "svr_denoise.hpp"
+#include "svr_noise.hpp"
 #include "svr_device.hpp"   // wang_hash (host)
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -35,6 +37,9 @@ static_assert(sizeof(svr_environment_light) == 32 && offsetof(svr_environment_li
 static_assert(sizeof(svr_render_params) == 16 && offsetof(svr_render_params, hdrBuffer) == 8, "RenderParams layout");
 static_assert(sizeof(svr_counters) == 8 * svr::CNT_N, "counter block");
 static_assert(sizeof(svr_denoise_params) == 28 && offsetof(svr_denoise_params, step) == 24, "svr_denoise_params layout");
+static_assert(sizeof(svr_noise_estimate) == 48 && offsetof(svr_noise_estimate, tiles_x) == 16 && offsetof(svr_noise_estimate, pixels) == 24 &&
+              offsetof(svr_noise_estimate, sse) == 40, "svr_noise_estimate layout");
+static_assert(sizeof(svr::NoiseTotals) == 32, "noise totals");
 
 namespace svr_fast { hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st); }   // svr_trace_tile_fast.hip
 
@@ -165,6 +170,33 @@ struct Context {
     uint64_t guide_builds = 0;
     float4* d_dn_scratch = nullptr;
     size_t dn_scratch_px = 0;
+    // noise estimate (SVR_OPT_NOISE_ESTIMATE, svr_noise.hip): the render it follows, its snapshot A(m) and the latest estimate.  A tracked
+    // render is a run of consecutive render calls (render_calls counts every call) on one accumulator, size, shape and trace depth
+    int opt_noise_estimate = 0;
+    uint64_t render_calls = 0;
+    struct NoiseBuf {                   // per-tile results + totals of one estimate: totals | tile_sse | tile_rmse | tile_cnt, one allocation
+        void* mem = nullptr;
+        size_t tiles = 0;
+        svr::NoiseTotals* totals() const { return (svr::NoiseTotals*)mem; }
+        double* sse() const { return (double*)((char*)mem + sizeof(svr::NoiseTotals)); }
+        float* rmse() const { return (float*)(sse() + tiles); }
+        uint32_t* cnt() const { return (uint32_t*)(rmse() + tiles); }
+    };
+    struct Noise {
+        bool tracking = false, unavailable = false;
+        uint64_t call = 0;              // render_calls after the last tracked call
+        void* hdr = nullptr;
+        uint32_t W = 0, H = 0, depth = 0;
+        svr::DevWork shape{};
+        uint32_t last_n = 0;            // frame count at the end of the last tracked call
+        uint32_t m = 0;                 // frames in the snapshot; 0 = none yet
+        bool have = false;              // an estimate of this render exists (in buf, on the stream)
+        uint32_t est_n = 0, est_m = 0, tiles_x = 0, tiles_y = 0;
+        float* d_snap = nullptr;
+        size_t snap_px = 0;
+        NoiseBuf buf;
+    } ns;
+    NoiseBuf nb_call;                   // svr_estimate_noise
     // ring of HIP event pairs around the path-tracing kernel (SVR_OPT_TIMING); drained lazily so the
     // timed launches never synchronise with the host
     static constexpr int EV_RING = 512;
@@ -1092,13 +1124,129 @@ int denoise_frame(void* img, float* hdr_out, const void* hdr, uint32_t W, uint32
     return 0;
 }
 
+// ---------------- noise estimate (svr_noise.hip) ----------------
+
+// per-tile buffers of `tiles` tiles; soft: an allocation failure sets ok = false and a message without an error code
+int ensure_noise_buf(Context::NoiseBuf& b, size_t tiles, bool soft, bool& ok)
+{
+    ok = true;
+    if (b.mem && b.tiles >= tiles) return 0;
+    if (b.mem) HIP_TRY(hipFree(b.mem));
+    b.mem = nullptr; b.tiles = 0;
+    const size_t bytes = sizeof(svr::NoiseTotals) + tiles * (sizeof(double) + sizeof(float) + 2 * sizeof(uint32_t));
+    const hipError_t e = hipMalloc(&b.mem, bytes);
+    if (e == hipSuccess) { b.tiles = tiles; return 0; }
+    b.mem = nullptr;
+    (void)hipGetLastError();
+    if (!soft) return fail((int)e, "noise estimate: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorName(e));
+    g.err_msg = std::string("noise estimate: device memory unavailable (") + hipGetErrorName(e) + "), no estimate for this render";
+    ok = false;
+    return 0;
+}
+
+// launch arguments for the estimate of A(n) against A(m) over the pixels of `own` (a DevWork of fill_work / fill_work_full)
+svr::NoiseArgs noise_args(uint32_t W, uint32_t H, const svr::DevWork& own, uint32_t m, uint32_t n, float exposure)
+{
+    svr::NoiseArgs a;
+    a.W = W; a.H = H;
+    a.tiles_x = (W + svr::NOISE_TILE - 1u) / svr::NOISE_TILE;
+    a.tiles_y = (H + svr::NOISE_TILE - 1u) / svr::NOISE_TILE;
+    a.x0 = own.x0; a.x1 = own.x1; a.y0 = own.y0; a.y1 = own.y1;
+    a.strip_rows = own.strip_rows ? own.strip_rows : 1u; a.rank = own.rank; a.world = own.world;
+    a.exposure = exposure;
+    a.ratio = (float)((double)m / (double)(n - m));
+    a.scale = (float)((double)m * (double)(n - m) / ((double)n * (double)n));
+    return a;
+}
+
+void noise_fill(svr_noise_estimate& out, const svr::NoiseTotals& t, uint32_t m, uint32_t n, uint32_t tiles_x, uint32_t tiles_y)
+{
+    out.frames = n;
+    out.frames_ref = m;
+    out.tiles_x = tiles_x;
+    out.tiles_y = tiles_y;
+    out.pixels = t.pixels;
+    out.nonfinite = t.nonfinite;
+    out.sse = t.sse;
+    out.rmse = t.pixels ? (float)std::sqrt(t.sse / (double)t.pixels) : std::nanf("");
+    out.tile_max = t.tile_max;
+}
+
+// would a render call of rp, made next, continue the render the estimate follows?
+bool noise_continues(const svr_render_params* rp, uint64_t call)
+{
+    const Context::Noise& ns = g.ns;
+    if (!ns.tracking || rp->frameNo == 0 || rp->frameNo != ns.last_n || ns.call + 1 != call || ns.hdr != rp->hdrBuffer ||
+        ns.W != g.cam.imageW || ns.H != g.cam.imageH || ns.depth != rp->traceDepth)
+        return false;
+    svr::DevWork w;
+    fill_work(w, g.cam.imageW, g.cam.imageH);
+    return w.x0 == ns.shape.x0 && w.x1 == ns.shape.x1 && w.y0 == ns.shape.y0 && w.y1 == ns.shape.y1 &&
+           w.strip_rows == ns.shape.strip_rows && w.rank == ns.shape.rank && w.world == ns.shape.world;
+}
+
+// the state rules of SVR_OPT_NOISE_ESTIMATE, behind a render call of rp that ended at n = frameNo + nframes (render call number `call`):
+// a new render (frameNo 0, a gap in the frame numbers or the calls, another accumulator / size / shape / depth) resets; the first call
+// that ends at n >= 4 takes the snapshot A(m), m = n; after that every call that ends at n >= 2m runs the fused estimate + snapshot, m = n.
+// All on the caller's stream behind the resolve / fold that wrote A(n); nothing waits for the host.
+int noise_after_render(const svr_render_params* rp, uint32_t nframes, uint64_t call)
+{
+    Context::Noise& ns = g.ns;
+    const uint64_t n64 = (uint64_t)rp->frameNo + nframes;
+    if (!noise_continues(rp, call)) {
+        ns.tracking = true;
+        ns.unavailable = false;
+        ns.m = 0;
+        ns.have = false;
+        ns.hdr = rp->hdrBuffer;
+        ns.W = g.cam.imageW; ns.H = g.cam.imageH;
+        ns.depth = rp->traceDepth;
+        fill_work(ns.shape, ns.W, ns.H);
+    }
+    ns.call = call;
+    if (n64 > 0xffffffffull) { ns.tracking = false; return 0; }
+    const uint32_t n = (uint32_t)n64;
+    ns.last_n = n;
+    if (ns.unavailable) return 0;
+    const size_t px = (size_t)ns.W * ns.H;
+    if (ns.m == 0) {
+        if (n < 4) return 0;
+        if (ns.snap_px < px || !ns.d_snap) {
+            if (ns.d_snap) HIP_TRY(hipFree(ns.d_snap));
+            ns.d_snap = nullptr; ns.snap_px = 0;
+            const hipError_t e = hipMalloc((void**)&ns.d_snap, px * 3 * sizeof(float));
+            if (e != hipSuccess) {
+                ns.d_snap = nullptr;
+                (void)hipGetLastError();
+                g.err_msg = std::string("noise estimate: device memory unavailable (") + hipGetErrorName(e) + "), no estimate for this render";
+                ns.unavailable = true;
+                return 0;
+            }
+            ns.snap_px = px;
+        }
+        HIP_TRY(hipMemcpyAsync(ns.d_snap, rp->hdrBuffer, px * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream));
+        ns.m = n;
+        return 0;
+    }
+    if ((uint64_t)n < 2ull * ns.m) return 0;
+    const svr::NoiseArgs a = noise_args(ns.W, ns.H, ns.shape, ns.m, n, g.cam.exposure);
+    bool ok = true;
+    if (ensure_noise_buf(ns.buf, (size_t)a.tiles_x * a.tiles_y, true, ok)) return g.err_code;
+    if (!ok) { ns.unavailable = true; ns.have = false; return 0; }
+    HIP_TRY(svr::launch_noise(ns.d_snap, (const float*)rp->hdrBuffer, true, a, ns.buf.rmse(), ns.buf.sse(), ns.buf.cnt(), ns.buf.totals(), g.stream));
+    ns.have = true;
+    ns.est_m = ns.m; ns.est_n = n;
+    ns.tiles_x = a.tiles_x; ns.tiles_y = a.tiles_y;
+    ns.m = n;
+    return 0;
+}
+
 // render_pathtracer / svr_render_pathtracer_frames.  SVR_OPT_DENOISE_PREVIEW = N > 0: while the frame shown has at most N samples per
 // pixel the traced frames are resolved WITHOUT their tone map, and guides (if stale) + filter + tone map follow on the caller's stream --
 // behind the resolve or fold that writes the accumulator, so svr_device_synchronize still waits for the shown image.  Inert under a row
 // shard, a render window or SVR_OPT_SKIP_TONEMAP.
-int render_frames(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
+int render_frames_shown(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
 {
-    if (ensure_init()) return g.err_code;
     const bool preview = rp && img && nframes > 0 && tonemap && !g.opt_skip_tonemap && g.opt_denoise_preview > 0 && g.have_vol && g.have_tf && g.have_cam &&
                          (uint64_t)rp->frameNo + nframes <= (uint64_t)g.opt_denoise_preview && !partial_frame(g.cam.imageW, g.cam.imageH);
     if (render_frames_traced(img, rp, nframes, tonemap && !preview)) return g.err_code;
@@ -1115,6 +1263,16 @@ int render_frames(void* img, const svr_render_params* rp, uint32_t nframes, bool
         HIP_TRY(svr::launch_tonemap(s, w, g.stream));
     }
     return 0;
+}
+
+// ... and, with SVR_OPT_NOISE_ESTIMATE on, the estimate's state rules behind the call (they only read the accumulator)
+int render_frames(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
+{
+    if (ensure_init()) return g.err_code;
+    const uint64_t call = ++g.render_calls;
+    if (render_frames_shown(img, rp, nframes, tonemap)) return g.err_code;
+    if (!g.opt_noise_estimate) return 0;
+    return noise_after_render(rp, nframes, call);
 }
 
 } // namespace
@@ -1176,6 +1334,9 @@ void svr_shutdown(void)
     if (g.d_split_pool) hipFree(g.d_split_pool);
     if (g.d_guides) hipFree(g.d_guides);
     if (g.d_dn_scratch) hipFree(g.d_dn_scratch);
+    if (g.ns.d_snap) hipFree(g.ns.d_snap);
+    if (g.ns.buf.mem) hipFree(g.ns.buf.mem);
+    if (g.nb_call.mem) hipFree(g.nb_call.mem);
     if (g_stage) { hipFree(g_stage); g_stage = nullptr; g_stage_floats = 0; }
     for (int i = 0; i < Context::EV_RING; ++i) {
         if (g.ev0[i]) hipEventDestroy(g.ev0[i]);
@@ -1535,6 +1696,107 @@ int svr_hdr_to_ldr_frame(void* img, const void* hdr, uint32_t w_, uint32_t h_)
     return 0;
 }
 
+// ---------------- noise estimate ----------------
+// is [p, p + bytes) inside one device allocation?
+static bool device_range_ok(const void* p, size_t bytes)
+{
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return (const char*)p + bytes <= (const char*)base + size;
+}
+
+int svr_get_noise_estimate(svr_noise_estimate* out, float* tile_rmse_device)
+{
+    if (ensure_init()) return g.err_code;
+    if (!out) return fail(-4, "svr_get_noise_estimate: out is null");
+    memset(out, 0, sizeof *out);
+    out->rmse = out->tile_max = std::nanf("");
+    const Context::Noise& ns = g.ns;
+    if (!ns.have) return 0;
+    if (tile_rmse_device) {
+        // the estimate is the library's (the render it last followed): its map may be larger than the caller expects
+        const size_t bytes = sizeof(float) * ns.tiles_x * ns.tiles_y;
+        if (!device_range_ok(tile_rmse_device, bytes))
+            return fail(-4, "svr_get_noise_estimate: the tile map must be a device buffer of %u x %u floats (the estimate's tiles_x x tiles_y)",
+                        ns.tiles_x, ns.tiles_y);
+        HIP_TRY(hipMemcpyAsync(tile_rmse_device, ns.buf.rmse(), bytes, hipMemcpyDeviceToDevice, g.stream));
+    }
+    svr::NoiseTotals t;
+    HIP_TRY(hipMemcpyAsync(&t, ns.buf.totals(), sizeof t, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    noise_fill(*out, t, ns.est_m, ns.est_n, ns.tiles_x, ns.tiles_y);
+    return 0;
+}
+
+int svr_estimate_noise(const void* hdr_m, uint32_t m, const void* hdr_n, uint32_t n, uint32_t w, uint32_t h, float* tile_rmse_device,
+                       svr_noise_estimate* out)
+{
+    if (ensure_init()) return g.err_code;
+    if (!hdr_m || !hdr_n || !out) return fail(-4, "svr_estimate_noise: null argument");
+    if (m == 0 || m >= n) return fail(-6, "svr_estimate_noise: the frame counts must satisfy 0 < m < n (got m = %u, n = %u)", m, n);
+    if (w == 0 || h == 0 || (size_t)3 * w * h >= ((size_t)1 << 32)) return fail(-4, "svr_estimate_noise: bad frame size %u x %u", w, h);
+    if (!g.have_cam) return fail(-4, "svr_estimate_noise before setup_camera (the exposure comes from the camera)");
+    const size_t bytes = sizeof(float) * 3 * (size_t)w * h;
+    const uint32_t tx = (w + svr::NOISE_TILE - 1u) / svr::NOISE_TILE, ty = (h + svr::NOISE_TILE - 1u) / svr::NOISE_TILE;
+    if (!device_range_ok(hdr_m, bytes) || !device_range_ok(hdr_n, bytes))
+        return fail(-4, "svr_estimate_noise: the accumulators must be device buffers of %u x %u x 3 floats", w, h);
+    if (tile_rmse_device && !device_range_ok(tile_rmse_device, sizeof(float) * tx * ty))
+        return fail(-4, "svr_estimate_noise: the tile map must be a device buffer of %u x %u floats", tx, ty);
+    bool ok = true;
+    if (ensure_noise_buf(g.nb_call, (size_t)tx * ty, false, ok)) return g.err_code;
+    svr::DevWork full;
+    fill_work_full(full, w, h);
+    const svr::NoiseArgs a = noise_args(w, h, full, m, n, g.cam.exposure);
+    HIP_TRY(svr::launch_noise((float*)const_cast<void*>(hdr_m), (const float*)hdr_n, false, a, tile_rmse_device ? tile_rmse_device : g.nb_call.rmse(),
+                              g.nb_call.sse(), g.nb_call.cnt(), g.nb_call.totals(), g.stream));
+    svr::NoiseTotals t;
+    HIP_TRY(hipMemcpyAsync(&t, g.nb_call.totals(), sizeof t, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    noise_fill(*out, t, m, n, tx, ty);
+    return 0;
+}
+
+int svr_render_pathtracer_until(void* img, svr_render_params* rp, float target_rmse, float target_tile_rmse, uint32_t max_frames,
+                                uint32_t* frames_done)
+{
+    if (ensure_init()) return g.err_code;
+    if (!img || !rp) return fail(-4, "svr_render_pathtracer_until: null argument");
+    if (!(target_rmse >= 0.f) || !(target_tile_rmse >= 0.f))
+        return fail(-6, "svr_render_pathtracer_until: the targets must be >= 0 (got %g, %g)", (double)target_rmse, (double)target_tile_rmse);
+    if (max_frames == 0) return fail(-6, "svr_render_pathtracer_until: max_frames must be > 0");
+    if ((uint64_t)rp->frameNo + max_frames > 0xffffffffull) return fail(-6, "svr_render_pathtracer_until: frameNo + max_frames exceeds 2^32 - 1");
+    if (frames_done) *frames_done = 0;
+    const uint32_t f0 = rp->frameNo;
+    const bool check = target_rmse > 0.f || target_tile_rmse > 0.f;
+    const int opt = g.opt_noise_estimate;
+    g.opt_noise_estimate = 1;                    // the estimator for the call's own duration
+    uint32_t done = 0;
+    int rc = 0;
+    while (done < max_frames) {
+        svr_render_params cur = *rp;
+        cur.frameNo = f0 + done;
+        // the next checkpoint of the state rules: the snapshot (n >= 4) of a new render, else n = 2m
+        const bool cont = noise_continues(&cur, g.render_calls + 1);
+        uint64_t next = (uint64_t)f0 + max_frames;
+        if (check && !(cont && g.ns.unavailable)) {
+            if (cont && g.ns.m > 0) next = 2ull * g.ns.m;
+            else next = cur.frameNo + 1u > 4u ? cur.frameNo + 1u : 4u;
+        }
+        const uint32_t chunk = (uint32_t)std::min<uint64_t>(next - cur.frameNo, max_frames - done);
+        if ((rc = render_frames(img, &cur, chunk, true)) != 0) break;
+        done += chunk;
+        if (!check || !g.ns.have || g.ns.est_n != f0 + done) continue;
+        svr_noise_estimate e;
+        if ((rc = svr_get_noise_estimate(&e, nullptr)) != 0) break;
+        if ((target_rmse == 0.f || e.rmse <= target_rmse) && (target_tile_rmse == 0.f || e.tile_max <= target_tile_rmse)) break;
+    }
+    g.opt_noise_estimate = opt;
+    rp->frameNo = f0 + done;
+    if (frames_done) *frames_done = done;
+    return rc;
+}
+
 // ---------------- denoised preview ----------------
 int svr_denoise_params_default(svr_denoise_params* p)
 {
@@ -1758,6 +2020,9 @@ int svr_set_option(int key, int value)
     case SVR_OPT_DENOISE_PREVIEW:
         if (value < 0) return fail(-6, "SVR_OPT_DENOISE_PREVIEW: bad value %d (0 = off, N > 0 = frames)", value);
         g.opt_denoise_preview = value; return 0;
+    case SVR_OPT_NOISE_ESTIMATE:
+        if (value != 0 && value != 1) return fail(-6, "SVR_OPT_NOISE_ESTIMATE: bad value %d (0 off, 1 on)", value);
+        g.opt_noise_estimate = value; return 0;
     case SVR_OPT_BLOCKS_PER_CU:
         if (value < 0 || value > 8) return fail(-6, "SVR_OPT_BLOCKS_PER_CU: bad value %d", value);
         g.opt_blocks_per_cu = value; return 0;
@@ -1841,6 +2106,7 @@ int svr_get_option(int key)
     case SVR_OPT_TIMING: return g.opt_timing;
     case SVR_OPT_SKIP_TONEMAP: return g.opt_skip_tonemap;
     case SVR_OPT_DENOISE_PREVIEW: return g.opt_denoise_preview;
+    case SVR_OPT_NOISE_ESTIMATE: return g.opt_noise_estimate;
     case SVR_OPT_BLOCKS_PER_CU: return g.opt_blocks_per_cu;
     case SVR_OPT_PIPELINE: return g.opt_pipeline;
     case SVR_OPT_EMPTY_SKIP: return g.opt_empty_skip;

@@ -264,6 +264,22 @@ class Device:
     def guide_builds(self) -> int:
         return int(self.lib.svr_guide_builds())
 
+    # ---- noise estimate (SVR_OPT_NOISE_ESTIMATE, svr_estimate_noise) ----
+    def estimate_noise(self, hdr_m_ptr: int, m: int, hdr_n_ptr: int, n: int, width: int, height: int,
+                       tile_ptr: Optional[int] = None) -> abi.NoiseEstimate:
+        """svr_estimate_noise: the predicted tone-mapped error of the whole width x height accumulator A(n) at hdr_n_ptr, from A(m) at
+        hdr_m_ptr (device pointers, 0 < m < n).  tile_ptr (device, ceil(W/16) x ceil(H/16) floats) receives the tile map if given."""
+        est = abi.NoiseEstimate()
+        self.check(self.lib.svr_estimate_noise(C.c_void_p(hdr_m_ptr), int(m), C.c_void_p(hdr_n_ptr), int(n), int(width), int(height),
+                                               C.c_void_p(tile_ptr) if tile_ptr else None, C.byref(est)))
+        return est
+
+    def noise_estimate(self, tile_ptr: Optional[int] = None) -> abi.NoiseEstimate:
+        """svr_get_noise_estimate: the latest estimate of the render being followed (frames == 0: none yet)."""
+        est = abi.NoiseEstimate()
+        self.check(self.lib.svr_get_noise_estimate(C.byref(est), C.c_void_p(tile_ptr) if tile_ptr else None))
+        return est
+
 
 class Canvas:
     """Headless replay of the reference's Qt `Canvas` render protocol (gui/canvas.{h,cpp}).
@@ -490,6 +506,42 @@ class Canvas:
         if params is not None:
             self.dev.set_denoise_params(params)
         self.dev.set_option(abi.OPT_DENOISE_PREVIEW, int(frames))
+
+    # ---- extension: noise estimate and render-until-converged ----
+    def SetNoiseEstimate(self, on: bool):
+        """SVR_OPT_NOISE_ESTIMATE: follow the render and estimate its remaining noise at 8, 16, 32 ... frames (read with noise_estimate)."""
+        self.dev.set_option(abi.OPT_NOISE_ESTIMATE, 1 if on else 0)
+
+    def noise_estimate(self, tiles: bool = False):
+        """The latest estimate of this canvas's render (abi.NoiseEstimate; frames == 0: none yet); tiles=True: (estimate, (tiles_y, tiles_x)
+        float32 tile RMSE map).  The library keeps one estimate per process, of the render it last followed: an estimate whose tile grid is
+        not this canvas's belongs to another canvas and reads as none."""
+        tx, ty = (self.W + 15) // 16, (self.H + 15) // 16
+        est = self.dev.noise_estimate()
+        if est.frames and (est.tiles_x, est.tiles_y) != (tx, ty):
+            est = abi.NoiseEstimate()
+        if not tiles:
+            return est
+        if not est.frames:
+            return est, np.full((ty, tx), np.nan, np.float32)
+        buf = self.dev.malloc(tx * ty * 4)
+        try:
+            est = self.dev.noise_estimate(buf)          # (the same estimate: nothing rendered in between)
+            return est, self.dev.to_host(buf, (ty, tx), np.float32)
+        finally:
+            self.dev.free(buf)
+
+    def paint_until(self, target: float, tile_target: float = 0.0, max_frames: int = 4096, sync: bool = False) -> int:
+        """Extension: render until the predicted image RMSE is <= target (and the largest tile RMSE <= tile_target; 0 = unchecked) or
+        max_frames frames were traced (svr_render_pathtracer_until).  Advances renderParams.frameNo like paint_frames; returns the frames
+        traced."""
+        done = C.c_uint32(0)
+        rc = self.lib.svr_render_pathtracer_until(C.c_void_p(self.img), C.byref(self.renderParams), C.c_float(target), C.c_float(tile_target),
+                                                  int(max_frames), C.byref(done))
+        self.dev.check(rc)
+        if sync:
+            self.dev.synchronize()
+        return int(done.value)
 
     def read_guides(self) -> np.ndarray:
         """The guide buffer of the current scene (svr_render_guides): (H, W, 8) float32 = N.xyz, D, A.rgb, O."""
