@@ -1,9 +1,9 @@
 // render_mhd.cpp -- the reference application's start-up sequence (main.cpp / gui/mainwindow.cpp:22-62, 229-238)
 // without the GUI: load a MetaImage volume, the GUI-default (or a saved .tf) transfer function, one area light, an
 // optional .hdr environment map; render N progressive frames (or, with -noise T, until the predicted RMSE of the tone-mapped
-// image is <= T, at most N frames); write the image as TGA.
+// image is <= T, at most N frames; with -adaptive T, 16 x 16 tiles stop once their predicted RMSE is <= T); write the image as TGA.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -14,11 +14,12 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
     float noiseTarget = 0.f;                                        // 0: render exactly -frames frames
+    float adaptiveTarget = 0.f;                                     // > 0: adaptive sampling, tiles stop at this predicted RMSE
     bool raycast = false;
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
@@ -32,6 +33,11 @@ int main(int argc, char** argv)
             char* end = nullptr;
             noiseTarget = strtof(argv[++i], &end);
             if (end == argv[i] || *end != '\0' || !(noiseTarget > 0.f)) { fprintf(stderr, "-noise needs a target RMSE > 0 (got %s)\n", argv[i]); return 2; }
+        }
+        else if (!strcmp(argv[i], "-adaptive") && i + 1 < argc) {                                       // adaptive sampling
+            char* end = nullptr;
+            adaptiveTarget = strtof(argv[++i], &end);
+            if (end == argv[i] || *end != '\0' || !(adaptiveTarget > 0.f)) { fprintf(stderr, "-adaptive needs a tile target RMSE > 0 (got %s)\n", argv[i]); return 2; }
         }
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -77,7 +83,16 @@ int main(int argc, char** argv)
         canvas.SetRenderMode(raycast ? RENDER_MODE_RAYCASTING : RENDER_MODE_PATHTRACER);
         canvas.SetDenoisePreview(denoisePreview);
 
-        if (noiseTarget > 0.f && !raycast) {
+        if (adaptiveTarget > 0.f && !raycast) {
+            const auto t0 = std::chrono::steady_clock::now();
+            svr_adaptive_result r = {};
+            const int rc = canvas.PaintAdaptive(adaptiveTarget, 0u, frames > 0 ? (uint32_t)frames : 1u, &r);
+            svr_device_synchronize();
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (rc != 0 || svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            printf("adaptive target %g: %u..%u frames per tile in %.1f ms, %llu samples, %u of %u x %u tiles still active; rmse %.5f, largest tile %.5f\n",
+                   adaptiveTarget, r.frames_min, r.frames_max, ms, (unsigned long long)r.pixel_frames, r.tiles_active, r.tiles_x, r.tiles_y, r.rmse, r.tile_max);
+        } else if (noiseTarget > 0.f && !raycast) {
             const auto t0 = std::chrono::steady_clock::now();
             const uint32_t used = canvas.RenderUntil(noiseTarget, 0.f, frames > 0 ? (uint32_t)frames : 1u);
             svr_device_synchronize();

@@ -330,6 +330,19 @@ public:
         return done;
     }
 
+    // extension: adaptive sampling (svr_render_pathtracer_adaptive): render on, freezing each 16 x 16 tile once its predicted RMSE was <=
+    // targetTileRmse at two consecutive estimates (and it holds >= minFrames frames), until no tile is active or after maxFrames frames.
+    // frameNo advances to the most frames a tile holds; the frozen tiles hold fewer, so ReStartRender before painting on.  Returns the
+    // call's status (0 = ok); *result (may be null) gets svr_adaptive_result
+    int PaintAdaptive(float targetTileRmse, uint32_t minFrames, uint32_t maxFrames, svr_adaptive_result* result = nullptr)
+    {
+        if (!ready || renderMode != RENDER_MODE_PATHTRACER) return -4;
+        svr_adaptive_result r = {};
+        const int rc = svr_render_pathtracer_adaptive(img, &renderParams, targetTileRmse, minFrames, maxFrames, &r);
+        if (result) *result = r;
+        return rc;
+    }
+
     bool SaveImage(const std::string& filename)
     {
         std::vector<uint8_t> host((size_t)WIDTH * HEIGHT * 4);

@@ -434,6 +434,36 @@ int svr_estimate_noise(const void* hdr_m, uint32_t m, const void* hdr_n, uint32_
 int svr_render_pathtracer_until(void* img, svr_render_params* renderParams, float target_rmse, float target_tile_rmse, uint32_t max_frames,
                                 uint32_t* frames_done);
 
+/* ---- adaptive sampling: 16 x 16 tiles stop being traced once their predicted noise meets a target ----
+ * The accumulator holds a uniform render of f0 = renderParams->frameNo frames (0: a fresh render).  The call renders like
+ * svr_render_pathtracer_until -- the snapshot at n = max(f0 + 1, 4) frames, then estimates at n = 2m -- but only the tiles still active:
+ * a tile freezes at an estimate when n >= min_frames and its tile RMSE was <= target_tile_rmse at this estimate and at the one before (a tile
+ * without a counted pixel counts as below the target), so the earliest freeze is at 16 frames of a fresh render.  A frozen tile is never
+ * traced or written again and keeps its estimate; a tile still active at the end has its last estimate scaled by sqrt(n_est / n_final).
+ * The call ends when no tile is active or after max_frames frames.  Every pixel then equals the uniform render of its tile's frame count, bit
+ * for bit.  renderParams->frameNo advances by frames_max - f0; img holds the tone map of the final accumulator (SVR_OPT_SKIP_TONEMAP,
+ * SVR_OPT_DENOISE_PREVIEW as for any call).  The noise estimate is left with no render followed and no estimate: the next render call starts a
+ * new render.  Continuing with render_pathtracer from renderParams->frameNo MIS-WEIGHTS the frozen tiles (they hold fewer frames): restart
+ * at frame 0 instead.  Whole frame, one process: under a row shard or a render window, and with SVR_OPT_KERNEL 1, 3 or 4, the call fails
+ * with -6 and changes nothing; so do a target that is not > 0 and finite, max_frames == 0 and f0 + max_frames >= 2^32.  Frames are never
+ * traced ahead for the call. */
+typedef struct svr_adaptive_result {
+    uint32_t frames_max, frames_min;   /* most / fewest frames a tile's pixels hold at the end (counting from 0, i.e. including f0) */
+    uint32_t tiles_x, tiles_y;         /* ceil(W / 16), ceil(H / 16): the tile maps, row-major */
+    uint32_t tiles_active;             /* tiles not frozen when the call ended (max_frames reached) */
+    uint32_t checkpoints;              /* estimates made */
+    uint64_t pixel_frames;             /* samples traced by this call: sum over tiles of pixels(t) * (frames_t - f0) */
+    uint64_t pixels, nonfinite;        /* as svr_noise_estimate, over the final accumulator */
+    double sse;                        /* sum over tiles of the tile's e^2 sum, each scaled to the tile's final frame count */
+    float rmse, tile_max;              /* sqrt(sse / pixels); largest final tile RMSE (NaN if there is none) */
+} svr_adaptive_result;
+int svr_render_pathtracer_adaptive(void* img, svr_render_params* renderParams, float target_tile_rmse, uint32_t min_frames, uint32_t max_frames,
+                                   svr_adaptive_result* out);
+/* per-tile maps of the last adaptive call of this process: its frame count and final tile RMSE (NaN: no counted pixel).  Either pointer may be
+ * NULL; otherwise a device allocation of tiles_x * tiles_y elements.  An error before any adaptive call or if a buffer is too small.
+ * Synchronises the library's stream */
+int svr_get_adaptive_tiles(uint32_t* tile_frames_device, float* tile_rmse_device);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

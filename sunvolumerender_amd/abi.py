@@ -150,6 +150,29 @@ class NoiseEstimate(C.Structure):  # svr_noise_estimate
 svr_noise_estimate = NoiseEstimate
 
 
+class AdaptiveResult(C.Structure):  # svr_adaptive_result
+    _fields_ = [
+        ("frames_max", C.c_uint32),
+        ("frames_min", C.c_uint32),
+        ("tiles_x", C.c_uint32),
+        ("tiles_y", C.c_uint32),
+        ("tiles_active", C.c_uint32),
+        ("checkpoints", C.c_uint32),
+        ("pixel_frames", C.c_uint64),
+        ("pixels", C.c_uint64),
+        ("nonfinite", C.c_uint64),
+        ("sse", C.c_double),
+        ("rmse", C.c_float),
+        ("tile_max", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+svr_adaptive_result = AdaptiveResult
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -163,6 +186,7 @@ EXPECTED_SIZES = {
     Counters: 96,
     DenoiseParams: 28,
     NoiseEstimate: 48,
+    AdaptiveResult: 64,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -276,6 +300,8 @@ PROTOTYPES = {
     "svr_get_noise_estimate": (C.c_int, [_P(NoiseEstimate), C.c_void_p]),
     "svr_estimate_noise": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _P(NoiseEstimate)]),
     "svr_render_pathtracer_until": (C.c_int, [C.c_void_p, _P(RenderParams), C.c_float, C.c_float, C.c_uint32, _P(C.c_uint32)]),
+    "svr_render_pathtracer_adaptive": (C.c_int, [C.c_void_p, _P(RenderParams), C.c_float, C.c_uint32, C.c_uint32, _P(AdaptiveResult)]),
+    "svr_get_adaptive_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

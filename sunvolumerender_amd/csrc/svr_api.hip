@@ -40,8 +40,17 @@ static_assert(sizeof(svr_denoise_params) == 28 && offsetof(svr_denoise_params, s
 static_assert(sizeof(svr_noise_estimate) == 48 && offsetof(svr_noise_estimate, tiles_x) == 16 && offsetof(svr_noise_estimate, pixels) == 24 &&
               offsetof(svr_noise_estimate, sse) == 40, "svr_noise_estimate layout");
 static_assert(sizeof(svr::NoiseTotals) == 32, "noise totals");
+static_assert(sizeof(svr_adaptive_result) == 64 && offsetof(svr_adaptive_result, pixel_frames) == 24 && offsetof(svr_adaptive_result, sse) == 48 &&
+              offsetof(svr_adaptive_result, tile_max) == 60, "svr_adaptive_result layout");
 
 namespace svr_fast { hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st); }   // svr_trace_tile_fast.hip
+// the trace kernels of adaptive launches (DevWork.tile_list set): svr_trace_{tile,lm,split,env}_list.hip
+namespace svr_list {
+hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
+hipError_t launch_trace_lm_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
+hipError_t launch_trace_split_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
+hipError_t launch_trace_env_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
+}
 
 namespace {
 
@@ -197,6 +206,18 @@ struct Context {
         NoiseBuf buf;
     } ns;
     NoiseBuf nb_call;                   // svr_estimate_noise
+    // adaptive sampling (svr_render_pathtracer_adaptive): the device tile list + active map of its launches (one allocation: ad_cap uint32 list
+    // entries, then ad_cap bytes), whether fill_work hands them to the launches, and the per-tile results of the last call
+    uint32_t* d_ad_list = nullptr;
+    uint8_t* d_ad_map = nullptr;
+    size_t ad_cap = 0;
+    uint32_t ad_len = 0;
+    bool ad_list_on = false;            // launches trace the listed tiles only
+    bool ad_call = false;               // inside an adaptive call: no frame-ahead tracing
+    bool ad_have = false;
+    uint32_t ad_tx = 0, ad_ty = 0;
+    std::vector<uint32_t> ad_frames;
+    std::vector<float> ad_rmse;
     // ring of HIP event pairs around the path-tracing kernel (SVR_OPT_TIMING); drained lazily so the
     // timed launches never synchronise with the host
     static constexpr int EV_RING = 512;
@@ -483,6 +504,13 @@ int fill_work(svr::DevWork& w, uint32_t W, uint32_t H)
         w.n_rows = w.y1 - w.y0;
     }
     w.n_items = w.n_rows * (w.x1 - w.x0);
+    if (g.ad_list_on) {
+        // adaptive launch (whole frame, one process): the listed tiles only; the ticket arithmetic of row_order assumes the full grid
+        w.tile_list = g.d_ad_list;
+        w.tile_count = g.ad_len;
+        w.tile_active = g.d_ad_map;
+        w.row_order = 0;
+    }
     return 0;
 }
 
@@ -788,7 +816,8 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
         if (ensure_record_queues((uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / 16u, g.opt_queue == 1 && !local_majorant, available)) return g.err_code;
         use_queue = use_queue && available;
     }
-    const bool frame_ahead_possible = nframes == 1 && g.opt_frame_ahead && g.opt_pipeline && !g.opt_count && !g.opt_debug_stop && cfg.kernel == svr::KERNEL_TILE;
+    const bool frame_ahead_possible = nframes == 1 && g.opt_frame_ahead && g.opt_pipeline && !g.opt_count && !g.opt_debug_stop && cfg.kernel == svr::KERNEL_TILE &&
+                                      !g.ad_call;
     // Deeper paths, bit-exact, as TWO kernels (svr_trace_split.hip: front half -> chunks of records -> lane machine; the launch's frames go through
     // the scratch slots and k_resolve): where the fused queue kernel would run and its primary walks are not pooled, the image fits a 26-bit pixel
     // index, and the device has room for the worst-case record pool of a launch (<= 24 GB; else the fused kernel)
@@ -806,7 +835,9 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
         uint32_t fl2 = 0;
         while ((1u << fl2) < n_max) ++fl2;
         const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
-        const uint64_t n_tasks = (uint64_t)((wq.x1 - wq.x0 + (1u << tw2) - 1u) >> tw2) * ((wq.n_rows + (1u << th2) - 1u) >> th2);
+        uint64_t n_tasks = (uint64_t)((wq.x1 - wq.x0 + (1u << tw2) - 1u) >> tw2) * ((wq.n_rows + (1u << th2) - 1u) >> th2);
+        // (adaptive launches: every wave tile of the listed 16 x 16 tiles, those past the image edge included)
+        if (wq.tile_list != nullptr) n_tasks = std::max<uint64_t>(n_tasks, (uint64_t)wq.tile_count << ((4u - tw2) + (4u - th2)));
         const uint64_t chunks = svr::split_chunks_worst_case(n_tasks * 64u, (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u);
         if (chunks * svr::SPLIT_CHUNK_WORDS * sizeof(uint32_t) <= (24ull << 30) && chunks < (1ull << 31)) {
             bool available = true;
@@ -816,6 +847,7 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
         if (use_split && ensure_slots(s.imageW, s.imageH, n_max < (uint32_t)Context::GROUP ? (uint32_t)Context::GROUP : n_max)) return g.err_code;
     }
     auto launch_tile = [&](const svr::DevWork& w, hipStream_t st) -> hipError_t {
+        if (w.tile_list != nullptr) return local_majorant ? svr_list::launch_trace_lm_raw(&s, &w, &cfg, st) : svr_list::launch_trace_tile_raw(&s, &w, &cfg, st);
         if (local_majorant) return svr::launch_trace_lm(s, w, cfg, st);
         return g.opt_fast_math ? svr_fast::launch_trace_tile_raw(&s, &w, &cfg, st) : svr::launch_trace_tile(s, w, cfg, st);
     };
@@ -891,7 +923,7 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
         }
         if (cfg.kernel == svr::KERNEL_WAVEFRONT)
             HIP_TRY(svr::launch_wavefront(s, w, cfg, set.planes, set.wf_counts, (uint32_t)g.queue_capacity, ts));
-        else if (cfg.kernel == svr::KERNEL_ENV_NEE) HIP_TRY(svr::launch_trace_env(s, w, cfg, ts));
+        else if (cfg.kernel == svr::KERNEL_ENV_NEE) HIP_TRY(w.tile_list != nullptr ? svr_list::launch_trace_env_raw(&s, &w, &cfg, ts) : svr::launch_trace_env(s, w, cfg, ts));
         else if (cfg.kernel == svr::KERNEL_TILE) {
             if (w.queue != nullptr && g.queue_used) HIP_TRY(hipStreamWaitEvent(ts, g.queue_done, 0));
             HIP_TRY(launch_tile(w, ts));
@@ -949,7 +981,7 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
             slot = g.ev_head;
             HIP_TRY(hipEventRecord(g.ev0[slot], g.stream));
         }
-        HIP_TRY(svr::launch_trace_split(s, w, cfg, g.stream));
+        HIP_TRY(w.tile_list != nullptr ? svr_list::launch_trace_split_raw(&s, &w, &cfg, g.stream) : svr::launch_trace_split(s, w, cfg, g.stream));
         if (g.opt_timing) {
             HIP_TRY(hipEventRecord(g.ev1[slot], g.stream));
             g.ev_head = (g.ev_head + 1) % Context::EV_RING;
@@ -1337,6 +1369,7 @@ void svr_shutdown(void)
     if (g.ns.d_snap) hipFree(g.ns.d_snap);
     if (g.ns.buf.mem) hipFree(g.ns.buf.mem);
     if (g.nb_call.mem) hipFree(g.nb_call.mem);
+    if (g.d_ad_list) hipFree(g.d_ad_list);
     if (g_stage) { hipFree(g_stage); g_stage = nullptr; g_stage_floats = 0; }
     for (int i = 0; i < Context::EV_RING; ++i) {
         if (g.ev0[i]) hipEventDestroy(g.ev0[i]);
@@ -1795,6 +1828,215 @@ int svr_render_pathtracer_until(void* img, svr_render_params* rp, float target_r
     rp->frameNo = f0 + done;
     if (frames_done) *frames_done = done;
     return rc;
+}
+
+// ---------------- adaptive sampling ----------------
+namespace {
+
+// HIP_TRY for a loop that must leave through its end: 0, or the error code with the message set
+int hip_check(hipError_t e)
+{
+    if (e == hipSuccess) return 0;
+    return fail((int)e, "HIP error in svr_render_pathtracer_adaptive: code=%d(%s)", (int)e, hipGetErrorName(e));
+}
+
+// the active tiles, packed tx | ty << 16, in the centre-out tile-row order of the full grid (svr_tile_tasks.hpp task_decode: rows c, c + 1,
+// c - 1, c + 2 ...), and their map -> device.  The library's streams are drained first: no launch still reads the previous list.
+int adaptive_upload(const std::vector<uint8_t>& active, uint32_t tiles_x, uint32_t tiles_y)
+{
+    std::vector<uint32_t> list;
+    list.reserve(active.size());
+    const uint32_t c = tiles_y >> 1;
+    for (uint32_t rr = 0; rr < 2u * tiles_y + 1u; ++rr) {
+        const uint32_t off = (rr + 1u) >> 1;
+        if ((rr & 1u) ? off > c : c + off >= tiles_y) continue;
+        const uint32_t ty = (rr & 1u) ? c - off : c + off;
+        for (uint32_t tx = 0; tx < tiles_x; ++tx)
+            if (active[(size_t)ty * tiles_x + tx]) list.push_back(tx | ty << 16);
+    }
+    for (auto& st : g.sets) if (st.stream) HIP_TRY(hipStreamSynchronize(st.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    if (!list.empty()) HIP_TRY(hipMemcpyAsync(g.d_ad_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemcpyAsync(g.d_ad_map, active.data(), active.size(), hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    g.ad_len = (uint32_t)list.size();
+    return 0;
+}
+
+} // namespace
+
+int svr_render_pathtracer_adaptive(void* img, svr_render_params* rp, float target_tile_rmse, uint32_t min_frames, uint32_t max_frames,
+                                   svr_adaptive_result* out)
+{
+    if (ensure_init()) return g.err_code;
+    if (!img || !rp || !out) return fail(-4, "svr_render_pathtracer_adaptive: null argument");
+    if (!(target_tile_rmse > 0.f) || !std::isfinite(target_tile_rmse))
+        return fail(-6, "svr_render_pathtracer_adaptive: target_tile_rmse must be > 0 and finite (got %g)", (double)target_tile_rmse);
+    if (max_frames == 0) return fail(-6, "svr_render_pathtracer_adaptive: max_frames must be > 0");
+    if ((uint64_t)rp->frameNo + max_frames > 0xffffffffull) return fail(-6, "svr_render_pathtracer_adaptive: frameNo + max_frames exceeds 2^32 - 1");
+    if (!g.have_vol || !g.have_tf || !g.have_cam) return fail(-4, "svr_render_pathtracer_adaptive before setup_volume/setup_transferfunction/setup_camera");
+    if (!rp->hdrBuffer) return fail(-4, "svr_render_pathtracer_adaptive: renderParams.hdrBuffer is null (call SetupHDRBuffer)");
+    const uint32_t W = g.cam.imageW, H = g.cam.imageH;
+    if (g.world > 1 || partial_frame(W, H))
+        return fail(-6, "svr_render_pathtracer_adaptive: the whole frame on one process only (a row shard or a render window is set)");
+    if (g.opt_kernel == svr::KERNEL_PIXEL || g.opt_kernel == svr::KERNEL_ULOOP || g.opt_kernel == svr::KERNEL_WAVEFRONT)
+        return fail(-6, "svr_render_pathtracer_adaptive: SVR_OPT_KERNEL %d does not trace tile lists (0 / 2 do)", g.opt_kernel);
+    if (g.opt_fast_math) return fail(-6, "svr_render_pathtracer_adaptive: the fast-math build (SVR_OPT_FAST_MATH) does not trace tile lists");
+    if ((size_t)3 * W * H >= ((size_t)1 << 32)) return fail(-3, "image too large");
+
+    const uint32_t tiles_x = (W + svr::NOISE_TILE - 1u) / svr::NOISE_TILE, tiles_y = (H + svr::NOISE_TILE - 1u) / svr::NOISE_TILE;
+    const size_t nt = (size_t)tiles_x * tiles_y, px = (size_t)W * H;
+    // memory: the tile list + map, and the estimator's snapshot and tile buffers (the call leaves the estimator without a render anyway)
+    if (g.ad_cap < nt) {
+        if (g.d_ad_list) HIP_TRY(hipFree(g.d_ad_list));
+        g.d_ad_list = nullptr; g.d_ad_map = nullptr; g.ad_cap = 0;
+        HIP_TRY(hipMalloc((void**)&g.d_ad_list, nt * (sizeof(uint32_t) + 1u)));
+        g.d_ad_map = (uint8_t*)(g.d_ad_list + nt);
+        g.ad_cap = nt;
+    }
+    Context::Noise& ns = g.ns;
+    ns.tracking = false; ns.have = false; ns.m = 0;
+    ++g.render_calls;                            // (the next render call starts a new render by the estimator's state rules)
+    if (ns.snap_px < px || !ns.d_snap) {
+        if (ns.d_snap) HIP_TRY(hipFree(ns.d_snap));
+        ns.d_snap = nullptr; ns.snap_px = 0;
+        HIP_TRY(hipMalloc((void**)&ns.d_snap, px * 3 * sizeof(float)));
+        ns.snap_px = px;
+    }
+    bool ok = true;
+    if (ensure_noise_buf(ns.buf, nt, false, ok)) return g.err_code;
+
+    const uint32_t f0 = rp->frameNo;
+    const uint64_t end = (uint64_t)f0 + max_frames;
+    const uint32_t snap_at = f0 + 1u > 4u ? f0 + 1u : 4u;
+    std::vector<uint32_t> frames(nt, f0), est_n(nt, 0u);
+    std::vector<uint8_t> active(nt, 1u), below_prev(nt, 0u);
+    std::vector<float> trmse(nt, std::nanf(""));
+    size_t n_active = nt;
+    uint32_t n = f0, m = 0, checkpoints = 0;
+    bool list_mode = false;
+    int rc = 0;
+    g.ad_call = true;
+    for (;;) {
+        uint64_t next = m == 0 ? (uint64_t)snap_at : 2ull * m;
+        const bool checkpoint = next <= end;
+        if (!checkpoint) next = end;
+        // frames n .. next - 1 of the active tiles (all of them until the first freeze: the ordinary launches)
+        svr_render_params cur = *rp;
+        cur.frameNo = n;
+        g.ad_list_on = list_mode;
+        rc = render_frames_traced(img, &cur, (uint32_t)(next - n), false);
+        g.ad_list_on = false;
+        if (rc) break;
+        n = (uint32_t)next;
+        for (size_t t = 0; t < nt; ++t) if (active[t]) frames[t] = n;
+        if (!checkpoint) break;
+        bool changed = false;
+        if (m == 0) {
+            if ((rc = hip_check(hipMemcpyAsync(ns.d_snap, rp->hdrBuffer, px * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream)))) break;
+        } else {
+            // the masked estimate of A(n) against A(m) + the snapshot, for the active tiles (the frozen ones keep theirs), then the freeze rule
+            svr::DevWork full;
+            fill_work_full(full, W, H);
+            const svr::NoiseArgs a = noise_args(W, H, full, m, n, g.cam.exposure);
+            if ((rc = hip_check(svr::launch_noise(ns.d_snap, (const float*)rp->hdrBuffer, true, a, ns.buf.rmse(), ns.buf.sse(), ns.buf.cnt(),
+                                                  ns.buf.totals(), g.stream, list_mode ? g.d_ad_map : nullptr)))) break;
+            std::vector<float> r(nt);
+            if ((rc = hip_check(hipMemcpyAsync(r.data(), ns.buf.rmse(), nt * sizeof(float), hipMemcpyDeviceToHost, g.stream)))) break;
+            if ((rc = hip_check(hipStreamSynchronize(g.stream)))) break;
+            ++checkpoints;
+            for (size_t t = 0; t < nt; ++t) {
+                if (!active[t]) continue;
+                trmse[t] = r[t];
+                est_n[t] = n;
+                const bool below = !(r[t] > target_tile_rmse);        // (NaN: a tile without a counted pixel counts as below)
+                if (n >= min_frames && below && below_prev[t]) { active[t] = 0u; --n_active; changed = true; }
+                below_prev[t] = below ? 1u : 0u;
+            }
+        }
+        m = n;
+        if (n_active == 0 || n >= end) break;
+        if (changed) {
+            if ((rc = adaptive_upload(active, tiles_x, tiles_y))) break;
+            list_mode = true;
+        }
+    }
+    g.ad_call = false;
+    if (rc) return rc;
+
+    // the result: frozen tiles keep the estimate they froze with, active ones scale their last one to the final frame count
+    svr_adaptive_result res;
+    memset(&res, 0, sizeof res);
+    res.tiles_x = tiles_x; res.tiles_y = tiles_y;
+    res.tiles_active = (uint32_t)n_active;
+    res.checkpoints = checkpoints;
+    res.frames_min = 0xffffffffu;
+    std::vector<double> sse(nt, 0.0);
+    std::vector<uint32_t> cnt(2 * nt, 0u);
+    if (checkpoints) {
+        HIP_TRY(hipMemcpyAsync(sse.data(), ns.buf.sse(), nt * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(cnt.data(), ns.buf.cnt(), 2 * nt * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    float tile_max = -1.f;
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            const size_t t = (size_t)ty * tiles_x + tx;
+            res.frames_max = std::max(res.frames_max, frames[t]);
+            res.frames_min = std::min(res.frames_min, frames[t]);
+            const uint64_t tp = (uint64_t)std::min(svr::NOISE_TILE, W - tx * svr::NOISE_TILE) * std::min(svr::NOISE_TILE, H - ty * svr::NOISE_TILE);
+            res.pixel_frames += tp * (frames[t] - f0);
+            if (est_n[t] == 0) { trmse[t] = std::nanf(""); continue; }
+            const double scale = (double)est_n[t] / (double)frames[t];
+            res.sse += sse[t] * scale;
+            res.pixels += cnt[2 * t];
+            res.nonfinite += cnt[2 * t + 1];
+            trmse[t] = cnt[2 * t] ? (float)((double)trmse[t] * std::sqrt(scale)) : std::nanf("");
+            if (cnt[2 * t]) tile_max = std::max(tile_max, trmse[t]);
+        }
+    res.rmse = res.pixels ? (float)std::sqrt(res.sse / (double)res.pixels) : std::nanf("");
+    res.tile_max = tile_max < 0.f ? std::nanf("") : tile_max;
+    g.ad_have = true;
+    g.ad_tx = tiles_x; g.ad_ty = tiles_y;
+    g.ad_frames = frames;
+    g.ad_rmse = trmse;
+
+    // the image: the tone map of the final accumulator (or the denoised preview while the render has at most SVR_OPT_DENOISE_PREVIEW frames)
+    if (!g.opt_skip_tonemap) {
+        svr::DevScene s;
+        if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
+        bool shown = false;
+        if (g.opt_denoise_preview > 0 && res.frames_max <= (uint32_t)g.opt_denoise_preview) {
+            bool dn_ok = true;
+            if (denoise_frame(img, nullptr, rp->hdrBuffer, W, H, g.dn, true, dn_ok)) return g.err_code;
+            shown = dn_ok;
+        }
+        if (!shown) {
+            svr::DevWork w;
+            fill_work_full(w, W, H);
+            w.hdr = (float*)rp->hdrBuffer;
+            w.img = (uint8_t*)img;
+            HIP_TRY(svr::launch_tonemap(s, w, g.stream));
+        }
+    }
+    rp->frameNo = res.frames_max;
+    *out = res;
+    return 0;
+}
+
+int svr_get_adaptive_tiles(uint32_t* tile_frames_device, float* tile_rmse_device)
+{
+    if (ensure_init()) return g.err_code;
+    if (!g.ad_have) return fail(-4, "svr_get_adaptive_tiles before any svr_render_pathtracer_adaptive call");
+    const size_t nt = (size_t)g.ad_tx * g.ad_ty;
+    if (tile_frames_device && !device_range_ok(tile_frames_device, nt * sizeof(uint32_t)))
+        return fail(-4, "svr_get_adaptive_tiles: the frame map must be a device buffer of %u x %u uint32", g.ad_tx, g.ad_ty);
+    if (tile_rmse_device && !device_range_ok(tile_rmse_device, nt * sizeof(float)))
+        return fail(-4, "svr_get_adaptive_tiles: the RMSE map must be a device buffer of %u x %u floats", g.ad_tx, g.ad_ty);
+    if (tile_frames_device) HIP_TRY(hipMemcpyAsync(tile_frames_device, g.ad_frames.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
+    if (tile_rmse_device) HIP_TRY(hipMemcpyAsync(tile_rmse_device, g.ad_rmse.data(), nt * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return 0;
 }
 
 // ---------------- denoised preview ----------------

@@ -431,6 +431,11 @@ __global__ __launch_bounds__(256) void k_resolve(const DevScene s, const DevWork
     uint32_t x = w.x0 + px, y = owned_row_to_y(w, r);
     size_t off = (size_t)y * s.imageW + x;
     float* h = w.hdr + 3 * off;
+    if (w.tile_active != nullptr && !w.tile_active[(y >> 4) * ((s.imageW + 15u) >> 4) + (x >> 4)]) {
+        // adaptive launch, a tile it does not trace: its slots hold nothing, its accumulator stays as it is (and is still tone-mapped)
+        if (w.img) reinterpret_cast<uint32_t*>(w.img)[off] = tonemap_pixel(V3(h[0], h[1], h[2]), s.exposure);
+        return;
+    }
     v3 acc = (w.frame0 == 0u) ? V3(0.f, 0.f, 0.f) : V3(h[0], h[1], h[2]);
     for (uint32_t f = 0; f < w.nframes; ++f) {
         const float* l = w.lbuf + (size_t)f * w.slot_stride + 3 * off;
@@ -575,7 +580,8 @@ hipError_t launch_resolve(const DevScene& s, const DevWork& w, hipStream_t st)
 {
     if (w.n_items == 0) return hipSuccess;
     const uint64_t n = (uint64_t)3 * s.imageW * s.imageH;
-    if (w.nframes == 1u && w.n_items == s.imageW * s.imageH && (n & 3u) == 0u && ((uintptr_t)w.hdr & 15u) == 0u && ((uintptr_t)w.lbuf & 15u) == 0u) {
+    // (adaptive launches take k_resolve, which leaves the pixels of untraced tiles alone: the same float operations per value)
+    if (w.nframes == 1u && w.tile_active == nullptr && w.n_items == s.imageW * s.imageH && (n & 3u) == 0u && ((uintptr_t)w.hdr & 15u) == 0u && ((uintptr_t)w.lbuf & 15u) == 0u) {
         const uint32_t n4 = (uint32_t)(n >> 2);
         hipLaunchKernelGGL(k_mean_flat, dim3((n4 + 255u) / 256u), dim3(256), 0, st, reinterpret_cast<float4*>(w.hdr), reinterpret_cast<const float4*>(w.lbuf), n4, w.frame0, w.nan_guard);
         if (w.img) hipLaunchKernelGGL(k_tonemap, dim3((w.n_items + 255u) / 256u), dim3(256), 0, st, s, w);

@@ -9,6 +9,8 @@
 //                 non-finite value are counted apart.  Writes the tile RMSE sqrt(sum e^2 / counted) (NaN for a tile without a counted
 //                 pixel), the tile's sum (double) and its two counts; optionally A(n) over A(m) in the same pass (the snapshot of the
 //                 library's state).  A block = 64 x 16 pixels = 4 tiles side by side: a wave reads 64 consecutive pixels of a row (768 B).
+//                 With a tile map (adaptive sampling: 1 = the tile is still traced) the other tiles are neither estimated nor snapshotted and
+//                 their tile arrays keep their values, so k_noise_total sums them with the rest.
 //  k_noise_total  one block: the sums over all tiles (double, fixed order: deterministic) and the largest tile RMSE.
 // Purely memory-bound: 24 B read + 12 B written per pixel (fused form).  The trace kernels and the accumulator are not touched.
 #include "svr_noise.hpp"
@@ -30,7 +32,8 @@ __device__ __forceinline__ bool fin(float v) { return __builtin_isfinite(v); }
 
 template <bool WRITE_REF>
 __global__ __launch_bounds__(256) void k_noise_tiles(float* __restrict__ ref, const float* __restrict__ hdr, const NoiseArgs a,
-                                                      float* __restrict__ tile_rmse, double* __restrict__ tile_sse, uint32_t* __restrict__ tile_cnt)
+                                                      float* __restrict__ tile_rmse, double* __restrict__ tile_sse, uint32_t* __restrict__ tile_cnt,
+                                                      const uint8_t* __restrict__ active)
 {
     __shared__ double s_sse[256];
     __shared__ uint32_t s_cnt[256], s_nf[256];
@@ -39,7 +42,8 @@ __global__ __launch_bounds__(256) void k_noise_tiles(float* __restrict__ ref, co
     const float k = -16.f * a.exposure;
     double sse = 0.0;
     uint32_t cnt = 0, nf = 0;
-    const bool col_owned = x < a.W && x >= a.x0 && x < a.x1;
+    bool col_owned = x < a.W && x >= a.x0 && x < a.x1;
+    if (active != nullptr && col_owned && !active[(size_t)blockIdx.y * a.tiles_x + x / NOISE_TILE]) col_owned = false;
 #pragma unroll
     for (uint32_t r = 0; r < NOISE_TILE / NB_ROWS; ++r) {
         const uint32_t y = blockIdx.y * NOISE_TILE + r * NB_ROWS + rg;
@@ -65,6 +69,7 @@ __global__ __launch_bounds__(256) void k_noise_tiles(float* __restrict__ ref, co
     const uint32_t t = threadIdx.x;
     const uint32_t tx = blockIdx.x * (NB_X / NOISE_TILE) + t;
     if (t >= NB_X / NOISE_TILE || tx >= a.tiles_x) return;
+    if (active != nullptr && !active[(size_t)blockIdx.y * a.tiles_x + tx]) return;
     double s = 0.0;
     uint32_t c = 0, f = 0;
     for (uint32_t g = 0; g < NB_ROWS; ++g)
@@ -122,11 +127,11 @@ __global__ __launch_bounds__(1024) void k_noise_total(const float* __restrict__ 
 } // namespace
 
 hipError_t launch_noise(float* ref, const float* hdr, bool write_ref, const NoiseArgs& a, float* tile_rmse, double* tile_sse,
-                        uint32_t* tile_cnt, NoiseTotals* totals, hipStream_t stream)
+                        uint32_t* tile_cnt, NoiseTotals* totals, hipStream_t stream, const uint8_t* active)
 {
     const dim3 grid((a.W + NB_X - 1u) / NB_X, a.tiles_y);
-    if (write_ref) hipLaunchKernelGGL(k_noise_tiles<true>, grid, dim3(256), 0, stream, ref, hdr, a, tile_rmse, tile_sse, tile_cnt);
-    else hipLaunchKernelGGL(k_noise_tiles<false>, grid, dim3(256), 0, stream, ref, hdr, a, tile_rmse, tile_sse, tile_cnt);
+    if (write_ref) hipLaunchKernelGGL(k_noise_tiles<true>, grid, dim3(256), 0, stream, ref, hdr, a, tile_rmse, tile_sse, tile_cnt, active);
+    else hipLaunchKernelGGL(k_noise_tiles<false>, grid, dim3(256), 0, stream, ref, hdr, a, tile_rmse, tile_sse, tile_cnt, active);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_noise_total, dim3(1), dim3(1024), 0, stream, tile_rmse, tile_sse, tile_cnt, a.tiles_x * a.tiles_y, totals);

@@ -27,8 +27,9 @@ struct NoiseTotals {
 
 // Per-tile buffers: tile_rmse (float), tile_sse (double) and tile_cnt (2 x uint32: counted, non-finite) of tiles_x * tiles_y tiles.
 // ref = A(m) (W x H packed float3); write_ref: A(n) is written over it in the same pass (each element is read, then overwritten, by the
-// same thread).  Both kernels run on `stream`: the tile pass, then one block that sums the tiles into *totals.
+// same thread).  Both kernels run on `stream`: the tile pass, then one block that sums the tiles into *totals.  active (adaptive sampling):
+// null = every tile, else one byte per tile (row-major): the tiles with 0 are skipped and keep their values in the tile arrays.
 hipError_t launch_noise(float* ref, const float* hdr, bool write_ref, const NoiseArgs& args, float* tile_rmse, double* tile_sse,
-                        uint32_t* tile_cnt, NoiseTotals* totals, hipStream_t stream);
+                        uint32_t* tile_cnt, NoiseTotals* totals, hipStream_t stream, const uint8_t* active = nullptr);
 
 } // namespace svr

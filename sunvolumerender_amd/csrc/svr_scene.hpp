@@ -122,6 +122,11 @@ struct DevWork {
     float* pend;                   // ... and the waves' pending-radiance rows, QUEUE_TASKS * 3 * 64 floats per wave
     uint32_t queue_blocks;         // blocks the queue memory is sized for
     uint32_t nan_guard;            // SVR_OPT_NAN_GUARD: the running mean skips non-finite samples (default 0 = the reference's behaviour)
+    // adaptive sampling (svr_render_pathtracer_adaptive; whole frame, one process): the launch traces only the listed 16 x 16 tiles of the image.
+    // Null / 0 outside adaptive launches (the full task grid, svr_tile_tasks.hpp)
+    const uint32_t* tile_list;     // active tiles, packed tx | ty << 16, in centre-out tile-row order
+    uint32_t tile_count;           // entries of tile_list
+    const uint8_t* tile_active;    // per 16 x 16 tile, row-major, ceil(W / 16) wide: 1 = traced by this launch (k_resolve leaves the others alone)
 };
 
 } // namespace svr

@@ -5,8 +5,31 @@
 
 namespace svr {
 
+// SVR_TILE_LIST = 1: the builds of adaptive launches (svr_render_pathtracer_adaptive; the *_list.hip sources compile the trace kernels a second
+// time, into namespace svr_list): the tasks run over DevWork.tile_list.  0 (the ordinary builds): the full grid, DevWork.tile_list is not read --
+// the remap costs registers in the persistent kernels, so it is not in their code at all
+#ifndef SVR_TILE_LIST
+#define SVR_TILE_LIST 0
+#endif
+
 // task index of the centre-out order -> tile row, tile column, frame group (see k_trace_tile)
-struct TaskShape { uint32_t tiles_x, tiles_y, fgroups, row_tasks, c_row, tw2, th2, P2, fl2, wv; };
+struct TaskShape {
+    uint32_t tiles_x, tiles_y, fgroups, row_tasks, c_row, tw2, th2, P2, fl2, wv, n_tasks;
+#if SVR_TILE_LIST
+    const uint32_t* list;
+#endif
+};
+
+// tasks of a launch: the wave tiles of the grid x frame groups, or (list builds with DevWork.tile_list set) the (16 >> tw2) x (16 >> th2)
+// wave tiles of every listed 16 x 16 tile x frame groups.  Host and device (the launchers size their grids with it)
+__host__ __device__ inline uint32_t launch_tasks(const DevWork& w, uint32_t tw2, uint32_t th2, uint32_t fgroups)
+{
+#if SVR_TILE_LIST
+    if (w.tile_list != nullptr) return (w.tile_count << ((4u - tw2) + (4u - th2))) * fgroups;
+#endif
+    return (((w.x1 - w.x0) + (1u << tw2) - 1u) >> tw2) * ((w.n_rows + (1u << th2) - 1u) >> th2) * fgroups;
+}
+
 SVR_DEV TaskShape task_shape(const DevWork& w)
 {
     TaskShape ts;
@@ -19,10 +42,29 @@ SVR_DEV TaskShape task_shape(const DevWork& w)
     ts.fgroups = (w.nframes + (1u << ts.fl2) - 1u) >> ts.fl2;
     ts.row_tasks = ts.tiles_x * ts.fgroups;                   // tasks of one tile row
     ts.c_row = ts.tiles_y >> 1;
+#if SVR_TILE_LIST
+    ts.list = w.tile_list;
+#endif
+    ts.n_tasks = launch_tasks(w, ts.tw2, ts.th2, ts.fgroups);
     return ts;
 }
 SVR_DEV void task_decode(const TaskShape& ts, uint32_t k, uint32_t& tx, uint32_t& ty, uint32_t& fg)
 {
+#if SVR_TILE_LIST
+    if (ts.list != nullptr) {
+        // adaptive launch (whole frame): task k = (listed 16 x 16 tile a, wave tile j inside it, frame group).  The wave tiles nest exactly in
+        // the 16 x 16 tiles, so tx, ty are coordinates of the ordinary grid; those past the image edge have no live lane
+        const uint32_t sx2 = 4u - ts.tw2, sy2 = 4u - ts.th2;
+        const uint32_t per = ts.fgroups << (sx2 + sy2);
+        const uint32_t a = k / per, in_t = k - a * per;
+        const uint32_t j = in_t / ts.fgroups;
+        fg = in_t - j * ts.fgroups;
+        const uint32_t p = ts.list[a];
+        tx = ((p & 0xffffu) << sx2) + (j & ((1u << sx2) - 1u));
+        ty = ((p >> 16) << sy2) + (j >> sx2);
+        return;
+    }
+#endif
     const uint32_t rr = k / ts.row_tasks, in_row = k - rr * ts.row_tasks;
     const uint32_t off = (rr + 1u) >> 1;
     ty = (rr & 1u) ? ts.c_row - off : ts.c_row + off;

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(ENV_THREADS, 4) void k_trace_env(const DevScene s, 
     const uint32_t lane = threadIdx.x & 63u;
     const TaskShape ts = task_shape(w);
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.tiles_x * ts.tiles_y * ts.fgroups;
+    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     Cnt c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (uint32_t si = 0; si < TICKET_SHARDS; ++si) {
@@ -261,7 +261,7 @@ static hipError_t launch_env_t(const DevScene& s, const DevWork& w, const Launch
     while (fl2 < 6u && (2u << fl2) <= w.nframes) ++fl2;
     const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
     const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
-    const uint32_t n_tasks = ((wv + (1u << tw2) - 1u) >> tw2) * ((w.n_rows + (1u << th2) - 1u) >> th2) * fgroups;
+    const uint32_t n_tasks = launch_tasks(w, tw2, th2, fgroups);
     constexpr uint32_t WPB = ENV_THREADS / 64;
     const uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
     uint32_t blocks = (n_tasks + WPB - 1u) / WPB;

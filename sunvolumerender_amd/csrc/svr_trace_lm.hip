@@ -577,7 +577,7 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const TaskShape ts = task_shape(w);
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.tiles_x * ts.tiles_y * ts.fgroups;
+    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     const size_t wslot = (size_t)(blockIdx.x * TILE_WAVES + wave);
     float* const gpend = w.pend + wslot * (QUEUE_TASKS * 3u * 64u);
@@ -949,7 +949,7 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const TaskShape ts = task_shape(w);
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.tiles_x * ts.tiles_y * ts.fgroups;
+    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     const uint32_t depth = w.traceDepth;
     const size_t wslot = (size_t)(blockIdx.x * TILE_WAVES + wave);
@@ -1122,7 +1122,7 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm(co
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const TaskShape ts = task_shape(w);
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.tiles_x * ts.tiles_y * ts.fgroups;
+    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     const bool fold = w.fold != 0u;                                   // the host guarantees one frame group then
     const uint32_t pend_max = P2 == 0u ? 21u : QUEUE_TASKS;           // 21 tasks x 3 channels = 63 fold lanes when a wave is one pixel
@@ -1194,7 +1194,7 @@ static hipError_t launch_lm_t(const DevScene& s, const DevWork& w, const LaunchC
     }
     const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
     const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
-    const uint32_t n_tasks = ((wv + (1u << tw2) - 1u) >> tw2) * ((w.n_rows + (1u << th2) - 1u) >> th2) * fgroups;
+    const uint32_t n_tasks = launch_tasks(w, tw2, th2, fgroups);
     constexpr uint32_t WPB = LM_THREADS / 64;
     const uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
     uint32_t blocks = (n_tasks + WPB - 1u) / WPB;

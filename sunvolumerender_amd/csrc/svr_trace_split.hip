@@ -56,7 +56,7 @@ __global__ __launch_bounds__(SPLIT_THREADS, 4) void k_split_front(const DevScene
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const TaskShape ts = task_shape(w);
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.tiles_x * ts.tiles_y * ts.fgroups;
+    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     Cnt c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t* const chunk_counter = w.ticket + TICKET_SHARDS * TICKET_STRIDE;          // chunks handed out so far (the launch zeroes it)
@@ -202,7 +202,7 @@ static hipError_t launch_split_t(const DevScene& s, const DevWork& w, const Laun
     uint32_t fl2 = 0;
     while ((1u << fl2) < w.nframes) ++fl2;
     const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
-    const uint32_t n_tasks = ((wv + (1u << tw2) - 1u) >> tw2) * ((w.n_rows + (1u << th2) - 1u) >> th2);
+    const uint32_t n_tasks = launch_tasks(w, tw2, th2, 1u);
     constexpr uint32_t WPB = SPLIT_THREADS / 64;
     const uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
     uint32_t blocks = (n_tasks + WPB - 1u) / WPB;

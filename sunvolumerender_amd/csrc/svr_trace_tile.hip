@@ -234,7 +234,7 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     // (skip / walk / hit, walk lengths) than 64 different pixels of one frame, and it touches fewer bricks.
     const TaskShape ts = task_shape(w);
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv, fgroups = ts.fgroups;
-    const uint32_t n_tasks = ts.tiles_x * ts.tiles_y * fgroups;
+    const uint32_t n_tasks = ts.n_tasks;
     Cnt c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
     // Work distribution.  A single returning atomic saturates near 88 dequeues/us chip-wide
@@ -517,7 +517,7 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
     }
     const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
     const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
-    uint32_t n_tasks = ((wv + (1u << tw2) - 1u) >> tw2) * ((w.n_rows + (1u << th2) - 1u) >> th2) * fgroups;
+    uint32_t n_tasks = launch_tasks(w, tw2, th2, fgroups);
     constexpr uint32_t WPB = SVR_TILE_THREADS / 64;                       // waves per block
     uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
     uint32_t need = (n_tasks + WPB - 1u) / WPB;

@@ -543,6 +543,33 @@ class Canvas:
             self.dev.synchronize()
         return int(done.value)
 
+    # ---- extension: adaptive sampling ----
+    def paint_adaptive(self, tile_target: float, min_frames: int = 0, max_frames: int = 4096, sync: bool = False) -> abi.AdaptiveResult:
+        """Extension: render on from renderParams.frameNo, freezing each 16 x 16 tile once its predicted RMSE was <= tile_target at two
+        consecutive estimates (and it holds >= min_frames frames), until no tile is active or after max_frames frames
+        (svr_render_pathtracer_adaptive).  Advances renderParams.frameNo by frames_max - f0.  Frozen tiles hold fewer frames: restart
+        the render (frameNo 0) before painting on."""
+        res = abi.AdaptiveResult()
+        rc = self.lib.svr_render_pathtracer_adaptive(C.c_void_p(self.img), C.byref(self.renderParams), C.c_float(tile_target),
+                                                     int(min_frames), int(max_frames), C.byref(res))
+        self.dev.check(rc)
+        if sync:
+            self.dev.synchronize()
+        return res
+
+    def adaptive_tiles(self):
+        """(frames[ty, tx] uint32, rmse[ty, tx] float32): the tile frame counts and final tile RMSE of the last adaptive call
+        (svr_get_adaptive_tiles; the maps of this canvas's size)."""
+        tx, ty = (self.W + 15) // 16, (self.H + 15) // 16
+        fbuf = self.dev.malloc(tx * ty * 4)
+        rbuf = self.dev.malloc(tx * ty * 4)
+        try:
+            self.dev.check(self.lib.svr_get_adaptive_tiles(C.c_void_p(fbuf), C.c_void_p(rbuf)))
+            return self.dev.to_host(fbuf, (ty, tx), np.uint32), self.dev.to_host(rbuf, (ty, tx), np.float32)
+        finally:
+            self.dev.free(fbuf)
+            self.dev.free(rbuf)
+
     def read_guides(self) -> np.ndarray:
         """The guide buffer of the current scene (svr_render_guides): (H, W, 8) float32 = N.xyz, D, A.rgb, O."""
         buf = self.dev.malloc(self.W * self.H * 32)
