@@ -283,12 +283,9 @@ int svr_assemble_frame(void* nccl_comm, void* frame_on_root, const void* hdr_loc
 #define SVR_OPT_MACRO_SHIFT_MIN 32  /* volume textures created from now on get macro-cells of at least 2^v voxels per axis (0..6; default 0 = the smallest cells
                                      * whose grid fits 64^3).  Coarser acceleration data; the default mode's results are unchanged (bit-exact), the local-majorant
                                      * mode's estimate changes with its grid.  For tests of the coarse-grid code paths on small volumes */
-#define SVR_OPT_SPLIT 33            /* OPT-IN, default 0: many-frame launches of deeper paths (traceDepth >= 2) as TWO kernels (csrc/svr_trace_split.hip): the front half (primary walks,
-                                     * first scatter events and their shadow walks in place) writes the paths that go on into a launch-wide pool of record chunks, the lane machine
-                                     * drains them in a kernel with a register budget of its own; the frames of the launch go through scratch slots and the resolve kernel.  Built to
-                                     * give the machine its own registers (+ 3-6 % over the fused kernel of the time); the fused kernel has since caught up and is 0.5-1.5 % ahead
-                                     * without the pool, so this is off by default.  1 / 2: on.  Needs room for the worst-case pool (14 GB for 64 frames at 1024^2; else the fused
-                                     * kernel renders; also for media whose primary walks are pooled and for launches of < 8 frames).  Results unchanged (bit-exact) */
+#define SVR_OPT_SPLIT 33            /* RETIRED, default 0; 0 / 1 / 2 are accepted and stored, and select nothing.  It chose a two-kernel form of many-frame launches of
+                                     * deeper paths whose results were always identical to the one-kernel form's, and which ran 0.5-1.5 % behind it with a record pool of up
+                                     * to 14 GB.  The one-kernel form now serves these launches whatever the value */
 #define SVR_OPT_ENV_NEE 34          /* OPT-IN, default 0: importance sampling of the environment MAP (csrc/svr_trace_env.hip).  With SVR_OPT_ENV_ON_ESCAPE the environment lights the
                                      * medium only through the directions the BSDF / phase sampling picks (core/lights/cuda_environment_light.h:58-72 is a lookup, nothing more).
                                      * 1: every scatter event that is followed by a bounce also draws one direction from the map's luminance (a table built on the GPU by

@@ -44,11 +44,10 @@ static_assert(sizeof(svr_adaptive_result) == 64 && offsetof(svr_adaptive_result,
               offsetof(svr_adaptive_result, tile_max) == 60, "svr_adaptive_result layout");
 
 namespace svr_fast { hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st); }   // svr_trace_tile_fast.hip
-// the trace kernels of adaptive launches (DevWork.tile_list set): svr_trace_{tile,lm,split,env}_list.hip
+// the trace kernels of adaptive launches (DevWork.tile_list set): svr_trace_{tile,lm,env}_list.hip
 namespace svr_list {
 hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
 hipError_t launch_trace_lm_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
-hipError_t launch_trace_split_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
 hipError_t launch_trace_env_raw(const void* scene, const void* work, const void* cfg, hipStream_t st);
 }
 
@@ -111,9 +110,6 @@ struct Context {
     uint32_t queue_blocks = 0;          // blocks both are sized for
     bool queue_alloc_failed = false;    // SVR_OPT_QUEUE = 1 and the device had no room for them: straight-line launches
     hipEvent_t prev_traced = nullptr;   // `traced` event of the latest trace launch (owned by its set)
-    uint32_t* d_split_pool = nullptr;   // chunks of path records of the split kernels of deeper paths (svr_trace_split.hip)
-    uint64_t split_chunks = 0;
-    bool split_alloc_failed = false;
     hipEvent_t queue_done = nullptr;    // recorded behind every launch that uses d_queue / d_pend (there is ONE such memory: its users run one after the other, on whatever stream)
     bool queue_used = false;
     // frames traced ahead of the host's render_pathtracer calls (render_frames)
@@ -207,13 +203,11 @@ struct Context {
     } ns;
     NoiseBuf nb_call;                   // svr_estimate_noise
     // adaptive sampling (svr_render_pathtracer_adaptive): the device tile list + active map of its launches (one allocation: ad_cap uint32 list
-    // entries, then ad_cap bytes), whether fill_work hands them to the launches, and the per-tile results of the last call
+    // entries, then ad_cap bytes), and the per-tile results of the last call
     uint32_t* d_ad_list = nullptr;
     uint8_t* d_ad_map = nullptr;
     size_t ad_cap = 0;
     uint32_t ad_len = 0;
-    bool ad_list_on = false;            // launches trace the listed tiles only
-    bool ad_call = false;               // inside an adaptive call: no frame-ahead tracing
     bool ad_have = false;
     uint32_t ad_tx = 0, ad_ty = 0;
     std::vector<uint32_t> ad_frames;
@@ -294,7 +288,7 @@ int ensure_init()
     g.info = buf;
     HIP_TRY(hipMalloc((void**)&g.d_counters, sizeof(svr_counters) + DEBUG_WORDS * 8));       // + the phase profile of experiment builds
     HIP_TRY(hipMemset(g.d_counters, 0, sizeof(svr_counters) + DEBUG_WORDS * 8));
-    HIP_TRY(hipMalloc((void**)&g.d_ticket, sizeof(uint32_t) * (svr::TICKET_SHARDS * svr::TICKET_STRIDE * (Context::NSETS + 1) + 64)));       // (+ the chunk counters of the split kernels behind the last set of task counters)
+    HIP_TRY(hipMalloc((void**)&g.d_ticket, sizeof(uint32_t) * (svr::TICKET_SHARDS * svr::TICKET_STRIDE * (Context::NSETS + 1) + 64)));       // (+ 64 words behind the last set of task counters)
     HIP_TRY(hipMemset(g.d_ticket, 0, sizeof(uint32_t) * (svr::TICKET_SHARDS * svr::TICKET_STRIDE * (Context::NSETS + 1) + 64)));
     HIP_TRY(hipMalloc((void**)&g.d_mask, svr::ACCEL_WORDS * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&g.d_mask_tmp, 2 * (size_t)svr::MASK_WORDS_MAX * 32));
@@ -504,13 +498,6 @@ int fill_work(svr::DevWork& w, uint32_t W, uint32_t H)
         w.n_rows = w.y1 - w.y0;
     }
     w.n_items = w.n_rows * (w.x1 - w.x0);
-    if (g.ad_list_on) {
-        // adaptive launch (whole frame, one process): the listed tiles only; the ticket arithmetic of row_order assumes the full grid
-        w.tile_list = g.d_ad_list;
-        w.tile_count = g.ad_len;
-        w.tile_active = g.d_ad_map;
-        w.row_order = 0;
-    }
     return 0;
 }
 
@@ -715,24 +702,6 @@ int ensure_record_queues(uint32_t blocks, bool soft, bool& available)
     return 0;
 }
 
-// the chunk pool of the split kernels (svr_trace_split.hip): worst case of the largest launch so far; soft -- without room for it the fused kernel renders
-int ensure_split_pool(uint64_t chunks, bool& available)
-{
-    available = true;
-    if (g.d_split_pool && g.split_chunks >= chunks) return 0;
-    if (g.split_alloc_failed) { available = false; return 0; }
-    HIP_TRY(hipDeviceSynchronize());
-    if (g.d_split_pool) { HIP_TRY(hipFree(g.d_split_pool)); g.d_split_pool = nullptr; g.split_chunks = 0; }
-    hipError_t e = hipMalloc((void**)&g.d_split_pool, (size_t)chunks * svr::SPLIT_CHUNK_WORDS * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        g.d_split_pool = nullptr;
-        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); g.split_alloc_failed = true; available = false; return 0; }
-        return fail((int)e, "HIP error allocating the record pool of the split kernels (%zu MB): %s", ((size_t)chunks * svr::SPLIT_CHUNK_WORDS * 4) >> 20, hipGetErrorName(e));
-    }
-    g.split_chunks = chunks;
-    return 0;
-}
-
 int ensure_queues(uint32_t W, uint32_t H)
 {
     size_t need = (size_t)W * H * Context::GROUP;
@@ -749,15 +718,39 @@ int ensure_queues(uint32_t W, uint32_t H)
     return 0;
 }
 
-int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap)
-{
-    if (ensure_init()) return g.err_code;
-    if (!rp) return fail(-4, "render_pathtracer: renderParams is null");
-    if (!g.have_vol || !g.have_tf || !g.have_cam)
-        return fail(-4, "render_pathtracer before setup_volume/setup_transferfunction/setup_camera");
-    if (!rp->hdrBuffer) return fail(-4, "render_pathtracer: renderParams.hdrBuffer is null (call SetupHDRBuffer)");
-    if (nframes == 0) return 0;
+// The launches of an adaptive call (svr_render_pathtracer_adaptive).  Such a call never traces frames ahead; once a tile has frozen
+// (list set) its launches trace the listed tiles only.
+struct TileList {
+    const uint32_t* list = nullptr;     // active tiles, packed tx | ty << 16, in centre-out tile-row order (null: the whole frame)
+    uint32_t count = 0;                 // entries of list
+    const uint8_t* active = nullptr;    // per-tile map, 1 = traced
+};
+
+// What a render call decides once (plan_launch) and every launch of the call reads
+struct LaunchPlan {
     svr::DevScene s;
+    svr::LaunchCfg cfg;
+    void* img = nullptr;
+    const svr_render_params* rp = nullptr;
+    const TileList* tiles = nullptr;    // the launches trace these tiles only
+    bool fold_batch = false;            // the tile kernel folds the frames of its launches into the accumulator
+    bool use_queue = false;             // ... in its QUEUE builds
+    bool local_majorant = false;        // the local-majorant kernel in place of the tile kernel
+    bool frame_ahead = false;           // one frame per call, the next ones traced ahead (render_ahead)
+};
+
+// short launches (< FOLD_MIN frames) keep the slots: they end in a tail of a few long tasks that only overlapping launches
+// on several streams hide, and a folding launch cannot overlap its predecessor (measured, 1 frame per call: 0.276 vs 0.366 ms)
+constexpr uint32_t FOLD_MIN = 8;
+
+// the launch plan of a render call of nframes >= 1 frames: every automatic decision, and the device memory its launches need
+int plan_launch(LaunchPlan& p, void* img, const svr_render_params* rp, uint32_t nframes, const TileList* adaptive)
+{
+    svr::DevScene& s = p.s;
+    svr::LaunchCfg& cfg = p.cfg;
+    p.img = img;
+    p.rp = rp;
+    p.tiles = adaptive != nullptr && adaptive->list != nullptr ? adaptive : nullptr;
     if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
     if (add_lights_env(s)) return g.err_code;
     if ((size_t)3 * s.imageW * s.imageH >= ((size_t)1 << 32)) return fail(-3, "image too large");
@@ -766,7 +759,6 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
     // summed into one frame: stale values outside the owned rows would corrupt it)
     if (rp->frameNo == 0 && partial_frame(s.imageW, s.imageH))
         HIP_TRY(hipMemsetAsync(rp->hdrBuffer, 0, sizeof(float) * 3 * (size_t)s.imageW * s.imageH, g.stream));
-    svr::LaunchCfg cfg;
     cfg.kernel = g.opt_kernel == svr::KERNEL_AUTO ? svr::KERNEL_TILE : g.opt_kernel;
     // OPT-IN importance sampling of the environment map (svr_trace_env.hip): where there is a map, the environment term is on and a bounce follows the
     // first scatter event (the env sample of event k pairs with the escape term of bounce k + 1)
@@ -787,279 +779,241 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
     // The tile kernel folds the frames of a launch into the accumulator itself (running mean in frame order, 12 B per
     // pixel per launch, svr_trace_tile.hip); the scratch slots + k_resolve remain for frames traced AHEAD of the calls
     // that ask for them (their radiance is folded later, one frame per call) and for the other kernels.
-    const bool fold_batch = cfg.kernel == svr::KERNEL_TILE && g.opt_fold && !g.opt_debug_stop && cfg.frames_log2 < 0;
+    p.fold_batch = cfg.kernel == svr::KERNEL_TILE && g.opt_fold && !g.opt_debug_stop && cfg.frames_log2 < 0;
     // QUEUE builds (the hits of a task are shaded in place, then their paths continue on a per-lane state machine,
     // svr_lanes.hpp) ride on the folding launches.  Auto: with empty-space skipping on (without it every walk is long and the
     // straight-line code wins: c3, 1660 against 1452 Msamples/s), for deep paths and media without exactly transparent space
     // always (c3 depth 2 / 4: +10 % / +30 %, c3n: +34 %), otherwise when the launch gives every wave at least 4 drains of
     // QUEUE_TASKS tasks (c3 / c4 / c5: +4 % / +3 % / +12 %; c2, 512^2 pixels: -2 %)
-    bool use_queue = fold_batch && g.opt_queue == 2;
-    if (fold_batch && g.opt_queue == 1 && g.opt_empty_skip) {
+    p.use_queue = p.fold_batch && g.opt_queue == 2;
+    if (p.fold_batch && g.opt_queue == 1 && g.opt_empty_skip) {
         svr::DevWork wq;
         fill_work(wq, s.imageW, s.imageH);
         const uint64_t waves = (uint64_t)(cfg.num_cus * cfg.blocks_per_cu) / 4u * svr::TILE_WAVES;    // blocks of 1024 threads
-        use_queue = rp->traceDepth >= 2 || s.bound_cull || (uint64_t)wq.n_items >= 4u * svr::QUEUE_TASKS * waves;
+        p.use_queue = rp->traceDepth >= 2 || s.bound_cull || (uint64_t)wq.n_items >= 4u * svr::QUEUE_TASKS * waves;
     }
     // OPT-IN local majorants (svr_trace_lm.hip): needs the class table and whole-ray validity; its folding launches keep the waves'
     // pending radiance in the rows next to the record queues
-    const bool local_majorant = g.opt_local_majorant && cfg.kernel == svr::KERNEL_TILE && s.empty_mask != nullptr && s.ray_skip && !g.opt_debug_stop;
+    p.local_majorant = g.opt_local_majorant && cfg.kernel == svr::KERNEL_TILE && s.empty_mask != nullptr && s.ray_skip && !g.opt_debug_stop;
     // the slot-per-path pool of deeper paths settles its walks (slot loads and stores) and refills less eagerly: 2 cells per turn, a
     // refill from 32 idle lanes, settling from 48 ended walks (c3 depth 4: 3 390 Msamples/s against 2 630 with the depth-1 setting,
     // c3n depth 4: 1 080 against 810; gpurun_out/r03u_tune.log)
-    if (local_majorant && !g.opt_lm_tune && rp->traceDepth > 1) s.lm_tune = 2u | (32u << 8) | (48u << 16) | (s.lm_tune & 0xff000000u);
-    if (local_majorant) use_queue = false;
+    if (p.local_majorant && !g.opt_lm_tune && rp->traceDepth > 1) s.lm_tune = 2u | (32u << 8) | (48u << 16) | (s.lm_tune & 0xff000000u);
+    if (p.local_majorant) p.use_queue = false;
     // POOL (svr_trace_tile.hip): pooled primary walks pay where the walks of a wave are not coherent -- media without exactly transparent
     // space under bound culling (c3n) -- and cost where they are (c3): auto = such media only
-    cfg.pool_primary = use_queue && (g.opt_pool == 2 || (g.opt_pool == 1 && s.bound_cull && !s.has_empty));
-    if (use_queue || (local_majorant && fold_batch)) {          // (a frame-ahead call traces its batches with the same kernels)
+    cfg.pool_primary = p.use_queue && (g.opt_pool == 2 || (g.opt_pool == 1 && s.bound_cull && !s.has_empty));
+    if (p.use_queue || (p.local_majorant && p.fold_batch)) {          // (a frame-ahead call traces its batches with the same kernels)
         bool available = true;
-        if (ensure_record_queues((uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / 16u, g.opt_queue == 1 && !local_majorant, available)) return g.err_code;
-        use_queue = use_queue && available;
+        if (ensure_record_queues((uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / 16u, g.opt_queue == 1 && !p.local_majorant, available)) return g.err_code;
+        p.use_queue = p.use_queue && available;
     }
-    const bool frame_ahead_possible = nframes == 1 && g.opt_frame_ahead && g.opt_pipeline && !g.opt_count && !g.opt_debug_stop && cfg.kernel == svr::KERNEL_TILE &&
-                                      !g.ad_call;
-    // Deeper paths, bit-exact, as TWO kernels (svr_trace_split.hip: front half -> chunks of records -> lane machine; the launch's frames go through
-    // the scratch slots and k_resolve): where the fused queue kernel would run and its primary walks are not pooled, the image fits a 26-bit pixel
-    // index, and the device has room for the worst-case record pool of a launch (<= 24 GB; else the fused kernel)
-    bool use_split = false;
-    const uint32_t split_group = (uint32_t)g.opt_group_frames;
-    // OPT-IN since the fused kernel caught up: the two changes that made the split machine fast (lights in LDS + laundered scene constants) also fix the fused
-    // deeper kernel when applied TOGETHER (each alone costs it 2.5-8 %).  Same box, two kernels / fused: depth 2 5 048 / 5 120, depth 3 3 735 / 3 782,
-    // depth 4 3 152 / 3 171, depth 6 2 844 / 2 876, c5 depth 2 3 306 / 3 333, c3b depth 4 1 846 / 1 830 -- and the fused form needs no 14-GB pool.
-    // (Against the fused kernel as it was, the two-kernel form won 3-6 %: 5 054 / 4 893, 3 728 / 3 555, 3 161 / 2 988, 2 859 / 2 693.)
-    if (g.opt_split && use_queue && rp->traceDepth >= 2u && rp->traceDepth < 32768u && !cfg.pool_primary && !local_majorant && !g.opt_fast_math && nframes >= 8 &&
-        s.layout != svr::LAYOUT_LINEAR && (uint64_t)s.imageW * s.imageH <= (1ull << 26) && !frame_ahead_possible) {
-        svr::DevWork wq;
-        fill_work(wq, s.imageW, s.imageH);
-        const uint32_t n_max = nframes < split_group ? nframes : split_group;
-        uint32_t fl2 = 0;
-        while ((1u << fl2) < n_max) ++fl2;
-        const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
-        uint64_t n_tasks = (uint64_t)((wq.x1 - wq.x0 + (1u << tw2) - 1u) >> tw2) * ((wq.n_rows + (1u << th2) - 1u) >> th2);
-        // (adaptive launches: every wave tile of the listed 16 x 16 tiles, those past the image edge included)
-        if (wq.tile_list != nullptr) n_tasks = std::max<uint64_t>(n_tasks, (uint64_t)wq.tile_count << ((4u - tw2) + (4u - th2)));
-        const uint64_t chunks = svr::split_chunks_worst_case(n_tasks * 64u, (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u);
-        if (chunks * svr::SPLIT_CHUNK_WORDS * sizeof(uint32_t) <= (24ull << 30) && chunks < (1ull << 31)) {
-            bool available = true;
-            if (ensure_split_pool(chunks, available)) return g.err_code;
-            use_split = available;
-        }
-        if (use_split && ensure_slots(s.imageW, s.imageH, n_max < (uint32_t)Context::GROUP ? (uint32_t)Context::GROUP : n_max)) return g.err_code;
-    }
-    auto launch_tile = [&](const svr::DevWork& w, hipStream_t st) -> hipError_t {
-        if (w.tile_list != nullptr) return local_majorant ? svr_list::launch_trace_lm_raw(&s, &w, &cfg, st) : svr_list::launch_trace_tile_raw(&s, &w, &cfg, st);
-        if (local_majorant) return svr::launch_trace_lm(s, w, cfg, st);
-        return g.opt_fast_math ? svr_fast::launch_trace_tile_raw(&s, &w, &cfg, st) : svr::launch_trace_tile(s, w, cfg, st);
-    };
-    const bool frame_ahead_call = frame_ahead_possible;
-    // short launches (< FOLD_MIN frames) keep the slots: they end in a tail of a few long tasks that only overlapping launches
-    // on several streams hide, and a folding launch cannot overlap its predecessor (measured, 1 frame per call: 0.276 vs 0.366 ms)
-    constexpr uint32_t FOLD_MIN = 8;
-    const uint32_t tail_frames = nframes % (uint32_t)(fold_batch ? g.opt_group_frames : Context::GROUP);
-    if ((!fold_batch || frame_ahead_call || (tail_frames != 0 && tail_frames < FOLD_MIN)) &&
+    p.frame_ahead = nframes == 1 && g.opt_frame_ahead && g.opt_pipeline && !g.opt_count && !g.opt_debug_stop && cfg.kernel == svr::KERNEL_TILE &&
+                    adaptive == nullptr;
+    const uint32_t tail_frames = nframes % (uint32_t)(p.fold_batch ? g.opt_group_frames : Context::GROUP);
+    if ((!p.fold_batch || p.frame_ahead || (tail_frames != 0 && tail_frames < FOLD_MIN)) &&
         ensure_slots(s.imageW, s.imageH, nframes < (uint32_t)Context::GROUP ? nframes : (uint32_t)Context::GROUP)) return g.err_code;
-    // one folding launch: trace + accumulate on the caller's stream (the launches of a render update the same accumulator,
-    // so they run in order anyway), tone map behind the last one
-    auto trace_fold = [&](uint32_t first, uint32_t n, bool want_img) -> int {
-        svr::DevWork w;
-        fill_work(w, s.imageW, s.imageH);
-        w.hdr = (float*)rp->hdrBuffer;
-        w.img = want_img ? (uint8_t*)img : nullptr;
-        w.ticket = g.d_ticket + (size_t)svr::TICKET_SHARDS * svr::TICKET_STRIDE * Context::NSETS;   // (the sets' own counters may be in use by frames traced ahead)
-        w.traceDepth = rp->traceDepth;
-        w.frame0 = first;
-        w.nframes = n;
-        w.fold = 1u;
-        w.queue = (use_queue || local_majorant) ? g.d_queue : nullptr;
-        w.pend = (use_queue || local_majorant) ? g.d_pend : nullptr;
-        w.queue_blocks = g.queue_blocks;
-        int slot = -1;
-        if (g.opt_timing) {
-            if (g.ev_count == Context::EV_RING) collect_timing();
-            slot = g.ev_head;
-            HIP_TRY(hipEventRecord(g.ev0[slot], g.stream));
-        }
-        if (w.queue != nullptr && g.queue_used) HIP_TRY(hipStreamWaitEvent(g.stream, g.queue_done, 0));
-        HIP_TRY(launch_tile(w, g.stream));
-        if (w.queue != nullptr) { HIP_TRY(hipEventRecord(g.queue_done, g.stream)); g.queue_used = true; }
-        if (g.opt_timing) {
-            HIP_TRY(hipEventRecord(g.ev1[slot], g.stream));
-            g.ev_head = (g.ev_head + 1) % Context::EV_RING;
-            g.ev_count++;
-        }
-        if (want_img) HIP_TRY(svr::launch_tonemap(s, w, g.stream));
-        return 0;
-    };
-    // one trace launch of n_trace frames starting at frame `first` into scratch set `si`, then the resolve of its
-    // first n_resolve frames
-    auto trace_group = [&](int si, uint32_t first, uint32_t n_trace, uint32_t n_resolve, bool want_img, bool with_queue = false) -> int {
-        Context::SlotSet& set = g.sets[si];
-        for (auto& a : g.ahead) if (a.valid && a.set == si) a.valid = false;     // its slots are about to be overwritten
-        hipStream_t ts = g.opt_pipeline ? set.stream : g.stream;
-        svr::DevWork w;
-        fill_work(w, s.imageW, s.imageH);
-        w.hdr = (float*)rp->hdrBuffer;
-        w.img = want_img ? (uint8_t*)img : nullptr;
-        w.lbuf = set.lbuf;
-        w.slot_stride = (uint32_t)g.slot_floats;
-        w.ticket = g.d_ticket + (size_t)svr::TICKET_SHARDS * svr::TICKET_STRIDE * si;
-        w.traceDepth = rp->traceDepth;
-        w.frame0 = first;
-        w.nframes = n_trace;
-        if (with_queue) { w.queue = g.d_queue; w.pend = g.d_pend; w.queue_blocks = g.queue_blocks; }
-        // the scratch slots of this set are free again once their previous resolve has run
-        if (g.opt_pipeline && set.used) HIP_TRY(hipStreamWaitEvent(ts, set.resolved, 0));
-        // A large trace launch fills the chip by itself; running two of them at once only makes them share L2
-        // and stretches both.  They are chained (the resolve of one still overlaps the trace of the next).
-        // Smaller launches (one frame per call; a GPU's share of the frame under row sharding) end in a ~0.1 ms
-        // tail of a few long tasks and overlap freely to hide it.
-        if (g.opt_pipeline && (uint64_t)w.n_items * n_trace >= Context::CHAIN_MIN_PATHS && g.prev_traced)
-            HIP_TRY(hipStreamWaitEvent(ts, g.prev_traced, 0));
-        int slot = -1;
-        if (g.opt_timing) {
-            if (g.ev_count == Context::EV_RING) collect_timing();
-            slot = g.ev_head;
-            HIP_TRY(hipEventRecord(g.ev0[slot], ts));
-        }
-        if (cfg.kernel == svr::KERNEL_WAVEFRONT)
-            HIP_TRY(svr::launch_wavefront(s, w, cfg, set.planes, set.wf_counts, (uint32_t)g.queue_capacity, ts));
-        else if (cfg.kernel == svr::KERNEL_ENV_NEE) HIP_TRY(w.tile_list != nullptr ? svr_list::launch_trace_env_raw(&s, &w, &cfg, ts) : svr::launch_trace_env(s, w, cfg, ts));
-        else if (cfg.kernel == svr::KERNEL_TILE) {
-            if (w.queue != nullptr && g.queue_used) HIP_TRY(hipStreamWaitEvent(ts, g.queue_done, 0));
-            HIP_TRY(launch_tile(w, ts));
-            if (w.queue != nullptr) { HIP_TRY(hipEventRecord(g.queue_done, ts)); g.queue_used = true; }
-        } else HIP_TRY(svr::launch_pathtrace(s, w, cfg, ts));
-        if (g.opt_timing) {
-            HIP_TRY(hipEventRecord(g.ev1[slot], ts));
-            g.ev_head = (g.ev_head + 1) % Context::EV_RING;
-            g.ev_count++;
-        }
-        if (g.opt_pipeline) {
-            HIP_TRY(hipEventRecord(set.traced, ts));
-            g.prev_traced = set.traced;
-            // (a batch traced purely AHEAD -- nothing of it is resolved by this call -- must not hold the caller's stream: the calls that
-            // consume the batch in stock run beside it and wait for `traced` when they get to this one)
-            if (n_resolve) HIP_TRY(hipStreamWaitEvent(g.stream, set.traced, 0));
-        }
-        if (n_resolve) {
-            w.nframes = n_resolve;
-            HIP_TRY(svr::launch_resolve(s, w, g.stream));
-            if (g.opt_pipeline) HIP_TRY(hipEventRecord(set.resolved, g.stream));
-        }
-        set.used = true;
-        if (n_resolve < n_trace) {
-            // a free entry, else the older batch
-            Context::Ahead& a = !g.ahead[0].valid ? g.ahead[0] : (!g.ahead[1].valid ? g.ahead[1] : (g.ahead[0].first < g.ahead[1].first ? g.ahead[0] : g.ahead[1]));
-            a.valid = true; a.scene = s; a.shape = w; a.content = g.content_version;
-            a.first = first; a.count = n_trace; a.depth = rp->traceDepth; a.set = si;
-        }
-        return 0;
-    };
-    auto next_set = [&]() { int si = g.next_set; g.next_set = (g.next_set + 1) % Context::NSETS; return si; };
-    const bool want_img = tonemap && !g.opt_skip_tonemap;
-    // one launch of the split kernels (n <= 64 frames of every owned pixel) + the fold of its scratch slots, all on the caller's stream
-    auto trace_split = [&](uint32_t first, uint32_t n, bool img_now) -> int {
-        const int si = next_set();
-        Context::SlotSet& set = g.sets[si];
-        for (auto& a : g.ahead) if (a.valid && a.set == si) a.valid = false;     // its slots are about to be overwritten
-        if (set.used) HIP_TRY(hipStreamWaitEvent(g.stream, set.traced, 0));       // (a batch still being traced ahead into this set)
-        svr::DevWork w;
-        fill_work(w, s.imageW, s.imageH);
-        w.hdr = (float*)rp->hdrBuffer;
-        w.img = img_now ? (uint8_t*)img : nullptr;
-        w.lbuf = set.lbuf;
-        w.slot_stride = (uint32_t)g.slot_floats;
-        w.ticket = g.d_ticket + (size_t)svr::TICKET_SHARDS * svr::TICKET_STRIDE * Context::NSETS;
-        w.traceDepth = rp->traceDepth;
-        w.frame0 = first;
-        w.nframes = n;
-        w.queue = g.d_split_pool;
-        w.queue_blocks = (uint32_t)g.split_chunks;
-        int slot = -1;
-        if (g.opt_timing) {
-            if (g.ev_count == Context::EV_RING) collect_timing();
-            slot = g.ev_head;
-            HIP_TRY(hipEventRecord(g.ev0[slot], g.stream));
-        }
-        HIP_TRY(w.tile_list != nullptr ? svr_list::launch_trace_split_raw(&s, &w, &cfg, g.stream) : svr::launch_trace_split(s, w, cfg, g.stream));
-        if (g.opt_timing) {
-            HIP_TRY(hipEventRecord(g.ev1[slot], g.stream));
-            g.ev_head = (g.ev_head + 1) % Context::EV_RING;
-            g.ev_count++;
-        }
-        HIP_TRY(svr::launch_resolve(s, w, g.stream));
-        HIP_TRY(hipEventRecord(set.traced, g.stream));
-        HIP_TRY(hipEventRecord(set.resolved, g.stream));
-        set.used = true;
-        return 0;
-    };
+    return 0;
+}
 
-    // The reference's host calls render_pathtracer once per frame (gui/canvas.cpp:96).  A frame's radiance is a pure
-    // function of (scene, pixel, frame number), so frames can be traced AHEAD of the calls that ask for them: a
-    // 32-frame launch costs 0.13 ms per frame on c3, a 1-frame launch 0.23.  The batch doubles with the frame number
-    // (1, 2, 4 ... GROUP), so a host that restarts the render on every mouse event never traces more than twice what
-    // it shows.  Anything that could change a frame -- scene PODs, texture contents, window, shard, trace depth --
-    // invalidates the frames in stock.
-    if (frame_ahead_call) {
-        const uint32_t n = rp->frameNo;
-        svr::DevWork shape;
-        fill_work(shape, s.imageW, s.imageH);
-        // at most 4 GB of scratch frames per set (64 frames up to ~2300^2 pixels; fewer for larger images)
-        const uint64_t slot_bytes = (uint64_t)3 * s.imageW * s.imageH * sizeof(float);
-        uint32_t batch_max = 1;
-        while (batch_max < (uint32_t)Context::AHEAD_MAX && 2ull * batch_max * slot_bytes <= (4ull << 30)) batch_max *= 2u;
-        // the queue builds of the tile kernel (first scatter events shaded in place, then the lane machine) for the batches too: they hand
-        // their radiance rows to the scratch slots instead of folding them (svr_tile_tasks.hpp, scatter_pending)
-        const bool ahead_queue = use_queue && !local_majorant && !g.opt_fast_math;
-        auto in_stock = [&](const Context::Ahead& a, uint32_t frame) {
-            return a.valid && a.content == g.content_version && a.depth == rp->traceDepth && frame >= a.first && frame - a.first < a.count &&
-                   memcmp(&a.scene, &s, sizeof s) == 0 && a.shape.x0 == shape.x0 && a.shape.x1 == shape.x1 && a.shape.y0 == shape.y0 &&
-                   a.shape.y1 == shape.y1 && a.shape.strip_rows == shape.strip_rows && a.shape.rank == shape.rank && a.shape.world == shape.world;
-        };
-        for (Context::Ahead& a : g.ahead) {
-            if (!in_stock(a, n)) continue;
-            // in stock: fold slot n - first into the accumulator
-            Context::SlotSet& set = g.sets[a.set];
-            svr::DevWork w = shape;
-            w.hdr = (float*)rp->hdrBuffer;
-            w.img = want_img ? (uint8_t*)img : nullptr;
-            w.slot_stride = (uint32_t)g.slot_floats;
-            w.lbuf = set.lbuf + (size_t)(n - a.first) * g.slot_floats;
-            w.traceDepth = rp->traceDepth;
-            w.frame0 = n;
-            w.nframes = 1;
-            HIP_TRY(hipStreamWaitEvent(g.stream, set.traced, 0));
-            HIP_TRY(svr::launch_resolve(s, w, g.stream));
-            HIP_TRY(hipEventRecord(set.resolved, g.stream));
-            // steady state: a full batch takes as long to trace as to consume, so the NEXT one starts when this one is first used (it runs on
-            // its set's stream beside the per-call resolves: the queue builds of the tile kernel leave the register room a resolve wave needs)
-            // (while the batches still grow -- 1, 2, 4 ... -- the next one, twice as long, is started the same way: the ramp's traces then run back to
-            // back instead of each waiting for its predecessor to be consumed; a host that restarts the render has at most two batches traced in vain)
-            const uint32_t next_first = a.first + a.count;
-            const uint32_t next_count = 2u * a.count < batch_max ? 2u * a.count : batch_max;
-            if (next_count > 1u && !in_stock(g.ahead[0], next_first) && !in_stock(g.ahead[1], next_first))
-                return trace_group(next_set(), next_first, next_count, 0, false, ahead_queue && next_count >= 16u);
-            return 0;
-        }
-        uint32_t batch = 1;
-        while (batch < batch_max && 2u * batch <= n + 1u) batch *= 2u;
-        if (batch_max > 1 && ensure_slots(s.imageW, s.imageH, batch_max)) return g.err_code;
-        if (trace_group(next_set(), n, batch, 1, want_img, ahead_queue && batch >= 16u)) return g.err_code;
-        if (batch_max > 1) {
-            const uint32_t next_count = 2u * batch < batch_max ? 2u * batch : batch_max;
-            return trace_group(next_set(), n + batch, next_count, 0, false, ahead_queue && next_count >= 16u);
-        }
+// the fields every trace launch of the plan shares: the owned pixels (fill_work), frames first .. first + n - 1 into rp's accumulator, the
+// image if want_img, and the tile list of an adaptive call
+svr::DevWork launch_work(const LaunchPlan& p, uint32_t first, uint32_t n, bool want_img)
+{
+    svr::DevWork w;
+    fill_work(w, p.s.imageW, p.s.imageH);
+    w.hdr = (float*)p.rp->hdrBuffer;
+    w.img = want_img ? (uint8_t*)p.img : nullptr;
+    w.traceDepth = p.rp->traceDepth;
+    w.frame0 = first;
+    w.nframes = n;
+    if (p.tiles) {
+        // adaptive launch (whole frame, one process): the listed tiles only; the ticket arithmetic of row_order assumes the full grid
+        w.tile_list = p.tiles->list;
+        w.tile_count = p.tiles->count;
+        w.tile_active = p.tiles->active;
+        w.row_order = 0;
+    }
+    return w;
+}
+
+// one launch of the plan's trace kernel on stream st (set: the scratch set it traces into, whose wavefront queues KERNEL_WAVEFRONT uses), between
+// the events of the timing ring (SVR_OPT_TIMING); a launch that uses the record queues runs behind their previous user
+int launch_trace(const LaunchPlan& p, const svr::DevWork& w, hipStream_t st, const Context::SlotSet* set)
+{
+    const svr::DevScene& s = p.s;
+    const svr::LaunchCfg& cfg = p.cfg;
+    const bool listed = w.tile_list != nullptr;
+    int slot = -1;
+    if (g.opt_timing) {
+        if (g.ev_count == Context::EV_RING) collect_timing();
+        slot = g.ev_head;
+        HIP_TRY(hipEventRecord(g.ev0[slot], st));
+    }
+    if (w.queue != nullptr && g.queue_used) HIP_TRY(hipStreamWaitEvent(st, g.queue_done, 0));
+    if (cfg.kernel == svr::KERNEL_WAVEFRONT)
+        HIP_TRY(svr::launch_wavefront(s, w, cfg, set->planes, set->wf_counts, (uint32_t)g.queue_capacity, st));
+    else if (cfg.kernel == svr::KERNEL_ENV_NEE) HIP_TRY(listed ? svr_list::launch_trace_env_raw(&s, &w, &cfg, st) : svr::launch_trace_env(s, w, cfg, st));
+    else if (cfg.kernel != svr::KERNEL_TILE) HIP_TRY(svr::launch_pathtrace(s, w, cfg, st));
+    else if (p.local_majorant) HIP_TRY(listed ? svr_list::launch_trace_lm_raw(&s, &w, &cfg, st) : svr::launch_trace_lm(s, w, cfg, st));
+    else if (listed) HIP_TRY(svr_list::launch_trace_tile_raw(&s, &w, &cfg, st));
+    else HIP_TRY(g.opt_fast_math ? svr_fast::launch_trace_tile_raw(&s, &w, &cfg, st) : svr::launch_trace_tile(s, w, cfg, st));
+    if (w.queue != nullptr) { HIP_TRY(hipEventRecord(g.queue_done, st)); g.queue_used = true; }
+    if (g.opt_timing) {
+        HIP_TRY(hipEventRecord(g.ev1[slot], st));
+        g.ev_head = (g.ev_head + 1) % Context::EV_RING;
+        g.ev_count++;
+    }
+    return 0;
+}
+
+// one folding launch: trace + accumulate on the caller's stream (the launches of a render update the same accumulator,
+// so they run in order anyway), tone map behind the last one
+int trace_fold(const LaunchPlan& p, uint32_t first, uint32_t n, bool want_img)
+{
+    svr::DevWork w = launch_work(p, first, n, want_img);
+    w.ticket = g.d_ticket + (size_t)svr::TICKET_SHARDS * svr::TICKET_STRIDE * Context::NSETS;   // (the sets' own counters may be in use by frames traced ahead)
+    w.fold = 1u;
+    const bool queues = p.use_queue || p.local_majorant;
+    w.queue = queues ? g.d_queue : nullptr;
+    w.pend = queues ? g.d_pend : nullptr;
+    w.queue_blocks = g.queue_blocks;
+    if (launch_trace(p, w, g.stream, nullptr)) return g.err_code;
+    if (want_img) HIP_TRY(svr::launch_tonemap(p.s, w, g.stream));
+    return 0;
+}
+
+int next_set()
+{
+    const int si = g.next_set;
+    g.next_set = (g.next_set + 1) % Context::NSETS;
+    return si;
+}
+
+// one trace launch of n_trace frames starting at frame `first` into scratch set `si`, then the resolve of its
+// first n_resolve frames (with_queue: the QUEUE build of the tile kernel)
+int trace_group(const LaunchPlan& p, int si, uint32_t first, uint32_t n_trace, uint32_t n_resolve, bool want_img, bool with_queue = false)
+{
+    Context::SlotSet& set = g.sets[si];
+    for (auto& a : g.ahead) if (a.valid && a.set == si) a.valid = false;     // its slots are about to be overwritten
+    hipStream_t ts = g.opt_pipeline ? set.stream : g.stream;
+    svr::DevWork w = launch_work(p, first, n_trace, want_img);
+    w.lbuf = set.lbuf;
+    w.slot_stride = (uint32_t)g.slot_floats;
+    w.ticket = g.d_ticket + (size_t)svr::TICKET_SHARDS * svr::TICKET_STRIDE * si;
+    if (with_queue) { w.queue = g.d_queue; w.pend = g.d_pend; w.queue_blocks = g.queue_blocks; }
+    // the scratch slots of this set are free again once their previous resolve has run
+    if (g.opt_pipeline && set.used) HIP_TRY(hipStreamWaitEvent(ts, set.resolved, 0));
+    // A large trace launch fills the chip by itself; running two of them at once only makes them share L2
+    // and stretches both.  They are chained (the resolve of one still overlaps the trace of the next).
+    // Smaller launches (one frame per call; a GPU's share of the frame under row sharding) end in a ~0.1 ms
+    // tail of a few long tasks and overlap freely to hide it.
+    if (g.opt_pipeline && (uint64_t)w.n_items * n_trace >= Context::CHAIN_MIN_PATHS && g.prev_traced)
+        HIP_TRY(hipStreamWaitEvent(ts, g.prev_traced, 0));
+    if (launch_trace(p, w, ts, &set)) return g.err_code;
+    if (g.opt_pipeline) {
+        HIP_TRY(hipEventRecord(set.traced, ts));
+        g.prev_traced = set.traced;
+        // (a batch traced purely AHEAD -- nothing of it is resolved by this call -- must not hold the caller's stream: the calls that
+        // consume the batch in stock run beside it and wait for `traced` when they get to this one)
+        if (n_resolve) HIP_TRY(hipStreamWaitEvent(g.stream, set.traced, 0));
+    }
+    if (n_resolve) {
+        w.nframes = n_resolve;
+        HIP_TRY(svr::launch_resolve(p.s, w, g.stream));
+        if (g.opt_pipeline) HIP_TRY(hipEventRecord(set.resolved, g.stream));
+    }
+    set.used = true;
+    if (n_resolve < n_trace) {
+        // a free entry, else the older batch
+        Context::Ahead& a = !g.ahead[0].valid ? g.ahead[0] : (!g.ahead[1].valid ? g.ahead[1] : (g.ahead[0].first < g.ahead[1].first ? g.ahead[0] : g.ahead[1]));
+        a.valid = true; a.scene = p.s; a.shape = w; a.content = g.content_version;
+        a.first = first; a.count = n_trace; a.depth = p.rp->traceDepth; a.set = si;
+    }
+    return 0;
+}
+
+// do two launches (fill_work) cover the same pixels: window, strip rows, rank, world?
+bool same_shape(const svr::DevWork& a, const svr::DevWork& b)
+{
+    return a.x0 == b.x0 && a.x1 == b.x1 && a.y0 == b.y0 && a.y1 == b.y1 && a.strip_rows == b.strip_rows && a.rank == b.rank && a.world == b.world;
+}
+
+// The reference's host calls render_pathtracer once per frame (gui/canvas.cpp:96).  A frame's radiance is a pure
+// function of (scene, pixel, frame number), so frames can be traced AHEAD of the calls that ask for them: a
+// 32-frame launch costs 0.13 ms per frame on c3, a 1-frame launch 0.23.  The batch doubles with the frame number
+// (1, 2, 4 ... GROUP), so a host that restarts the render on every mouse event never traces more than twice what
+// it shows.  Anything that could change a frame -- scene PODs, texture contents, window, shard, trace depth --
+// invalidates the frames in stock.
+int render_ahead(const LaunchPlan& p, bool want_img)
+{
+    const svr::DevScene& s = p.s;
+    const uint32_t n = p.rp->frameNo;
+    svr::DevWork shape;
+    fill_work(shape, s.imageW, s.imageH);
+    // at most 4 GB of scratch frames per set (64 frames up to ~2300^2 pixels; fewer for larger images)
+    const uint64_t slot_bytes = (uint64_t)3 * s.imageW * s.imageH * sizeof(float);
+    uint32_t batch_max = 1;
+    while (batch_max < (uint32_t)Context::AHEAD_MAX && 2ull * batch_max * slot_bytes <= (4ull << 30)) batch_max *= 2u;
+    // the queue builds of the tile kernel (first scatter events shaded in place, then the lane machine) for the batches too: they hand
+    // their radiance rows to the scratch slots instead of folding them (svr_tile_tasks.hpp, scatter_pending)
+    const bool ahead_queue = p.use_queue && !p.local_majorant && !g.opt_fast_math;
+    auto in_stock = [&](const Context::Ahead& a, uint32_t frame) {
+        return a.valid && a.content == g.content_version && a.depth == p.rp->traceDepth && frame >= a.first && frame - a.first < a.count &&
+               memcmp(&a.scene, &s, sizeof s) == 0 && same_shape(a.shape, shape);
+    };
+    for (Context::Ahead& a : g.ahead) {
+        if (!in_stock(a, n)) continue;
+        // in stock: fold slot n - first into the accumulator
+        Context::SlotSet& set = g.sets[a.set];
+        svr::DevWork w = launch_work(p, n, 1, want_img);
+        w.slot_stride = (uint32_t)g.slot_floats;
+        w.lbuf = set.lbuf + (size_t)(n - a.first) * g.slot_floats;
+        HIP_TRY(hipStreamWaitEvent(g.stream, set.traced, 0));
+        HIP_TRY(svr::launch_resolve(s, w, g.stream));
+        HIP_TRY(hipEventRecord(set.resolved, g.stream));
+        // steady state: a full batch takes as long to trace as to consume, so the NEXT one starts when this one is first used (it runs on
+        // its set's stream beside the per-call resolves: the queue builds of the tile kernel leave the register room a resolve wave needs)
+        // (while the batches still grow -- 1, 2, 4 ... -- the next one, twice as long, is started the same way: the ramp's traces then run back to
+        // back instead of each waiting for its predecessor to be consumed; a host that restarts the render has at most two batches traced in vain)
+        const uint32_t next_first = a.first + a.count;
+        const uint32_t next_count = 2u * a.count < batch_max ? 2u * a.count : batch_max;
+        if (next_count > 1u && !in_stock(g.ahead[0], next_first) && !in_stock(g.ahead[1], next_first))
+            return trace_group(p, next_set(), next_first, next_count, 0, false, ahead_queue && next_count >= 16u);
         return 0;
     }
+    uint32_t batch = 1;
+    while (batch < batch_max && 2u * batch <= n + 1u) batch *= 2u;
+    if (batch_max > 1 && ensure_slots(s.imageW, s.imageH, batch_max)) return g.err_code;
+    if (trace_group(p, next_set(), n, batch, 1, want_img, ahead_queue && batch >= 16u)) return g.err_code;
+    if (batch_max > 1) {
+        const uint32_t next_count = 2u * batch < batch_max ? 2u * batch : batch_max;
+        return trace_group(p, next_set(), n + batch, next_count, 0, false, ahead_queue && next_count >= 16u);
+    }
+    return 0;
+}
 
+// nframes frames into rp's accumulator, tone-mapped into img if `tonemap` (adaptive: the launches of an adaptive call, else null)
+int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap, const TileList* adaptive)
+{
+    if (ensure_init()) return g.err_code;
+    if (!rp) return fail(-4, "render_pathtracer: renderParams is null");
+    if (!g.have_vol || !g.have_tf || !g.have_cam)
+        return fail(-4, "render_pathtracer before setup_volume/setup_transferfunction/setup_camera");
+    if (!rp->hdrBuffer) return fail(-4, "render_pathtracer: renderParams.hdrBuffer is null (call SetupHDRBuffer)");
+    if (nframes == 0) return 0;
+    LaunchPlan p;
+    if (plan_launch(p, img, rp, nframes, adaptive)) return g.err_code;
+    const bool want_img = tonemap && !g.opt_skip_tonemap;
+    if (p.frame_ahead) return render_ahead(p, want_img);
     // folding launches may take 64 frames (a wave = ONE pixel x 64 frames): half as many launch boundaries
-    const uint32_t group = fold_batch ? (uint32_t)g.opt_group_frames : (uint32_t)Context::GROUP;
+    const uint32_t group = p.fold_batch ? (uint32_t)g.opt_group_frames : (uint32_t)Context::GROUP;
     for (uint32_t g0 = 0; g0 < nframes; g0 += group) {
-        uint32_t n = nframes - g0 < group ? nframes - g0 : group;
-        bool last = g0 + n >= nframes;
-        if (fold_batch && n >= FOLD_MIN) {
-            if (use_split ? trace_split(rp->frameNo + g0, n, want_img && last) : trace_fold(rp->frameNo + g0, n, want_img && last)) return g.err_code;
-        } else if (trace_group(next_set(), rp->frameNo + g0, n, n, want_img && last)) return g.err_code;
+        const uint32_t n = nframes - g0 < group ? nframes - g0 : group;
+        const bool img_now = want_img && g0 + n >= nframes;
+        if (p.fold_batch && n >= FOLD_MIN) {
+            if (trace_fold(p, rp->frameNo + g0, n, img_now)) return g.err_code;
+        } else if (trace_group(p, next_set(), rp->frameNo + g0, n, n, img_now)) return g.err_code;
     }
     return 0;
 }
@@ -1213,8 +1167,25 @@ bool noise_continues(const svr_render_params* rp, uint64_t call)
         return false;
     svr::DevWork w;
     fill_work(w, g.cam.imageW, g.cam.imageH);
-    return w.x0 == ns.shape.x0 && w.x1 == ns.shape.x1 && w.y0 == ns.shape.y0 && w.y1 == ns.shape.y1 &&
-           w.strip_rows == ns.shape.strip_rows && w.rank == ns.shape.rank && w.world == ns.shape.world;
+    return same_shape(w, ns.shape);
+}
+
+// the snapshot A(m) of the tracked render for px pixels; soft: an allocation failure sets ok = false and a message without an error code
+int ensure_noise_snap(size_t px, bool soft, bool& ok)
+{
+    Context::Noise& ns = g.ns;
+    ok = true;
+    if (ns.d_snap && ns.snap_px >= px) return 0;
+    if (ns.d_snap) HIP_TRY(hipFree(ns.d_snap));
+    ns.d_snap = nullptr; ns.snap_px = 0;
+    const hipError_t e = hipMalloc((void**)&ns.d_snap, px * 3 * sizeof(float));
+    if (e == hipSuccess) { ns.snap_px = px; return 0; }
+    ns.d_snap = nullptr;
+    (void)hipGetLastError();
+    if (!soft) return fail((int)e, "noise estimate: hipMalloc of %zu bytes failed: %s", px * 3 * sizeof(float), hipGetErrorName(e));
+    g.err_msg = std::string("noise estimate: device memory unavailable (") + hipGetErrorName(e) + "), no estimate for this render";
+    ok = false;
+    return 0;
 }
 
 // the state rules of SVR_OPT_NOISE_ESTIMATE, behind a render call of rp that ended at n = frameNo + nframes (render call number `call`):
@@ -1243,19 +1214,9 @@ int noise_after_render(const svr_render_params* rp, uint32_t nframes, uint64_t c
     const size_t px = (size_t)ns.W * ns.H;
     if (ns.m == 0) {
         if (n < 4) return 0;
-        if (ns.snap_px < px || !ns.d_snap) {
-            if (ns.d_snap) HIP_TRY(hipFree(ns.d_snap));
-            ns.d_snap = nullptr; ns.snap_px = 0;
-            const hipError_t e = hipMalloc((void**)&ns.d_snap, px * 3 * sizeof(float));
-            if (e != hipSuccess) {
-                ns.d_snap = nullptr;
-                (void)hipGetLastError();
-                g.err_msg = std::string("noise estimate: device memory unavailable (") + hipGetErrorName(e) + "), no estimate for this render";
-                ns.unavailable = true;
-                return 0;
-            }
-            ns.snap_px = px;
-        }
+        bool ok = true;
+        if (ensure_noise_snap(px, true, ok)) return g.err_code;
+        if (!ok) { ns.unavailable = true; return 0; }
         HIP_TRY(hipMemcpyAsync(ns.d_snap, rp->hdrBuffer, px * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream));
         ns.m = n;
         return 0;
@@ -1273,6 +1234,24 @@ int noise_after_render(const svr_render_params* rp, uint32_t nframes, uint64_t c
     return 0;
 }
 
+// show the whole accumulator hdr in img: the denoised preview if `denoise` and its memory is available, else the tone map
+int show_full_frame(void* img, const void* hdr, bool denoise)
+{
+    if (denoise) {
+        bool ok = true;
+        if (denoise_frame(img, nullptr, hdr, g.cam.imageW, g.cam.imageH, g.dn, true, ok)) return g.err_code;
+        if (ok) return 0;
+    }
+    svr::DevScene s;
+    if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
+    svr::DevWork w;
+    fill_work_full(w, s.imageW, s.imageH);
+    w.hdr = (float*)const_cast<void*>(hdr);
+    w.img = (uint8_t*)img;
+    HIP_TRY(svr::launch_tonemap(s, w, g.stream));
+    return 0;
+}
+
 // render_pathtracer / svr_render_pathtracer_frames.  SVR_OPT_DENOISE_PREVIEW = N > 0: while the frame shown has at most N samples per
 // pixel the traced frames are resolved WITHOUT their tone map, and guides (if stale) + filter + tone map follow on the caller's stream --
 // behind the resolve or fold that writes the accumulator, so svr_device_synchronize still waits for the shown image.  Inert under a row
@@ -1281,20 +1260,9 @@ int render_frames_shown(void* img, const svr_render_params* rp, uint32_t nframes
 {
     const bool preview = rp && img && nframes > 0 && tonemap && !g.opt_skip_tonemap && g.opt_denoise_preview > 0 && g.have_vol && g.have_tf && g.have_cam &&
                          (uint64_t)rp->frameNo + nframes <= (uint64_t)g.opt_denoise_preview && !partial_frame(g.cam.imageW, g.cam.imageH);
-    if (render_frames_traced(img, rp, nframes, tonemap && !preview)) return g.err_code;
+    if (render_frames_traced(img, rp, nframes, tonemap && !preview, nullptr)) return g.err_code;
     if (!preview) return 0;
-    bool ok = true;
-    if (denoise_frame(img, nullptr, rp->hdrBuffer, g.cam.imageW, g.cam.imageH, g.dn, true, ok)) return g.err_code;
-    if (!ok) {
-        svr::DevScene s;
-        if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
-        svr::DevWork w;
-        fill_work_full(w, s.imageW, s.imageH);
-        w.hdr = (float*)rp->hdrBuffer;
-        w.img = (uint8_t*)img;
-        HIP_TRY(svr::launch_tonemap(s, w, g.stream));
-    }
-    return 0;
+    return show_full_frame(img, rp->hdrBuffer, true);
 }
 
 // ... and, with SVR_OPT_NOISE_ESTIMATE on, the estimate's state rules behind the call (they only read the accumulator)
@@ -1363,7 +1331,6 @@ void svr_shutdown(void)
     if (g.d_queue) hipFree(g.d_queue);
     if (g.d_pend) hipFree(g.d_pend);
     if (g.queue_done) hipEventDestroy(g.queue_done);
-    if (g.d_split_pool) hipFree(g.d_split_pool);
     if (g.d_guides) hipFree(g.d_guides);
     if (g.d_dn_scratch) hipFree(g.d_dn_scratch);
     if (g.ns.d_snap) hipFree(g.ns.d_snap);
@@ -1897,14 +1864,8 @@ int svr_render_pathtracer_adaptive(void* img, svr_render_params* rp, float targe
     Context::Noise& ns = g.ns;
     ns.tracking = false; ns.have = false; ns.m = 0;
     ++g.render_calls;                            // (the next render call starts a new render by the estimator's state rules)
-    if (ns.snap_px < px || !ns.d_snap) {
-        if (ns.d_snap) HIP_TRY(hipFree(ns.d_snap));
-        ns.d_snap = nullptr; ns.snap_px = 0;
-        HIP_TRY(hipMalloc((void**)&ns.d_snap, px * 3 * sizeof(float)));
-        ns.snap_px = px;
-    }
     bool ok = true;
-    if (ensure_noise_buf(ns.buf, nt, false, ok)) return g.err_code;
+    if (ensure_noise_snap(px, false, ok) || ensure_noise_buf(ns.buf, nt, false, ok)) return g.err_code;
 
     const uint32_t f0 = rp->frameNo;
     const uint64_t end = (uint64_t)f0 + max_frames;
@@ -1916,7 +1877,6 @@ int svr_render_pathtracer_adaptive(void* img, svr_render_params* rp, float targe
     uint32_t n = f0, m = 0, checkpoints = 0;
     bool list_mode = false;
     int rc = 0;
-    g.ad_call = true;
     for (;;) {
         uint64_t next = m == 0 ? (uint64_t)snap_at : 2ull * m;
         const bool checkpoint = next <= end;
@@ -1924,10 +1884,8 @@ int svr_render_pathtracer_adaptive(void* img, svr_render_params* rp, float targe
         // frames n .. next - 1 of the active tiles (all of them until the first freeze: the ordinary launches)
         svr_render_params cur = *rp;
         cur.frameNo = n;
-        g.ad_list_on = list_mode;
-        rc = render_frames_traced(img, &cur, (uint32_t)(next - n), false);
-        g.ad_list_on = false;
-        if (rc) break;
+        const TileList tiles = {list_mode ? g.d_ad_list : nullptr, g.ad_len, g.d_ad_map};
+        if ((rc = render_frames_traced(img, &cur, (uint32_t)(next - n), false, &tiles))) break;
         n = (uint32_t)next;
         for (size_t t = 0; t < nt; ++t) if (active[t]) frames[t] = n;
         if (!checkpoint) break;
@@ -1961,7 +1919,6 @@ int svr_render_pathtracer_adaptive(void* img, svr_render_params* rp, float targe
             list_mode = true;
         }
     }
-    g.ad_call = false;
     if (rc) return rc;
 
     // the result: frozen tiles keep the estimate they froze with, active ones scale their last one to the final frame count
@@ -2002,23 +1959,8 @@ int svr_render_pathtracer_adaptive(void* img, svr_render_params* rp, float targe
     g.ad_rmse = trmse;
 
     // the image: the tone map of the final accumulator (or the denoised preview while the render has at most SVR_OPT_DENOISE_PREVIEW frames)
-    if (!g.opt_skip_tonemap) {
-        svr::DevScene s;
-        if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
-        bool shown = false;
-        if (g.opt_denoise_preview > 0 && res.frames_max <= (uint32_t)g.opt_denoise_preview) {
-            bool dn_ok = true;
-            if (denoise_frame(img, nullptr, rp->hdrBuffer, W, H, g.dn, true, dn_ok)) return g.err_code;
-            shown = dn_ok;
-        }
-        if (!shown) {
-            svr::DevWork w;
-            fill_work_full(w, W, H);
-            w.hdr = (float*)rp->hdrBuffer;
-            w.img = (uint8_t*)img;
-            HIP_TRY(svr::launch_tonemap(s, w, g.stream));
-        }
-    }
+    if (!g.opt_skip_tonemap && show_full_frame(img, rp->hdrBuffer, g.opt_denoise_preview > 0 && res.frames_max <= (uint32_t)g.opt_denoise_preview))
+        return g.err_code;
     rp->frameNo = res.frames_max;
     *out = res;
     return 0;
@@ -2313,7 +2255,7 @@ int svr_set_option(int key, int value)
         g.opt_park_end = value; return 0;
     case SVR_OPT_SPLIT:
         if (value < 0 || value > 2) return fail(-6, "SVR_OPT_SPLIT: bad value %d (0 off, 1 or 2 on)", value);
-        g.opt_split = value; g.split_alloc_failed = false; return 0;
+        g.opt_split = value; return 0;
     case SVR_OPT_ENV_NEE: g.opt_env_nee = value ? 1 : 0; g.ahead[0].valid = g.ahead[1].valid = false; return 0;
     case SVR_OPT_NAN_GUARD: g.opt_nan_guard = value ? 1 : 0; return 0;
     case SVR_OPT_FAST_BOUND: g.opt_fast_bound = value ? 1 : 0; return 0;

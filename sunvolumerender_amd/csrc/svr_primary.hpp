@@ -1,5 +1,4 @@
-// svr_primary.hpp -- a path up to its first scatter event, shared by the tile kernel (svr_trace_tile.hip) and the split kernels of
-// deeper paths (svr_trace_split.hip).
+// svr_primary.hpp -- a path up to its first scatter event, for the QUEUE builds of the tile kernel (svr_trace_tile.hip).
 #pragma once
 #include "svr_walk.hpp"
 #include "svr_lanes.hpp"

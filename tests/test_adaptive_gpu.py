@@ -144,7 +144,7 @@ CASES = [
     ("tiny_head_noisy", 1, {}, 0),                                   # media without exactly transparent space: pooled primary walks
     ("tiny_bone", 1, {}, 0),
     ("tiny_head", 1, {abi.OPT_FOLD: 0}, 0),                           # scratch slots + k_resolve
-    ("tiny_head", 3, {abi.OPT_SPLIT: 1}, 0),                          # the two split kernels
+    ("tiny_head", 3, {abi.OPT_SPLIT: 1}, 0),                          # the retired SVR_OPT_SPLIT: changes nothing
     ("tiny_head", 2, {abi.OPT_LOCAL_MAJORANT: 1}, 0),                 # local-majorant pools (against their own uniform render)
     ("tiny_head_env", 3, {abi.OPT_ENV_NEE: 1}, 0),                    # env-map importance sampling (against its own uniform render)
     ("tiny_head", 1, {}, 8),                                          # f0 > 0: on from a uniform 8-frame accumulator

@@ -904,10 +904,9 @@ def test_nan_guard_drops_non_finite_samples(hip_dev, depth):
 
 @pytest.mark.parametrize("name,depth", [("tiny_head", 2), ("tiny_head", 4), ("tiny_bone", 6), ("small_head", 3), ("odd", 3), ("tiny_head_noisy", 3)])
 def test_split_kernels_bit_exact(hip_dev, name, depth):
-    """Deeper paths as two kernels (csrc/svr_trace_split.hip: front half -> chunks of path records -> lane machine -> scratch slots -> k_resolve),
-    forced on (SVR_OPT_SPLIT = 2: from traceDepth 2) and off, one 70-frame call (a 64-frame and a 6-frame launch: the short one takes the ordinary
-    path) and one 40-frame call; production and counting builds against the oracle: accumulator, image and the reference's counters.
-    (tiny_head_noisy: its primary walks are pooled, so the fused kernel renders whatever the switch says.)"""
+    """Deeper paths with the retired SVR_OPT_SPLIT at 2 (it once chose a two-kernel form from traceDepth 2) and at 0: the option changes nothing.
+    One 70-frame call (a 64-frame and a 6-frame launch: the short one goes through the scratch slots) and one 40-frame call; production and
+    counting builds against the oracle: accumulator, image and the reference's counters."""
     from tests.test_local_majorant_gpu import _make
     sc = _make(name, trace_depth=depth)
     for frames in (70, 40):
@@ -926,9 +925,9 @@ def test_split_kernels_bit_exact(hip_dev, name, depth):
 
 @pytest.mark.parametrize("case", ["window", "shard", "window_direct", "shard_direct"])
 def test_split_and_direct_builds_under_a_window_and_a_row_shard(hip_dev, case):
-    """The round-4 launch forms where pixels are not the whole frame: the two-kernel form of deeper paths (path ids = frame << 26 | GLOBAL pixel index)
-    and the DIRECT queue builds of frames traced ahead (a path writes its scratch slot itself), under a render window and under an interleaved row
-    shard; against the oracle on the owned pixels, untouched elsewhere."""
+    """The round-4 launch forms where pixels are not the whole frame: many-frame launches of deeper paths with the retired SVR_OPT_SPLIT at 2 (it
+    changes nothing) and the DIRECT queue builds of frames traced ahead (a path writes its scratch slot itself), under a render window and under an
+    interleaved row shard; against the oracle on the owned pixels, untouched elsewhere."""
     sc = scenes.make_scene("small_head", trace_depth=3 if "direct" not in case else 1)
     kw = dict(window=(37, 50, 201, 190)) if "window" in case else dict(shard=(8, 2, 3))
     frames = 72

@@ -2,7 +2,7 @@
 """Turn a tools/profile.sh summary into the per-launch PMC record bench.py reads (profiles/r04_pmc_<tag>.json).
 Usage: tools/pmc_json.py <summary.txt> <kernel-prefix>[+<kernel-prefix>...] <tag> <out.json> [note]
 Counters are per-dispatch averages of separate rocprofv3 --pmc passes; several prefixes joined by '+' are kernels that are each dispatched
-once per launch (the split kernels of deeper paths: k_split_front+k_split_machine): their counters and durations are summed.
+once per launch (a trace kernel and the resolve behind it: k_trace_env+k_resolve): their counters and durations are summed.
 FETCH_SIZE is doubled per the gfx950 correction of MI355X_MICROARCH.md (HBM section).  The correction was calibrated for THIS code's access
 pattern (16-byte gathers, one per lane: profiles/r04_fetch_size_calibration.txt): one TCC_EA0_RDREQ per missing gather, tallied at 64 B,
 while a miss moves the whole 128-byte line (whole-line and half-line random reads run at the same request rate) -- so the factor 2
