@@ -2,8 +2,10 @@
 // without the GUI: load a MetaImage volume, the GUI-default (or a saved .tf) transfer function, one area light, an
 // optional .hdr environment map; render N progressive frames (or, with -noise T, until the predicted RMSE of the tone-mapped
 // image is <= T, at most N frames; with -adaptive T, 16 x 16 tiles stop once their predicted RMSE is <= T); write the image as TGA.
+// -mip / -mean / -iso LEVEL draw one projection image instead (svr_render_projection): maximum intensity, mean intensity through the
+// grey window -window LO HI (default 0 1), or the head-light shaded isosurface at LEVEL; -tfcolor colours them with the transfer function.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -14,13 +16,14 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
     float noiseTarget = 0.f;                                        // 0: render exactly -frames frames
     float adaptiveTarget = 0.f;                                     // > 0: adaptive sampling, tiles stop at this predicted RMSE
-    bool raycast = false;
+    bool raycast = false, project = false;
+    svr_projection_params proj = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
         else if (!strcmp(argv[i], "-env") && i + 1 < argc) envFile = argv[++i];
@@ -28,6 +31,11 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-depth") && i + 1 < argc) depth = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-size") && i + 2 < argc) { W = atoi(argv[i + 1]); H = atoi(argv[i + 2]); i += 2; }
         else if (!strcmp(argv[i], "-raycast")) raycast = true;
+        else if (!strcmp(argv[i], "-mip")) { project = true; proj.mode = SVR_PROJ_MIP; }
+        else if (!strcmp(argv[i], "-mean")) { project = true; proj.mode = SVR_PROJ_MEAN; }
+        else if (!strcmp(argv[i], "-iso") && i + 1 < argc) { project = true; proj.mode = SVR_PROJ_ISO; proj.iso = strtof(argv[++i], nullptr); }
+        else if (!strcmp(argv[i], "-window") && i + 2 < argc) { proj.window_lo = strtof(argv[i + 1], nullptr); proj.window_hi = strtof(argv[i + 2], nullptr); i += 2; }
+        else if (!strcmp(argv[i], "-tfcolor")) proj.flags |= SVR_PROJ_COLOR_TF;
         else if (!strcmp(argv[i], "-denoise-preview") && i + 1 < argc) denoisePreview = atoi(argv[++i]);   // denoised image up to N spp
         else if (!strcmp(argv[i], "-noise") && i + 1 < argc) {                                          // render until converged
             char* end = nullptr;
@@ -80,7 +88,9 @@ int main(int argc, char** argv)
             svr_set_option(SVR_OPT_ENV_ON_ESCAPE, 1);
         }
         canvas.SetScatterTimes(depth);
-        canvas.SetRenderMode(raycast ? RENDER_MODE_RAYCASTING : RENDER_MODE_PATHTRACER);
+        canvas.SetRenderMode(project ? RENDER_MODE_PROJECTION : (raycast ? RENDER_MODE_RAYCASTING : RENDER_MODE_PATHTRACER));
+        canvas.SetProjection(proj);
+        raycast = raycast || project;                                  // one deterministic image either way
         canvas.SetDenoisePreview(denoisePreview);
 
         if (adaptiveTarget > 0.f && !raycast) {
@@ -103,6 +113,7 @@ int main(int argc, char** argv)
                    noiseTarget, used, ms, e.frames, e.frames_ref, e.rmse, e.tile_max, (unsigned long long)e.pixels, (unsigned long long)e.nonfinite);
         } else
             for (int f = 0; f < (raycast ? 1 : frames); ++f) canvas.paintGL();
+        if (svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         if (!canvas.SaveImage(out)) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%u frame(s) on %s -> %s\n", canvas.FrameNo(), svr_device_info(), out.c_str());
     }

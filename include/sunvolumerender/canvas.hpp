@@ -197,7 +197,7 @@ private:
 // ---------------------------------------------------------------------------------------------------
 // gui/canvas.h
 // ---------------------------------------------------------------------------------------------------
-enum RenderMode { RENDER_MODE_PATHTRACER, RENDER_MODE_RAYCASTING };
+enum RenderMode { RENDER_MODE_PATHTRACER, RENDER_MODE_RAYCASTING, RENDER_MODE_PROJECTION /* extension: svr_render_projection with the SetProjection parameters */ };
 
 class Canvas {
 public:
@@ -251,6 +251,8 @@ public:
     void SetGradientFactor(double g) { deviceVolume.SetGradientFactor((float)g); setup_volume(deviceVolume); ReStartRender(); }
     void SetScatterTimes(double val) { renderParams.traceDepth = (uint32_t)val; ReStartRender(); }
     void SetRenderMode(RenderMode mode) { renderMode = mode; ReStartRender(); }
+    // extension: what RENDER_MODE_PROJECTION draws (maximum / mean intensity projection, isosurface; include/svr_abi.h)
+    void SetProjection(const svr_projection_params& p) { projection = p; ReStartRender(); }
 
     // lights, canvas.h:96-133
     void SetEnvLightBackground(const glm::vec3& color) { lights.SetEnvionmentLight(color); setup_env_lights(lights.environmentLight); ReStartRender(); }
@@ -304,6 +306,8 @@ public:
         if (!ready) return;
         if (renderMode == RENDER_MODE_RAYCASTING)
             render_raycasting(img, deviceVolume, transferFunction, camera, volumeReader->GetElementBoundingSphereRadius());
+        else if (renderMode == RENDER_MODE_PROJECTION)
+            svr_render_projection(img, &deviceVolume, &transferFunction, &camera, volumeReader->GetElementBoundingSphereRadius(), &projection);
         else {
             render_pathtracer(img, renderParams);
             if (renderParams.frameNo == 0 && dumpFirstFrame) SaveImage("0.tga");   // canvas.cpp:97-104
@@ -392,6 +396,7 @@ private:
     cudaVolume deviceVolume;
     cudaTransferFunction transferFunction;
     RenderMode renderMode = RENDER_MODE_RAYCASTING;
+    svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
 };
 
 #endif  // SUNVOLUMERENDER_CANVAS_HPP

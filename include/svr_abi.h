@@ -461,6 +461,49 @@ int svr_render_pathtracer_adaptive(void* img, svr_render_params* renderParams, f
  * Synchronises the library's stream */
 int svr_get_adaptive_tiles(uint32_t* tile_frames_device, float* tile_rmse_device);
 
+/* ---- projection modes of the ray caster (csrc/svr_project.hip) ----
+ * One deterministic ray per pixel, stateless, scene by argument like render_raycasting.  Everything below is float32 without contraction.
+ * RAY AND SAMPLES: exactly the ray caster's.  The pinhole centre ray of the pixel (cuda_camera.h:85-95), the clipped box interval
+ *   [tNear, tFar] of volume.Intersect, samples t_0 = tNear, t_{n+1} = fl(t_n + h) with h = stepSize * 0.5f, while t_n <= tFar;
+ *   p(t) = orig + dir * t and I_n = volume(p(t_n)), the ray caster's sampler (trilinear on raw u16, x 1/65535, x densityScale).
+ *   N = the number of samples the mode looks at: all of them for MIP and MEAN; for ISO the samples up to and including the first
+ *   crossing n*, all of them if there is none.
+ * MISS (no intersection): RGBA8 (0, 0, 0, 0).
+ * MIP:  M = max(0.0f, I_0, ..., I_{N-1}).
+ * MEAN: S_0 = 0, S_{n+1} = fl(S_n + I_n) in sample order, M = S_N / (float)N (a correctly rounded division).
+ * COLOUR of MIP / MEAN: grey g = clamp((M - window_lo) / (window_hi - window_lo), 0, 1) -- one subtraction each, one correctly rounded
+ *   division -- rgb = (g, g, g).  With SVR_PROJ_COLOR_TF: rgb = the transfer function's rgb at M (the ray caster's table look-up), each
+ *   channel clamped to [0, 1].  Alpha 255.  Conversion to u8 as the ray caster's: truncation of c * 255.
+ * ISO:  n* = the first n with I_n >= iso; none: RGBA8 (0, 0, 0, 0).  If n* = 0 the surface parameter is t_0 (the box face or a clip cap).
+ *   Otherwise bisect 8 times: lo = t_{n*-1}, hi = t_{n*}; mid = 0.5f * (lo + hi); volume(p(mid)) >= iso ? hi = mid : lo = mid.  The
+ *   surface point is P = p(hi).  Shading is the ray caster's head-light term (raycasting.cu:40-58) with opacity 1: the central-difference
+ *   gradient at P, cosTerm = 1 and specularTerm = 0 unless its magnitude is > 1e-3, else normal = normalize(gradient), lightDir =
+ *   normalize(cam.pos - P) (normalize(v) = v * (1 / sqrt(dot))), cosTerm = |dot(normal, lightDir)|, specularTerm = powf(cosTerm, 30);
+ *   channel = base * 1 * cosTerm * 0.8f + 1 * specularTerm * 0.2f, clamped to 1, with base = 1 (white) or, with SVR_PROJ_COLOR_TF, the
+ *   transfer function's rgb at volume(P) (a value the search has already fetched).  Alpha 255.
+ * The call honours svr_set_row_shard, svr_set_render_window (pixels outside stay untouched), svr_set_stream, the error mode,
+ * SVR_OPT_EMPTY_SKIP (1: samples that provably cannot change the result are not fetched, and runs of them are passed in closed form;
+ * 0: every sample is fetched; identical images) and SVR_OPT_COUNT: raycast_steps += N, vol_taps += the fetches of the definition (N per
+ * ray, + 8 per bisected pixel, + 6 for the gradient of a surface pixel), vol_taps_executed += the fetches issued.
+ * It returns non-zero and leaves img untouched for: a null argument, an unknown mode or flag, a stepSize that is not finite and > 0, a
+ * non-finite iso, a non-finite window or window_hi <= window_lo, a negative or non-finite densityScale. */
+#define SVR_PROJ_MIP  1   /* largest sample along the ray */
+#define SVR_PROJ_MEAN 2   /* mean of the samples along the ray */
+#define SVR_PROJ_ISO  3   /* first crossing of `iso`, refined, head-light shaded */
+
+#define SVR_PROJ_COLOR_TF 1u  /* flags: colour from the transfer function, else grey / white */
+
+typedef struct svr_projection_params {
+    int32_t  mode;            /* SVR_PROJ_* */
+    uint32_t flags;
+    float    iso;             /* SVR_PROJ_ISO: level, in the units volume(p) returns */
+    float    window_lo, window_hi;   /* grey mapping for MIP / MEAN */
+} svr_projection_params;
+
+int svr_projection_params_default(svr_projection_params* p);   /* MIP, grey, window 0..1, iso 0.5 */
+int svr_render_projection(void* img, const svr_volume* volume, const svr_transfer_function* tf,
+                          const svr_camera* camera, float stepSize, const svr_projection_params* p);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

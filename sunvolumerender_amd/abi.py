@@ -173,6 +173,24 @@ class AdaptiveResult(C.Structure):  # svr_adaptive_result
 svr_adaptive_result = AdaptiveResult
 
 
+class ProjectionParams(C.Structure):  # svr_projection_params
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("flags", C.c_uint32),
+        ("iso", C.c_float),
+        ("window_lo", C.c_float),
+        ("window_hi", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+svr_projection_params = ProjectionParams
+PROJ_MIP, PROJ_MEAN, PROJ_ISO = 1, 2, 3
+PROJ_COLOR_TF = 1
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -187,6 +205,7 @@ EXPECTED_SIZES = {
     DenoiseParams: 28,
     NoiseEstimate: 48,
     AdaptiveResult: 64,
+    ProjectionParams: 20,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -302,6 +321,8 @@ PROTOTYPES = {
     "svr_render_pathtracer_until": (C.c_int, [C.c_void_p, _P(RenderParams), C.c_float, C.c_float, C.c_uint32, _P(C.c_uint32)]),
     "svr_render_pathtracer_adaptive": (C.c_int, [C.c_void_p, _P(RenderParams), C.c_float, C.c_uint32, C.c_uint32, _P(AdaptiveResult)]),
     "svr_get_adaptive_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "svr_projection_params_default": (C.c_int, [_P(ProjectionParams)]),
+    "svr_render_projection": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), _P(cudaCamera), C.c_float, _P(ProjectionParams)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

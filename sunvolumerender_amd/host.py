@@ -499,6 +499,17 @@ class Canvas:
             self.dev.synchronize()
         self.renderParams.frameNo += int(nframes)
 
+    # ---- extension: projection modes of the ray caster (svr_render_projection) ----
+    def paint_projection(self, mode: int, iso: float = 0.5, window=(0.0, 1.0), color_tf: bool = False, sync: bool = False):
+        """One maximum-intensity (abi.PROJ_MIP), mean-intensity (abi.PROJ_MEAN) or isosurface (abi.PROJ_ISO) image of the canvas's
+        volume, transfer function and camera at its step size into the canvas image.  Stateless: the render mode, the accumulator and
+        frameNo are untouched.  window = the grey mapping (lo, hi) of MIP / MEAN; color_tf: colours from the transfer function."""
+        p = abi.ProjectionParams(int(mode), abi.PROJ_COLOR_TF if color_tf else 0, float(iso), float(window[0]), float(window[1]))
+        self.dev.check(self.lib.svr_render_projection(C.c_void_p(self.img), C.byref(self.deviceVolume), C.byref(self.transferFunction),
+                                                      C.byref(self.camera), C.c_float(self.stepSize), C.byref(p)))
+        if sync:
+            self.dev.synchronize()
+
     # ---- extension: denoised preview of the first frames after a restart ----
     def SetDenoisePreview(self, frames: int, params: Optional[abi.DenoiseParams] = None):
         """SVR_OPT_DENOISE_PREVIEW = frames (0 = off): the image of a frame with at most `frames` samples per pixel is the
