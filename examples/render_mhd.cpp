@@ -4,19 +4,24 @@
 // image is <= T, at most N frames; with -adaptive T, 16 x 16 tiles stop once their predicted RMSE is <= T); write the image as TGA.
 // -mip / -mean / -iso LEVEL draw one projection image instead (svr_render_projection): maximum intensity, mean intensity through the
 // grey window -window LO HI (default 0 1), or the head-light shaded isosurface at LEVEL; -tfcolor colours them with the transfer function.
+// -slice x|y|z POS draws the plane perpendicular to that axis at POS in [0, 1] across the volume (svr_render_slice; -window and -tfcolor
+// apply); -slab THICKNESS mip|minip|mean thickens it into a slab (world units, one sample per pixel size); -stack N writes N parallel
+// slices from POS to the far face as name_0000.tga ... in one launch (svr_render_slice_stack).
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <string>
+#include <vector>
 
 #include "sunvolumerender/canvas.hpp"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -24,6 +29,8 @@ int main(int argc, char** argv)
     float adaptiveTarget = 0.f;                                     // > 0: adaptive sampling, tiles stop at this predicted RMSE
     bool raycast = false, project = false;
     svr_projection_params proj = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
+    int sliceAxis = -1, stack = 0, slabMode = 0;                    // -slice: axis 0 / 1 / 2; -stack: slices; -slab: SVR_SLAB_*
+    float slicePos = 0.5f, slabThickness = 0.f;
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
         else if (!strcmp(argv[i], "-env") && i + 1 < argc) envFile = argv[++i];
@@ -34,6 +41,24 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-mip")) { project = true; proj.mode = SVR_PROJ_MIP; }
         else if (!strcmp(argv[i], "-mean")) { project = true; proj.mode = SVR_PROJ_MEAN; }
         else if (!strcmp(argv[i], "-iso") && i + 1 < argc) { project = true; proj.mode = SVR_PROJ_ISO; proj.iso = strtof(argv[++i], nullptr); }
+        else if (!strcmp(argv[i], "-slice") && i + 2 < argc) {
+            const char* a = argv[i + 1];
+            sliceAxis = (a[0] == 'x' || a[0] == 'y' || a[0] == 'z') && a[1] == '\0' ? a[0] - 'x' : -1;
+            slicePos = strtof(argv[i + 2], nullptr);
+            if (sliceAxis < 0 || !(slicePos >= 0.f && slicePos <= 1.f)) { fprintf(stderr, "-slice needs an axis x, y or z and a position in [0, 1] (got %s %s)\n", a, argv[i + 2]); return 2; }
+            i += 2;
+        }
+        else if (!strcmp(argv[i], "-slab") && i + 2 < argc) {
+            slabThickness = strtof(argv[i + 1], nullptr);
+            const char* m = argv[i + 2];
+            slabMode = !strcmp(m, "mip") ? SVR_SLAB_MIP : !strcmp(m, "minip") ? SVR_SLAB_MINIP : !strcmp(m, "mean") ? SVR_SLAB_MEAN : 0;
+            if (!(slabThickness > 0.f) || !slabMode) { fprintf(stderr, "-slab needs a thickness > 0 and mip, minip or mean (got %s %s)\n", argv[i + 1], m); return 2; }
+            i += 2;
+        }
+        else if (!strcmp(argv[i], "-stack") && i + 1 < argc) {
+            stack = atoi(argv[++i]);
+            if (stack < 1 || stack > 9999) { fprintf(stderr, "-stack needs 1 .. 9999 slices (got %s)\n", argv[i]); return 2; }
+        }
         else if (!strcmp(argv[i], "-window") && i + 2 < argc) { proj.window_lo = strtof(argv[i + 1], nullptr); proj.window_hi = strtof(argv[i + 2], nullptr); i += 2; }
         else if (!strcmp(argv[i], "-tfcolor")) proj.flags |= SVR_PROJ_COLOR_TF;
         else if (!strcmp(argv[i], "-denoise-preview") && i + 1 < argc) denoisePreview = atoi(argv[++i]);   // denoised image up to N spp
@@ -50,6 +75,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if ((slabMode || stack) && sliceAxis < 0) { fprintf(stderr, "-slab and -stack need -slice\n"); return 2; }
     if (svr_init(0)) return 1;
     {
         Canvas canvas(W, H);
@@ -92,6 +118,47 @@ int main(int argc, char** argv)
         canvas.SetProjection(proj);
         raycast = raycast || project;                                  // one deterministic image either way
         canvas.SetDenoisePreview(denoisePreview);
+
+        if (sliceAxis >= 0) {
+            // one slice (or a stack of them) instead of a rendering
+            if (canvas.SetSlice(sliceAxis, slicePos) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            svr_slice_params sp = canvas.Slice();
+            if (slabMode) { sp.thickness = slabThickness; sp.mode = slabMode; sp.step = sqrtf(sp.u.x * sp.u.x + sp.u.y * sp.u.y + sp.u.z * sp.u.z); }
+            sp.window_lo = proj.window_lo; sp.window_hi = proj.window_hi;
+            sp.flags = (proj.flags & SVR_PROJ_COLOR_TF) ? SVR_SLICE_COLOR_TF : 0u;
+            canvas.SetSlice(sp);
+            if (stack == 0) {
+                canvas.SetRenderMode(RENDER_MODE_SLICE);
+                canvas.paintGL();
+                if (svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (!canvas.SaveImage(out)) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                printf("slice %c at %g on %s -> %s\n", "xyz"[sliceAxis], slicePos, svr_device_info(), out.c_str());
+            } else {
+                // from POS to the far face along the plane's normal n = normalize(cross(u, v)): -x, +y, -z for the three axes
+                svr_slice_params far;
+                if (svr_slice_params_axis(&far, &canvas.Volume(), sliceAxis, sliceAxis == 1 ? 1.f : 0.f, (uint32_t)W, (uint32_t)H) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                const float c0 = sliceAxis == 0 ? sp.center.x : sliceAxis == 1 ? sp.center.y : sp.center.z;
+                const float c1 = sliceAxis == 0 ? far.center.x : sliceAxis == 1 ? far.center.y : far.center.z;
+                const float spacing = stack > 1 ? fabsf(c1 - c0) / (float)(stack - 1) : 0.f;
+                const size_t bytes = (size_t)W * H * 4;
+                void* imgs = svr_device_malloc(bytes * (size_t)stack);
+                if (!imgs) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                const int rc = svr_render_slice_stack(imgs, &canvas.Volume(), &canvas.TransferFunctionPod(), (uint32_t)W, (uint32_t)H, &sp, (uint32_t)stack, spacing);
+                std::vector<uint8_t> host(bytes);
+                const std::string stem = out.size() > 4 && out.compare(out.size() - 4, 4, ".tga") == 0 ? out.substr(0, out.size() - 4) : out;
+                for (int k = 0; rc == 0 && k < stack; ++k) {
+                    char name[32];
+                    snprintf(name, sizeof name, "_%04d.tga", k);
+                    if (svr_memcpy_d2h(host.data(), (const uint8_t*)imgs + bytes * (size_t)k, bytes) != 0 ||
+                        svr_tga_write((stem + name).c_str(), W, H, host.data()) != 0) break;
+                }
+                svr_device_free(imgs);
+                if (rc != 0 || svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                printf("%d slices %c from %g, %g apart, on %s -> %s_0000.tga ...\n", stack, "xyz"[sliceAxis], slicePos, spacing, svr_device_info(), stem.c_str());
+            }
+            svr_shutdown();
+            return 0;
+        }
 
         if (adaptiveTarget > 0.f && !raycast) {
             const auto t0 = std::chrono::steady_clock::now();

@@ -197,7 +197,8 @@ private:
 // ---------------------------------------------------------------------------------------------------
 // gui/canvas.h
 // ---------------------------------------------------------------------------------------------------
-enum RenderMode { RENDER_MODE_PATHTRACER, RENDER_MODE_RAYCASTING, RENDER_MODE_PROJECTION /* extension: svr_render_projection with the SetProjection parameters */ };
+enum RenderMode { RENDER_MODE_PATHTRACER, RENDER_MODE_RAYCASTING, RENDER_MODE_PROJECTION /* extension: svr_render_projection with the SetProjection parameters */,
+                  RENDER_MODE_SLICE /* extension: svr_render_slice with the SetSlice parameters */ };
 
 class Canvas {
 public:
@@ -253,6 +254,20 @@ public:
     void SetRenderMode(RenderMode mode) { renderMode = mode; ReStartRender(); }
     // extension: what RENDER_MODE_PROJECTION draws (maximum / mean intensity projection, isosurface; include/svr_abi.h)
     void SetProjection(const svr_projection_params& p) { projection = p; ReStartRender(); }
+    // extension: what RENDER_MODE_SLICE draws (a plane or slab through the volume; include/svr_abi.h)
+    void SetSlice(const svr_slice_params& p) { slice = p; ReStartRender(); }
+    // ... the plane perpendicular to world axis 0 / 1 / 2 at `position` in [0, 1] across the clipped box, fitted to the canvas; the slab
+    // (thickness, step, mode), the window and the flags stay as they are.  Returns svr_slice_params_axis's status
+    int SetSlice(int axis, float position)
+    {
+        svr_slice_params p;
+        const int rc = svr_slice_params_axis(&p, &deviceVolume, axis, position, (uint32_t)WIDTH, (uint32_t)HEIGHT);
+        if (rc != 0) return rc;
+        slice.center = p.center; slice.u = p.u; slice.v = p.v;
+        ReStartRender();
+        return 0;
+    }
+    const svr_slice_params& Slice() const { return slice; }
 
     // lights, canvas.h:96-133
     void SetEnvLightBackground(const glm::vec3& color) { lights.SetEnvionmentLight(color); setup_env_lights(lights.environmentLight); ReStartRender(); }
@@ -308,6 +323,8 @@ public:
             render_raycasting(img, deviceVolume, transferFunction, camera, volumeReader->GetElementBoundingSphereRadius());
         else if (renderMode == RENDER_MODE_PROJECTION)
             svr_render_projection(img, &deviceVolume, &transferFunction, &camera, volumeReader->GetElementBoundingSphereRadius(), &projection);
+        else if (renderMode == RENDER_MODE_SLICE)
+            svr_render_slice(img, &deviceVolume, &transferFunction, (uint32_t)WIDTH, (uint32_t)HEIGHT, &slice);
         else {
             render_pathtracer(img, renderParams);
             if (renderParams.frameNo == 0 && dumpFirstFrame) SaveImage("0.tga");   // canvas.cpp:97-104
@@ -363,6 +380,7 @@ public:
     void* HdrBuffer() const { return renderParams.hdrBuffer; }               // the accumulator (device): what svr_assemble_frame sends
     const cudaCamera& Camera() const { return camera; }
     const cudaVolume& Volume() const { return deviceVolume; }
+    const cudaTransferFunction& TransferFunctionPod() const { return transferFunction; }   // (TransferFunction is the editor class above)
 
     VolumeReader* volumeReader;
     Lights lights;
@@ -397,6 +415,7 @@ private:
     cudaTransferFunction transferFunction;
     RenderMode renderMode = RENDER_MODE_RAYCASTING;
     svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
+    svr_slice_params slice = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, 0.f, 1.f, SVR_SLAB_MIP, 0u, 0.f, 1.f};
 };
 
 #endif  // SUNVOLUMERENDER_CANVAS_HPP

@@ -504,6 +504,66 @@ int svr_projection_params_default(svr_projection_params* p);   /* MIP, grey, win
 int svr_render_projection(void* img, const svr_volume* volume, const svr_transfer_function* tf,
                           const svr_camera* camera, float stepSize, const svr_projection_params* p);
 
+/* ---- slice views: a plane through the volume, optionally thickened into a slab (csrc/svr_slice.hip) ----
+ * One deterministic pixel value per pixel, stateless, scene by argument, no camera: the image is an orthographic window of w x h pixels
+ * onto the plane through `center` spanned by u and v.  Everything below is float32 without contraction; x, y, w, h, k are converted to
+ * float exactly.
+ * FRAME: cr = cross(u, v) = (u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x) (two products and one subtraction per
+ *   component), n = cr * (1 / sqrt((cr.x * cr.x + cr.y * cr.y) + cr.z * cr.z)) (correctly rounded square root and division).
+ * SLICE k of a stack (k = 0 .. count - 1; svr_render_slice is slice 0 alone): center_0 = center; for k > 0
+ *   center_k = center + n * fl(spacing * (float)k), per component one product and one addition.
+ * PLANE POINT of pixel (x, y), y counted downwards: a = ((float)x + 0.5f) - 0.5f * (float)w, b = ((float)y + 0.5f) - 0.5f * (float)h,
+ *   c = (center_k + u * a) + v * b, per component one product and one addition each, in this order.
+ * SLAB SAMPLES: thickness == 0: K = 1 and d_0 = 0 (step and mode are not looked at beyond the checks below).  thickness > 0:
+ *   K = (int)floor(thickness / step) + 1 (a correctly rounded division) and d_j = fl(fl((float)j * step) - fl(0.5f * thickness)) -- a
+ *   product, not a running sum.  Sample point p_j = c + n * d_j, per component one product and one addition, j = 0 .. K - 1.
+ * BOX: the box volume.Intersect clips to (core/geometry/cuda_bbox.h:38-39): per axis e0 = bbox.vmin * (-clip.x), e1 = bbox.vmax * clip.y
+ *   (clip = x_clip, y_clip, z_clip), lo = min(e0, e1), hi = max(e0, e1).  Sample j COUNTS iff lo <= p_j <= hi on all three axes (closed
+ *   comparisons on the float p_j itself).  I_j = volume(p_j), the ray caster's sampler (trilinear on raw u16, x 1/65535, x densityScale).
+ * VALUE: no sample counts: the pixel is RGBA8 (0, 0, 0, 0).  Otherwise alpha is 255 and, over the counting samples in the order of j,
+ *   thickness == 0: M = I_0;  SVR_SLAB_MIP: M = max(0.0f, I_j ...);  SVR_SLAB_MINIP: M = min(I_j ...);
+ *   SVR_SLAB_MEAN: S = 0, S = fl(S + I_j), M = S / (float)N with N the number of counting samples (a correctly rounded division).
+ * COLOUR: as MIP / MEAN of the projection section: grey g = clamp((M - window_lo) / (window_hi - window_lo), 0, 1), rgb = (g, g, g); with
+ *   SVR_SLICE_COLOR_TF the transfer function's rgb at M, each channel clamped to [0, 1].  u8 by truncation of c * 255.
+ * The calls honour svr_set_row_shard and svr_set_render_window (pixels outside stay untouched; for a stack, in every image),
+ * svr_set_stream, the error mode, SVR_OPT_EMPTY_SKIP (1: samples that provably cannot change M are not fetched; identical images) and
+ * SVR_OPT_COUNT: raycast_steps += counting samples, vol_taps += the same, vol_taps_executed += the fetches issued.  They keep no state.
+ * They return non-zero and leave the image(s) untouched for: a null argument; w or h of 0; a non-finite member of center, u, v,
+ * thickness, step, window_lo, window_hi or spacing; a cross(u, v) whose length is 0 or not finite; thickness < 0; thickness > 0 with a
+ * step that is not > 0, with an unknown mode or with floor(thickness / step) + 1 > SVR_SLICE_MAX_SAMPLES (refused, not clamped); unknown
+ * flags; window_hi <= window_lo; a negative or non-finite densityScale; count == 0; more than 2^32 - 1 tile tasks (tiles x count). */
+#define SVR_SLAB_MIP   1   /* largest sample of the slab */
+#define SVR_SLAB_MINIP 2   /* smallest sample of the slab */
+#define SVR_SLAB_MEAN  3   /* mean of the samples of the slab */
+
+#define SVR_SLICE_COLOR_TF 1u   /* flags: colour from the transfer function, else grey through the window */
+#define SVR_SLICE_MAX_SAMPLES 4096   /* most samples K of a slab */
+
+typedef struct svr_slice_params {
+    svr_vec3 center;               /* world point shown at the image centre */
+    svr_vec3 u, v;                 /* world displacement of one pixel to the right / one pixel down (length = pixel size) */
+    float    thickness;            /* slab thickness along n = normalize(cross(u, v)), world units; 0 = a single plane */
+    float    step;                 /* distance between slab samples along n; not used when thickness == 0 */
+    int32_t  mode;                 /* SVR_SLAB_*; not used when thickness == 0 */
+    uint32_t flags;
+    float    window_lo, window_hi; /* grey mapping */
+} svr_slice_params;                /* 4-byte members only, no padding: 60 bytes */
+
+/* centre 0, u = (1, 0, 0), v = (0, 1, 0), thickness 0, step 1, SVR_SLAB_MIP, grey, window 0..1.  Plain host code */
+int svr_slice_params_default(svr_slice_params* p);
+/* The plane perpendicular to world axis 0 / 1 / 2 (x / y / z) at `position` in [0, 1] across the CLIPPED box (0 = its lo face, 1 = its hi
+ * face, the BOX of the contract), fitted to w x h pixels with square pixels and the whole box face visible and centred.  Image right /
+ * down are world +y / -z for axis 0, +x / -z for axis 1, +x / -y for axis 2 (so n = -x, +y, -z); pixel size = max(extent_right /
+ * w, extent_down / h); thickness 0, step = the pixel size, SVR_SLAB_MIP, grey, window 0..1.  Plain host code: no GPU is needed.  Non-zero
+ * for a null argument, an axis outside 0..2, a position outside [0, 1], w or h of 0, a box that is not finite or has no extent. */
+int svr_slice_params_axis(svr_slice_params* p, const svr_volume* volume, int axis, float position, uint32_t w, uint32_t h);
+/* one slice into img (w x h RGBA8, device memory) */
+int svr_render_slice(void* img, const svr_volume* volume, const svr_transfer_function* tf, uint32_t w, uint32_t h,
+                     const svr_slice_params* p);
+/* `count` parallel slices in one launch: slice k as defined above; writes count images of w x h RGBA8 back to back */
+int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_transfer_function* tf, uint32_t w, uint32_t h,
+                           const svr_slice_params* p, uint32_t count, float spacing);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

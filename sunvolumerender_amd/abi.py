@@ -191,6 +191,29 @@ PROJ_MIP, PROJ_MEAN, PROJ_ISO = 1, 2, 3
 PROJ_COLOR_TF = 1
 
 
+class SliceParams(C.Structure):  # svr_slice_params
+    _fields_ = [
+        ("center", vec3),
+        ("u", vec3),
+        ("v", vec3),
+        ("thickness", C.c_float),
+        ("step", C.c_float),
+        ("mode", C.c_int32),
+        ("flags", C.c_uint32),
+        ("window_lo", C.c_float),
+        ("window_hi", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {n: ((getattr(self, n).x, getattr(self, n).y, getattr(self, n).z) if t is vec3 else getattr(self, n)) for n, t in self._fields_}
+
+
+svr_slice_params = SliceParams
+SLAB_MIP, SLAB_MINIP, SLAB_MEAN = 1, 2, 3
+SLICE_COLOR_TF = 1
+SLICE_MAX_SAMPLES = 4096
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -206,6 +229,7 @@ EXPECTED_SIZES = {
     NoiseEstimate: 48,
     AdaptiveResult: 64,
     ProjectionParams: 20,
+    SliceParams: 60,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -323,6 +347,11 @@ PROTOTYPES = {
     "svr_get_adaptive_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "svr_projection_params_default": (C.c_int, [_P(ProjectionParams)]),
     "svr_render_projection": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), _P(cudaCamera), C.c_float, _P(ProjectionParams)]),
+    "svr_slice_params_default": (C.c_int, [_P(SliceParams)]),
+    "svr_slice_params_axis": (C.c_int, [_P(SliceParams), _P(cudaVolume), C.c_int, C.c_float, C.c_uint32, C.c_uint32]),
+    "svr_render_slice": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), C.c_uint32, C.c_uint32, _P(SliceParams)]),
+    "svr_render_slice_stack": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), C.c_uint32, C.c_uint32, _P(SliceParams),
+                                         C.c_uint32, C.c_float]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

@@ -281,6 +281,32 @@ class Device:
         return est
 
 
+def slice_params_axis(lib, volume: cudaVolume, axis: int, position: float, w: int, h: int) -> abi.SliceParams:
+    """svr_slice_params_axis: the plane perpendicular to world axis 0 / 1 / 2 at `position` in [0, 1] across the clipped box of
+    `volume`, fitted to w x h pixels.  Host code of the library: no device is needed."""
+    p = abi.SliceParams()
+    if lib.svr_slice_params_axis(C.byref(p), C.byref(volume), int(axis), C.c_float(float(position)), int(w), int(h)) != 0:
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise SvrError(f"svr_slice_params_axis: {msg}")
+    return p
+
+
+def _slice_params(params, thickness, step, mode, window, color_tf) -> abi.SliceParams:
+    p = abi.SliceParams.from_buffer_copy(params)
+    if thickness is not None:
+        p.thickness = float(thickness)
+    if step is not None:
+        p.step = float(step)
+    if mode is not None:
+        p.mode = int(mode)
+    if window is not None:
+        p.window_lo, p.window_hi = float(window[0]), float(window[1])
+    if color_tf is not None:
+        p.flags = (p.flags & ~abi.SLICE_COLOR_TF) | (abi.SLICE_COLOR_TF if color_tf else 0)
+    return p
+
+
 class Canvas:
     """Headless replay of the reference's Qt `Canvas` render protocol (gui/canvas.{h,cpp}).
 
@@ -507,6 +533,33 @@ class Canvas:
         p = abi.ProjectionParams(int(mode), abi.PROJ_COLOR_TF if color_tf else 0, float(iso), float(window[0]), float(window[1]))
         self.dev.check(self.lib.svr_render_projection(C.c_void_p(self.img), C.byref(self.deviceVolume), C.byref(self.transferFunction),
                                                       C.byref(self.camera), C.c_float(self.stepSize), C.byref(p)))
+        if sync:
+            self.dev.synchronize()
+
+    # ---- extension: slice views (svr_render_slice, svr_render_slice_stack) ----
+    def slice_params_axis(self, axis: int, position: float, w: Optional[int] = None, h: Optional[int] = None) -> abi.SliceParams:
+        """svr_slice_params for the plane perpendicular to world axis 0 / 1 / 2 at `position` in [0, 1] across the clipped box of the
+        canvas's volume, fitted to w x h pixels (default: the canvas)."""
+        return slice_params_axis(self.lib, self.deviceVolume, axis, position, self.W if w is None else w, self.H if h is None else h)
+
+    def paint_slice(self, params: abi.SliceParams, thickness: Optional[float] = None, step: Optional[float] = None, mode: Optional[int] = None,
+                    window=None, color_tf: Optional[bool] = None, sync: bool = False):
+        """One slice of the canvas's volume into the canvas image: the plane (or slab) of `params`, with the named members replaced.
+        Stateless: the render mode, the accumulator and frameNo are untouched."""
+        p = _slice_params(params, thickness, step, mode, window, color_tf)
+        self.dev.check(self.lib.svr_render_slice(C.c_void_p(self.img), C.byref(self.deviceVolume), C.byref(self.transferFunction),
+                                                 self.W, self.H, C.byref(p)))
+        if sync:
+            self.dev.synchronize()
+
+    def paint_slice_stack(self, imgs: int, params: abi.SliceParams, count: int, spacing: float, thickness: Optional[float] = None,
+                          step: Optional[float] = None, mode: Optional[int] = None, window=None, color_tf: Optional[bool] = None,
+                          sync: bool = False):
+        """`count` parallel slices, `spacing` apart along the plane's normal, in one launch into the device buffer `imgs`
+        (count x H x W x 4 bytes; Device.malloc)."""
+        p = _slice_params(params, thickness, step, mode, window, color_tf)
+        self.dev.check(self.lib.svr_render_slice_stack(C.c_void_p(int(imgs)), C.byref(self.deviceVolume), C.byref(self.transferFunction),
+                                                       self.W, self.H, C.byref(p), int(count), C.c_float(float(spacing))))
         if sync:
             self.dev.synchronize()
 
