@@ -326,6 +326,32 @@ Texture* find_tex(uint64_t h, int kind)
 
 bool finite3(const svr_vec3& v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
 
+// argument checks that the image calls (ray caster, projection, slice) share; `who` is the name the message reports
+int check_step(const char* who, float stepSize)
+{
+    if (!(stepSize > 0.f) || !std::isfinite(stepSize)) return fail(-3, "%s: stepSize must be finite and > 0 (got %g)", who, (double)stepSize);
+    return 0;
+}
+int check_window(const char* who, float lo, float hi)
+{
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo))
+        return fail(-3, "%s: the window must be finite with window_hi > window_lo (got %g .. %g)", who, (double)lo, (double)hi);
+    return 0;
+}
+// (the skipping argument of svr_walk.hpp, raw_bound, needs a monotone, non-negative sampler)
+int check_density_scale(const char* who, float densityScale)
+{
+    if (!std::isfinite(densityScale) || densityScale < 0.f) return fail(-3, "%s: densityScale must be finite and >= 0 (got %g)", who, (double)densityScale);
+    return 0;
+}
+
+// the macro-cell grid of a volume texture (its min/max table, the masks built from it) as the kernels index it
+void use_macro_grid(svr::DevScene& s, const Texture* tv)
+{
+    s.mc_shift = tv->mc_shift;
+    s.mc_gx = tv->mc_gx; s.mc_gy = tv->mc_gy; s.mc_gz = tv->mc_gz; s.mc_gxy = tv->mc_gx * tv->mc_gy;
+}
+
 // Build the device scene from the PODs.  All derived values use the same float operations, in
 // the same order, as the reference's device code would (they are part of the numeric contract).
 int build_scene(const svr_volume& vol, const svr_transfer_function& tf, const svr_camera& cam,
@@ -510,6 +536,16 @@ int fill_work(svr::DevWork& w, uint32_t W, uint32_t H)
     return 0;
 }
 
+// what an image call (ray caster, projection, slice) does between its argument checks and its launch: the device scene, and the owned
+// pixels of the camera's image as the work, drawn into img
+int image_scene(const svr_volume& vol, const svr_transfer_function& tf, const svr_camera& cam, void* img, svr::DevScene& s, svr::DevWork& w)
+{
+    if (build_scene(vol, tf, cam, s)) return g.err_code;
+    fill_work(w, s.imageW, s.imageH);
+    w.img = (uint8_t*)img;
+    return 0;
+}
+
 // the whole frame, whatever shard or window is set
 void fill_work_full(svr::DevWork& w, uint32_t W, uint32_t H)
 {
@@ -600,9 +636,7 @@ int ensure_mask(svr::DevScene& s, const svr_volume& vol, const svr_transfer_func
         s.mc_hgx = hgx; s.mc_hgxy = hgx * hgy;
         s.dist_words = ((uint32_t)hgx * (uint32_t)hgy * (uint32_t)hgz + 7u) / 8u;
     }
-    s.mc_shift = tv->mc_shift;
-    s.mc_gx = tv->mc_gx; s.mc_gy = tv->mc_gy; s.mc_gz = tv->mc_gz;
-    s.mc_gxy = tv->mc_gx * tv->mc_gy;
+    use_macro_grid(s, tv);
     // macro-grid coordinate of a world point: ((p - vmin) * invSize * N + 0.5) / S  (cell c' = c + 1)
     float invS = 1.f / (float)(1 << tv->mc_shift);
     s.mc_scale[0] = s.invSize[0] * s.fnx * invS;
@@ -2055,12 +2089,10 @@ void render_raycasting(void* img, svr_volume* volume, svr_transfer_function* tra
 {
     if (ensure_init()) return;
     if (!img || !volume || !transferFunction || !camera) { fail(-4, "render_raycasting: null argument"); return; }
-    if (!(stepSize > 0.f) || !std::isfinite(stepSize)) { fail(-3, "render_raycasting: stepSize must be finite and > 0 (got %g)", (double)stepSize); return; }
+    if (check_step("render_raycasting", stepSize)) return;
     svr::DevScene s;
-    if (build_scene(*volume, *transferFunction, *camera, s)) return;
     svr::DevWork w;
-    fill_work(w, s.imageW, s.imageH);
-    w.img = (uint8_t*)img;
+    if (image_scene(*volume, *transferFunction, *camera, img, s, w)) return;
     if (ensure_mask(s, *volume, *transferFunction)) return;
     hipError_t e = svr::launch_raycast(s, w, stepSize, g.opt_count != 0, g.num_cus, g.opt_rc_lanes, g.stream);
     if (e != hipSuccess) fail((int)e, "render_raycasting launch failed: %s", hipGetErrorName(e));
@@ -2081,26 +2113,20 @@ int svr_render_projection(void* img, const svr_volume* volume, const svr_transfe
     if (!img || !volume || !tf || !camera || !p) return fail(-4, "svr_render_projection: null argument");
     if (p->mode != SVR_PROJ_MIP && p->mode != SVR_PROJ_MEAN && p->mode != SVR_PROJ_ISO) return fail(-3, "svr_render_projection: unknown mode %d", (int)p->mode);
     if (p->flags & ~SVR_PROJ_COLOR_TF) return fail(-3, "svr_render_projection: unknown flags 0x%x", (unsigned)p->flags);
-    if (!(stepSize > 0.f) || !std::isfinite(stepSize)) return fail(-3, "svr_render_projection: stepSize must be finite and > 0 (got %g)", (double)stepSize);
+    if (int e = check_step("svr_render_projection", stepSize)) return e;
     if (!std::isfinite(p->iso)) return fail(-3, "svr_render_projection: iso must be finite");
-    if (!std::isfinite(p->window_lo) || !std::isfinite(p->window_hi) || !(p->window_hi > p->window_lo))
-        return fail(-3, "svr_render_projection: the window must be finite with window_hi > window_lo (got %g .. %g)", (double)p->window_lo, (double)p->window_hi);
-    // the skipping argument needs a monotone, non-negative sampler
-    if (!std::isfinite(volume->densityScale) || volume->densityScale < 0.f)
-        return fail(-3, "svr_render_projection: densityScale must be finite and >= 0 (got %g)", (double)volume->densityScale);
+    if (int e = check_window("svr_render_projection", p->window_lo, p->window_hi)) return e;
+    if (int e = check_density_scale("svr_render_projection", volume->densityScale)) return e;
     svr::DevScene s;
-    if (build_scene(*volume, *tf, *camera, s)) return g.err_code;
     svr::DevWork w;
-    fill_work(w, s.imageW, s.imageH);
-    w.img = (uint8_t*)img;
+    if (int e = image_scene(*volume, *tf, *camera, img, s, w)) return e;
     svr::DevProjection pj;
     memset(&pj, 0, sizeof pj);
     pj.mode = p->mode; pj.flags = p->flags; pj.iso = p->iso; pj.window_lo = p->window_lo; pj.window_hi = p->window_hi;
     Texture* tv = find_tex(volume->tex, TEX_VOLUME);
     if (g.opt_empty_skip && tv && tv->mm) {
         pj.mm = tv->mm;
-        s.mc_shift = tv->mc_shift;
-        s.mc_gx = tv->mc_gx; s.mc_gy = tv->mc_gy; s.mc_gz = tv->mc_gz; s.mc_gxy = tv->mc_gx * tv->mc_gy;
+        use_macro_grid(s, tv);
         // Leaps (svr_project.hip): every sample must map into the grid (the clipped box inside the texture domain), and the float error of
         // p = orig + dir * t -- a few ulp of the largest magnitude involved, |orig| + |p| with p in the box -- must stay below 0.02 macro-cells
         const float invS = 1.f / (float)(1 << tv->mc_shift);
@@ -2195,8 +2221,7 @@ int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_trans
     if (!finite3(p->center) || !finite3(p->u) || !finite3(p->v) || !std::isfinite(p->thickness) || !std::isfinite(p->step) || !std::isfinite(spacing))
         return fail(-3, "svr_render_slice: center, u, v, thickness, step and spacing must be finite");
     if (p->flags & ~SVR_SLICE_COLOR_TF) return fail(-3, "svr_render_slice: unknown flags 0x%x", (unsigned)p->flags);
-    if (!std::isfinite(p->window_lo) || !std::isfinite(p->window_hi) || !(p->window_hi > p->window_lo))
-        return fail(-3, "svr_render_slice: the window must be finite with window_hi > window_lo (got %g .. %g)", (double)p->window_lo, (double)p->window_hi);
+    if (int e = check_window("svr_render_slice", p->window_lo, p->window_hi)) return e;
     if (p->thickness < 0.f) return fail(-3, "svr_render_slice: thickness must be >= 0 (got %g)", (double)p->thickness);
     svr::DevSlice sl;
     memset(&sl, 0, sizeof sl);
@@ -2211,9 +2236,7 @@ int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_trans
         sl.step = p->step;
         sl.half_thickness = 0.5f * p->thickness;
     }
-    // the skipping argument needs a monotone, non-negative sampler
-    if (!std::isfinite(volume->densityScale) || volume->densityScale < 0.f)
-        return fail(-3, "svr_render_slice: densityScale must be finite and >= 0 (got %g)", (double)volume->densityScale);
+    if (int e = check_density_scale("svr_render_slice", volume->densityScale)) return e;
     // n = normalize(cross(u, v)), the operations the header names (this file is compiled without contraction)
     const float crx = p->u.y * p->v.z - p->u.z * p->v.y, cry = p->u.z * p->v.x - p->u.x * p->v.z, crz = p->u.x * p->v.y - p->u.y * p->v.x;
     const float len2 = (crx * crx + cry * cry) + crz * crz;
@@ -2226,10 +2249,8 @@ int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_trans
     memset(&cam, 0, sizeof cam);
     cam.imageW = w; cam.imageH = h;
     svr::DevScene s;
-    if (build_scene(*volume, *tf, cam, s)) return g.err_code;
     svr::DevWork wk;
-    fill_work(wk, w, h);
-    wk.img = (uint8_t*)imgs;
+    if (int e = image_scene(*volume, *tf, cam, imgs, s, wk)) return e;
     sl.center[0] = p->center.x; sl.center[1] = p->center.y; sl.center[2] = p->center.z;
     sl.u[0] = p->u.x; sl.u[1] = p->u.y; sl.u[2] = p->u.z;
     sl.v[0] = p->v.x; sl.v[1] = p->v.y; sl.v[2] = p->v.z;
@@ -2244,8 +2265,7 @@ int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_trans
     // and thickness measured (c3, 256 samples: 0.665 ms against 0.625 ms; c3n: 0.90 against 0.63).  MIP and MINIP keep it
     if (g.opt_empty_skip && sl.K > 1u && sl.mode != svr::SLAB_MEAN && tv && tv->mm) {
         sl.mm = tv->mm;
-        s.mc_shift = tv->mc_shift;
-        s.mc_gx = tv->mc_gx; s.mc_gy = tv->mc_gy; s.mc_gz = tv->mc_gz; s.mc_gxy = tv->mc_gx * tv->mc_gy;
+        use_macro_grid(s, tv);
     }
     hipError_t e = svr::launch_slice(s, wk, sl, g.num_cus, g.stream);
     if (e != hipSuccess) return fail((int)e, "svr_render_slice launch failed: %s", hipGetErrorName(e));

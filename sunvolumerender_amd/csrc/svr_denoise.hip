@@ -197,20 +197,12 @@ __global__ __launch_bounds__(256) void k_atrous(const float4* __restrict__ cin, 
     else { hdr_out[3 * p] = L.x; hdr_out[3 * p + 1] = L.y; hdr_out[3 * p + 2] = L.z; }
 }
 
-template <int LAYOUT>
-static void launch_guides_t(const DevScene& s, float4* out, float h, hipStream_t st)
-{
-    const dim3 grid((s.imageW + GUIDE_TILE - 1u) / GUIDE_TILE, (s.imageH + GUIDE_TILE - 1u) / GUIDE_TILE);
-    if (s.empty_mask != nullptr) hipLaunchKernelGGL((k_guides<LAYOUT, true>), grid, dim3(1024), 0, st, s, out, h);
-    else hipLaunchKernelGGL((k_guides<LAYOUT, false>), grid, dim3(1024), 0, st, s, out, h);
-}
-
 hipError_t launch_guides(const DevScene& s, float4* out, float h, hipStream_t st)
 {
-    if (s.layout == LAYOUT_CELL) launch_guides_t<LAYOUT_CELL>(s, out, h, st);
-    else if (s.layout == LAYOUT_PAIR) launch_guides_t<LAYOUT_PAIR>(s, out, h, st);
-    else if (s.layout == LAYOUT_LINEAR) launch_guides_t<LAYOUT_LINEAR>(s, out, h, st);
-    else launch_guides_t<LAYOUT_BRICK>(s, out, h, st);
+    const dim3 grid((s.imageW + GUIDE_TILE - 1u) / GUIDE_TILE, (s.imageH + GUIDE_TILE - 1u) / GUIDE_TILE);
+    with_layout(s.layout, [&](auto lay) {
+        with_bool(s.empty_mask != nullptr, [&](auto sk) { hipLaunchKernelGGL((k_guides<decltype(lay)::value, decltype(sk)::value>), grid, dim3(1024), 0, st, s, out, h); });
+    });
     return hipGetLastError();
 }
 

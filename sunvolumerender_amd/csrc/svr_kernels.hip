@@ -539,13 +539,9 @@ static hipError_t launch_pathtrace_t(const DevScene& s, const DevWork& w, const 
 
 hipError_t launch_pathtrace(const DevScene& s, const DevWork& w, const LaunchCfg& cfg, hipStream_t st)
 {
-    if (s.layout == LAYOUT_CELL)
-        return cfg.count ? launch_pathtrace_t<LAYOUT_CELL, true>(s, w, cfg, st) : launch_pathtrace_t<LAYOUT_CELL, false>(s, w, cfg, st);
-    if (s.layout == LAYOUT_PAIR)
-        return cfg.count ? launch_pathtrace_t<LAYOUT_PAIR, true>(s, w, cfg, st) : launch_pathtrace_t<LAYOUT_PAIR, false>(s, w, cfg, st);
-    if (s.layout == LAYOUT_LINEAR)
-        return cfg.count ? launch_pathtrace_t<LAYOUT_LINEAR, true>(s, w, cfg, st) : launch_pathtrace_t<LAYOUT_LINEAR, false>(s, w, cfg, st);
-    return cfg.count ? launch_pathtrace_t<LAYOUT_BRICK, true>(s, w, cfg, st) : launch_pathtrace_t<LAYOUT_BRICK, false>(s, w, cfg, st);
+    return with_layout(s.layout, [&](auto lay) {
+        return with_bool(cfg.count, [&](auto cnt) { return launch_pathtrace_t<decltype(lay)::value, decltype(cnt)::value>(s, w, cfg, st); });
+    });
 }
 
 // The resolve of ONE frame over the WHOLE image -- what a render_pathtracer call does when its frame was traced ahead (svr_api.hip) -- beside
@@ -705,6 +701,7 @@ hipError_t launch_strips(float* packed, float* frame, uint32_t row_floats, uint3
 hipError_t launch_repack(const uint16_t* src, uint16_t* dst, int nx, int ny, int nz, int layout,
                          int sy, int sz, int bnx, int bny, hipStream_t st)
 {
+    // (one kernel per element format, not one template over the layout: CELL and PAIR write other element types)
     if (layout == LAYOUT_CELL) {
         const int bnz = (nz + 2 * VOL_PAD + BRICK_Z - 1) / BRICK_Z;
         hipLaunchKernelGGL(k_repack_cell, dim3(8192), dim3(256), 0, st, src, reinterpret_cast<uint4*>(dst), nx, ny, nz, bnx, bny, bnz);

@@ -2,6 +2,7 @@
 // gfx950 kernels (svr_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "svr_scene.hpp"
 
 namespace svr {
@@ -50,6 +51,23 @@ struct LaunchCfg {
     bool pool_primary;     // tile kernel, QUEUE builds at traceDepth 1: the primary walks go through the lane machine too (POOL)
 };
 
+// Launchers turn run-time choices into template arguments: with_layout(s.layout, f) calls f(std::integral_constant<int, LAYOUT_*>{}),
+// with_bool(b, f) calls f(std::true_type{}) or f(std::false_type{}); f is a generic lambda that reads the value from its argument's
+// type, and the calls nest.  Any layout that is not CELL, PAIR or LINEAR is BRICK.  A launcher that builds only some combinations on
+// purpose keeps its own code.
+template <typename F>
+inline auto with_layout(int layout, F&& f)
+{
+    if (layout == LAYOUT_CELL) return f(std::integral_constant<int, LAYOUT_CELL>{});
+    if (layout == LAYOUT_PAIR) return f(std::integral_constant<int, LAYOUT_PAIR>{});
+    if (layout == LAYOUT_LINEAR) return f(std::integral_constant<int, LAYOUT_LINEAR>{});
+    return f(std::integral_constant<int, LAYOUT_BRICK>{});
+}
+template <typename F>
+inline auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// blocks of a persistent kernel: one per `need`ed group of tasks, at least one, at most what the device holds at once
+inline uint32_t persistent_blocks(uint64_t need, uint32_t max_blocks) { return need < max_blocks ? (need ? (uint32_t)need : 1u) : max_blocks; }
+
 // trace work.nframes paths per owned pixel into the scratch slots work.lbuf
 hipError_t launch_pathtrace(const DevScene& scene, const DevWork& work, const LaunchCfg& cfg, hipStream_t stream);
 // fold the scratch slots into the running mean (frame order) and, if work.img, tone-map
@@ -97,7 +115,7 @@ hipError_t launch_strips(float* packed, float* frame, uint32_t row_floats, uint3
                          int to_packed, hipStream_t stream);
 // hdr_to_ldr over the owned pixels
 hipError_t launch_tonemap(const DevScene& scene, const DevWork& work, hipStream_t stream);
-// self-test of the ray caster's sample-chain replay (tests only): in = (t, h, bound, n) per item
+// self-test of the sample-chain replay of svr_chain.hpp (tests only, svr_selftest.hip): in = (t, h, bound, n) per item
 hipError_t launch_chain_selftest(const float4* in, float4* out, uint32_t n, hipStream_t stream);
 // device-side known-answer tests (tests only): out[i] = fn(in[i * in_stride ...]); fn ids in svr_selftest.hip
 hipError_t launch_math_selftest(int fn, const float* in, uint32_t in_stride, float* out, uint32_t n, hipStream_t stream);

@@ -6,14 +6,9 @@
 // One lane owns one ray (MEAN needs its sum in sample order, and nothing here is as heavy as a shaded sample of
 // k_raycast); a wave is an 8 x 8 pixel tile, persistent 256-thread blocks pull tiles from sharded tickets.
 //
-// SKIPPING (all of it result-neutral).  The volume's macro-cell table mm (svr_accel.hip, k_minmax) holds the smallest
-// and largest raw voxel rmin(m), rmax(m) over the footprint of every trilinear cell of macro-cell m.  A fetch is seven
-// lerps fma(t, q - p, p), t in [0, 1), each of which rounds monotonically and stays within [min(p, q), max(p, q)], so
-// the filtered raw value lies in [rmin, rmax]; the sampler's two multiplies (x 1/65535, x densityScale, the latter
-// checked non-negative and finite on the host) are monotone, so every intensity a fetch in m can return is
-//     I <= Imax(m) = ((float)rmax(m) * 1/65535) * densityScale                       (k_empty_mask's argument).
-// The macro-cell of a sample is taken from the sampler's own trilinear cell (cell_of), as k_raycast's `empty` test
-// does, so the per-sample test needs no margin.  Cells outside the grid (clip planes beyond the volume) always fetch.
+// SKIPPING (all of it result-neutral).  Every intensity a fetch in macro-cell m can return is I <= Imax(m) = raw_bound(rmax(m)),
+// with rmax(m) from the volume's macro-cell table mm and the macro-cell from the sampler's own cell (svr_walk.hpp, macro_of and
+// raw_bound, where the argument stands), so the per-sample test needs no margin.
 //   MIP:   a sample with Imax(m) <= M leaves M = max(M, I) as it is: not fetched.
 //   ISO:   a sample with Imax(m) <  iso cannot be the first crossing I >= iso: not fetched.  The 8 bisection fetches,
 //          the gradient's 6 and nothing else of the surface point are ever skipped.
@@ -25,11 +20,12 @@
 // sample in m the ray may advance until its largest-axis displacement is 0.95 macro-cells: every point before that lies
 // in m or a neighbour (the host only allows leaps when the float error of p = orig + dir * t, in macro-cells, is below
 // 0.02 and the clipped box lies inside the texture domain, so that every sample maps into the grid).  The samples
-// before that parameter are counted with the closed form of the float chain (chain_count) and passed with
+// before that parameter are counted with the closed form of the float chain (svr_chain.hpp, chain_count) and passed with
 // chain_advance, which replay t += h exactly; wherever the closed form gives up (t < 1, a tie, a binade the form does
 // not cover) the ray takes single steps.  ISO needs the chain element BEFORE the one a leap lands on (the bisection's
 // lower end): a leap of k steps advances k - 1 in closed form and takes the last step with a real addition.
 #include "svr_walk.hpp"
+#include "svr_chain.hpp"
 #include "svr_project.hpp"
 
 namespace svr {
@@ -38,106 +34,12 @@ namespace svr {
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------------------------
-// The sample parameters are a float accumulation chain t_{n+1} = fl(t_n + h).  Within one binade every t is a multiple
-// of u = ulp, and fl(t + h) = t + delta with ONE delta for the whole binade (unless the rounding error is exactly u / 2,
-// where ties-to-even alternates).  So k steps inside a binade are t + k * delta on the integer mantissas; the step that
-// crosses into the next binade is a real float addition.  (The same closed form as svr_raycast.hip, whose text stays as
-// it is; tests/test_more_gpu.py checks that one against a plain loop, tests/test_projection_gpu.py this one through the
-// images.)
-// ------------------------------------------------------------------------------------------------------------------
-struct ChainSeg { uint32_t A, J, kmax; float u; bool ok; };     // t = A u, delta = J u, steps k <= kmax stay in the binade
-
-SVR_DEV ChainSeg chain_segment(float t, float h)
-{
-    ChainSeg g;
-    const uint32_t tb = __float_as_uint(t);
-    const uint32_t ex = tb >> 23;                                   // t >= 1: sign 0, exponent >= 127
-    g.u = __uint_as_float((ex - 23u) << 23);
-    g.A = (tb & 0x7fffffu) | 0x800000u;
-    const float t1 = t + h;
-    const float delta = t1 - t;                                     // exact
-    const float err = h - delta;                                    // exact: the rounding error of t + h
-    const bool same = (__float_as_uint(t1) >> 23) == ex;
-    g.J = (uint32_t)(delta * __uint_as_float((127u + 127u + 23u - ex) << 23));        // delta / u, an integer < 2^24
-    g.ok = same && delta > 0.f && __builtin_fabsf(err) != 0.5f * g.u && t >= 1.f && ex < 127u + 100u;
-    g.kmax = g.ok ? (0xffffffu - g.A) / g.J : 0u;
-    return g;
-}
-
-// number of chain elements t^[0] = t, t^[1], ... that are < bound (inclusive: <= bound).  If the chain leaves the closed
-// form first, the count is a lower bound (still safe to skip) and exact is false.
-SVR_DEV uint32_t chain_count(float t, float h, float bound, bool inclusive, bool& exact)
-{
-    uint32_t n = 0;
-    exact = true;
-    for (int seg = 0; seg < 6; ++seg) {
-        if (!(inclusive ? t <= bound : t < bound)) return n;
-        const ChainSeg g = chain_segment(t, h);
-        if (!g.ok) {
-            const float t1 = t + h;                                 // one real step (binade crossing), or give up
-            if (!(t1 > t) || !(t >= 1.f)) { exact = false; return n; }
-            n += 1u; t = t1;
-            continue;
-        }
-        const float xs = bound * __uint_as_float((254u - (__float_as_uint(g.u) >> 23)) << 23);      // bound / u (exact scaling)
-        uint32_t k_in;
-        if (xs >= 16777216.f) k_in = g.kmax + 1u;                  // the bound lies beyond this binade
-        else {
-            const float fl = __builtin_floorf(xs);
-            uint32_t X = (uint32_t)fl;                               // t is before the bound, so X >= A >= 2^23
-            if (!inclusive && fl == xs) X -= 1u;
-            k_in = X >= g.A ? (X - g.A) / g.J + 1u : 0u;
-            if (k_in > g.kmax + 1u) k_in = g.kmax + 1u;
-        }
-        n += k_in;
-        if (k_in <= g.kmax) return n;                              // the bound was met inside the binade
-        t = (float)(g.A + g.kmax * g.J) * g.u;                     // continue from the first element of the next binade
-        t = t + h;
-    }
-    exact = false;
-    return n;
-}
-
-// t after n chain steps; ok = false if the closed form gave up (t is then unchanged)
-SVR_DEV float chain_advance(float t, float h, uint32_t n, bool& ok)
-{
-    const float t_in = t;
-    ok = true;
-    for (int seg = 0; seg < 8 && n != 0u; ++seg) {
-        const ChainSeg g = chain_segment(t, h);
-        if (!g.ok) {
-            const float t1 = t + h;
-            if (!(t1 > t) || !(t >= 1.f)) { ok = false; return t_in; }
-            t = t1; n -= 1u;
-            continue;
-        }
-        const uint32_t k = n < g.kmax ? n : g.kmax;
-        t = (float)(g.A + k * g.J) * g.u;                          // exact: an integer below 2^24 times a power of two
-        n -= k;
-        if (n != 0u) { t = t + h; n -= 1u; }                       // the crossing step
-    }
-    if (n != 0u) { ok = false; return t_in; }
-    return t;
-}
-
-// macro-cell of a trilinear cell (cell_is_empty's index); false outside the grid
-SVR_DEV bool macro_of(const DevScene& s, const Cell& c, uint32_t& m)
-{
-    const uint32_t ux = (uint32_t)(c.cx + 1), uy = (uint32_t)(c.cy + 1), uz = (uint32_t)(c.cz + 1);
-    const bool inb = (ux <= (uint32_t)s.nx) & (uy <= (uint32_t)s.ny) & (uz <= (uint32_t)s.nz);
-    const uint32_t sh = (uint32_t)s.mc_shift;
-    const uint32_t qx = min(ux >> sh, (uint32_t)s.mc_gx - 1u), qy = min(uy >> sh, (uint32_t)s.mc_gy - 1u), qz = min(uz >> sh, (uint32_t)s.mc_gz - 1u);
-    m = inb ? qx + qy * (uint32_t)s.mc_gx + qz * (uint32_t)s.mc_gxy : 0u;
-    return inb;
-}
-
 // can no fetch whose raw values are <= r change the ray's state?  (MIP: st = M; ISO: st = iso; MEAN: unused)
 template <int MODE>
 SVR_DEV bool skippable(const DevScene& s, uint32_t r, float st)
 {
     if (MODE == PROJ_MEAN) return r == 0u;
-    const float imax = ((float)r * 1.5259021896696422e-05f) * s.densityScale;       // the two multiplies of tex_fetch / intensity_at
+    const float imax = raw_bound(s, r);
     return MODE == PROJ_MIP ? imax <= st : imax < st;
 }
 
@@ -317,27 +219,6 @@ hipError_t launch_nbmax(const uint16_t* mm, uint16_t* nbmax, int gx, int gy, int
     return hipGetLastError();
 }
 
-template <int LAYOUT, int MODE>
-static void launch_cs(const DevScene& s, const DevWork& w, const DevProjection& pj, float stepSize, bool count, bool skip, uint32_t blocks, hipStream_t st)
-{
-    const dim3 g(blocks), b(SVR_PJ_THREADS);
-    if (count) {
-        if (skip) hipLaunchKernelGGL((k_project<LAYOUT, MODE, true, true>), g, b, 0, st, s, w, pj, stepSize);
-        else hipLaunchKernelGGL((k_project<LAYOUT, MODE, true, false>), g, b, 0, st, s, w, pj, stepSize);
-    } else {
-        if (skip) hipLaunchKernelGGL((k_project<LAYOUT, MODE, false, true>), g, b, 0, st, s, w, pj, stepSize);
-        else hipLaunchKernelGGL((k_project<LAYOUT, MODE, false, false>), g, b, 0, st, s, w, pj, stepSize);
-    }
-}
-
-template <int LAYOUT>
-static void launch_m(const DevScene& s, const DevWork& w, const DevProjection& pj, float stepSize, bool count, bool skip, uint32_t blocks, hipStream_t st)
-{
-    if (pj.mode == PROJ_MIP) launch_cs<LAYOUT, PROJ_MIP>(s, w, pj, stepSize, count, skip, blocks, st);
-    else if (pj.mode == PROJ_MEAN) launch_cs<LAYOUT, PROJ_MEAN>(s, w, pj, stepSize, count, skip, blocks, st);
-    else launch_cs<LAYOUT, PROJ_ISO>(s, w, pj, stepSize, count, skip, blocks, st);
-}
-
 hipError_t launch_projection(const DevScene& s, const DevWork& w, const DevProjection& pj, float stepSize, bool count, int num_cus, hipStream_t st)
 {
     if (w.x1 == w.x0 || w.n_rows == 0) return hipSuccess;
@@ -347,12 +228,20 @@ hipError_t launch_projection(const DevScene& s, const DevWork& w, const DevProje
     const uint32_t n_tasks = ((w.x1 - w.x0 + 7u) >> 3) * ((w.n_rows + 7u) >> 3);
     const uint32_t need = (n_tasks + SVR_PJ_THREADS / 64 - 1u) / (SVR_PJ_THREADS / 64);
     const uint32_t max_blocks = (uint32_t)num_cus * 8u;                  // 8 blocks of 4 waves per CU, no LDS
-    const uint32_t blocks = need < max_blocks ? (need ? need : 1u) : max_blocks;
+    const dim3 g(persistent_blocks(need, max_blocks)), b(SVR_PJ_THREADS);
     const bool skip = pj.mm != nullptr;
-    if (s.layout == LAYOUT_CELL) launch_m<LAYOUT_CELL>(s, w, pj, stepSize, count, skip, blocks, st);
-    else if (s.layout == LAYOUT_PAIR) launch_m<LAYOUT_PAIR>(s, w, pj, stepSize, count, skip, blocks, st);
-    else if (s.layout == LAYOUT_LINEAR) launch_m<LAYOUT_LINEAR>(s, w, pj, stepSize, count, skip, blocks, st);
-    else launch_m<LAYOUT_BRICK>(s, w, pj, stepSize, count, skip, blocks, st);
+    with_layout(s.layout, [&](auto lay) {
+        auto go = [&](auto mode) {
+            with_bool(count, [&](auto cnt) {
+                with_bool(skip, [&](auto sk) {
+                    hipLaunchKernelGGL((k_project<decltype(lay)::value, decltype(mode)::value, decltype(cnt)::value, decltype(sk)::value>), g, b, 0, st, s, w, pj, stepSize);
+                });
+            });
+        };
+        if (pj.mode == PROJ_MIP) go(std::integral_constant<int, PROJ_MIP>{});
+        else if (pj.mode == PROJ_MEAN) go(std::integral_constant<int, PROJ_MEAN>{});
+        else go(std::integral_constant<int, PROJ_ISO>{});
+    });
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // svr_slice.hip -- slice views (svr_render_slice, svr_render_slice_stack, include/svr_abi.h): an orthographic window onto a
 // plane through the volume, axis-aligned or oblique, optionally thickened into a slab of K samples along the plane's normal
 // that is reduced by maximum, minimum or mean.  The definition is in the header and is implemented here literally, float32
-// without contraction.  Nothing of it is shared with k_raycast or k_project but the sampler and the colour mapping.
+// without contraction.  With k_project it shares the macro-cell bound (svr_walk.hpp: macro_of, raw_bound), with every kernel the sampler.
 //
 // One lane owns one pixel (MEAN needs its sum in sample order); a wave is an 8 x 8 pixel tile, persistent 256-thread blocks
 // pull tasks from the sharded tickets.  A task is (slice, tile), slice-major, so a stack of any size is one launch.  Mode,
@@ -10,14 +10,10 @@
 // SAMPLES.  The offset of sample j is the product d_j = fl(fl(j * step) - half_thickness), not a running sum, so a sample
 // that is not fetched costs one multiply, one subtraction, the point and the inside test, and nothing has to be replayed.
 //
-// SKIPPING (result-neutral, SVR_OPT_EMPTY_SKIP).  The volume's macro-cell table mm (svr_accel.hip, k_minmax) holds the
-// smallest and largest raw voxel rmin(m), rmax(m) over the footprint of every trilinear cell of macro-cell m.  A fetch is
-// seven lerps fma(t, q - p, p), t in [0, 1), each of which rounds monotonically and stays within [min(p, q), max(p, q)], so
-// the filtered raw value lies in [rmin, rmax]; the sampler's two multiplies (x 1/65535, x densityScale, the latter checked
-// non-negative and finite on the host) are monotone, so every intensity a fetch in m can return satisfies
-//     Imin(m) = ((float)rmin(m) * 1/65535) * densityScale  <=  I  <=  Imax(m) = ((float)rmax(m) * 1/65535) * densityScale.
-// The macro-cell of a sample is taken from the sampler's own trilinear cell (cell_of), so the test needs no margin.  Cells
-// outside the grid (clip members beyond the volume) always fetch.
+// SKIPPING (result-neutral, SVR_OPT_EMPTY_SKIP).  Every intensity a fetch in macro-cell m can return satisfies
+//     Imin(m) = raw_bound(rmin(m))  <=  I  <=  Imax(m) = raw_bound(rmax(m)),
+// with rmin, rmax from the volume's macro-cell table mm and the macro-cell from the sampler's own cell (svr_walk.hpp, macro_of and
+// raw_bound, where the argument stands), so the test needs no margin.
 //   MIP:    a sample with Imax(m) <= M leaves M = max(M, I) as it is: not fetched.
 //   MINIP:  a sample with Imin(m) >= M leaves M = min(M, I) as it is: not fetched (M starts at +inf: the first counting
 //           sample is always fetched).
@@ -37,24 +33,6 @@
 namespace svr {
 
 #define SVR_SL_THREADS 256
-
-namespace {
-
-// macro-cell of a trilinear cell (cell_is_empty's index); false outside the grid
-SVR_DEV bool slice_macro_of(const DevScene& s, const Cell& c, uint32_t& m)
-{
-    const uint32_t ux = (uint32_t)(c.cx + 1), uy = (uint32_t)(c.cy + 1), uz = (uint32_t)(c.cz + 1);
-    const bool inb = (ux <= (uint32_t)s.nx) & (uy <= (uint32_t)s.ny) & (uz <= (uint32_t)s.nz);
-    const uint32_t sh = (uint32_t)s.mc_shift;
-    const uint32_t qx = min(ux >> sh, (uint32_t)s.mc_gx - 1u), qy = min(uy >> sh, (uint32_t)s.mc_gy - 1u), qz = min(uz >> sh, (uint32_t)s.mc_gz - 1u);
-    m = inb ? qx + qy * (uint32_t)s.mc_gx + qz * (uint32_t)s.mc_gxy : 0u;
-    return inb;
-}
-
-// the two multiplies of tex_fetch / intensity_at on a raw table value
-SVR_DEV float slice_bound(const DevScene& s, uint32_t r) { return ((float)r * 1.5259021896696422e-05f) * s.densityScale; }
-
-} // namespace
 
 template <int LAYOUT>
 __global__ __launch_bounds__(SVR_SL_THREADS) void k_slice(const DevScene s, const DevWork w, const DevSlice sl)
@@ -111,12 +89,12 @@ __global__ __launch_bounds__(SVR_SL_THREADS) void k_slice(const DevScene s, cons
                 bool skip = false;
                 if (skip_on) {
                     uint32_t m;
-                    const bool inb = slice_macro_of(s, cl, m);
+                    const bool inb = macro_of(s, cl, m);
                     if (inb && m == seen_m) skip = seen_skip;
                     else {
                         if (inb) {
-                            if (mode == SLAB_MIP) skip = slice_bound(s, sl.mm[2u * m + 1u]) <= M;
-                            else if (mode == SLAB_MINIP) skip = slice_bound(s, sl.mm[2u * m]) >= M;
+                            if (mode == SLAB_MIP) skip = raw_bound(s, sl.mm[2u * m + 1u]) <= M;
+                            else if (mode == SLAB_MINIP) skip = raw_bound(s, sl.mm[2u * m]) >= M;
                             else skip = sl.mm[2u * m + 1u] == 0u;
                         }
                         seen_m = inb ? m : 0xffffffffu; seen_skip = skip;
@@ -170,12 +148,8 @@ hipError_t launch_slice(const DevScene& s, const DevWork& w, const DevSlice& sl,
     if (e != hipSuccess) return e;
     const uint64_t need = (n_tasks + SVR_SL_THREADS / 64 - 1u) / (SVR_SL_THREADS / 64);
     const uint32_t max_blocks = (uint32_t)num_cus * 8u;                  // 8 blocks of 4 waves per CU, no LDS
-    const uint32_t blocks = need < max_blocks ? (need ? (uint32_t)need : 1u) : max_blocks;
-    const dim3 g(blocks), b(SVR_SL_THREADS);
-    if (s.layout == LAYOUT_CELL) hipLaunchKernelGGL((k_slice<LAYOUT_CELL>), g, b, 0, st, s, w, sl);
-    else if (s.layout == LAYOUT_PAIR) hipLaunchKernelGGL((k_slice<LAYOUT_PAIR>), g, b, 0, st, s, w, sl);
-    else if (s.layout == LAYOUT_LINEAR) hipLaunchKernelGGL((k_slice<LAYOUT_LINEAR>), g, b, 0, st, s, w, sl);
-    else hipLaunchKernelGGL((k_slice<LAYOUT_BRICK>), g, b, 0, st, s, w, sl);
+    const dim3 g(persistent_blocks(need, max_blocks)), b(SVR_SL_THREADS);
+    with_layout(s.layout, [&](auto lay) { hipLaunchKernelGGL((k_slice<decltype(lay)::value>), g, b, 0, st, s, w, sl); });
     return hipGetLastError();
 }
 

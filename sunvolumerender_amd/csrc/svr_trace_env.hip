@@ -279,6 +279,7 @@ static hipError_t launch_env_t(const DevScene& s, const DevWork& w, const Launch
 
 hipError_t launch_trace_env(const DevScene& s, const DevWork& w, const LaunchCfg& cfg, hipStream_t st)
 {
+    // (not with_layout: BRICK comes before LINEAR here, and the order of instantiation is the order of the kernels in the object file)
     if (s.layout == LAYOUT_CELL) return cfg.count ? launch_env_t<LAYOUT_CELL, true>(s, w, cfg, st) : launch_env_t<LAYOUT_CELL, false>(s, w, cfg, st);
     if (s.layout == LAYOUT_PAIR) return cfg.count ? launch_env_t<LAYOUT_PAIR, true>(s, w, cfg, st) : launch_env_t<LAYOUT_PAIR, false>(s, w, cfg, st);
     if (s.layout == LAYOUT_BRICK) return cfg.count ? launch_env_t<LAYOUT_BRICK, true>(s, w, cfg, st) : launch_env_t<LAYOUT_BRICK, false>(s, w, cfg, st);

@@ -576,13 +576,9 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
 
 hipError_t launch_trace_tile(const DevScene& s, const DevWork& w, const LaunchCfg& cfg, hipStream_t st)
 {
-    if (s.layout == LAYOUT_CELL)
-        return cfg.count ? launch_tile_t<LAYOUT_CELL, true>(s, w, cfg, st) : launch_tile_t<LAYOUT_CELL, false>(s, w, cfg, st);
-    if (s.layout == LAYOUT_PAIR)
-        return cfg.count ? launch_tile_t<LAYOUT_PAIR, true>(s, w, cfg, st) : launch_tile_t<LAYOUT_PAIR, false>(s, w, cfg, st);
-    if (s.layout == LAYOUT_LINEAR)
-        return cfg.count ? launch_tile_t<LAYOUT_LINEAR, true>(s, w, cfg, st) : launch_tile_t<LAYOUT_LINEAR, false>(s, w, cfg, st);
-    return cfg.count ? launch_tile_t<LAYOUT_BRICK, true>(s, w, cfg, st) : launch_tile_t<LAYOUT_BRICK, false>(s, w, cfg, st);
+    return with_layout(s.layout, [&](auto lay) {
+        return with_bool(cfg.count, [&](auto cnt) { return launch_tile_t<decltype(lay)::value, decltype(cnt)::value>(s, w, cfg, st); });
+    });
 }
 
 } // namespace svr

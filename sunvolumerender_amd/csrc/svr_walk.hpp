@@ -204,6 +204,27 @@ SVR_DEV bool cell_is_empty(const LDS& L, const DevScene& s, const Cell& c)
     return inb && ((word >> (m & 31u)) & 1u);
 }
 
+// The same index for kernels that read the macro-cell min/max table mm (svr_accel.hip, k_minmax) from global memory: k_project, k_slice.
+// False outside the grid.
+SVR_DEV bool macro_of(const DevScene& s, const Cell& c, uint32_t& m)
+{
+    const uint32_t ux = (uint32_t)(c.cx + 1), uy = (uint32_t)(c.cy + 1), uz = (uint32_t)(c.cz + 1);
+    const bool inb = (ux <= (uint32_t)s.nx) & (uy <= (uint32_t)s.ny) & (uz <= (uint32_t)s.nz);
+    const uint32_t sh = (uint32_t)s.mc_shift;
+    const uint32_t qx = min(ux >> sh, (uint32_t)s.mc_gx - 1u), qy = min(uy >> sh, (uint32_t)s.mc_gy - 1u), qz = min(uz >> sh, (uint32_t)s.mc_gz - 1u);
+    m = inb ? qx + qy * (uint32_t)s.mc_gx + qz * (uint32_t)s.mc_gxy : 0u;
+    return inb;
+}
+
+// WHAT A FETCH IN A MACRO-CELL CAN RETURN.  mm holds the smallest and largest raw voxel rmin(m), rmax(m) over the footprint of every
+// trilinear cell of macro-cell m.  A fetch is seven lerps fma(t, q - p, p), t in [0, 1), each of which rounds monotonically and stays
+// within [min(p, q), max(p, q)], so the filtered raw value lies in [rmin, rmax]; the sampler's two multiplies (x 1/65535, x densityScale,
+// the latter checked non-negative and finite on the host) are monotone, so every intensity a fetch in m can return satisfies
+//     Imin(m) = raw_bound(rmin(m))  <=  I  <=  Imax(m) = raw_bound(rmax(m))                    (k_empty_mask's argument).
+// The macro-cell of a sample is taken from the sampler's own trilinear cell (cell_of), as k_raycast's `empty` test does, so a per-sample
+// test needs no margin.  Cells outside the grid (clip planes beyond the volume) always fetch.
+SVR_DEV float raw_bound(const DevScene& s, uint32_t r) { return ((float)r * 1.5259021896696422e-05f) * s.densityScale; }   // the two multiplies of tex_fetch / intensity_at
+
 // One look at the macro grid for a trilinear cell: CELL_EMPTY (no fetch can return a non-zero opacity), CELL_DEEP
 // (so are the 26 neighbours), and the bound on the accept draw below which a fetch is needed at all (+inf outside
 // the grid and when culling is off).

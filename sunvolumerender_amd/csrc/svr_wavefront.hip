@@ -377,14 +377,11 @@ hipError_t launch_wavefront(const DevScene& s, const DevWork& w, const LaunchCfg
     q.counts = counts;
     q.capacity = capacity;
     const bool skip = s.empty_mask != nullptr;
-#define SVR_WF_DISPATCH(LAY)                                                                       \
-    if (cfg.count) return skip ? launch_wf_t<LAY, true, true>(s, w, cfg, q, st) : launch_wf_t<LAY, true, false>(s, w, cfg, q, st); \
-    return skip ? launch_wf_t<LAY, false, true>(s, w, cfg, q, st) : launch_wf_t<LAY, false, false>(s, w, cfg, q, st);
-    if (s.layout == LAYOUT_CELL) { SVR_WF_DISPATCH(LAYOUT_CELL) }
-    if (s.layout == LAYOUT_PAIR) { SVR_WF_DISPATCH(LAYOUT_PAIR) }
-    if (s.layout == LAYOUT_LINEAR) { SVR_WF_DISPATCH(LAYOUT_LINEAR) }
-    SVR_WF_DISPATCH(LAYOUT_BRICK)
-#undef SVR_WF_DISPATCH
+    return with_layout(s.layout, [&](auto lay) {
+        return with_bool(cfg.count, [&](auto cnt) {
+            return with_bool(skip, [&](auto sk) { return launch_wf_t<decltype(lay)::value, decltype(cnt)::value, decltype(sk)::value>(s, w, cfg, q, st); });
+        });
+    });
 }
 
 } // namespace svr

@@ -708,8 +708,9 @@ def test_raycasting_sample_chain_replay(hip_dev, eye):
 
 
 def test_sample_chain_primitives(hip_dev):
-    """chain_count / chain_advance of svr_raycast.hip (closed-form replay of t += h) against the brute-force float32
-    loop: counts are exact when flagged exact and never too large otherwise; advanced values are the chain's."""
+    """chain_count / chain_advance of svr_chain.hpp (closed-form replay of t += h; the one copy that the ray caster and
+    the projection kernel both use) against the brute-force float32 loop: counts are exact when flagged exact and never
+    too large otherwise; advanced values are the chain's."""
     import random
     f = np.float32
     random.seed(5)
