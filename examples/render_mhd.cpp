@@ -7,8 +7,11 @@
 // -slice x|y|z POS draws the plane perpendicular to that axis at POS in [0, 1] across the volume (svr_render_slice; -window and -tfcolor
 // apply); -slab THICKNESS mip|minip|mean thickens it into a slab (world units, one sample per pixel size); -stack N writes N parallel
 // slices from POS to the far face as name_0000.tga ... in one launch (svr_render_slice_stack).
+// -pick X Y (repeatable) renders no frame: it prints, one line per pick, where the ray of that pixel meets what the picture shows
+// (svr_pick) -- -hit opacity A: the ray caster's opacity exceeds A (default, 0.5); -hit iso L: the isosurface at L; -hit max: the sample
+// of the MIP value.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -21,7 +24,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -31,6 +34,8 @@ int main(int argc, char** argv)
     svr_projection_params proj = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
     int sliceAxis = -1, stack = 0, slabMode = 0;                    // -slice: axis 0 / 1 / 2; -stack: slices; -slab: SVR_SLAB_*
     float slicePos = 0.5f, slabThickness = 0.f;
+    std::vector<uint32_t> picks;                                    // -pick: (x, y) pairs
+    svr_hit_params hitParams = {SVR_HIT_OPACITY, 0.5f, 0.5f};
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
         else if (!strcmp(argv[i], "-env") && i + 1 < argc) envFile = argv[++i];
@@ -58,6 +63,19 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-stack") && i + 1 < argc) {
             stack = atoi(argv[++i]);
             if (stack < 1 || stack > 9999) { fprintf(stderr, "-stack needs 1 .. 9999 slices (got %s)\n", argv[i]); return 2; }
+        }
+        else if (!strcmp(argv[i], "-pick") && i + 2 < argc) {
+            const int px = atoi(argv[i + 1]), py = atoi(argv[i + 2]);
+            if (px < 0 || py < 0 || picks.size() >= 2u * SVR_PICK_MAX) { fprintf(stderr, "-pick needs a pixel X Y >= 0, at most %d of them (got %s %s)\n", SVR_PICK_MAX, argv[i + 1], argv[i + 2]); return 2; }
+            picks.push_back((uint32_t)px); picks.push_back((uint32_t)py);
+            i += 2;
+        }
+        else if (!strcmp(argv[i], "-hit") && i + 1 < argc) {
+            const char* m = argv[++i];
+            if (!strcmp(m, "max")) hitParams.mode = SVR_HIT_MAX;
+            else if (!strcmp(m, "opacity") && i + 1 < argc) { hitParams.mode = SVR_HIT_OPACITY; hitParams.alpha = strtof(argv[++i], nullptr); }
+            else if (!strcmp(m, "iso") && i + 1 < argc) { hitParams.mode = SVR_HIT_ISO; hitParams.iso = strtof(argv[++i], nullptr); }
+            else { fprintf(stderr, "-hit needs opacity A, iso L or max (got %s)\n", m); return 2; }
         }
         else if (!strcmp(argv[i], "-window") && i + 2 < argc) { proj.window_lo = strtof(argv[i + 1], nullptr); proj.window_hi = strtof(argv[i + 2], nullptr); i += 2; }
         else if (!strcmp(argv[i], "-tfcolor")) proj.flags |= SVR_PROJ_COLOR_TF;
@@ -118,6 +136,29 @@ int main(int argc, char** argv)
         canvas.SetProjection(proj);
         raycast = raycast || project;                                  // one deterministic image either way
         canvas.SetDenoisePreview(denoisePreview);
+
+        if (!picks.empty()) {
+            // point picks instead of a rendering: one line per pick
+            const uint32_t n = (uint32_t)(picks.size() / 2);
+            std::vector<svr_hit> hits(n);
+            void* d = svr_device_malloc(n * sizeof(svr_hit));
+            if (!d) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            int rc = svr_pick(d, picks.data(), n, &canvas.Volume(), &canvas.TransferFunctionPod(), &canvas.Camera(),
+                              canvas.volumeReader->GetElementBoundingSphereRadius(), &hitParams);
+            if (rc == 0) rc = svr_memcpy_d2h(hits.data(), d, n * sizeof(svr_hit));
+            svr_device_free(d);
+            if (rc != 0 || svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            for (uint32_t i = 0; i < n; ++i) {
+                const svr_hit& hh = hits[i];
+                if (hh.status == SVR_HIT_STATUS_FOUND)
+                    printf("pick %u %u: hit at sample %d, t %g, value %g, position %g %g %g, normal %g %g %g\n", picks[2 * i], picks[2 * i + 1], hh.sample, hh.t, hh.value,
+                           hh.position.x, hh.position.y, hh.position.z, hh.normal.x, hh.normal.y, hh.normal.z);
+                else
+                    printf("pick %u %u: %s\n", picks[2 * i], picks[2 * i + 1], hh.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray");
+            }
+            svr_shutdown();
+            return 0;
+        }
 
         if (sliceAxis >= 0) {
             // one slice (or a stack of them) instead of a rendering

@@ -364,6 +364,34 @@ public:
         return rc;
     }
 
+    // extension: where the ray of pixel (x, y) meets what the picture shows (svr_pick with the canvas's scene; include/svr_abi.h, "hit maps
+    // and picks"): one record into *hit (host memory).  Synchronises.  Returns the call's status (0 = ok)
+    int Pick(uint32_t x, uint32_t y, svr_hit* hit, const svr_hit_params& params = svr_hit_params{SVR_HIT_OPACITY, 0.5f, 0.5f})
+    {
+        if (!ready || !hit) return -4;
+        void* d = svr_device_malloc(sizeof(svr_hit));
+        if (!d) return -4;
+        const uint32_t xy[2] = {x, y};
+        int rc = svr_pick(d, xy, 1u, &deviceVolume, &transferFunction, &camera, volumeReader->GetElementBoundingSphereRadius(), &params);
+        if (rc == 0) rc = svr_memcpy_d2h(hit, d, sizeof(svr_hit));
+        svr_device_free(d);
+        return rc;
+    }
+    // ... and of every pixel: WIDTH x HEIGHT records, row-major, into `hits` (svr_render_hits).  Synchronises
+    int HitMap(std::vector<svr_hit>& hits, const svr_hit_params& params = svr_hit_params{SVR_HIT_OPACITY, 0.5f, 0.5f})
+    {
+        if (!ready) return -4;
+        hits.assign((size_t)WIDTH * HEIGHT, svr_hit{});
+        const size_t bytes = hits.size() * sizeof(svr_hit);
+        void* d = svr_device_malloc(bytes);
+        if (!d) return -4;
+        int rc = svr_memset_device(d, 0, bytes);          // (records outside a row shard or render window in force read as MISS)
+        if (rc == 0) rc = svr_render_hits(d, &deviceVolume, &transferFunction, &camera, volumeReader->GetElementBoundingSphereRadius(), &params);
+        if (rc == 0) rc = svr_memcpy_d2h(hits.data(), d, bytes);
+        svr_device_free(d);
+        return rc;
+    }
+
     bool SaveImage(const std::string& filename)
     {
         std::vector<uint8_t> host((size_t)WIDTH * HEIGHT * 4);

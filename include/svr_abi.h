@@ -563,6 +563,76 @@ int svr_render_slice(void* img, const svr_volume* volume, const svr_transfer_fun
 /* `count` parallel slices in one launch: slice k as defined above; writes count images of w x h RGBA8 back to back */
 int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_transfer_function* tf, uint32_t w, uint32_t h,
                            const svr_slice_params* p, uint32_t count, float spacing);
+/* svr_slice_params_axis through a world point instead of at a relative position: every field as svr_slice_params_axis fills it, except
+ * that the component of `center` on `axis` is the point's component, taken verbatim (the link from a picked point, svr_pick below, to
+ * the slice views).  Plain host code.  Non-zero for what svr_slice_params_axis refuses, for a non-finite point, and for a point outside
+ * the clipped box on that axis (the faces are inside). */
+int svr_slice_params_through(svr_slice_params* p, const svr_volume* volume, int axis, const svr_vec3* point, uint32_t w, uint32_t h);
+
+/* ---- hit maps and picks (csrc/svr_hits.hip) ----
+ * Where in the volume a pixel's ray meets what the picture shows: one deterministic ray per pixel, stateless, scene by argument like
+ * render_raycasting.  Everything below is float32 without contraction.
+ * RAY AND SAMPLES: exactly those of the projection section.  The pinhole centre ray of the pixel, the clipped box interval
+ *   [tNear, tFar] of volume.Intersect, samples t_0 = tNear, t_{n+1} = fl(t_n + h) with h = stepSize * 0.5f, while t_n <= tFar;
+ *   p(t) = orig + dir * t (per component one product and one addition) and I_n = volume(p(t_n)).  tNear may be negative (the camera inside
+ *   the box), so the status is a member of its own and is not encoded in t.
+ * STATUS: SVR_HIT_STATUS_MISS: the ray does not intersect the clipped box.  SVR_HIT_STATUS_NONE: it does, and no sample meets the mode's
+ *   condition; `sample` = the number of samples N of the ray.  SVR_HIT_STATUS_FOUND: `sample` = the index n of the hit sample, t = the ray
+ *   parameter of the hit, position = p(t), value = volume(position), normal as below.  Members not named for a status are +0.
+ * SVR_HIT_OPACITY: a_n = the alpha channel of the ray caster's transfer-function look-up at I_n; A_0 = 0,
+ *   A_{n+1} = fl(A_n + fl(fl(1 - A_n) * a_n)), the ray caster's accumulation.  The hit is the first n with A_{n+1} > alpha; no refinement:
+ *   t = t_n, value = I_n.  alpha lies in [0, 0.95]: 0 gives the first sample with any opacity, 0.95 the sample at which render_raycasting
+ *   stops.
+ * SVR_HIT_ISO: the search and the 8 bisections of SVR_PROJ_ISO, to the letter: n* = the first n with I_n >= iso; if n* = 0, hi = t_0;
+ *   otherwise lo = t_{n*-1}, hi = t_{n*}, 8 times mid = 0.5f * (lo + hi), volume(p(mid)) >= iso ? hi = mid : lo = mid.  sample = n*, t = hi,
+ *   position = p(hi) -- the point svr_render_projection shades -- and value = the fetch the search made at hi.
+ * SVR_HIT_MAX: M = max(0.0f, I_0, ...) with strict updates (I_n > M), the SVR_PROJ_MIP value; the hit is the first n with I_n == M,
+ *   t = t_n, value = M.  M == 0: NONE.
+ * NORMAL, every mode: g = the ray caster's central-difference gradient at position (cuda_volume.h:54-61).  If sqrt(dot(g, g)) > 1e-3 (the
+ *   ray caster's comparison) normal = g * (1 / sqrt(dot(g, g))), else (0, 0, 0).  It is not flipped towards the camera.
+ * svr_render_hits honours svr_set_row_shard and svr_set_render_window (records outside stay untouched); svr_pick is a query and ignores
+ * both.  Both honour svr_set_stream, the error mode, SVR_OPT_EMPTY_SKIP (1: samples that provably cannot change the result are not
+ * fetched -- ISO and MAX by the projection's rules, OPACITY by the ray caster's `empty` macro-cells, where a_n = 0 exactly -- and runs of
+ * them are passed in closed form; 0: every sample is fetched; identical records) and SVR_OPT_COUNT: raycast_steps += the samples looked
+ * at (n + 1 for an OPACITY or ISO hit at n, else N), vol_taps += the fetches of the definition (one per sample looked at, + 8 for a
+ * bisected pixel, + 6 for the gradient of a FOUND pixel), vol_taps_executed += the fetches issued.  They keep no state.
+ * Both return non-zero and leave the output untouched for: a null argument, an unknown mode, a stepSize that is not finite and > 0, a
+ * non-finite iso, an alpha outside [0, 0.95] or non-finite, a negative or non-finite densityScale; svr_pick also for n == 0,
+ * n > SVR_PICK_MAX and a pixel outside the image. */
+#define SVR_HIT_OPACITY 1   /* where the ray caster's accumulated opacity first exceeds `alpha` */
+#define SVR_HIT_ISO     2   /* the refined first crossing of `iso`: the point SVR_PROJ_ISO shades */
+#define SVR_HIT_MAX     3   /* the first sample that attains the SVR_PROJ_MIP maximum */
+
+#define SVR_HIT_STATUS_MISS  0  /* the ray does not intersect the clipped box */
+#define SVR_HIT_STATUS_NONE  1  /* it does, and no sample meets the mode's condition */
+#define SVR_HIT_STATUS_FOUND 2
+
+#define SVR_PICK_MAX 4096       /* most pixels of one svr_pick call */
+
+typedef struct svr_hit {      /* 4-byte members only, 40 bytes */
+    int32_t  status;          /* SVR_HIT_STATUS_* */
+    int32_t  sample;          /* FOUND: the index n of the hit sample; NONE: the number of samples N; MISS: 0 */
+    float    t;               /* ray parameter of the hit */
+    float    value;           /* volume(position) */
+    svr_vec3 position;        /* world */
+    svr_vec3 normal;          /* normalize(gradient) at position, or (0,0,0) */
+} svr_hit;
+
+typedef struct svr_hit_params {
+    int32_t mode;             /* SVR_HIT_* */
+    float   alpha;            /* SVR_HIT_OPACITY: opacity level in [0, 0.95] */
+    float   iso;              /* SVR_HIT_ISO: level, in the units volume(p) returns */
+} svr_hit_params;
+
+int svr_hit_params_default(svr_hit_params* p);   /* OPACITY, alpha 0.5, iso 0.5.  Plain host code */
+/* imageW x imageH svr_hit records, row-major, into hits (device memory) */
+int svr_render_hits(void* hits, const svr_volume* volume, const svr_transfer_function* tf, const svr_camera* camera, float stepSize,
+                    const svr_hit_params* p);
+/* the records of the n pixels (x_i, y_i) = (pixels_xy[2 i], pixels_xy[2 i + 1]) of a HOST array, in list order, into hits (device
+ * memory, n records) in one launch; record i is bit-identical to record (x_i, y_i) of the full map.  The list is read before the call
+ * returns */
+int svr_pick(void* hits, const uint32_t* pixels_xy, uint32_t n, const svr_volume* volume, const svr_transfer_function* tf,
+             const svr_camera* camera, float stepSize, const svr_hit_params* p);
 
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);

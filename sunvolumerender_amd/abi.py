@@ -214,6 +214,30 @@ SLICE_COLOR_TF = 1
 SLICE_MAX_SAMPLES = 4096
 
 
+class Hit(C.Structure):  # svr_hit
+    _fields_ = [
+        ("status", C.c_int32),
+        ("sample", C.c_int32),
+        ("t", C.c_float),
+        ("value", C.c_float),
+        ("position", vec3),
+        ("normal", vec3),
+    ]
+
+
+class HitParams(C.Structure):  # svr_hit_params
+    _fields_ = [("mode", C.c_int32), ("alpha", C.c_float), ("iso", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+svr_hit, svr_hit_params = Hit, HitParams
+HIT_OPACITY, HIT_ISO, HIT_MAX = 1, 2, 3
+HIT_STATUS_MISS, HIT_STATUS_NONE, HIT_STATUS_FOUND = 0, 1, 2
+PICK_MAX = 4096
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -230,6 +254,8 @@ EXPECTED_SIZES = {
     AdaptiveResult: 64,
     ProjectionParams: 20,
     SliceParams: 60,
+    Hit: 40,
+    HitParams: 12,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -352,6 +378,11 @@ PROTOTYPES = {
     "svr_render_slice": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), C.c_uint32, C.c_uint32, _P(SliceParams)]),
     "svr_render_slice_stack": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), C.c_uint32, C.c_uint32, _P(SliceParams),
                                          C.c_uint32, C.c_float]),
+    "svr_slice_params_through": (C.c_int, [_P(SliceParams), _P(cudaVolume), C.c_int, _P(vec3), C.c_uint32, C.c_uint32]),
+    "svr_hit_params_default": (C.c_int, [_P(HitParams)]),
+    "svr_render_hits": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), _P(cudaCamera), C.c_float, _P(HitParams)]),
+    "svr_pick": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32, _P(cudaVolume), _P(cudaTransferFunction), _P(cudaCamera), C.c_float,
+                           _P(HitParams)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

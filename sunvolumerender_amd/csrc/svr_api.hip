@@ -10,6 +10,7 @@
 #include "svr_noise.hpp"
 #include "svr_project.hpp"
 #include "svr_slice.hpp"
+#include "svr_hits.hpp"
 #include "svr_device.hpp"   // wang_hash (host)
 
 #include <hip/hip_runtime.h>
@@ -44,6 +45,11 @@ static_assert(sizeof(svr_noise_estimate) == 48 && offsetof(svr_noise_estimate, t
 static_assert(sizeof(svr::NoiseTotals) == 32, "noise totals");
 static_assert(sizeof(svr_adaptive_result) == 64 && offsetof(svr_adaptive_result, pixel_frames) == 24 && offsetof(svr_adaptive_result, sse) == 48 &&
               offsetof(svr_adaptive_result, tile_max) == 60, "svr_adaptive_result layout");
+static_assert(sizeof(svr_hit) == 40 && sizeof(svr_hit) == svr::HIT_WORDS * 4 && offsetof(svr_hit, sample) == 4 && offsetof(svr_hit, t) == 8 && offsetof(svr_hit, value) == 12 &&
+              offsetof(svr_hit, position) == 16 && offsetof(svr_hit, normal) == 28, "svr_hit layout");
+static_assert(sizeof(svr_hit_params) == 12 && offsetof(svr_hit_params, alpha) == 4 && offsetof(svr_hit_params, iso) == 8, "svr_hit_params layout");
+static_assert(SVR_HIT_OPACITY == svr::HIT_OPACITY && SVR_HIT_ISO == svr::HIT_ISO && SVR_HIT_MAX == svr::HIT_MAX && SVR_HIT_STATUS_MISS == svr::HIT_STATUS_MISS &&
+              SVR_HIT_STATUS_NONE == svr::HIT_STATUS_NONE && SVR_HIT_STATUS_FOUND == svr::HIT_STATUS_FOUND, "SVR_HIT_* constants");
 static_assert(sizeof(svr_projection_params) == 20 && offsetof(svr_projection_params, flags) == 4 && offsetof(svr_projection_params, iso) == 8 &&
               offsetof(svr_projection_params, window_lo) == 12 && offsetof(svr_projection_params, window_hi) == 16, "svr_projection_params layout");
 static_assert(sizeof(svr_slice_params) == 60 && offsetof(svr_slice_params, u) == 12 && offsetof(svr_slice_params, v) == 24 && offsetof(svr_slice_params, thickness) == 36 &&
@@ -164,6 +170,7 @@ struct Context {
     bool sub8_valid = false;
     bool bnd8_valid = false;
     uint8_t* d_mask_tmp = nullptr;     // scratch of the distance transform
+    uint32_t* d_pick = nullptr;        // device copy of svr_pick's pixel list (SVR_PICK_MAX pairs; allocated at the first pick)
     bool mask_valid = false;
     uint64_t mask_vol = 0, mask_tf = 0, mask_tf_version = 0;
     uint32_t mask_ds_bits = 0, mask_sigma_bits = 0;
@@ -613,7 +620,9 @@ int ensure_mask(svr::DevScene& s, const svr_volume& vol, const svr_transfer_func
         HIP_TRY(svr::launch_bound_class(tv->mm, tv->mc_gx, tv->mc_gy, tv->mc_gz, (const float*)tt->data, tt->nx, vol.densityScale,
                                         s.invSigmaMax, g.d_mask, g.stream));
         g.bnd8_valid = false;
-        if (tv->mm_wide) {
+        // (the byte table has fixed rows of BOUND8_DIM entries: a half-resolution grid with more cells on an axis -- an elongated volume -- does without it)
+        const int b8 = (int)svr::BOUND8_DIM - 2;
+        if (tv->mm_wide && (tv->mc_gx + 1) / 2 <= b8 && (tv->mc_gy + 1) / 2 <= b8 && (tv->mc_gz + 1) / 2 <= b8) {
             if (!g.d_bnd8) HIP_TRY(hipMalloc((void**)&g.d_bnd8, svr::BOUND8_BYTES));
             HIP_TRY(svr::launch_bound8(tv->mm_wide, (tv->mc_gx + 1) / 2, (tv->mc_gy + 1) / 2, (tv->mc_gz + 1) / 2, (const float*)tt->data, tt->nx, vol.densityScale,
                                        s.invSigmaMax, g.d_bnd8, g.stream));
@@ -1369,6 +1378,7 @@ void svr_shutdown(void)
     if (g.d_mask_tmp) hipFree(g.d_mask_tmp);
     if (g.d_fine_mask) hipFree(g.d_fine_mask);
     if (g.d_sub8) hipFree(g.d_sub8);
+    if (g.d_pick) hipFree(g.d_pick);
     if (g.d_bnd8) hipFree(g.d_bnd8);
     if (g.d_counters) hipFree(g.d_counters);
     if (g.d_ticket) hipFree(g.d_ticket);
@@ -2106,6 +2116,43 @@ int svr_projection_params_default(svr_projection_params* p)
     return 0;
 }
 
+// Leaps of the projection and hit kernels (svr_project.hip, LEAPS): every sample must map into the macro grid (the clipped box inside the
+// texture domain), and the float error of p = orig + dir * t -- a few ulp of the largest magnitude involved, |orig| + |p| with p in the
+// box -- must stay below 0.02 macro-cells.  mc_scale = macro-cells per world unit (s holds the scene and tv's macro grid)
+static bool leaps_allowed(const svr::DevScene& s, const svr_volume& vol, const Texture* tv, float mc_scale[3])
+{
+    const float invS = 1.f / (float)(1 << tv->mc_shift);
+    mc_scale[0] = s.invSize[0] * s.fnx * invS; mc_scale[1] = s.invSize[1] * s.fny * invS; mc_scale[2] = s.invSize[2] * s.fnz * invS;
+    const float lo[3] = {vol.bbox.vmin.x, vol.bbox.vmin.y, vol.bbox.vmin.z}, hi[3] = {vol.bbox.vmax.x, vol.bbox.vmax.y, vol.bbox.vmax.z};
+    bool inside = true;
+    double mag = 0.0, scale = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const float cl = std::min(s.clip_vmin[a], s.clip_vmax[a]), ch = std::max(s.clip_vmin[a], s.clip_vmax[a]);
+        inside = inside && cl >= lo[a] && ch <= hi[a] && lo[a] < hi[a];
+        mag = std::max(mag, (double)std::fabs(s.cam_pos[a]) + std::max(std::fabs((double)lo[a]), std::fabs((double)hi[a])));
+        scale = std::max(scale, (double)std::fabs(mc_scale[a]));
+    }
+    const double err_cells = 2.0 * mag * 4.0 * 5.9604644775390625e-08 * scale;       // 4 ulp of 2 (|orig| + |p|), in macro-cells
+    return inside && std::isfinite(err_cells) && err_cells <= 0.02;
+}
+
+// the neighbour-max table of a volume texture (svr_project.hip, k_nbmax), built at the first call that leaps over it
+static int ensure_nbmax(const char* who, Texture* tv)
+{
+    if (tv->nbmax) return 0;
+    hipError_t e = hipMalloc((void**)&tv->nbmax, (size_t)tv->mc_gx * tv->mc_gy * tv->mc_gz * sizeof(uint16_t));
+    if (e == hipSuccess) e = svr::launch_nbmax(tv->mm, tv->nbmax, tv->mc_gx, tv->mc_gy, tv->mc_gz, g.stream);
+    std::vector<uint16_t> nb((size_t)tv->mc_gx * tv->mc_gy * tv->mc_gz);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e == hipSuccess) e = hipMemcpy(nb.data(), tv->nbmax, nb.size() * sizeof(uint16_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        if (tv->nbmax) { hipFree(tv->nbmax); tv->nbmax = nullptr; }
+        return fail((int)e, "%s: neighbourhood table failed: %s", who, hipGetErrorName(e));
+    }
+    tv->nb_zero = (uint32_t)std::count(nb.begin(), nb.end(), (uint16_t)0);
+    return 0;
+}
+
 int svr_render_projection(void* img, const svr_volume* volume, const svr_transfer_function* tf, const svr_camera* camera, float stepSize,
                           const svr_projection_params* p)
 {
@@ -2127,33 +2174,8 @@ int svr_render_projection(void* img, const svr_volume* volume, const svr_transfe
     if (g.opt_empty_skip && tv && tv->mm) {
         pj.mm = tv->mm;
         use_macro_grid(s, tv);
-        // Leaps (svr_project.hip): every sample must map into the grid (the clipped box inside the texture domain), and the float error of
-        // p = orig + dir * t -- a few ulp of the largest magnitude involved, |orig| + |p| with p in the box -- must stay below 0.02 macro-cells
-        const float invS = 1.f / (float)(1 << tv->mc_shift);
-        pj.mc_scale[0] = s.invSize[0] * s.fnx * invS; pj.mc_scale[1] = s.invSize[1] * s.fny * invS; pj.mc_scale[2] = s.invSize[2] * s.fnz * invS;
-        const float lo[3] = {volume->bbox.vmin.x, volume->bbox.vmin.y, volume->bbox.vmin.z}, hi[3] = {volume->bbox.vmax.x, volume->bbox.vmax.y, volume->bbox.vmax.z};
-        bool inside = true;
-        double mag = 0.0, scale = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            const float cl = std::min(s.clip_vmin[a], s.clip_vmax[a]), ch = std::max(s.clip_vmin[a], s.clip_vmax[a]);
-            inside = inside && cl >= lo[a] && ch <= hi[a] && lo[a] < hi[a];
-            mag = std::max(mag, (double)std::fabs(s.cam_pos[a]) + std::max(std::fabs((double)lo[a]), std::fabs((double)hi[a])));
-            scale = std::max(scale, (double)std::fabs(pj.mc_scale[a]));
-        }
-        const double err_cells = 2.0 * mag * 4.0 * 5.9604644775390625e-08 * scale;       // 4 ulp of 2 (|orig| + |p|), in macro-cells
-        if (inside && std::isfinite(err_cells) && err_cells <= 0.02) {
-            if (!tv->nbmax) {
-                hipError_t e = hipMalloc((void**)&tv->nbmax, (size_t)tv->mc_gx * tv->mc_gy * tv->mc_gz * sizeof(uint16_t));
-                if (e == hipSuccess) e = svr::launch_nbmax(tv->mm, tv->nbmax, tv->mc_gx, tv->mc_gy, tv->mc_gz, g.stream);
-                std::vector<uint16_t> nb((size_t)tv->mc_gx * tv->mc_gy * tv->mc_gz);
-                if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-                if (e == hipSuccess) e = hipMemcpy(nb.data(), tv->nbmax, nb.size() * sizeof(uint16_t), hipMemcpyDeviceToHost);
-                if (e != hipSuccess) {
-                    if (tv->nbmax) { hipFree(tv->nbmax); tv->nbmax = nullptr; }
-                    return fail((int)e, "svr_render_projection: neighbourhood table failed: %s", hipGetErrorName(e));
-                }
-                tv->nb_zero = (uint32_t)std::count(nb.begin(), nb.end(), (uint16_t)0);
-            }
+        if (leaps_allowed(s, *volume, tv, pj.mc_scale)) {
+            if (int e = ensure_nbmax("svr_render_projection", tv)) return e;
             pj.nbmax = tv->nbmax;
             pj.leap = 1u;
         }
@@ -2275,6 +2297,97 @@ int svr_render_slice_stack(void* imgs, const svr_volume* volume, const svr_trans
 int svr_render_slice(void* img, const svr_volume* volume, const svr_transfer_function* tf, uint32_t w, uint32_t h, const svr_slice_params* p)
 {
     return svr_render_slice_stack(img, volume, tf, w, h, p, 1u, 0.f);
+}
+
+int svr_slice_params_through(svr_slice_params* p, const svr_volume* volume, int axis, const svr_vec3* point, uint32_t w, uint32_t h)
+{
+    if (!p || !volume || !point) return fail(-4, "svr_slice_params_through: null argument");
+    if (axis < 0 || axis > 2) return fail(-3, "svr_slice_params_through: axis must be 0, 1 or 2 (got %d)", axis);
+    if (!finite3(*point)) return fail(-3, "svr_slice_params_through: the point is not finite");
+    svr_slice_params q;
+    if (int e = svr_slice_params_axis(&q, volume, axis, 0.5f, w, h)) return e;
+    float lo[3], hi[3];
+    slice_box(*volume, lo, hi);
+    const float c = axis == 0 ? point->x : axis == 1 ? point->y : point->z;
+    if (!(c >= lo[axis] && c <= hi[axis]))
+        return fail(-3, "svr_slice_params_through: the point (%g on axis %d) lies outside the clipped box (%g .. %g)", (double)c, axis, (double)lo[axis], (double)hi[axis]);
+    (axis == 0 ? q.center.x : axis == 1 ? q.center.y : q.center.z) = c;
+    *p = q;
+    return 0;
+}
+
+// ---------------- hit maps and picks (svr_hits.hip) ----------------
+int svr_hit_params_default(svr_hit_params* p)
+{
+    if (!p) return fail(-4, "svr_hit_params_default: null argument");
+    p->mode = SVR_HIT_OPACITY; p->alpha = 0.5f; p->iso = 0.5f;
+    return 0;
+}
+
+// svr_render_hits (pixels_xy null) and svr_pick
+static int hits_call(const char* who, void* hits, const uint32_t* pixels_xy, uint32_t n, const svr_volume* volume, const svr_transfer_function* tf,
+                     const svr_camera* camera, float stepSize, const svr_hit_params* p)
+{
+    if (ensure_init()) return g.err_code;
+    if (!hits || !volume || !tf || !camera || !p) return fail(-4, "%s: null argument", who);
+    if (p->mode != SVR_HIT_OPACITY && p->mode != SVR_HIT_ISO && p->mode != SVR_HIT_MAX) return fail(-3, "%s: unknown mode %d", who, (int)p->mode);
+    if (int e = check_step(who, stepSize)) return e;
+    if (!std::isfinite(p->iso)) return fail(-3, "%s: iso must be finite", who);
+    if (!(p->alpha >= 0.f && p->alpha <= 0.95f)) return fail(-3, "%s: alpha must lie in [0, 0.95] (got %g)", who, (double)p->alpha);
+    if (int e = check_density_scale(who, volume->densityScale)) return e;
+    svr::DevScene s;
+    svr::DevWork w;
+    if (int e = image_scene(*volume, *tf, *camera, nullptr, s, w)) return e;
+    svr::DevHits hp;
+    memset(&hp, 0, sizeof hp);
+    hp.mode = p->mode; hp.alpha = p->alpha; hp.iso = p->iso;
+    hp.out = (uint32_t*)hits;
+    if (pixels_xy) {
+        // a pick is a query: the whole image is in reach, whatever shard or window is set
+        for (uint32_t i = 0; i < n; ++i)
+            if (pixels_xy[2u * i] >= s.imageW || pixels_xy[2u * i + 1u] >= s.imageH)
+                return fail(-3, "%s: pixel %u (%u, %u) lies outside the %u x %u image", who, i, pixels_xy[2u * i], pixels_xy[2u * i + 1u], s.imageW, s.imageH);
+        fill_work_full(w, s.imageW, s.imageH);
+        if (!g.d_pick) HIP_TRY(hipMalloc((void**)&g.d_pick, sizeof(uint32_t) * 2u * SVR_PICK_MAX));
+    }
+    Texture* tv = find_tex(volume->tex, TEX_VOLUME);
+    if (p->mode == SVR_HIT_OPACITY) {
+        // k_raycast's mask of the (volume, transfer function) pair: `empty` bits per sample, deep-empty bits for the leaps
+        if (int e = ensure_mask(s, *volume, *tf)) return e;
+        if (s.empty_mask && tv) {
+            hp.empty = s.empty_mask + svr::DIST_WORDS_MAX + svr::MASK_WORDS_MAX;
+            hp.deep = s.empty_mask + svr::DIST_WORDS_MAX;
+            hp.leap = leaps_allowed(s, *volume, tv, hp.mc_scale) ? 1u : 0u;
+        }
+    } else if (g.opt_empty_skip && tv && tv->mm) {
+        hp.mm = tv->mm;
+        use_macro_grid(s, tv);
+        if (leaps_allowed(s, *volume, tv, hp.mc_scale)) {
+            if (int e = ensure_nbmax(who, tv)) return e;
+            hp.nbmax = tv->nbmax;
+            hp.leap = 1u;
+        }
+    }
+    if (pixels_xy) {
+        HIP_TRY(hipMemcpyAsync(g.d_pick, pixels_xy, sizeof(uint32_t) * 2u * n, hipMemcpyHostToDevice, g.stream));
+        hp.pixels = g.d_pick; hp.n_pick = n;
+    }
+    hipError_t e = svr::launch_hits(s, w, hp, stepSize, g.opt_count != 0, g.num_cus, g.stream);
+    if (e != hipSuccess) return fail((int)e, "%s launch failed: %s", who, hipGetErrorName(e));
+    return 0;
+}
+
+int svr_render_hits(void* hits, const svr_volume* volume, const svr_transfer_function* tf, const svr_camera* camera, float stepSize, const svr_hit_params* p)
+{
+    return hits_call("svr_render_hits", hits, nullptr, 0u, volume, tf, camera, stepSize, p);
+}
+
+int svr_pick(void* hits, const uint32_t* pixels_xy, uint32_t n, const svr_volume* volume, const svr_transfer_function* tf, const svr_camera* camera,
+             float stepSize, const svr_hit_params* p)
+{
+    if (!pixels_xy) { ensure_init(); return fail(-4, "svr_pick: null argument"); }
+    if (n == 0u || n > SVR_PICK_MAX) { ensure_init(); return fail(-3, "svr_pick: n must lie in 1 .. %d (got %u)", SVR_PICK_MAX, n); }
+    return hits_call("svr_pick", hits, pixels_xy, n, volume, tf, camera, stepSize, p);
 }
 
 // ---------------- extensions ----------------

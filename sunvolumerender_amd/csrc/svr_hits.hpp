@@ -1,0 +1,31 @@
+// svr_hits.hpp -- launch interface of the hit kernel (svr_hits.hip): the hit maps of svr_render_hits and the point picks of
+// svr_pick (include/svr_abi.h, "hit maps and picks").
+#pragma once
+#include "svr_kernels.hpp"
+
+namespace svr {
+
+enum { HIT_OPACITY = 1, HIT_ISO = 2, HIT_MAX = 3 };               // SVR_HIT_*
+enum { HIT_STATUS_MISS = 0, HIT_STATUS_NONE = 1, HIT_STATUS_FOUND = 2 };   // SVR_HIT_STATUS_*
+constexpr uint32_t HIT_WORDS = 10;                                // svr_hit: ten 4-byte members
+
+// what the kernel needs beyond the scene.  The macro grid itself (mc_shift, mc_gx .. mc_gxy) travels in DevScene.
+struct DevHits {
+    int32_t mode;                  // HIT_*
+    float alpha, iso;
+    uint32_t* out;                 // svr_hit records: the map (imageW x imageH, row-major) or the pick list (n_pick)
+    const uint32_t* pixels;        // device copy of the pick list, (x, y) pairs; null = the map over the owned pixels of the work
+    uint32_t n_pick;
+    // skipping (svr_hits.hip, SKIPPING): the tables of the mode, or all null = every sample is fetched
+    const uint16_t* mm;            // ISO, MAX: the volume's min/max table (2 x u16 per macro-cell)
+    const uint16_t* nbmax;         // ISO, MAX: largest raw value over a macro-cell and its neighbours (launch_nbmax); read only if leap
+    const uint32_t* empty;         // OPACITY: `empty` bits of the (volume, transfer function) mask, one per macro-cell
+    const uint32_t* deep;          // OPACITY: deep-empty bits (the macro-cell and its 26 neighbours are `empty`); read only if leap
+    uint32_t leap;                 // 1: runs of skippable samples may be passed in closed form (svr_project.hip, LEAPS)
+    float mc_scale[3];             // macro-cells per world unit, per axis
+};
+
+// hit records of the owned pixels of work, or of the pick list
+hipError_t launch_hits(const DevScene& scene, const DevWork& work, const DevHits& hp, float stepSize, bool count, int num_cus, hipStream_t stream);
+
+} // namespace svr

@@ -292,6 +292,24 @@ def slice_params_axis(lib, volume: cudaVolume, axis: int, position: float, w: in
     return p
 
 
+def slice_params_through(lib, volume: cudaVolume, axis: int, point, w: int, h: int) -> abi.SliceParams:
+    """svr_slice_params_through: the axis plane of slice_params_axis through the world point `point` (a picked position).  Host code
+    of the library: no device is needed."""
+    p = abi.SliceParams()
+    q = _to_vec3(point)
+    if lib.svr_slice_params_through(C.byref(p), C.byref(volume), int(axis), C.byref(q), int(w), int(h)) != 0:
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise SvrError(f"svr_slice_params_through: {msg}")
+    return p
+
+
+# numpy view of svr_hit records (40 bytes, 4-byte members)
+HIT_DTYPE = np.dtype([("status", np.int32), ("sample", np.int32), ("t", np.float32), ("value", np.float32),
+                      ("position", np.float32, 3), ("normal", np.float32, 3)])
+assert HIT_DTYPE.itemsize == C.sizeof(abi.Hit)
+
+
 def _slice_params(params, thickness, step, mode, window, color_tf) -> abi.SliceParams:
     p = abi.SliceParams.from_buffer_copy(params)
     if thickness is not None:
@@ -542,6 +560,11 @@ class Canvas:
         canvas's volume, fitted to w x h pixels (default: the canvas)."""
         return slice_params_axis(self.lib, self.deviceVolume, axis, position, self.W if w is None else w, self.H if h is None else h)
 
+    def slice_params_through(self, axis: int, point, w: Optional[int] = None, h: Optional[int] = None) -> abi.SliceParams:
+        """svr_slice_params for the plane perpendicular to world axis 0 / 1 / 2 through the world point `point` (for instance the
+        position of a pick), fitted to w x h pixels (default: the canvas)."""
+        return slice_params_through(self.lib, self.deviceVolume, axis, point, self.W if w is None else w, self.H if h is None else h)
+
     def paint_slice(self, params: abi.SliceParams, thickness: Optional[float] = None, step: Optional[float] = None, mode: Optional[int] = None,
                     window=None, color_tf: Optional[bool] = None, sync: bool = False):
         """One slice of the canvas's volume into the canvas image: the plane (or slab) of `params`, with the named members replaced.
@@ -562,6 +585,42 @@ class Canvas:
                                                        self.W, self.H, C.byref(p), int(count), C.c_float(float(spacing))))
         if sync:
             self.dev.synchronize()
+
+    # ---- extension: hit maps and picks (svr_render_hits, svr_pick) ----
+    def hit_map(self, mode: int = abi.HIT_OPACITY, alpha: float = 0.5, iso: float = 0.5) -> np.ndarray:
+        """Where every pixel's ray meets what the picture shows: an (H, W) array of HIT_DTYPE records (status, sample, t, value,
+        position, normal) for abi.HIT_OPACITY (the ray caster's opacity exceeds alpha), abi.HIT_ISO (the isosurface point
+        paint_projection shades) or abi.HIT_MAX (the sample of the MIP value).  Stateless; synchronises.  Records outside a row shard
+        or render window in force are zero."""
+        p = abi.HitParams(int(mode), float(alpha), float(iso))
+        nbytes = self.W * self.H * HIT_DTYPE.itemsize
+        buf = self.dev.malloc(nbytes)
+        try:
+            self.dev.check(self.lib.svr_memset_device(C.c_void_p(buf), 0, nbytes))
+            self.dev.check(self.lib.svr_render_hits(C.c_void_p(buf), C.byref(self.deviceVolume), C.byref(self.transferFunction),
+                                                    C.byref(self.camera), C.c_float(self.stepSize), C.byref(p)))
+            self.dev.synchronize()
+            return self.dev.to_host(buf, (self.H, self.W), HIT_DTYPE)
+        finally:
+            self.dev.free(buf)
+
+    def pick(self, pixels, mode: int = abi.HIT_OPACITY, alpha: float = 0.5, iso: float = 0.5) -> np.ndarray:
+        """The hit records of the listed pixels ((x, y) pairs, at most abi.PICK_MAX), in list order, in one launch: each is the record
+        hit_map has at that pixel.  A query: a row shard or render window in force does not matter.  Stateless; synchronises."""
+        xy = np.ascontiguousarray(np.asarray(pixels, dtype=np.int64).reshape(-1, 2))
+        if len(xy) and (xy.min() < 0 or xy.max() > 0xffffffff):
+            raise SvrError("pick: pixel coordinates must be non-negative")
+        xy = xy.astype(np.uint32)
+        n = len(xy)
+        p = abi.HitParams(int(mode), float(alpha), float(iso))
+        buf = self.dev.malloc(max(n, 1) * HIT_DTYPE.itemsize)
+        try:
+            self.dev.check(self.lib.svr_pick(C.c_void_p(buf), xy.ctypes.data_as(C.POINTER(C.c_uint32)), n, C.byref(self.deviceVolume),
+                                             C.byref(self.transferFunction), C.byref(self.camera), C.c_float(self.stepSize), C.byref(p)))
+            self.dev.synchronize()
+            return self.dev.to_host(buf, (n,), HIT_DTYPE)
+        finally:
+            self.dev.free(buf)
 
     # ---- extension: denoised preview of the first frames after a restart ----
     def SetDenoisePreview(self, frames: int, params: Optional[abi.DenoiseParams] = None):
