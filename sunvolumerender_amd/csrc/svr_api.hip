@@ -2116,7 +2116,7 @@ int svr_projection_params_default(svr_projection_params* p)
     return 0;
 }
 
-// Leaps of the projection and hit kernels (svr_project.hip, LEAPS): every sample must map into the macro grid (the clipped box inside the
+// Leaps of the projection and hit kernels (svr_march.hpp, LEAPS): every sample must map into the macro grid (the clipped box inside the
 // texture domain), and the float error of p = orig + dir * t -- a few ulp of the largest magnitude involved, |orig| + |p| with p in the
 // box -- must stay below 0.02 macro-cells.  mc_scale = macro-cells per world unit (s holds the scene and tv's macro grid)
 static bool leaps_allowed(const svr::DevScene& s, const svr_volume& vol, const Texture* tv, float mc_scale[3])
@@ -2153,6 +2153,19 @@ static int ensure_nbmax(const char* who, Texture* tv)
     return 0;
 }
 
+// the tables a march over tv's min/max table skips by (svr_march.hpp): the table, and the neighbourhood table where leaps are allowed
+static int fill_march_tables(const char* who, svr::DevScene& s, const svr_volume& vol, Texture* tv, svr::MarchTables& tb)
+{
+    tb.mm = tv->mm;
+    use_macro_grid(s, tv);
+    if (leaps_allowed(s, vol, tv, tb.mc_scale)) {
+        if (int e = ensure_nbmax(who, tv)) return e;
+        tb.nbmax = tv->nbmax;
+        tb.leap = 1u;
+    }
+    return 0;
+}
+
 int svr_render_projection(void* img, const svr_volume* volume, const svr_transfer_function* tf, const svr_camera* camera, float stepSize,
                           const svr_projection_params* p)
 {
@@ -2172,17 +2185,11 @@ int svr_render_projection(void* img, const svr_volume* volume, const svr_transfe
     pj.mode = p->mode; pj.flags = p->flags; pj.iso = p->iso; pj.window_lo = p->window_lo; pj.window_hi = p->window_hi;
     Texture* tv = find_tex(volume->tex, TEX_VOLUME);
     if (g.opt_empty_skip && tv && tv->mm) {
-        pj.mm = tv->mm;
-        use_macro_grid(s, tv);
-        if (leaps_allowed(s, *volume, tv, pj.mc_scale)) {
-            if (int e = ensure_nbmax("svr_render_projection", tv)) return e;
-            pj.nbmax = tv->nbmax;
-            pj.leap = 1u;
-        }
+        if (int e = fill_march_tables("svr_render_projection", s, *volume, tv, pj.tb)) return e;
         // MEAN skips only samples whose eight voxels are 0.  A volume without a macro-cell whose neighbourhood is all zero (noisy air)
         // has next to nothing to skip and nothing to leap over, and the per-sample test then only costs (c3n: 2.5 ms against 1.6 ms,
         // DESIGN.md 8e): such volumes are rendered without the test
-        if (pj.mode == SVR_PROJ_MEAN && (!pj.leap || tv->nb_zero == 0u)) pj.mm = nullptr;
+        if (pj.mode == SVR_PROJ_MEAN && (!pj.tb.leap || tv->nb_zero == 0u)) pj.tb.mm = nullptr;
     }
     hipError_t e = svr::launch_projection(s, w, pj, stepSize, g.opt_count != 0, g.num_cus, g.stream);
     if (e != hipSuccess) return fail((int)e, "svr_render_projection launch failed: %s", hipGetErrorName(e));
@@ -2355,18 +2362,12 @@ static int hits_call(const char* who, void* hits, const uint32_t* pixels_xy, uin
         // k_raycast's mask of the (volume, transfer function) pair: `empty` bits per sample, deep-empty bits for the leaps
         if (int e = ensure_mask(s, *volume, *tf)) return e;
         if (s.empty_mask && tv) {
-            hp.empty = s.empty_mask + svr::DIST_WORDS_MAX + svr::MASK_WORDS_MAX;
-            hp.deep = s.empty_mask + svr::DIST_WORDS_MAX;
-            hp.leap = leaps_allowed(s, *volume, tv, hp.mc_scale) ? 1u : 0u;
+            hp.tb.empty = s.empty_mask + svr::DIST_WORDS_MAX + svr::MASK_WORDS_MAX;
+            hp.tb.deep = s.empty_mask + svr::DIST_WORDS_MAX;
+            hp.tb.leap = leaps_allowed(s, *volume, tv, hp.tb.mc_scale) ? 1u : 0u;
         }
     } else if (g.opt_empty_skip && tv && tv->mm) {
-        hp.mm = tv->mm;
-        use_macro_grid(s, tv);
-        if (leaps_allowed(s, *volume, tv, hp.mc_scale)) {
-            if (int e = ensure_nbmax(who, tv)) return e;
-            hp.nbmax = tv->nbmax;
-            hp.leap = 1u;
-        }
+        if (int e = fill_march_tables(who, s, *volume, tv, hp.tb)) return e;
     }
     if (pixels_xy) {
         HIP_TRY(hipMemcpyAsync(g.d_pick, pixels_xy, sizeof(uint32_t) * 2u * n, hipMemcpyHostToDevice, g.stream));

@@ -1,5 +1,6 @@
-// svr_chain.hpp -- exact replay of the ray caster's sample-parameter chain, shared by k_raycast (svr_raycast.hip) and
-// k_project (svr_project.hip); svr_selftest.hip checks these very functions against a plain loop (k_chain_selftest).
+// svr_chain.hpp -- exact replay of the ray caster's sample-parameter chain, shared by k_raycast (svr_raycast.hip) and the
+// one-lane march of k_project and k_hits (svr_march.hpp); svr_selftest.hip checks these very functions against a plain loop
+// (k_chain_selftest).
 #pragma once
 #include "svr_math.hpp"
 

@@ -16,13 +16,7 @@ struct DevHits {
     uint32_t* out;                 // svr_hit records: the map (imageW x imageH, row-major) or the pick list (n_pick)
     const uint32_t* pixels;        // device copy of the pick list, (x, y) pairs; null = the map over the owned pixels of the work
     uint32_t n_pick;
-    // skipping (svr_hits.hip, SKIPPING): the tables of the mode, or all null = every sample is fetched
-    const uint16_t* mm;            // ISO, MAX: the volume's min/max table (2 x u16 per macro-cell)
-    const uint16_t* nbmax;         // ISO, MAX: largest raw value over a macro-cell and its neighbours (launch_nbmax); read only if leap
-    const uint32_t* empty;         // OPACITY: `empty` bits of the (volume, transfer function) mask, one per macro-cell
-    const uint32_t* deep;          // OPACITY: deep-empty bits (the macro-cell and its 26 neighbours are `empty`); read only if leap
-    uint32_t leap;                 // 1: runs of skippable samples may be passed in closed form (svr_project.hip, LEAPS)
-    float mc_scale[3];             // macro-cells per world unit, per axis
+    MarchTables tb;                // skipping (MarchTables, svr_kernels.hpp): mm / nbmax for ISO and MAX, empty / deep for OPACITY; all null = every sample is fetched
 };
 
 // hit records of the owned pixels of work, or of the pick list

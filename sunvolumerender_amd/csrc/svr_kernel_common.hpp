@@ -98,6 +98,34 @@ SVR_DEV unsigned long long wave_sum(unsigned long long v)
     return v;
 }
 
+// ------------------------------------------------------------------------------------------
+// the one-lane-per-ray views k_project and k_hits: persistent blocks of SVR_VIEW_THREADS threads whose waves pull
+// tasks -- an 8 x 8 pixel tile of the owned pixels, or 64 entries of a list -- from the sharded tickets.  The ticket
+// loop and the tile decoding stay written out in each kernel (and in k_slice, which has the same shape): as shared
+// functions they cost registers and time (profiles/viewer_march_refactor.txt).
+// ------------------------------------------------------------------------------------------
+#define SVR_VIEW_THREADS 256
+
+// 8 x 8 tiles of the owned pixels (kernels and launchers)
+__host__ __device__ inline uint32_t view_tiles(const DevWork& w) { return ((w.x1 - w.x0 + 7u) >> 3) * ((w.n_rows + 7u) >> 3); }
+
+// the three counters of a view: samples visited, fetches they stand for, fetches issued (per-lane sums of the whole kernel)
+SVR_DEV void view_counters_flush(const DevWork& w, uint32_t steps, uint32_t taps, uint32_t exec)
+{
+    const unsigned long long st = wave_sum((unsigned long long)steps), tp = wave_sum((unsigned long long)taps), ex = wave_sum((unsigned long long)exec);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicAdd(&w.counters[CNT_RAYCAST], st);
+        atomicAdd(&w.counters[CNT_VOL_TAPS], tp);
+        atomicAdd(&w.counters[CNT_TAPS_EXEC], ex);
+    }
+}
+
+// host side: blocks of such a kernel for n_tasks tasks -- one per 4 tasks (a wave each), at most 8 blocks of 4 waves per CU
+inline uint32_t view_blocks(uint64_t n_tasks, int num_cus)
+{
+    return persistent_blocks((n_tasks + SVR_VIEW_THREADS / 64 - 1u) / (SVR_VIEW_THREADS / 64), (uint32_t)num_cus * 8u);
+}
+
 struct Cnt { uint32_t taps, iters, scatter, shadow, paths, loops, exec, wskip, iskip, ipre, cull; };
 
 SVR_DEV void cnt_flush(const DevWork& w, const Cnt& c)

@@ -51,6 +51,17 @@ struct LaunchCfg {
     bool pool_primary;     // tile kernel, QUEUE builds at traceDepth 1: the primary walks go through the lane machine too (POOL)
 };
 
+// The tables the one-lane march of k_project and k_hits skips by (svr_march.hpp, SKIPPING and LEAPS), or all null = every sample is
+// fetched.  The macro grid itself (mc_shift, mc_gx .. mc_gxy) travels in DevScene.
+struct MarchTables {
+    const uint32_t* empty;         // OPACITY: `empty` bits of the (volume, transfer function) mask, one per macro-cell
+    const uint32_t* deep;          // OPACITY: deep-empty bits (the macro-cell and its 26 neighbours are `empty`); read only if leap
+    const uint16_t* mm;            // all other rules: the volume's min/max table (2 x u16 per macro-cell)
+    const uint16_t* nbmax;         // ... the largest raw value over a macro-cell and its neighbours (launch_nbmax); read only if leap
+    uint32_t leap;                 // 1: runs of skippable samples may be passed in closed form
+    float mc_scale[3];             // macro-cells per world unit, per axis
+};
+
 // Launchers turn run-time choices into template arguments: with_layout(s.layout, f) calls f(std::integral_constant<int, LAYOUT_*>{}),
 // with_bool(b, f) calls f(std::true_type{}) or f(std::false_type{}); f is a generic lambda that reads the value from its argument's
 // type, and the calls nest.  Any layout that is not CELL, PAIR or LINEAR is BRICK.  A launcher that builds only some combinations on

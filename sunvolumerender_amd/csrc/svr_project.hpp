@@ -13,10 +13,7 @@ struct DevProjection {
     int32_t mode;                  // PROJ_*
     uint32_t flags;
     float iso, window_lo, window_hi;
-    const uint16_t* mm;            // the volume's min/max table (2 x u16 per macro-cell); null = every sample is fetched
-    const uint16_t* nbmax;         // largest raw value over a macro-cell and its neighbours (launch_nbmax); read only if leap
-    uint32_t leap;                 // 1: runs of skippable samples may be passed in closed form (svr_project.hip, LEAPS)
-    float mc_scale[3];             // macro-cells per world unit, per axis
+    MarchTables tb;                // skipping (MarchTables, svr_kernels.hpp): mm, and nbmax if leap; mm null = every sample is fetched
 };
 
 // nbmax[m] = max of mm[2 m' + 1] over the in-grid 3 x 3 x 3 neighbourhood of m

@@ -8,7 +8,7 @@ import pytest
 
 from sunvolumerender_amd import abi, host, scenes
 from tests import hit_ref as hr
-from tests.test_projection_gpu import LEVELS, _crop_scene, _long_scene
+from tests.test_projection_gpu import COUNTERS, LEVELS, SKIP_COUNTS, _crop_scene, _long_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -158,6 +158,25 @@ def test_skip_on_off_and_counters(hip_dev, shift):
             assert executed[0] == rc["vol_taps"] and executed[1] < executed[0], (mname, executed)
     finally:
         rig.close()
+
+
+def skip_counts(dev, shift):
+    """{mode name: {counter: value}} of tiny_head at 96 x 80, macro shift `shift`, skipping on: OPACITY 0.5, ISO 0.15 and MAX."""
+    dev.set_option(abi.OPT_MACRO_SHIFT_MIN, shift)
+    rig = Rig(dev, scenes.make_scene("tiny_head"))
+    try:
+        return {mname: {k: int(c[k]) for k in COUNTERS}
+                for mode, mname, alpha, iso in cases((0.15,), alphas=(0.5,)) for c in [rig.hits(mode, alpha=alpha, iso=iso, skip=1, count=True)[1]]}
+    finally:
+        rig.close()
+
+
+@pytest.mark.parametrize("shift", [0, 2])
+def test_skip_counts_are_the_recorded_ones(hip_dev, shift):
+    """As in tests/test_projection_gpu.py: the samples passed by the kept verdicts and the leaps are exactly the recorded ones."""
+    got = skip_counts(hip_dev, shift)
+    print(f"shift {shift}: {got}")
+    assert got == SKIP_COUNTS["hits"][f"shift{shift}"]
 
 
 # ------------------------------------------------------------------------------------------------ geometry

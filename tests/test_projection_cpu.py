@@ -1,5 +1,5 @@
 """svr_render_projection without a GPU: the ABI of the new struct, properties of the test-side reference (tests/projection_ref.py),
-and the skipping argument of csrc/svr_project.hip checked directly against the oracle's sampler."""
+and the skipping argument of csrc/svr_march.hpp checked directly against the oracle's sampler."""
 import ctypes as C
 import re
 from pathlib import Path

@@ -2,6 +2,8 @@
 (tests/projection_ref.py), which implements the contract of include/svr_abi.h literally on the CPU oracle's primitives and
 skips nothing."""
 import ctypes as C
+import json
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -10,6 +12,11 @@ from sunvolumerender_amd import abi, host, scenes
 from tests import projection_ref as pr
 
 pytestmark = pytest.mark.gpu
+
+# raycast_steps / vol_taps / vol_taps_executed of tiny_head with skipping on, per view, macro shift and mode, recorded from the kernels before
+# k_project and k_hits were put on one march (svr_march.hpp): sums of per-ray integers, so they are deterministic
+SKIP_COUNTS = json.loads((Path(__file__).parent / "golden" / "viewer_skip_counts.json").read_text())
+COUNTERS = ("raycast_steps", "vol_taps", "vol_taps_executed")
 
 MODES = ((pr.MIP, "mip"), (pr.MEAN, "mean"), (pr.ISO, "iso"))
 FILL = 0xAB                                          # images start as this byte: untouched pixels keep it
@@ -126,6 +133,25 @@ def test_skip_on_off_and_counters(hip_dev, shift):
                     assert c["vol_taps_executed"] == c["vol_taps"], (mname, c)
     finally:
         rig.close()
+
+
+def skip_counts(dev, shift):
+    """{mode name: {counter: value}} of tiny_head at 96 x 80, macro shift `shift`, skipping on: MIP, MEAN and ISO 0.15."""
+    dev.set_option(abi.OPT_MACRO_SHIFT_MIN, shift)
+    rig = Rig(dev, scenes.make_scene("tiny_head"))
+    try:
+        return {mname: {k: int(c[k]) for k in COUNTERS} for mode, mname in MODES for c in [rig.render(mode, iso=0.15, skip=1, count=True)[1]]}
+    finally:
+        rig.close()
+
+
+@pytest.mark.parametrize("shift", [0, 2])
+def test_skip_counts_are_the_recorded_ones(hip_dev, shift):
+    """The skipping itself, not only its result: the verdict kept per macro-cell and the leaps pass exactly the samples they passed when
+    the counts were recorded (test_skip_on_off_and_counters only asks for fewer fetches than without skipping)."""
+    got = skip_counts(hip_dev, shift)
+    print(f"shift {shift}: {got}")
+    assert got == SKIP_COUNTS["projection"][f"shift{shift}"]
 
 
 # ------------------------------------------------------------------------------------------------ geometry
