@@ -3,6 +3,7 @@
 #pragma once
 #include "svr_kernels.hpp"
 #include "svr_device.hpp"
+#include "svr_path.hpp"
 
 namespace svr {
 

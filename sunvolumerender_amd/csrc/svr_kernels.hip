@@ -64,9 +64,7 @@ SVR_DEV v3 trace_path(const DevScene& s, const LdsTF& tf, uint32_t x, uint32_t y
         if (k == 0 && ls_id >= 0) {
             t = t < 0.f ? SVR_FLT_MAX : t;
             if (ls_t < t) {
-                const DevLight& l = s.lights[ls_id];
-                float cosTerm = dot(V3(l.normal[0], l.normal[1], l.normal[2]), -dir);
-                L = L + (T * V3(l.radiance[0], l.radiance[1], l.radiance[2])) * (cosTerm <= 0.f ? 0.f : 1.f);
+                L = light_seen(L, T, s.lights[ls_id], dir);
                 break;
             }
         }
@@ -95,19 +93,13 @@ SVR_DEV v3 trace_path(const DevScene& s, const LdsTF& tf, uint32_t x, uint32_t y
                 float sMin = (float)1e-6, sMax = SVR_FLT_MAX;
                 if (COUNT) c.shadow++;
                 float ts = sample_distance<LAYOUT, COUNT>(s, tf, vs.pt, wiL, rng, sMin, sMax, c);
-                float Tr = ((ts > sMin) && (ts < sMax)) ? 0.f : 1.f;
-                float kf = Tr * (float)s.num_lights;
-                Ld = ((bsdf_eval(vs, wiL) * kf) * Li) / pdfL;
+                Ld = direct_light(ts, sMin, sMax, s.num_lights, Li, bsdf_eval(vs, wiL), pdfL);          // transmittance.h:15-16
             }
         }
         L = L + T * Ld;
         v3 wi; float pdf = 0.f;
         v3 f = bsdf_sample(vs, wi, pdf, rng);
-        float cosTerm = __builtin_fabsf(dot(normalize(vs.gradient), wi));
-        if (fmax_(f.x, fmax_(f.y, f.z)) > 0.f && pdf > 0.f) {
-            if (vs.st == 0) T = T * (f / (pdf * (1.f - vs.Pbrdf)));
-            else T = T * ((f * cosTerm) / (pdf * vs.Pbrdf));
-        }
+        T = bsdf_throughput(T, vs, f, wi, pdf);
         orig = vs.pt;
         dir = wi;
         if (k >= 3) {
@@ -256,19 +248,13 @@ __global__ __launch_bounds__(256, SVR_WAVES_PER_EU) void k_pathtrace_uloop(const
         if (state == S_SCATTER) {
             v3 Ld = V3(0.f, 0.f, 0.f);
             if (nee_valid) {
-                const DevLight& l = s.lights[nee_light];
-                float kf = Tr * (float)s.num_lights;
-                Ld = ((nee_bsdf * kf) * V3(l.radiance[0], l.radiance[1], l.radiance[2])) / nee_pdf;
+                Ld = direct_light_tr(Tr, s.num_lights, light_radiance(s.lights[nee_light]), nee_bsdf, nee_pdf);
             }
             L = L + T * Ld;
             if (k + 1u < w.traceDepth) {
                 v3 wi; float pdf = 0.f;
                 v3 f = bsdf_sample(vs, wi, pdf, rng);
-                float cosTerm = __builtin_fabsf(dot(normalize(vs.gradient), wi));
-                if (fmax_(f.x, fmax_(f.y, f.z)) > 0.f && pdf > 0.f) {
-                    if (vs.st == 0) T = T * (f / (pdf * (1.f - vs.Pbrdf)));
-                    else T = T * ((f * cosTerm) / (pdf * vs.Pbrdf));
-                }
+                T = bsdf_throughput(T, vs, f, wi, pdf);
                 o = vs.pt;
                 d = wi;
                 bool term = false;
@@ -364,7 +350,7 @@ __global__ __launch_bounds__(256, SVR_WAVES_PER_EU) void k_pathtrace_uloop(const
                     float sigma_t = lds_tf_alpha(tf, s, val);
                     if (rng_uniform(rng) < sigma_t * s.invSigmaMax) {
                         if (shadow) {
-                            Tr = ((t > tMin) && (t < tMax)) ? 0.f : 1.f;
+                            Tr = shadow_transmittance(t, tMin, tMax);
                             state = S_SCATTER;
                         } else pend_hit = true;
                     }
@@ -389,9 +375,7 @@ __global__ __launch_bounds__(256, SVR_WAVES_PER_EU) void k_pathtrace_uloop(const
             if (k == 0u && ls_id >= 0) {
                 tt = tt < 0.f ? SVR_FLT_MAX : tt;
                 if (ls_t < tt) {
-                    const DevLight& l = s.lights[ls_id];
-                    float cosTerm = dot(V3(l.normal[0], l.normal[1], l.normal[2]), -d);
-                    L = L + (T * V3(l.radiance[0], l.radiance[1], l.radiance[2])) * (cosTerm <= 0.f ? 0.f : 1.f);
+                    L = light_seen(L, T, s.lights[ls_id], d);
                     done = true;
                 }
             }
@@ -592,9 +576,11 @@ hipError_t launch_resolve(const DevScene& s, const DevWork& w, hipStream_t st)
 // Sampling table of an environment map (SVR_OPT_ENV_NEE, svr_trace_env.hip): weight of texel (i, j) = the largest luminance among the texel
 // and its 8 wrap-neighbours (the bilinear lookup at any point of the texel's cell reads only those) x sin(theta of the row) + a floor of
 // 1e-3 of the mean, so that the density is positive wherever the lookup can be; cdf = h rows of w + 1 prefix sums, then h + 1 prefix sums
-// of the row totals.  Built once per map.
+// of the row totals.  Built once per map.  The mean behind the floor is summed in a FIXED order (one partial per wave, then the partials in
+// index order): with one float atomic per wave the floor, and with it the table and an image of the mode, changed by an ulp with the
+// order in which the waves happened to arrive -- a frame of the mode is a pure function of (scene, pixel, frame) only if its table is.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_env_weights(const float4* __restrict__ env, int w, int h, float* __restrict__ wgt, float* __restrict__ mean_acc)
+__global__ __launch_bounds__(256) void k_env_weights(const float4* __restrict__ env, int w, int h, float* __restrict__ wgt, float* __restrict__ wave_sums)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     float v = 0.f;
@@ -612,7 +598,14 @@ __global__ __launch_bounds__(256) void k_env_weights(const float4* __restrict__ 
         wgt[e] = v;
     }
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(mean_acc, v);
+    if ((threadIdx.x & 63) == 0) wave_sums[blockIdx.x * 4 + (threadIdx.x >> 6)] = v;
+}
+__global__ void k_env_mean(const float* __restrict__ wave_sums, int n, float* __restrict__ mean_acc)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float acc = 0.f;
+    for (int i = 0; i < n; ++i) acc += wave_sums[i];
+    *mean_acc = acc;
 }
 __global__ __launch_bounds__(64) void k_env_rows(const float* __restrict__ wgt, int w, int h, const float* __restrict__ mean_acc, float* __restrict__ cdf)
 {
@@ -634,10 +627,11 @@ __global__ void k_env_marginal(int w, int h, float* __restrict__ cdf)
 }
 hipError_t launch_env_cdf(const float* env_rgba, int w, int h, float* cdf, float* tmp, hipStream_t st)
 {
-    // tmp: w * h + 1 floats (weights, then the sum)
-    hipError_t e = hipMemsetAsync(tmp + (size_t)w * h, 0, sizeof(float), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_env_weights, dim3((w * h + 255) / 256), dim3(256), 0, st, reinterpret_cast<const float4*>(env_rgba), w, h, tmp, tmp + (size_t)w * h);
+    // tmp: w * h + 1 floats (weights, then the sum).  The waves' partial sums wait in the front of cdf, which is written after they are read
+    // (4 per block of 256 texels: never more than cdf's h * (w + 1) + h + 1 floats)
+    const int blocks = (w * h + 255) / 256;
+    hipLaunchKernelGGL(k_env_weights, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float4*>(env_rgba), w, h, tmp, cdf);
+    hipLaunchKernelGGL(k_env_mean, dim3(1), dim3(1), 0, st, cdf, 4 * blocks, tmp + (size_t)w * h);
     hipLaunchKernelGGL(k_env_rows, dim3((h + 63) / 64), dim3(64), 0, st, tmp, w, h, tmp + (size_t)w * h, cdf);
     hipLaunchKernelGGL(k_env_marginal, dim3(1), dim3(1), 0, st, w, h, cdf);
     return hipGetLastError();

@@ -54,6 +54,36 @@ SVR_DEV uint32_t lane_rank(uint64_t m)  // number of set bits of m below this la
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// records, slots and radiance rows in global memory that one lane of a wave writes and another lane of the SAME wave reads back
+SVR_DEV void wave_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// the radiance of the path with id = (pending task << 6 | lane) into its wave's rows [task * 3 + channel][64] (DevWork.pend; fold_pending reads them)
+SVR_DEV void pend_row_put(float* rows, uint32_t id, v3 L)
+{
+    float* p = rows + (id >> 6) * (3u * 64u) + (id & 63u);
+    p[0] = L.x; p[64] = L.y; p[128] = L.z;
+}
+// a block's copy of the scene's 8 lights in LDS, where a per-lane index is a ds_read (the caller's lds_tile_load has the barrier)
+SVR_DEV void lds_lights_load(DevLight* dst, const DevScene& s)
+{
+    if (threadIdx.x < 8u * (sizeof(DevLight) / 4u)) reinterpret_cast<float*>(dst)[threadIdx.x] = reinterpret_cast<const float*>(s.lights)[threadIdx.x];
+}
+// ON: a pointer to the kernel's DevScene (its first argument: offset 0 of the kernarg segment, a constant address space -- the loads stay scalar) that is
+// LAUNDERED per use, so that the compiler loads the constants read through it where they are used instead of keeping them in (spilled) scalar registers
+// across the walk loops.  Off: null = read `s` (see shade_event's scp)
+template <bool ON>
+SVR_DEV const DevScene* cold_scene()
+{
+    if constexpr (ON) {
+        auto p = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(p));
+        return (const DevScene*)p;
+    } else return nullptr;
+}
+
 // queue memory of one wave: word j of record i of a stack at base[j * cap + i]
 struct LaneQueue { uint32_t* q; uint32_t cap; };
 

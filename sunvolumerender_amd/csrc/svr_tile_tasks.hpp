@@ -1,5 +1,6 @@
-// svr_tile_tasks.hpp -- what the persistent tile kernels (svr_trace_tile.hip, svr_trace_lm.hip) share: the order in which a
-// launch's wave-tasks are handed out, and the running mean of a pixel's frames inside the kernel (fold_pending).
+// svr_tile_tasks.hpp -- what the persistent tile kernels (svr_trace_tile.hip, svr_trace_lm.hip, svr_trace_env.hip) share: the order in which a
+// launch's wave-tasks are handed out (task_take, task_lanes; task_launch_setup on the host), and the running mean of a pixel's frames
+// inside the kernel (fold_pending).
 #pragma once
 #include "svr_kernel_common.hpp"
 
@@ -70,6 +71,67 @@ SVR_DEV void task_decode(const TaskShape& ts, uint32_t k, uint32_t& tx, uint32_t
     ty = (rr & 1u) ? ts.c_row - off : ts.c_row + off;
     tx = in_row / ts.fgroups;
     fg = in_row - tx * ts.fgroups;
+}
+
+// The next task of ticket counter `shard` for this wave, or TASK_NONE: the counter is drained.  si = how many counters the wave has
+// visited before this one: away from its home counter (si != 0) it looks before taking -- when the launch runs out every wave visits
+// every counter once, and a plain load of a drained counter is free (the counters only grow: a stale value just means one atomic more).
+constexpr uint32_t TASK_NONE = 0xffffffffu;
+SVR_DEV uint32_t task_take(const DevWork& w, const TaskShape& ts, uint32_t shard, uint32_t si, uint32_t lane)
+{
+    uint32_t* ticket = w.ticket + shard * TICKET_STRIDE;
+    if (si != 0u && __atomic_load_n(ticket, __ATOMIC_RELAXED) * TICKET_SHARDS + shard >= ts.n_tasks) return TASK_NONE;
+    uint32_t u = 0;
+    if (lane == 0) u = atomicAdd(ticket, 1u);
+    u = __builtin_amdgcn_readfirstlane(u);
+    const uint32_t k = u * TICKET_SHARDS + shard;
+    return k < ts.n_tasks ? k : TASK_NONE;
+}
+
+// What lane `lane` of the wave holds of task k: pixel column px and row r (of the launch's window / owned rows), frame slot, and whether
+// all three lie inside the launch.  The low P2 bits of a lane number its pixel in the task's tw x th block, the rest its frame.
+struct TaskLanes { uint32_t px, r, slot; bool live; };
+SVR_DEV TaskLanes task_lanes(const TaskShape& ts, const DevWork& w, uint32_t k, uint32_t lane)
+{
+    uint32_t tx, ty, fg;
+    task_decode(ts, k, tx, ty, fg);
+    const uint32_t pl = lane & ((1u << ts.P2) - 1u);
+    TaskLanes t;
+    t.slot = (fg << ts.fl2) + (lane >> ts.P2);
+    t.px = (tx << ts.tw2) + (pl & ((1u << ts.tw2) - 1u));
+    t.r = (ty << ts.th2) + (pl >> ts.tw2);
+    t.live = t.px < ts.wv && t.r < w.n_rows && t.slot < w.nframes;
+    return t;
+}
+
+// Host side of the same, for the launchers of the persistent kernels (launch_tile_t, launch_lm_t, launch_env_t): frames per wave, the
+// task count and the grid of a launch, its DevWork (unit = one task per ticket) and the reset of the ticket counters.
+//   frames per wave: the largest power of two <= min(nframes, 64), unless frames_log2 >= 0 asks for fewer; a FOLDING launch (fold:
+//   in-kernel accumulation) keeps every frame of a pixel in ONE wave -- frame lanes 0 .. nframes - 1 of its group; the caller has
+//   checked nframes <= 64
+//   grid: one wave per task up to num_cus x blocks_per_cu x 4 waves
+struct TaskGrid { uint32_t n_tasks, blocks; };
+inline hipError_t task_launch_setup(const DevWork& w, const LaunchCfg& cfg, uint32_t waves_per_block, bool fold, int frames_log2, hipStream_t st,
+                                    DevWork& w2, TaskGrid& g)
+{
+    uint32_t fl2 = 0;
+    while (fl2 < 6u && (2u << fl2) <= w.nframes) ++fl2;
+    if (frames_log2 >= 0 && (uint32_t)frames_log2 < fl2) fl2 = (uint32_t)frames_log2;
+    if (fold) {
+        fl2 = 0;
+        while ((1u << fl2) < w.nframes) ++fl2;
+    }
+    const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
+    const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
+    g.n_tasks = launch_tasks(w, tw2, th2, fgroups);
+    const uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / waves_per_block;
+    g.blocks = (g.n_tasks + waves_per_block - 1u) / waves_per_block;
+    if (g.blocks > max_blocks) g.blocks = max_blocks;
+    if (g.blocks == 0) g.blocks = 1;
+    w2 = w;
+    w2.unit = 1u;
+    w2.frames_log2 = fl2;
+    return hipMemsetAsync(w.ticket, 0, sizeof(uint32_t) * TICKET_SHARDS * TICKET_STRIDE, st);
 }
 
 // running_estimate (pathtracer.cu:81-84,279) for the pending tasks of this wave: the 1 << fl2 lanes of a task that

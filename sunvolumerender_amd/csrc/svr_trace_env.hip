@@ -145,9 +145,7 @@ SVR_DEV v3 trace_path_env(const DevScene& s, const LDS& L_, uint32_t x, uint32_t
         if (k == 0 && ls_id >= 0) {
             t = t < 0.f ? SVR_FLT_MAX : t;
             if (ls_t < t) {
-                const DevLight& l = s.lights[ls_id];
-                const float cosTerm = dot(V3(l.normal[0], l.normal[1], l.normal[2]), -dir);
-                L = L + (T * V3(l.radiance[0], l.radiance[1], l.radiance[2])) * (cosTerm <= 0.f ? 0.f : 1.f);
+                L = light_seen(L, T, s.lights[ls_id], dir);
                 break;
             }
         }
@@ -163,10 +161,7 @@ SVR_DEV v3 trace_path_env(const DevScene& s, const LDS& L_, uint32_t x, uint32_t
         if (ne.have) {
             float sMin = (float)1e-6, sMax = SVR_FLT_MAX, sval = 0.f;
             const float ts = walk<LAYOUT, COUNT, SKIP, SVR_SHADOW_REMARCH_ENV>(s, L_, vs.pt, ne.wi, rng, sMin, sMax, sval, true, c);
-            const float Tr = ((ts > sMin) && (ts < sMax)) ? 0.f : 1.f;
-            const float kf = Tr * (float)s.num_lights;
-            const DevLight& l = s.lights[ne.light];
-            L = L + T * (((ne.B * kf) * V3(l.radiance[0], l.radiance[1], l.radiance[2])) / ne.pdf);
+            L = L + T * direct_light(ts, sMin, sMax, s.num_lights, light_radiance(s.lights[ne.light]), ne.B, ne.pdf);
         }
         if (k + 1u >= traceDepth) break;
         // ---- the env sample of this event, paired with the escape term of bounce k + 1 ----
@@ -182,14 +177,13 @@ SVR_DEV v3 trace_path_env(const DevScene& s, const LDS& L_, uint32_t x, uint32_t
                 if (fmax_(F.x, fmax_(F.y, F.z)) > 0.f) {
                     float sMin = (float)1e-6, sMax = SVR_FLT_MAX, sval = 0.f;
                     const float ts = walk<LAYOUT, COUNT, SKIP, SVR_SHADOW_REMARCH_ENV>(s, L_, vs.pt, we, rng, sMin, sMax, sval, true, c);
-                    const float Tr = ((ts > sMin) && (ts < sMax)) ? 0.f : 1.f;
+                    const float Tr = shadow_transmittance(ts, sMin, sMax);
                     L = L + (T * F) * (Tr / (pe + q));
                 }
             }
         }
         v3 wi; float pdf = 0.f;
         const v3 f = bsdf_sample(vs, wi, pdf, rng);
-        const float cosTerm = __builtin_fabsf(dot(normalize(vs.gradient), wi));
         {
             // weight of what this direction will find if it escapes (the throughput T is still the one the env sample used)
             float q;
@@ -197,10 +191,7 @@ SVR_DEV v3 trace_path_env(const DevScene& s, const LDS& L_, uint32_t x, uint32_t
             const float pe = env_pdf(s, wi);
             esc_w = (q + pe) > 0.f ? q / (q + pe) : 1.f;
         }
-        if (fmax_(f.x, fmax_(f.y, f.z)) > 0.f && pdf > 0.f) {
-            if (vs.st == 0) T = T * (f / (pdf * (1.f - vs.Pbrdf)));
-            else T = T * ((f * cosTerm) / (pdf * vs.Pbrdf));
-        }
+        T = bsdf_throughput(T, vs, f, wi, pdf);
         orig = vs.pt;
         dir = wi;
         if (k >= 3 && russian_roulette(T, rng)) break;
@@ -219,31 +210,19 @@ __global__ __launch_bounds__(ENV_THREADS, 4) void k_trace_env(const DevScene s, 
     lds_tile_load(lds, s, SKIP);
     const uint32_t lane = threadIdx.x & 63u;
     const TaskShape ts = task_shape(w);
-    const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     Cnt c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (uint32_t si = 0; si < TICKET_SHARDS; ++si) {
         const uint32_t shard = (shard0 + si) % TICKET_SHARDS;
-        uint32_t* ticket = w.ticket + shard * TICKET_STRIDE;
         for (;;) {
-            if (si != 0u && __atomic_load_n(ticket, __ATOMIC_RELAXED) * TICKET_SHARDS + shard >= n_tasks) break;
-            uint32_t u = 0;
-            if (lane == 0) u = atomicAdd(ticket, 1u);
-            u = __builtin_amdgcn_readfirstlane(u);
-            const uint32_t k = u * TICKET_SHARDS + shard;
-            if (k >= n_tasks) break;
-            uint32_t tx, ty, fg;
-            task_decode(ts, k, tx, ty, fg);
+            const uint32_t k = task_take(w, ts, shard, si, lane);
+            if (k == TASK_NONE) break;
+            const TaskLanes tl = task_lanes(ts, w, k, lane);
             if (COUNT) c.loops += (lane == 0);
-            const uint32_t pl = lane & ((1u << P2) - 1u);
-            const uint32_t slot = (fg << fl2) + (lane >> P2);
-            const uint32_t px = (tx << tw2) + (pl & ((1u << tw2) - 1u));
-            const uint32_t r = (ty << th2) + (pl >> tw2);
-            if (px < wv && r < w.n_rows && slot < w.nframes) {
-                const uint32_t x = w.x0 + px, y = owned_row_to_y(w, r);
-                const v3 L = trace_path_env<LAYOUT, COUNT, SKIP>(s, lds, x, y, w.traceDepth, wang_hash(w.frame0 + slot), c);
-                float* o = w.lbuf + (size_t)slot * w.slot_stride + 3 * ((size_t)y * s.imageW + x);
+            if (tl.live) {
+                const uint32_t x = w.x0 + tl.px, y = owned_row_to_y(w, tl.r);
+                const v3 L = trace_path_env<LAYOUT, COUNT, SKIP>(s, lds, x, y, w.traceDepth, wang_hash(w.frame0 + tl.slot), c);
+                float* o = w.lbuf + (size_t)tl.slot * w.slot_stride + 3 * ((size_t)y * s.imageW + x);
                 o[0] = L.x; o[1] = L.y; o[2] = L.z;
             }
         }
@@ -257,21 +236,11 @@ static hipError_t launch_env_t(const DevScene& s, const DevWork& w, const Launch
     const uint32_t wv = w.x1 - w.x0;
     if (wv == 0 || w.n_rows == 0) return hipSuccess;
     if (s.env == nullptr || s.env_cdf == nullptr || w.lbuf == nullptr) return hipErrorInvalidValue;
-    uint32_t fl2 = 0;
-    while (fl2 < 6u && (2u << fl2) <= w.nframes) ++fl2;
-    const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
-    const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
-    const uint32_t n_tasks = launch_tasks(w, tw2, th2, fgroups);
-    constexpr uint32_t WPB = ENV_THREADS / 64;
-    const uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
-    uint32_t blocks = (n_tasks + WPB - 1u) / WPB;
-    if (blocks > max_blocks) blocks = max_blocks;
-    if (blocks == 0) blocks = 1;
-    DevWork w2 = w;
-    w2.unit = 1u;
-    w2.frames_log2 = fl2;
-    hipError_t e = hipMemsetAsync(w.ticket, 0, sizeof(uint32_t) * TICKET_SHARDS * TICKET_STRIDE, st);
+    DevWork w2;
+    TaskGrid g;
+    hipError_t e = task_launch_setup(w, cfg, ENV_THREADS / 64, false, -1, st, w2, g);        // (the mode never folds and takes no frames-per-wave override)
     if (e != hipSuccess) return e;
+    const uint32_t blocks = g.blocks;
     if (s.empty_mask != nullptr) hipLaunchKernelGGL((k_trace_env<LAYOUT, COUNT, true>), dim3(blocks), dim3(ENV_THREADS), 0, st, s, w2);
     else hipLaunchKernelGGL((k_trace_env<LAYOUT, COUNT, false>), dim3(blocks), dim3(ENV_THREADS), 0, st, s, w2);
     return hipGetLastError();

@@ -21,13 +21,17 @@
 // SVR_OPT_FAST_MATH.  Everything else (camera, shading, lights, BSDF, accumulation) is the bit-exact code.
 //
 // Three forms of one algorithm, bit-identical to each other: straight-line paths (k_trace_lm: non-folding launches, cross-check),
-// the record pool of traceDepth 1 (k_trace_lm_pool) and the slot-per-path pool of deeper paths (k_trace_lm_pool_deep).
+// the record pool of traceDepth 1 (k_trace_lm_pool) and the slot-per-path pool of deeper paths (k_trace_lm_pool_deep).  They share the
+// walk (lm_step, lm_tentative); tests/test_refactor_pins_gpu.py pins their common bits.
 #include "svr_walk.hpp"
 #include "svr_lanes.hpp"
 #include "svr_tile_tasks.hpp"
 
 #ifndef SVR_LM_DEEP_COLD
 #define SVR_LM_DEEP_COLD 1           // the slot-per-path pool of deeper paths: lights in LDS, set-up / shading / settling constants through the laundered kernarg pointer
+#endif
+#ifndef SVR_LM_COLD_SCENE
+#define SVR_LM_COLD_SCENE 1          // the depth-1 pool: set-up / shading / settling constants through the laundered kernarg pointer (svr_lanes.hpp, cold_scene)
 #endif
 #ifndef SVR_LM_LDS_LIGHTS
 #define SVR_LM_LDS_LIGHTS 1          // the depth-1 pool reads the lights from a copy in LDS (light sampling and settling index them per lane)
@@ -122,32 +126,20 @@ SVR_DEV int lm_step(const DevScene& s, const LDS& L, const LmGrid& g, LmWalk& w,
     if (COUNT) c.ipre++;
     uint32_t cl;
     if (g.fine) {
-        // (the three table words are read together -- one LDS round trip per cell instead of two dependent ones)
+        // (the class and distance words are read where they are needed: reading the three table words up front -- one LDS round trip per
+        // cell instead of two dependent ones -- was 0.5 % SLOWER on c3 / c5)
         const uint32_t hq = (uint32_t)((w.ix >> 1) + (w.iy >> 1) * s.mc_hgx + (w.iz >> 1) * s.mc_hgxy);
-#ifndef SVR_LM_LDS_TOGETHER
-#define SVR_LM_LDS_TOGETHER 0        // (reading the three table words up front -- one LDS round trip per cell instead of two dependent ones -- was 0.5 % SLOWER on c3 / c5)
-#endif
-#if SVR_LM_LDS_TOGETHER
-        const uint32_t ew = L.emask[(uint32_t)w.q >> 5], cw = L.cls[hq >> 3], dw = L.dist[hq >> 3];
-#else
         const uint32_t ew = L.emask[(uint32_t)w.q >> 5];
-#define cw L.cls[hq >> 3]
-#define dw L.dist[hq >> 3]
-#endif
         const bool empty = (ew >> ((uint32_t)w.q & 31u)) & 1u;
         cl = 0u;
-        if (!empty) { cl = (cw >> ((hq & 7u) << 2)) & 15u; w.run = 0u; }
+        if (!empty) { cl = (L.cls[hq >> 3] >> ((hq & 7u) << 2)) & 15u; w.run = 0u; }
         else if (++w.run >= 3u) {
             // Empty space: no free path is spent, so the walk may LEAP.  Every macro-cell within Chebyshev distance dd - 1 of this
             // one is empty (distance field, svr_accel.hip): the ray may advance until its largest-axis displacement is dd - 1
             // cells (first_occupied's sphere tracing, svr_walk.hpp) and pick up the DDA in the cell it lands in.  Boundaries are
             // absolute, so where exactly a leap lands does not change what follows.  (Tried from the third empty cell in a row on:
             // the gaps between the cells of a surface are shorter than that.)
-            const uint32_t dd = (dw >> ((hq & 7u) << 2)) & 15u;
-#if !SVR_LM_LDS_TOGETHER
-#undef cw
-#undef dw
-#endif
+            const uint32_t dd = (L.dist[hq >> 3] >> ((hq & 7u) << 2)) & 15u;
             if (dd >= 4u) {
                 const float inv = fmin_(__builtin_fabsf(w.rx), fmin_(__builtin_fabsf(w.ry), __builtin_fabsf(w.rz))) * 0.999f;      // 1 / largest |B|
                 const float tl = fma_((float)dd - 1.05f, inv, w.t);
@@ -424,6 +416,53 @@ static_assert((LM_RAY_WORDS + LM_HIT_WORDS) * LM_CAP1 <= REC_WORDS * QUEUE_CAP, 
 static_assert(LM_BATCH <= QUEUE_TASKS && LM_BATCH1 <= QUEUE_TASKS, "pending-radiance rows");
 // meta: id (11 bits: task-in-batch << 6 | lane) | light or (nearest light + 1) << 12
 SVR_DEV uint32_t lm_meta(uint32_t id, uint32_t light) { return id | (light << 12); }
+
+// kernel_pathtracer up to the primary walk (pathtracer.cu:205-218), as in trace_path_lm: generator, camera ray, nearest light, box, whole-ray
+// test (shared by the pixel's frames when the wave is full).  run = the ray has something occupied ahead; otherwise L is final.
+struct LmGen { bool run; v3 L, orig, dir; Rng rng; float ls_t, t0, tMax; int ls_id; };
+template <bool COUNT, typename LDS>
+SVR_DEV LmGen lm_gen(const DevScene& s, const LDS& lds, GroupMapShared* gm, bool live, bool group_march, uint32_t P2, uint32_t x, uint32_t y, uint32_t hashed, Cnt& c,
+                     const DevScene* scp = nullptr)
+{
+    const DevScene& sc = scp ? *scp : s;
+    const float INF = u2f(SVR_INF_BITS);
+    LmGen g;
+    g.run = false; g.L = V3(0.f, 0.f, 0.f); g.orig = g.L; g.dir = V3(0.f, 0.f, 1.f);
+    g.rng = Rng{0u, 0u, 0u, 0u, 0u, 0u};
+    g.ls_t = 0.f; g.t0 = 0.f; g.tMax = 0.f; g.ls_id = -1;
+    if (live) {
+        rng_init(g.rng, hashed + (y * sc.imageW + x));
+        if (COUNT) c.paths++;
+        camera_ray(sc, x, y, g.rng, g.orig, g.dir);
+        g.ls_id = nearest_light(sc, g.orig, g.dir, g.ls_t);
+        float tMin = (float)1e-6;
+        g.tMax = SVR_FLT_MAX;
+        if (group_march) {
+            float t_occ;
+            GroupMap map;
+            map.g = gm + ((threadIdx.x & 63u) & ((1u << P2) - 1u) & (GROUP_MAPS_PER_WAVE - 1u));
+            const int rr = walk_setup_group<true, true>(s, lds, P2, g.orig, g.dir, false, tMin, g.tMax, t_occ, map);
+            g.run = rr > 0 && t_occ != INF;
+            g.t0 = fmax_(t_occ, tMin);                                   // (the shared test starts at the group's earliest box entry)
+        } else {
+            float tNear, tFar;
+            if (volume_intersect(s, g.orig, g.dir, tNear, tFar)) {
+                tMin = tNear < 0.f ? (float)1e-6 : tNear;
+                g.tMax = tFar;
+                g.t0 = first_occupied(s, lds, g.orig, g.dir, tMin, g.tMax);      // (per-lane whole-ray test: the same early end as under the shared one)
+                g.run = g.t0 != INF;
+            }
+        }
+        if (!g.run) {
+            if (g.ls_id >= 0) {                                           // t = FLT_MAX > ls.t: the light is seen (pathtracer.cu:220-229)
+                const DevLight& l = sc.lights[g.ls_id];
+                const float cosTerm = dot(V3(l.normal[0], l.normal[1], l.normal[2]), -g.dir);
+                g.L = V3(l.radiance[0], l.radiance[1], l.radiance[2]) * (cosTerm <= 0.f ? 0.f : 1.f);
+            } else if (sc.env_on_escape) g.L = env_radiance(sc, g.dir);
+        }
+    }
+    return g;
+}
 
 template <int LAYOUT, bool COUNT, uint32_t NB, typename LDS>
 SVR_DEV void lm_walk_pool(const DevScene& s, const LDS& L_, const uint32_t* R, uint32_t n, const bool shadows, uint32_t* H, uint32_t& nH,
@@ -879,53 +918,6 @@ SVR_DEV void lm_walk_pool_deep(const DevScene& s, const LDS& L_, uint32_t* F, co
     }
 }
 
-// kernel_pathtracer up to the primary walk (pathtracer.cu:205-218), as in trace_path_lm: generator, camera ray, nearest light, box, whole-ray
-// test (shared by the pixel's frames when the wave is full).  run = the ray has something occupied ahead; otherwise L is final.
-struct LmGen { bool run; v3 L, orig, dir; Rng rng; float ls_t, t0, tMax; int ls_id; };
-template <bool COUNT, typename LDS>
-SVR_DEV LmGen lm_gen(const DevScene& s, const LDS& lds, GroupMapShared* gm, bool live, bool group_march, uint32_t P2, uint32_t x, uint32_t y, uint32_t hashed, Cnt& c,
-                     const DevScene* scp = nullptr)
-{
-    const DevScene& sc = scp ? *scp : s;
-    const float INF = u2f(SVR_INF_BITS);
-    LmGen g;
-    g.run = false; g.L = V3(0.f, 0.f, 0.f); g.orig = g.L; g.dir = V3(0.f, 0.f, 1.f);
-    g.rng = Rng{0u, 0u, 0u, 0u, 0u, 0u};
-    g.ls_t = 0.f; g.t0 = 0.f; g.tMax = 0.f; g.ls_id = -1;
-    if (live) {
-        rng_init(g.rng, hashed + (y * sc.imageW + x));
-        if (COUNT) c.paths++;
-        camera_ray(sc, x, y, g.rng, g.orig, g.dir);
-        g.ls_id = nearest_light(sc, g.orig, g.dir, g.ls_t);
-        float tMin = (float)1e-6;
-        g.tMax = SVR_FLT_MAX;
-        if (group_march) {
-            float t_occ;
-            GroupMap map;
-            map.g = gm + ((threadIdx.x & 63u) & ((1u << P2) - 1u) & (GROUP_MAPS_PER_WAVE - 1u));
-            const int rr = walk_setup_group<true, true>(s, lds, P2, g.orig, g.dir, false, tMin, g.tMax, t_occ, map);
-            g.run = rr > 0 && t_occ != INF;
-            g.t0 = fmax_(t_occ, tMin);                                   // (the shared test starts at the group's earliest box entry)
-        } else {
-            float tNear, tFar;
-            if (volume_intersect(s, g.orig, g.dir, tNear, tFar)) {
-                tMin = tNear < 0.f ? (float)1e-6 : tNear;
-                g.tMax = tFar;
-                g.t0 = first_occupied(s, lds, g.orig, g.dir, tMin, g.tMax);      // (per-lane whole-ray test: the same early end as under the shared one)
-                g.run = g.t0 != INF;
-            }
-        }
-        if (!g.run) {
-            if (g.ls_id >= 0) {                                           // t = FLT_MAX > ls.t: the light is seen (pathtracer.cu:220-229)
-                const DevLight& l = sc.lights[g.ls_id];
-                const float cosTerm = dot(V3(l.normal[0], l.normal[1], l.normal[2]), -g.dir);
-                g.L = V3(l.radiance[0], l.radiance[1], l.radiance[2]) * (cosTerm <= 0.f ? 0.f : 1.f);
-            } else if (sc.env_on_escape) g.L = env_radiance(sc, g.dir);
-        }
-    }
-    return g;
-}
-
 template <int LAYOUT, bool COUNT>
 __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_pool_deep(const DevScene s, const DevWork w)
 {
@@ -933,23 +925,13 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
     __shared__ GroupMapShared gmaps[TILE_WAVES][GROUP_MAPS_PER_WAVE];
     __shared__ uint32_t pend_task[TILE_WAVES][QUEUE_TASKS];
     __shared__ DevLight lds_lights[8];                                   // (as in k_trace_lm_pool)
-    if (threadIdx.x < 8u * (sizeof(DevLight) / 4u)) reinterpret_cast<float*>(lds_lights)[threadIdx.x] = reinterpret_cast<const float*>(s.lights)[threadIdx.x];
+    lds_lights_load(lds_lights, s);
     const DevLight* const lts = lds_lights;
-    auto cold_scene = [&]() -> const DevScene* {
-#if SVR_LM_DEEP_COLD
-        auto p = __builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(p));
-        return (const DevScene*)p;
-#else
-        return nullptr;
-#endif
-    };
+    constexpr bool COLD = SVR_LM_DEEP_COLD != 0;
     lds_tile_load(lds, s, true);
 
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const TaskShape ts = task_shape(w);
-    const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
-    const uint32_t n_tasks = ts.n_tasks;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
     const uint32_t depth = w.traceDepth;
     const size_t wslot = (size_t)(blockIdx.x * TILE_WAVES + wave);
@@ -960,10 +942,6 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
     uint32_t* const LS = LH + LM_CAP;
     uint32_t* const LA = LS + LM_CAP;
     Cnt c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto fence = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");            // slots, lists and radiance rows are read back by other lanes of this wave
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
     uint32_t si = 0u;
     for (;;) {
         // ---- gen: up to LM_BATCH tasks ----
@@ -971,22 +949,23 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
         while (nb < LM_BATCH && si < TICKET_SHARDS) {
             const uint32_t shard = (shard0 + si) % TICKET_SHARDS;
             uint32_t* ticket = w.ticket + shard * TICKET_STRIDE;
-            if (si != 0u && __atomic_load_n(ticket, __ATOMIC_RELAXED) * TICKET_SHARDS + shard >= n_tasks) { ++si; continue; }
+            if (si != 0u && __atomic_load_n(ticket, __ATOMIC_RELAXED) * TICKET_SHARDS + shard >= ts.n_tasks) { ++si; continue; }
             uint32_t u = 0;
             if (lane == 0) u = atomicAdd(ticket, 1u);
             u = __builtin_amdgcn_readfirstlane(u);
             const uint32_t k = u * TICKET_SHARDS + shard;
-            if (k >= n_tasks) { ++si; continue; }
+            if (k >= ts.n_tasks) { ++si; continue; }
             uint32_t tx, ty, fg;
             task_decode(ts, k, tx, ty, fg);
             if (COUNT) c.loops += (lane == 0);
-            const uint32_t pl = lane & ((1u << P2) - 1u);
+            const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv;
+            const uint32_t pl_ = lane & ((1u << P2) - 1u);
             const uint32_t fslot = (fg << fl2) + (lane >> P2);
-            const uint32_t px = (tx << tw2) + (pl & ((1u << tw2) - 1u));
-            const uint32_t r = (ty << th2) + (pl >> tw2);
+            const uint32_t px = (tx << tw2) + (pl_ & ((1u << tw2) - 1u));
+            const uint32_t r = (ty << th2) + (pl_ >> tw2);
             const bool live = px < wv && r < w.n_rows && fslot < w.nframes;
             const bool group_march = fl2 >= 3u && __ballot(live) == ~0ull;
-            const LmGen g = lm_gen<COUNT>(s, lds, &gmaps[wave][0], live, group_march, P2, w.x0 + px, live ? owned_row_to_y(w, r) : 0u, wang_hash(w.frame0 + fslot), c, cold_scene());
+            const LmGen g = lm_gen<COUNT>(s, lds, &gmaps[wave][0], live, group_march, P2, w.x0 + px, live ? owned_row_to_y(w, r) : 0u, wang_hash(w.frame0 + fslot), c, cold_scene<COLD>());
             {
                 float* p = gpend + (size_t)nb * (3u * 64u) + lane;       // (queued paths overwrite theirs when they end)
                 p[0] = g.L.x; p[64] = g.L.y; p[128] = g.L.z;
@@ -1010,10 +989,10 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
         for (uint32_t k = 0; k < depth && nW != 0u; ++k) {
             const bool last = k + 1u >= depth;
             // ---- walk: this bounce's rays -> hits ----
+            wave_fence();
             uint32_t nH = 0u;
-            fence();
-            lm_walk_pool_deep<LAYOUT, COUNT>(s, lds, F, LW, nW, k == 0u ? LMK_PRIMARY : LMK_CONT, last, LH, nH, gpend, c, cold_scene(), lts);
-            fence();
+            lm_walk_pool_deep<LAYOUT, COUNT>(s, lds, F, LW, nW, k == 0u ? LMK_PRIMARY : LMK_CONT, last, LH, nH, gpend, c, cold_scene<COLD>(), lts);
+            wave_fence();
             // ---- shade the hits, 64 at a time (VolumeSample + light sampling, pathtracer.cu:237-257) ----
             uint32_t nS = 0u, nA = 0u;
             for (uint32_t i0 = 0u; i0 < nH; i0 += 64u) {
@@ -1029,7 +1008,7 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
                     Rng rng;
                     rec_rng_load(f + SF_RNG * LM_CAP, LM_CAP, rng);
                     Nee ne;
-                    shade_event<LAYOUT, COUNT, SVR_LM_DEEP_COLD != 0>(s, vs, val, rng, ne, c, cold_scene(), lts);
+                    shade_event<LAYOUT, COUNT, SVR_LM_DEEP_COLD != 0>(s, vs, val, rng, ne, c, cold_scene<COLD>(), lts);
                     rec_rng_store(f + SF_RNG * LM_CAP, LM_CAP, rng);
                     if (!last) {                                            // what sample_bsdf needs of the event
                         rec_v3_store(f + SF_GRAD * LM_CAP, LM_CAP, vs.gradient);
@@ -1042,11 +1021,8 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
                         rec_v3_store(f + SF_B * LM_CAP, LM_CAP, ne.B);
                         f[SF_PDF * LM_CAP] = f2u(ne.pdf);
                         to_s = true;
-                    } else if (last) {                                      // no light sample reaches the event and nothing follows: L is final
-                        const v3 L = rec_v3_load(f + SF_L * LM_CAP, LM_CAP);
-                        float* p = gpend + (id >> 6) * (3u * 64u) + (id & 63u);
-                        p[0] = L.x; p[64] = L.y; p[128] = L.z;
-                    } else to_a = true;
+                    } else if (last) pend_row_put(gpend, id, rec_v3_load(f + SF_L * LM_CAP, LM_CAP));      // no light sample reaches the event and nothing follows: L is final
+                    else to_a = true;
                 }
                 const uint64_t ms = __ballot(to_s), ma = __ballot(to_a);
                 if (to_s) LS[nS + lane_rank(ms)] = id;
@@ -1054,9 +1030,9 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
                 nS += (uint32_t)__popcll(ms); nA += (uint32_t)__popcll(ma);
             }
             // ---- walk: the shadow rays -> A (or final, at the last bounce) ----
-            fence();
-            lm_walk_pool_deep<LAYOUT, COUNT>(s, lds, F, LS, nS, LMK_SHADOW, last, LA, nA, gpend, c, cold_scene(), lts);
-            fence();
+            wave_fence();
+            lm_walk_pool_deep<LAYOUT, COUNT>(s, lds, F, LS, nS, LMK_SHADOW, last, LA, nA, gpend, c, cold_scene<COLD>(), lts);
+            wave_fence();
             nW = 0u;
             if (last) break;
             // ---- sample_bsdf, throughput, roulette (pathtracer.cu:258-276), 64 at a time -> the next bounce's rays ----
@@ -1078,16 +1054,9 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
                     rec_rng_load(f + SF_RNG * LM_CAP, LM_CAP, rng);
                     v3 wi; float pdf = 0.f;
                     const v3 fr = bsdf_sample(vs, wi, pdf, rng);
-                    const float cosTerm = __builtin_fabsf(dot(normalize(vs.gradient), wi));
-                    if (fmax_(fr.x, fmax_(fr.y, fr.z)) > 0.f && pdf > 0.f) {
-                        if (vs.st == 0) T = T * (fr / (pdf * (1.f - vs.Pbrdf)));
-                        else T = T * ((fr * cosTerm) / (pdf * vs.Pbrdf));
-                    }
-                    if (k >= 3u && russian_roulette(T, rng)) {              // the path ends: L is final
-                        const v3 L = rec_v3_load(f + SF_L * LM_CAP, LM_CAP);
-                        float* p = gpend + (id >> 6) * (3u * 64u) + (id & 63u);
-                        p[0] = L.x; p[64] = L.y; p[128] = L.z;
-                    } else {
+                    T = bsdf_throughput(T, vs, fr, wi, pdf);
+                    if (k >= 3u && russian_roulette(T, rng)) pend_row_put(gpend, id, rec_v3_load(f + SF_L * LM_CAP, LM_CAP));     // the path ends: L is final
+                    else {
                         rec_v3_store(f + SF_D * LM_CAP, LM_CAP, wi);        // (the next ray starts at the event: SF_O already holds it)
                         rec_v3_store(f + SF_T * LM_CAP, LM_CAP, T);
                         rec_rng_store(f + SF_RNG * LM_CAP, LM_CAP, rng);
@@ -1100,9 +1069,9 @@ __global__ __launch_bounds__(LM_THREADS, SVR_LM_WAVES_PER_EU) void k_trace_lm_po
             }
         }
         // ---- fold the batch ----
-        fence();
+        wave_fence();
         fold_pending(s, w, gpend, 64u, &pend_task[wave][0], nb);
-        fence();
+        wave_fence();
     }
     if (COUNT) cnt_flush(w, c);
 }
@@ -1183,29 +1152,13 @@ static hipError_t launch_lm_t(const DevScene& s, const DevWork& w, const LaunchC
 {
     const uint32_t wv = w.x1 - w.x0;
     if (wv == 0 || w.n_rows == 0) return hipSuccess;
-    // frames per wave: as many as the launch holds (<= 64); a folding launch keeps every frame of a pixel in one wave
-    uint32_t fl2 = 0;
-    while (fl2 < 6u && (2u << fl2) <= w.nframes) ++fl2;
-    if (cfg.frames_log2 >= 0 && (uint32_t)cfg.frames_log2 < fl2) fl2 = (uint32_t)cfg.frames_log2;
-    if (w.fold) {
-        if (w.nframes > 64u || w.pend == nullptr) return hipErrorInvalidValue;
-        fl2 = 0;
-        while ((1u << fl2) < w.nframes) ++fl2;
-    }
-    const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
-    const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
-    const uint32_t n_tasks = launch_tasks(w, tw2, th2, fgroups);
-    constexpr uint32_t WPB = LM_THREADS / 64;
-    const uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
-    uint32_t blocks = (n_tasks + WPB - 1u) / WPB;
-    if (blocks > max_blocks) blocks = max_blocks;
-    if (w.fold && blocks > w.queue_blocks) return hipErrorInvalidValue;       // the rows are sized for queue_blocks blocks
-    if (blocks == 0) blocks = 1;
-    DevWork w2 = w;
-    w2.unit = 1u;
-    w2.frames_log2 = fl2;
-    hipError_t e = hipMemsetAsync(w.ticket, 0, sizeof(uint32_t) * TICKET_SHARDS * TICKET_STRIDE, st);
+    if (w.fold && (w.nframes > 64u || w.pend == nullptr)) return hipErrorInvalidValue;
+    DevWork w2;
+    TaskGrid g;
+    hipError_t e = task_launch_setup(w, cfg, LM_THREADS / 64, w.fold != 0u, cfg.frames_log2, st, w2, g);
     if (e != hipSuccess) return e;
+    const uint32_t blocks = g.blocks;
+    if (w.fold && blocks > w.queue_blocks) return hipErrorInvalidValue;       // the rows are sized for queue_blocks blocks
     // traceDepth 1 (the reference's default), folding launch, queue memory at hand: the pool form
     if (w.traceDepth == 1u && w.fold && w.queue != nullptr && !cfg.lm_straight) {
         // tasks per batch (DevScene.lm_tune bits 24-31): two builds -- 10 (scenes with transparent space) and 21 (fog: 63 of 64 lanes in the fold)

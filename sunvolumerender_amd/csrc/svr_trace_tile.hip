@@ -505,35 +505,17 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
 {
     uint32_t wv = w.x1 - w.x0;
     if (wv == 0 || w.n_rows == 0) return hipSuccess;
-    // frames per wave: the largest power of two <= min(nframes, 64), unless overridden
-    uint32_t fl2 = 0;
-    while (fl2 < 6u && (2u << fl2) <= w.nframes) ++fl2;
-    if (cfg.frames_log2 >= 0 && (uint32_t)cfg.frames_log2 < fl2) fl2 = (uint32_t)cfg.frames_log2;
-    if (w.fold) {
-        // in-kernel accumulation: every frame of a pixel must sit in ONE wave (frame lanes 0 .. nframes-1 of its group)
-        if (w.nframes > 64u) return hipErrorInvalidValue;
-        fl2 = 0;
-        while ((1u << fl2) < w.nframes) ++fl2;
-    }
-    const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
-    const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
-    uint32_t n_tasks = launch_tasks(w, tw2, th2, fgroups);
-    constexpr uint32_t WPB = SVR_TILE_THREADS / 64;                       // waves per block
-    uint32_t max_blocks = (uint32_t)(cfg.num_cus * cfg.blocks_per_cu) * 4u / WPB;
-    uint32_t need = (n_tasks + WPB - 1u) / WPB;
-    uint32_t blocks = need < max_blocks ? need : max_blocks;
-    if (blocks == 0) blocks = 1;
+    if (w.fold && w.nframes > 64u) return hipErrorInvalidValue;         // in-kernel accumulation: every frame of a pixel sits in ONE wave
+    DevWork w2;
+    TaskGrid g;
+    hipError_t e = task_launch_setup(w, cfg, SVR_TILE_THREADS / 64, w.fold != 0u, cfg.frames_log2, st, w2, g);
+    if (e != hipSuccess) return e;
+    const uint32_t blocks = g.blocks;
     // ticket unit: ONE task.  Task costs differ by two orders of magnitude (a block of skipped rays vs a block of
     // grazing rays), so coarser units leave most waves idle behind the last heavy unit: measured 0.183 / 0.189 /
     // 0.208 / 0.230 / 0.279 ms per frame at 1 / 2 / 4 / 8 / 16 tasks per ticket (8-frame groups).  With 8 ticket
     // shards the atomics are not a limit (~130 k per launch).
-    DevWork w2 = w;
-    uint32_t unit = 1u;
-    if (cfg.unit_override > 0) unit = (uint32_t)cfg.unit_override;
-    w2.unit = unit;
-    w2.frames_log2 = fl2;
-    hipError_t e = hipMemsetAsync(w.ticket, 0, sizeof(uint32_t) * TICKET_SHARDS * TICKET_STRIDE, st);
-    if (e != hipSuccess) return e;
+    if (cfg.unit_override > 0) w2.unit = (uint32_t)cfg.unit_override;
     const bool skip = s.empty_mask != nullptr, d1 = w.traceDepth == 1u;
     // QUEUE builds need the per-wave record queues (DevWork.queue, sized for `queue_blocks` blocks) and exist for the BRICK layout only
     // (launches that do not fold -- frames traced ahead -- have the queue builds in their DIRECT form, which is not built with counters)

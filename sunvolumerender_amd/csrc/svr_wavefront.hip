@@ -86,9 +86,7 @@ SVR_DEV v3 finish_miss(const DevScene& s, uint32_t k, int ls_id, v3 dir, v3 T, v
 {
     if (k == 0u && ls_id >= 0) {
         // t = FLT_MAX, ls.t < t always
-        const DevLight& l = s.lights[ls_id];
-        float cosTerm = dot(V3(l.normal[0], l.normal[1], l.normal[2]), -dir);
-        return L + (T * V3(l.radiance[0], l.radiance[1], l.radiance[2])) * (cosTerm <= 0.f ? 0.f : 1.f);
+        return light_seen(L, T, s.lights[ls_id], dir);
     }
     if (s.env_on_escape) L = L + T * env_radiance(s, dir);
     return L;
@@ -306,9 +304,7 @@ __global__ __launch_bounds__(256) void k_wf_shade(const DevScene s, const DevWor
                     float sMin = (float)1e-6, sMax = SVR_FLT_MAX, sval = 0.f;
                     if (COUNT) c.shadow++;
                     float ts = walk<LAYOUT, COUNT, SKIP, false>(s, lds, vs.pt, wiL, rng, sMin, sMax, sval, k + 1u < traceDepth, c);
-                    float Tr = ((ts > sMin) && (ts < sMax)) ? 0.f : 1.f;
-                    float kf = Tr * (float)s.num_lights;
-                    Ld = ((bsdf_eval(vs, wiL) * kf) * Li) / pdfL;
+                    Ld = direct_light(ts, sMin, sMax, s.num_lights, Li, bsdf_eval(vs, wiL), pdfL);          // transmittance.h:15-16
                 }
             }
             L = L + T * Ld;
@@ -316,11 +312,7 @@ __global__ __launch_bounds__(256) void k_wf_shade(const DevScene s, const DevWor
             if (!done) {
                 v3 wi; float pdf = 0.f;
                 v3 f = bsdf_sample(vs, wi, pdf, rng);
-                float cosTerm = __builtin_fabsf(dot(normalize(vs.gradient), wi));
-                if (fmax_(f.x, fmax_(f.y, f.z)) > 0.f && pdf > 0.f) {
-                    if (vs.st == 0) T = T * (f / (pdf * (1.f - vs.Pbrdf)));
-                    else T = T * ((f * cosTerm) / (pdf * vs.Pbrdf));
-                }
+                T = bsdf_throughput(T, vs, f, wi, pdf);
                 if (k >= 3u && russian_roulette(T, rng)) done = true;
                 if (!done) {
                     float tMin = (float)1e-6, tMax = SVR_FLT_MAX, t_occ = 0.f;

@@ -270,6 +270,38 @@ def test_local_majorant_pool_equals_straight_line_full_frame(hip_dev, name, dept
         canvas.close()
 
 
+@pytest.mark.parametrize("depth", [1, 3])
+def test_local_majorant_pool_equals_straight_line_full_and_partial_batches(hip_dev, depth):
+    """A wave of the pool kernels that takes SEVERAL batches, the last one partial.  small_head (256^2, 128^3), one 64-frame call: 65 536
+    one-pixel tasks; with SVR_OPT_BLOCKS_PER_CU = 1 the launcher's num_cus x 1 x 4 / 16 gives at most 64 blocks = 1 024 waves, i.e. about 64
+    tasks per wave -- several full batches and a partial one for both builds of the record pool (SVR_OPT_LM_TUNE bits 24-31: 10 and 21 tasks
+    per batch) and for the 16-task batches of the slot pool (depth 3).  Bit-identical to the straight-line form."""
+    sc, canvas = _canvas(hip_dev, "small_head", trace_depth=depth)
+    dev = hip_dev
+    old = [(o, dev.lib.svr_get_option(o)) for o in (abi.OPT_BLOCKS_PER_CU, abi.OPT_LM_TUNE)]
+    try:
+        dev.set_option(abi.OPT_BLOCKS_PER_CU, 1)
+
+        def run(mode):
+            dev.set_option(abi.OPT_LOCAL_MAJORANT, mode)
+            canvas.ReStartRender()
+            canvas.paint_frames(64, sync=True)
+            return canvas.read_hdr(), canvas.read_img()
+
+        ref, ref_img = run(2)
+        assert ref.max() > 0
+        for tasks in (10, 21):
+            dev.set_option(abi.OPT_LM_TUNE, 1 | (16 << 8) | (16 << 16) | (tasks << 24))      # (the depth-1 default gates of a scene with transparent space, at both depths)
+            hdr, img = run(1)
+            assert_bit_exact(hdr, ref, f"small_head depth {depth}, {tasks} tasks per batch, 1 block per CU: pools vs straight-line paths")
+            assert np.array_equal(img, ref_img)
+    finally:
+        for o, v in old:
+            dev.set_option(o, v)
+        dev.set_option(abi.OPT_LOCAL_MAJORANT, 0)
+        canvas.close()
+
+
 @pytest.mark.parametrize("name,depth", [("small_head", 1), ("small_head_noisy", 3), ("odd", 2)])
 def test_local_majorant_image_does_not_depend_on_scheduling_or_layout(hip_dev, name, depth):
     """What is scheduling or storage stays scheduling or storage in this mode too: the pool's cells per turn and refill /
