@@ -355,6 +355,18 @@ int svr_selftest_math(int fn, const float* in, uint32_t in_stride, float* out, u
  * accept test forms there (exact cell, fetch, alpha, invSigmaMax).  out[i] = 1 tested | 2 VIOLATION (a draw the byte culls could be accepted)
  * | 4 index outside the table | byte << 8; 0 = the ray misses the box.  Fails (-3) when the look-up is not in use for the scene */
 int svr_selftest_bound8(const float* rays, uint32_t n, uint32_t* out);
+/* The macro-cell grid a volume texture of nx x ny x nz voxels gets (plain host code, no GPU needed): the smallest shift >= shift_min whose grid
+ * (ceil(n / 2^shift) cells per axis) has at most 64^3 cells AND whose half-resolution grid (ceil(g / 2) per axis: the 4-bit distance and
+ * bound-class tables) has at most 32^3 -- a flat or line-like volume is limited by the second.  out = { shift, gx, gy, gz, hgx, hgy, hgz,
+ * words of the packed half-resolution tables }.  Returns the shift, -1 on bad arguments */
+int svr_macro_grid(int nx, int ny, int nz, int shift_min, int out[8]);
+/* test hook: the skipping tables of the scene set up as for render_pathtracer, copied to the host exactly as the kernels read them.
+ * info (always filled) = { shift, gx, gy, gz, hgx, hgy, hgz, fgx, fgy, fgz (0 without a fine level), mask_words, dist_words,
+ * bound8 (1 built | 2 in use for this scene), sub8 built, words of the accel buffer, bytes of the bound8 table }.
+ * table: 0 none (info only)  1 mm (gx gy gz x {min, max} u16)  2 mm_fine (fgx fgy fgz x 2 u16)  3 mm_wide (hgx hgy hgz x 2 u16)
+ * 4 the accel buffer (u32: dist | deep | empty | classes | thresholds | census)  5 fine `empty` bits (ceil(fgx fgy fgz / 32) u32)
+ * 6 sub8 (gx gy gz bytes)  7 bound8 (bytes).  out_bytes must be the table's size; -3 when the scene has no such table */
+int svr_selftest_accel(int table, void* out, size_t out_bytes, int32_t info[16]);
 /* ---- denoised preview (SVR_OPT_DENOISE_PREVIEW; csrc/svr_denoise.hip) ----
  * GUIDES: one deterministic ray per pixel (the pinhole centre ray, cuda_camera.h:85-95) is marched through the clipped box
  * (the path tracer's interval, tNear < 0 -> 1e-6) at a fixed step h with the path tracer's extinction sigma = TF alpha of

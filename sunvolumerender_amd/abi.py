@@ -359,6 +359,8 @@ PROTOTYPES = {
     "svr_selftest_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "svr_selftest_math": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "svr_selftest_bound8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "svr_macro_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int)]),
+    "svr_selftest_accel": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, _P(C.c_int32)]),
     "svr_denoise_params_default": (C.c_int, [_P(DenoiseParams)]),
     "svr_set_denoise_params": (C.c_int, [_P(DenoiseParams)]),
     "svr_get_denoise_params": (C.c_int, [_P(DenoiseParams)]),

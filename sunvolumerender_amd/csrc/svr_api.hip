@@ -601,6 +601,14 @@ int ensure_mask(svr::DevScene& s, const svr_volume& vol, const svr_transfer_func
     uint32_t words = (n_cells + 31u) / 32u;
     if (!(g.mask_valid && g.mask_vol == vol.tex && g.mask_tf == tf.tex && g.mask_tf_version == tt->version &&
           g.mask_ds_bits == ds_bits && g.mask_sigma_bits == sg_bits)) {
+        {
+            // the tables built here, their scratch (d_mask_tmp, d_sub8: one byte per cell) and the walks' LDS copies have these fixed capacities
+            // (svr_macro_grid keeps every grid within them, so no volume texture reaches this): never launch beyond
+            const size_t hn = (size_t)((tv->mc_gx + 1) / 2) * (size_t)((tv->mc_gy + 1) / 2) * (size_t)((tv->mc_gz + 1) / 2);
+            if ((size_t)tv->mc_gx * (size_t)tv->mc_gy * (size_t)tv->mc_gz > (size_t)svr::MASK_WORDS_MAX * 32 || (hn + 7) / 8 > svr::DIST_WORDS_MAX)
+                return fail(-6, "macro grid %d x %d x %d exceeds the acceleration tables (%u mask words of %u, %zu distance words of %u)", tv->mc_gx, tv->mc_gy,
+                            tv->mc_gz, words, svr::MASK_WORDS_MAX, (hn + 7) / 8, svr::DIST_WORDS_MAX);
+        }
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(svr::launch_empty_mask(tv->mm, tv->mc_gx, tv->mc_gy, tv->mc_gz, tt->zero_prefix, tt->nx,
                                        vol.densityScale, g.d_mask, words, g.d_mask_tmp, g.stream));
@@ -1445,6 +1453,24 @@ uint64_t svr_create_volume_texture(const uint16_t* voxels, int nx, int ny, int n
     return h;
 }
 
+// The macro-cell grid of a volume (plain host code): the smallest cells, of 2^shift >= 2^shift_min voxels per axis, whose tables fit the
+// fixed LDS arrays of the walks (svr_walk.hpp) -- one bit per cell in MASK_WORDS_MAX words (`empty`, deep-empty) AND one nibble per
+// HALF-resolution cell in DIST_WORDS_MAX words (distances, bound classes).  For a box-like volume the half-resolution grid has about an
+// eighth of the cells and the first limit decides; a flat volume (512 x 512 x 1: a quarter) or a line (a half) is limited by the second.
+int svr_macro_grid(int nx, int ny, int nz, int shift_min, int out[8])
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0 || shift_min < 0 || shift_min > 30 || !out) return -1;
+    for (int sh = shift_min;; ++sh) {
+        const size_t gx = (((size_t)nx - 1) >> sh) + 1, gy = (((size_t)ny - 1) >> sh) + 1, gz = (((size_t)nz - 1) >> sh) + 1;
+        const size_t hgx = (gx + 1) / 2, hgy = (gy + 1) / 2, hgz = (gz + 1) / 2;
+        if (gx * gy * gz <= (size_t)svr::MASK_WORDS_MAX * 32 && hgx * hgy * hgz <= (size_t)svr::DIST_WORDS_MAX * 8) {      // (sh = 31: one cell)
+            out[0] = sh; out[1] = (int)gx; out[2] = (int)gy; out[3] = (int)gz; out[4] = (int)hgx; out[5] = (int)hgy; out[6] = (int)hgz;
+            out[7] = (int)((hgx * hgy * hgz + 7) / 8);
+            return sh;
+        }
+    }
+}
+
 // oom != null: running out of device memory is reported through *oom instead of as an error (the caller retries with a smaller layout)
 // auto_rank: under AUTO, 0 = best layout that fits the addressing limits, 1 = skip CELL, 2 = skip CELL and PAIR
 static uint64_t create_volume_texture(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, int layout, int auto_rank, bool* oom)
@@ -1482,13 +1508,11 @@ static uint64_t create_volume_texture(const uint16_t* voxels, int nx, int ny, in
         elems = bx * by * bz * (size_t)(svr::BRICK_X * svr::BRICK_Y * svr::BRICK_Z);
     }
     if (elems >= ((size_t)1 << 32) || (layout != SVR_LAYOUT_CELL && elems >= ((size_t)1 << 31))) { delete t; fail(-6, "svr_create_volume_texture: %zu padded voxels exceed 32-bit byte offsets", elems); return 0; }
-    // macro-cell grid for empty-space skipping: smallest cell size whose bitmask fits MASK_WORDS_MAX words
+    // macro-cell grid for empty-space skipping (SVR_OPT_MACRO_SHIFT_MIN: coarser cells on request)
     {
-        int sh = g.opt_macro_shift_min;                       // (SVR_OPT_MACRO_SHIFT_MIN: coarser cells on request)
-        for (;; ++sh) {
-            size_t gx = (((size_t)nx - 1) >> sh) + 1, gy = (((size_t)ny - 1) >> sh) + 1, gz = (((size_t)nz - 1) >> sh) + 1;
-            if (gx * gy * gz <= (size_t)svr::MASK_WORDS_MAX * 32) { t->mc_shift = sh; t->mc_gx = (int)gx; t->mc_gy = (int)gy; t->mc_gz = (int)gz; break; }
-        }
+        int mg[8];
+        t->mc_shift = svr_macro_grid(nx, ny, nz, g.opt_macro_shift_min, mg);
+        t->mc_gx = mg[1]; t->mc_gy = mg[2]; t->mc_gz = mg[3];
     }
     t->bytes = elems * (layout == SVR_LAYOUT_CELL ? 16u : (layout == SVR_LAYOUT_PAIR ? sizeof(uint32_t) : sizeof(uint16_t)));
     size_t src_bytes = (size_t)nx * ny * nz * sizeof(uint16_t);
@@ -2714,6 +2738,43 @@ int svr_selftest_bound8(const float* rays, uint32_t n, uint32_t* out)
     hipFree(d_rays);
     if (d_out) hipFree(d_out);
     if (e != hipSuccess) return fail((int)e, "svr_selftest_bound8 failed: %s", hipGetErrorName(e));
+    return 0;
+}
+
+// test hook: the skipping tables of the CURRENT scene as the kernels will read them (tests/accel_ref.py restates them in numpy)
+int svr_selftest_accel(int table, void* out, size_t out_bytes, int32_t info[16])
+{
+    if (ensure_init()) return g.err_code;
+    if (!info || table < 0 || table > 7 || (table != 0 && !out)) return fail(-4, "svr_selftest_accel: bad arguments");
+    if (!g.have_vol || !g.have_tf || !g.have_cam) return fail(-4, "svr_selftest_accel before setup_volume/setup_transferfunction/setup_camera");
+    svr::DevScene s;
+    if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
+    if (ensure_mask(s, g.vol, g.tf)) return g.err_code;
+    const Texture* tv = find_tex(g.vol.tex, TEX_VOLUME);
+    if (s.empty_mask == nullptr || !tv) return fail(-3, "svr_selftest_accel: the scene has no acceleration data (SVR_OPT_EMPTY_SKIP off?)");
+    const int hgx = (tv->mc_gx + 1) / 2, hgy = (tv->mc_gy + 1) / 2, hgz = (tv->mc_gz + 1) / 2;
+    const size_t n = (size_t)tv->mc_gx * tv->mc_gy * tv->mc_gz, hn = (size_t)hgx * hgy * hgz;
+    const size_t fn = tv->mm_fine ? (size_t)tv->fg_x * tv->fg_y * tv->fg_z : 0;
+    const int32_t filled[16] = {tv->mc_shift, tv->mc_gx, tv->mc_gy, tv->mc_gz, hgx, hgy, hgz, tv->mm_fine ? tv->fg_x : 0, tv->mm_fine ? tv->fg_y : 0,
+                                tv->mm_fine ? tv->fg_z : 0, (int32_t)s.mask_words, (int32_t)s.dist_words, (g.bnd8_valid ? 1 : 0) | (s.bnd8 ? 2 : 0),
+                                g.sub8_valid ? 1 : 0, (int32_t)svr::ACCEL_WORDS, (int32_t)svr::BOUND8_BYTES};
+    memcpy(info, filled, sizeof filled);
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (table) {
+    case 0: return 0;
+    case 1: src = tv->mm; bytes = n * 2 * sizeof(uint16_t); break;
+    case 2: src = tv->mm_fine; bytes = fn * 2 * sizeof(uint16_t); break;
+    case 3: src = tv->mm_wide; bytes = hn * 2 * sizeof(uint16_t); break;
+    case 4: src = g.d_mask; bytes = (size_t)svr::ACCEL_WORDS * sizeof(uint32_t); break;
+    case 5: src = tv->mm_fine ? g.d_fine_mask : nullptr; bytes = (fn + 31) / 32 * sizeof(uint32_t); break;
+    case 6: src = g.sub8_valid ? g.d_sub8 : nullptr; bytes = n; break;
+    default: src = g.bnd8_valid ? g.d_bnd8 : nullptr; bytes = svr::BOUND8_BYTES; break;
+    }
+    if (!src) return fail(-3, "svr_selftest_accel: the scene has no table %d", table);
+    if (out_bytes != bytes) return fail(-4, "svr_selftest_accel: table %d has %zu bytes, not %zu", table, bytes, out_bytes);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
