@@ -10,8 +10,12 @@
 // -pick X Y (repeatable) renders no frame: it prints, one line per pick, where the ray of that pixel meets what the picture shows
 // (svr_pick) -- -hit opacity A: the ray caster's opacity exceeds A (default, 0.5); -hit iso L: the isosurface at L; -hit max: the sample
 // of the MIP value.
+// -grow X Y LO HI picks at pixel (X, Y) with the -hit mode in force, grows the connected region of the voxels with raw value LO .. HI
+// (0 .. 65535) around the picked voxel (svr_region_grow; -conn 6|18|26, default 6), prints its voxel count, volume, mean +- standard
+// deviation, bounding box and surface area, and renders the volume with everything else removed (-keep, the default) or with the
+// region removed (-remove) into the output image.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +28,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -36,6 +40,8 @@ int main(int argc, char** argv)
     float slicePos = 0.5f, slabThickness = 0.f;
     std::vector<uint32_t> picks;                                    // -pick: (x, y) pairs
     svr_hit_params hitParams = {SVR_HIT_OPACITY, 0.5f, 0.5f};
+    bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
+    int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
     for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
         else if (!strcmp(argv[i], "-env") && i + 1 < argc) envFile = argv[++i];
@@ -70,6 +76,18 @@ int main(int argc, char** argv)
             picks.push_back((uint32_t)px); picks.push_back((uint32_t)py);
             i += 2;
         }
+        else if (!strcmp(argv[i], "-grow") && i + 4 < argc) {
+            growX = atoi(argv[i + 1]); growY = atoi(argv[i + 2]); growLo = atoi(argv[i + 3]); growHi = atoi(argv[i + 4]);
+            if (growX < 0 || growY < 0 || growLo < 0 || growHi > 65535 || growLo > growHi) { fprintf(stderr, "-grow needs a pixel X Y >= 0 and a raw window 0 <= LO <= HI <= 65535 (got %s %s %s %s)\n", argv[i + 1], argv[i + 2], argv[i + 3], argv[i + 4]); return 2; }
+            grow = true;
+            i += 4;
+        }
+        else if (!strcmp(argv[i], "-conn") && i + 1 < argc) {
+            growConn = atoi(argv[++i]);
+            if (growConn != 6 && growConn != 18 && growConn != 26) { fprintf(stderr, "-conn needs 6, 18 or 26 (got %s)\n", argv[i]); return 2; }
+        }
+        else if (!strcmp(argv[i], "-keep")) growMode = SVR_REGION_KEEP;
+        else if (!strcmp(argv[i], "-remove")) growMode = SVR_REGION_REMOVE;
         else if (!strcmp(argv[i], "-hit") && i + 1 < argc) {
             const char* m = argv[++i];
             if (!strcmp(m, "max")) hitParams.mode = SVR_HIT_MAX;
@@ -115,6 +133,7 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
+        canvas.volumeReader->KeepVoxels(grow);                         // the region calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%s: %d x %d x %d, range %.0f..%.0f, max gradient magnitude %.0f, %zu histogram bins\n", volume.c_str(),
@@ -158,6 +177,25 @@ int main(int argc, char** argv)
             }
             svr_shutdown();
             return 0;
+        }
+
+        if (grow) {
+            // pick, segment, measure; what follows renders the kept (or the remaining) volume
+            svr_hit hit;
+            if (canvas.Pick((uint32_t)growX, (uint32_t)growY, &hit, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            if (hit.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-grow: %s at pixel %d %d\n", hit.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", growX, growY); return 1; }
+            svr_region_stats st;
+            if (canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            const double sp[3] = {canvas.Volume().spacing.x, canvas.Volume().spacing.y, canvas.Volume().spacing.z};
+            svr_region_measurement m;
+            if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            if (st.status == SVR_REGION_STATUS_EMPTY)
+                printf("grow %d %d window %d..%d: the picked voxel (value %g) is outside the window; the region is empty\n", growX, growY, growLo, growHi, hit.value);
+            else
+                printf("grow %d %d window %d..%d conn %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %u sweeps\n",
+                       growX, growY, growLo, growHi, growConn, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                       st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
+            if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         }
 
         if (sliceAxis >= 0) {

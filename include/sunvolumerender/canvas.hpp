@@ -38,7 +38,8 @@ public:
         ClearDevice();
         histogram.assign(65536, 0u);
         svr_volume_info info;
-        if (svr_load_mhd(filename.c_str(), layout, &loaded, &info, histogram.data(), (uint32_t)histogram.size()) != 0) {
+        if ((keepVoxels ? ReadKeeping(filename, layout, &info) : svr_load_mhd(filename.c_str(), layout, &loaded, &info, histogram.data(), (uint32_t)histogram.size())) != 0) {
+            ClearDevice();
             histogram.clear();
             return;                                   // svr_last_error() tells why (fatal mode has already exited)
         }
@@ -66,6 +67,11 @@ public:
     float GetElementBoundingSphereRadius() const { return glm::length(spacing) * 0.5f; }
     bool IsLoaded() const { return have; }
 
+    // extension: keep the plain [z][y][x] u16 volume on the device after Read (set before Read; off by default, and then nothing
+    // changes): what the region calls of Canvas segment and mask (svr_region_*)
+    void KeepVoxels(bool keep) { keepVoxels = keep; }
+    const uint16_t* DeviceVoxels() const { return voxels; }     // null unless KeepVoxels(true) was set before Read
+
     std::vector<uint32_t> histogram;
     int dim[3] = {0, 0, 0};
     double range[2] = {0, 0};
@@ -74,13 +80,46 @@ public:
 private:
     void ClearDevice()
     {
-        if (have && loaded.tex) svr_destroy_texture(loaded.tex);
+        if (loaded.tex) svr_destroy_texture(loaded.tex);
+        if (voxels) svr_device_free(voxels);
+        voxels = nullptr;
         loaded = svr_volume();
         have = false;
+    }
+    // svr_load_mhd in its parts, so that the preprocessed u16 volume stays: header, elements, GPU preprocessing, texture from the device
+    // buffer; the svr_volume fields as svr_load_mhd fills them (VolumeReader.cpp:174-185, cuda_bbox.h)
+    int ReadKeeping(const std::string& filename, int layout, svr_volume_info* info)
+    {
+        svr_mhd_header h;
+        int rc = svr_mhd_read_header(filename.c_str(), &h);
+        if (rc != 0) return rc;
+        const size_t n = (size_t)h.dim[0] * h.dim[1] * h.dim[2];
+        std::vector<uint8_t> elems(n * (size_t)h.elem_size);
+        rc = svr_mhd_read_elements(&h, elems.data(), elems.size());
+        if (rc != 0) return rc;
+        voxels = (uint16_t*)svr_device_malloc(n * sizeof(uint16_t));
+        if (!voxels) return -4;
+        rc = svr_volume_preprocess(elems.data(), h.elem_type, h.dim[0], h.dim[1], h.dim[2], h.spacing, 0, voxels, histogram.data(),
+                                   (uint32_t)histogram.size(), info);
+        if (rc != 0) return rc;
+        loaded.tex = svr_create_volume_texture(voxels, h.dim[0], h.dim[1], h.dim[2], 1, layout);
+        if (!loaded.tex) return svr_last_error_code() ? svr_last_error_code() : -4;
+        const float sx = info->spacing[0], sy = info->spacing[1], sz = info->spacing[2];
+        const float ex = (float)h.dim[0] * sx, ey = (float)h.dim[1] * sy, ez = (float)h.dim[2] * sz;
+        const float mx = ex - ex * 0.5f, my = ey - ey * 0.5f, mz = ez - ez * 0.5f;
+        loaded.bbox.vmin = svr_vec3{-mx, -my, -mz};
+        loaded.bbox.vmax = svr_vec3{mx, my, mz};
+        loaded.bbox.invSize = svr_vec3{1.f / (mx - -mx), 1.f / (my - -my), 1.f / (mz - -mz)};
+        loaded.spacing = svr_vec3{sx, sy, sz};
+        loaded.invSpacing = svr_vec3{1.f / sx, 1.f / sy, 1.f / sz};
+        loaded.invMaxMagnitude = 1.f / info->maxMagnitude;
+        return 0;
     }
     glm::vec3 spacing;
     svr_volume loaded = svr_volume();
     bool have = false;
+    bool keepVoxels = false;
+    uint16_t* voxels = nullptr;                                // the preprocessed volume (device), with KeepVoxels
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -217,6 +256,7 @@ public:
     ~Canvas()
     {
         svr_device_synchronize();
+        ClearRegion();
         renderParams.Clear();
         if (img) svr_device_free(img);
         delete volumeReader;
@@ -226,6 +266,7 @@ public:
 
     void LoadVolume(std::string filename)                                       // canvas.cpp:27-41
     {
+        ClearRegion();
         volumeReader->Read(filename);
         if (!volumeReader->IsLoaded()) return;
         volumeReader->CreateDeviceVolume(&deviceVolume);
@@ -392,6 +433,68 @@ public:
         return rc;
     }
 
+    // extension: pick -> segment -> measure -> show (svr_region_*; include/svr_abi.h, "seeded region growing").  Needs the plain voxels:
+    // volumeReader->KeepVoxels(true) before LoadVolume.
+    // GrowRegion: the connected component (connectivity 6, 18 or 26) of the voxels with lo <= raw value <= hi around the voxel whose cell
+    // holds hit.position (a FOUND record of Pick / HitMap); the Canvas keeps the mask, *stats (may be null) gets the statistics
+    // (svr_region_measure turns them into volume, mean, deviation, centroid, surface area).  Returns the call's status (0 = ok)
+    int GrowRegion(const svr_hit& hit, uint32_t lo, uint32_t hi, int connectivity, svr_region_stats* stats = nullptr)
+    {
+        const uint16_t* vox = volumeReader->DeviceVoxels();
+        if (!ready || !vox || hit.status != SVR_HIT_STATUS_FOUND) return -4;
+        const int* dim = volumeReader->dim;
+        int32_t seed[3];
+        int rc = svr_region_seed_from_world(&deviceVolume, dim[0], dim[1], dim[2], &hit.position, seed);
+        if (rc != 0) return rc;
+        if (!regionMask) regionMask = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
+        if (!regionMask) return -4;
+        svr_region_params p;
+        svr_region_params_default(&p);
+        p.lo = lo; p.hi = hi; p.connectivity = connectivity;
+        svr_region_stats st = {};
+        rc = svr_region_grow(vox, dim[0], dim[1], dim[2], 1, seed, 1u, &p, regionMask, &st);
+        haveRegion = rc == 0;
+        if (stats) *stats = st;
+        return rc;
+    }
+    // ShowRegion: every renderer now draws the volume with the voxels outside (SVR_REGION_KEEP) or inside (SVR_REGION_REMOVE) the grown
+    // region set to `fill`; ShowAll goes back to the loaded volume.  The Canvas owns the extra texture
+    int ShowRegion(int mode, uint32_t fill)
+    {
+        const uint16_t* vox = volumeReader->DeviceVoxels();
+        if (!ready || !vox || !haveRegion) return -4;
+        const int* dim = volumeReader->dim;
+        uint16_t* shown = (uint16_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint16_t));
+        if (!shown) return -4;
+        int rc = svr_region_apply(vox, dim[0], dim[1], dim[2], 1, regionMask, mode, fill, shown);
+        cudaTextureObject_t tex = 0;
+        if (rc == 0) {
+            tex = svr_create_volume_texture(shown, dim[0], dim[1], dim[2], 1, SVR_LAYOUT_AUTO);    // (copies: `shown` is free afterwards)
+            if (!tex) rc = svr_last_error_code() ? svr_last_error_code() : -4;
+        }
+        svr_device_free(shown);
+        if (rc != 0) return rc;
+        svr_device_synchronize();                      // no frame in flight still reads the texture that goes
+        if (regionTex) svr_destroy_texture(regionTex);
+        regionTex = tex;
+        deviceVolume.tex = tex;
+        setup_volume(deviceVolume);
+        ReStartRender();
+        return 0;
+    }
+    void ShowAll()
+    {
+        if (!regionTex) return;
+        volumeReader->CreateDeviceVolume(&deviceVolume);           // the loaded texture again (the other fields are the same)
+        setup_volume(deviceVolume);
+        svr_device_synchronize();
+        svr_destroy_texture(regionTex);
+        regionTex = 0;
+        ReStartRender();
+    }
+    bool HasRegion() const { return haveRegion; }
+    const uint32_t* RegionMask() const { return haveRegion ? regionMask : nullptr; }   // device; svr_region_mask_words words
+
     bool SaveImage(const std::string& filename)
     {
         std::vector<uint8_t> host((size_t)WIDTH * HEIGHT * 4);
@@ -424,6 +527,12 @@ private:
         maxSpan *= 1.5f;
         eyeDist = maxSpan / (2 * tan((fov * 0.5f) * 0.01745329251994329576923690768489f));
     }
+    void ClearRegion()
+    {
+        if (regionTex) svr_destroy_texture(regionTex);
+        if (regionMask) svr_device_free(regionMask);
+        regionTex = 0; regionMask = nullptr; haveRegion = false;
+    }
     void UpdateCamera()                                                         // canvas.cpp:178-188
     {
         const glm::vec3 u = view[0], v = view[1], w = view[2];
@@ -442,6 +551,9 @@ private:
     cudaVolume deviceVolume;
     cudaTransferFunction transferFunction;
     RenderMode renderMode = RENDER_MODE_RAYCASTING;
+    uint32_t* regionMask = nullptr;                // GrowRegion's bit mask (device)
+    cudaTextureObject_t regionTex = 0;             // ShowRegion's masked volume
+    bool haveRegion = false;
     svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
     svr_slice_params slice = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, 0.f, 1.f, SVR_SLAB_MIP, 0u, 0.f, 1.f};
 };

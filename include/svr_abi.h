@@ -646,6 +646,87 @@ int svr_render_hits(void* hits, const svr_volume* volume, const svr_transfer_fun
 int svr_pick(void* hits, const uint32_t* pixels_xy, uint32_t n, const svr_volume* volume, const svr_transfer_function* tf,
              const svr_camera* camera, float stepSize, const svr_hit_params* p);
 
+/* ---- seeded region growing: pick a point, segment, measure, show (csrc/svr_region.hip) ----
+ * Integers only; every result is exact.
+ * INPUT: a plain u16 volume [nz][ny][nx] (host, or device with src_is_device = 1, as svr_create_volume_texture takes it; at most 2^31
+ *   voxels, which keeps sum_sq inside 64 bits), 1 .. SVR_REGION_MAX_SEEDS seed voxels (x, y, z), an inclusive raw-value window
+ *   lo <= v <= hi, a connectivity 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners), and an inclusive voxel box
+ *   box_min .. box_max that growth may not leave (it is intersected with the volume; the default 0 .. INT32_MAX is the whole volume).
+ * REGION: candidates = {voxel in the box : lo <= v <= hi}.  The region is the union, over the seeds, of the connected component
+ *   (chosen connectivity) of the candidates that contains the seed; a seed that is not a candidate contributes nothing, and if none is
+ *   the region is empty: status SVR_REGION_STATUS_EMPTY, return 0 -- not an error.  The region is the least fixpoint of a monotone rule
+ *   and therefore unique: the mask is defined bit for bit, whatever order the GPU grows in.
+ * MASK: uint32 words on the device; voxel (x, y, z) is bit x & 31 of word (z * ny + y) * wx + (x >> 5), wx = (nx + 31) / 32; padding bits
+ *   are 0.  svr_region_mask_words(nx, ny, nz) = wx * ny * nz is the word count (0 for a dimension <= 0).
+ * STATS (svr_region_stats): voxels = the region's size; sum, sum_sq = the sums of v and v^2 over it; sum_x, sum_y, sum_z = the sums of
+ *   the voxel indices; faces_x / _y / _z = the number of pairs (region voxel, neighbour at +-1 on that axis) whose neighbour is outside
+ *   the region or outside the volume; vmin, vmax = the extreme values (65535 and 0 for an empty region); bbox_min, bbox_max = the
+ *   inclusive index bounds (the dimensions and -1 for an empty region); sweeps = the grow passes launched (0 from svr_region_stats_of).
+ * MEASURE (svr_region_measure; plain host code, double): volume = voxels sx sy sz; mean = sum / voxels; stddev = the population
+ *   standard deviation sqrt(voxels sum_sq - sum^2) / voxels (the radicand in exact integers); centroid = (sum_x, sum_y, sum_z) / voxels,
+ *   in voxel index space; surface_area = faces_x sy sz + faces_y sx sz + faces_z sx sy.  An empty region gives zeros.
+ * SWEEPS: growth runs in passes over tiles of 128 x 8 x 8 voxels; a pass that adds a voxel moves the front of the region across at least
+ *   one tile boundary, so a region whose way out from its seeds enters every tile at most twice is complete after 2 T passes (T = the
+ *   number of tiles) and one more that confirms it.  The default cap (max_sweeps = 0) is svr_region_default_max_sweeps = min(64 + 2 T,
+ *   65536) launches; a region that winds through its tiles more often needs max_sweeps set by the caller.  At the cap the call returns
+ *   SVR_REGION_ERR_SWEEPS, the mask holds the part grown so far and stats->sweeps the launches; it does not go on.
+ * All calls run on the library's stream (svr_set_stream); svr_region_grow and svr_region_stats_of synchronise it, since they return
+ * host statistics.  None touches the scene, the options or the render accumulators.  Arguments are checked before the device is
+ * touched.  A negative code is returned, with svr_last_error() set and nothing written, for: a null pointer (-4); a dimension <= 0 or
+ * more than 2^31 voxels (-6); lo > hi or hi > 65535, a connectivity other than 6 / 18 / 26, nseeds == 0 or > SVR_REGION_MAX_SEEDS, a seed
+ * outside the volume, a box with box_min > box_max on an axis or with no voxel of the volume in it, an unknown mode, a fill > 65535, a
+ * point outside the volume's box, a spacing that is not positive and finite (-3). */
+#define SVR_REGION_MAX_SEEDS 64
+#define SVR_REGION_KEEP   1     /* svr_region_apply: voxels outside the region become `fill` */
+#define SVR_REGION_REMOVE 2     /* svr_region_apply: voxels inside the region become `fill` */
+#define SVR_REGION_STATUS_OK    0
+#define SVR_REGION_STATUS_EMPTY 1
+#define SVR_REGION_ERR_SWEEPS (-9)   /* the region was still growing after max_sweeps passes */
+
+typedef struct svr_region_params {   /* 4-byte members only, 40 bytes */
+    uint32_t lo, hi;                 /* inclusive raw-value window */
+    int32_t  connectivity;           /* 6, 18 or 26 */
+    int32_t  box_min[3], box_max[3]; /* inclusive voxel box (x, y, z) */
+    uint32_t max_sweeps;             /* 0 = svr_region_default_max_sweeps(nx, ny, nz) */
+} svr_region_params;
+
+typedef struct svr_region_stats {    /* 112 bytes */
+    uint64_t voxels, sum, sum_sq, sum_x, sum_y, sum_z;
+    uint64_t faces_x, faces_y, faces_z;
+    uint32_t vmin, vmax;
+    int32_t  bbox_min[3], bbox_max[3];
+    uint32_t sweeps;
+    int32_t  status;                 /* SVR_REGION_STATUS_* */
+} svr_region_stats;
+
+typedef struct svr_region_measurement {   /* 56 bytes */
+    double volume, mean, stddev;
+    double centroid[3];
+    double surface_area;
+} svr_region_measurement;
+
+/* window 0..65535, connectivity 6, the whole volume, max_sweeps 0.  Plain host code */
+int svr_region_params_default(svr_region_params* p);
+uint64_t svr_region_mask_words(int nx, int ny, int nz);
+uint32_t svr_region_default_max_sweeps(int nx, int ny, int nz);
+/* seeds_xyz: a HOST array of 3 * nseeds int32 (x, y, z).  mask_device (svr_region_mask_words words) is overwritten */
+int svr_region_grow(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, const int32_t* seeds_xyz, uint32_t nseeds,
+                    const svr_region_params* params, uint32_t* mask_device, svr_region_stats* stats_host);
+/* the same statistics for any mask in this format (padding bits 0), e.g. one the caller edited */
+int svr_region_stats_of(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, const uint32_t* mask_device,
+                        svr_region_stats* stats_host);
+/* out (device, nx * ny * nz u16) = the volume with the voxels outside (SVR_REGION_KEEP) or inside (SVR_REGION_REMOVE) the region set to
+ * `fill`.  out may be the device `voxels` itself.  Asynchronous on the library's stream for a device source */
+int svr_region_apply(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, const uint32_t* mask_device, int mode, uint32_t fill,
+                     uint16_t* out_u16_device);
+/* the voxel whose cell contains a world point (e.g. svr_hit.position), by the mapping with which the sampler addresses the texture: the
+ * float32 texture coordinate c = (point - bbox.vmin) * bbox.invSize per axis (the unclipped box); voxel i covers [i / n, (i + 1) / n),
+ * i = floor(c n), and c = 1 (the far face) belongs to voxel n - 1.  A point with a c outside [0, 1] is refused.  Plain host code */
+int svr_region_seed_from_world(const svr_volume* volume, int nx, int ny, int nz, const svr_vec3* point, int32_t ijk[3]);
+int svr_region_measure(const svr_region_stats* stats, const double spacing[3], svr_region_measurement* out);
+/* HIP-event times of the phases of the last svr_region_grow: classify (with the seeds), grow (all sweeps), stats.  Pointers may be NULL */
+int svr_region_last_ms(float* classify_ms, float* grow_ms, float* stats_ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

@@ -238,6 +238,49 @@ HIT_STATUS_MISS, HIT_STATUS_NONE, HIT_STATUS_FOUND = 0, 1, 2
 PICK_MAX = 4096
 
 
+class RegionParams(C.Structure):  # svr_region_params
+    _fields_ = [
+        ("lo", C.c_uint32),
+        ("hi", C.c_uint32),
+        ("connectivity", C.c_int32),
+        ("box_min", C.c_int32 * 3),
+        ("box_max", C.c_int32 * 3),
+        ("max_sweeps", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n.startswith("box") else getattr(self, n)) for n, _ in self._fields_}
+
+
+class RegionStats(C.Structure):  # svr_region_stats
+    _fields_ = [(n, C.c_uint64) for n in ("voxels", "sum", "sum_sq", "sum_x", "sum_y", "sum_z", "faces_x", "faces_y", "faces_z")] + [
+        ("vmin", C.c_uint32),
+        ("vmax", C.c_uint32),
+        ("bbox_min", C.c_int32 * 3),
+        ("bbox_max", C.c_int32 * 3),
+        ("sweeps", C.c_uint32),
+        ("status", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n.startswith("bbox") else int(getattr(self, n))) for n, _ in self._fields_}
+
+
+class RegionMeasurement(C.Structure):  # svr_region_measurement
+    _fields_ = [("volume", C.c_double), ("mean", C.c_double), ("stddev", C.c_double), ("centroid", C.c_double * 3),
+                ("surface_area", C.c_double)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n == "centroid" else getattr(self, n)) for n, _ in self._fields_}
+
+
+svr_region_params, svr_region_stats, svr_region_measurement = RegionParams, RegionStats, RegionMeasurement
+REGION_MAX_SEEDS = 64
+REGION_KEEP, REGION_REMOVE = 1, 2
+REGION_STATUS_OK, REGION_STATUS_EMPTY = 0, 1
+REGION_ERR_SWEEPS = -9
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -256,6 +299,9 @@ EXPECTED_SIZES = {
     SliceParams: 60,
     Hit: 40,
     HitParams: 12,
+    RegionParams: 40,
+    RegionStats: 112,
+    RegionMeasurement: 56,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -385,6 +431,16 @@ PROTOTYPES = {
     "svr_render_hits": (C.c_int, [C.c_void_p, _P(cudaVolume), _P(cudaTransferFunction), _P(cudaCamera), C.c_float, _P(HitParams)]),
     "svr_pick": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint32, _P(cudaVolume), _P(cudaTransferFunction), _P(cudaCamera), C.c_float,
                            _P(HitParams)]),
+    "svr_region_params_default": (C.c_int, [_P(RegionParams)]),
+    "svr_region_mask_words": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
+    "svr_region_default_max_sweeps": (C.c_uint32, [C.c_int, C.c_int, C.c_int]),
+    "svr_region_grow": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int32), C.c_uint32, _P(RegionParams), C.c_void_p,
+                                  _P(RegionStats)]),
+    "svr_region_stats_of": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _P(RegionStats)]),
+    "svr_region_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
+    "svr_region_seed_from_world": (C.c_int, [_P(cudaVolume), C.c_int, C.c_int, C.c_int, _P(vec3), _P(C.c_int32)]),
+    "svr_region_measure": (C.c_int, [_P(RegionStats), _P(C.c_double), _P(RegionMeasurement)]),
+    "svr_region_last_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

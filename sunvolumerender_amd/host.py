@@ -280,6 +280,131 @@ class Device:
         self.check(self.lib.svr_get_noise_estimate(C.byref(est), C.c_void_p(tile_ptr) if tile_ptr else None))
         return est
 
+    # ---- seeded region growing (svr_region_*): pick, segment, measure, show ----
+    def _region_source(self, vox, shape):
+        """(pointer argument, (nz, ny, nx), src_is_device, keep-alive) of a host u16 array or a device pointer with `shape`."""
+        if isinstance(vox, np.ndarray):
+            a = np.ascontiguousarray(vox, dtype=np.uint16)
+            if a.ndim != 3:
+                raise ValueError("the volume must be [nz][ny][nx]")
+            return a.ctypes.data_as(C.c_void_p), a.shape, 0, a
+        if shape is None:
+            raise ValueError("a device volume needs shape=(nz, ny, nx)")
+        return C.c_void_p(int(vox)), tuple(int(n) for n in shape), 1, None
+
+    def region_params(self, lo: int = 0, hi: int = 65535, connectivity: int = 6, box=None, max_sweeps: int = 0) -> abi.RegionParams:
+        """svr_region_params_default with the window, connectivity, box ((x0, y0, z0), (x1, y1, z1), inclusive) and cap replaced."""
+        p = abi.RegionParams()
+        self.check(self.lib.svr_region_params_default(C.byref(p)))
+        p.lo, p.hi, p.connectivity, p.max_sweeps = int(lo), int(hi), int(connectivity), int(max_sweeps)
+        if box is not None:
+            for a in range(3):
+                p.box_min[a], p.box_max[a] = int(box[0][a]), int(box[1][a])
+        return p
+
+    def region_grow(self, vox, seeds, lo: int, hi: int, connectivity: int = 6, box=None, max_sweeps: int = 0, shape=None,
+                    mask_ptr: Optional[int] = None):
+        """svr_region_grow: the connected component(s) of {lo <= v <= hi} (inside `box`) around the seed voxels (x, y, z).  vox is a
+        host [nz][ny][nx] u16 array, or a device pointer with shape=(nz, ny, nx).  Returns (mask, stats): the region as a bool array
+        [nz][ny][nx] and the svr_region_stats.  mask_ptr: a device buffer of region_mask_words(shape) uint32 that receives the bit mask
+        (else a temporary one is used)."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        p = self.region_params(lo, hi, connectivity, box, max_sweeps)
+        words = region_mask_words((nz, ny, nx))
+        buf = mask_ptr if mask_ptr is not None else self.malloc(4 * max(words, 1))
+        st = abi.RegionStats()
+        try:
+            self.check(self.lib.svr_region_grow(src, nx, ny, nz, on_dev, xyz.ctypes.data_as(C.POINTER(C.c_int32)), len(xyz), C.byref(p),
+                                                C.c_void_p(buf), C.byref(st)))
+            mask = region_mask_unpack(self.to_host(buf, (words,), np.uint32), (nz, ny, nx))
+        finally:
+            if mask_ptr is None:
+                self.free(buf)
+        return mask, st
+
+    def region_stats_of(self, vox, mask, shape=None) -> abi.RegionStats:
+        """svr_region_stats_of: the statistics of any mask (a bool array [nz][ny][nx], or a device pointer to the bit mask)."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        st = abi.RegionStats()
+        try:
+            self.check(self.lib.svr_region_stats_of(src, nx, ny, nz, on_dev, C.c_void_p(buf), C.byref(st)))
+        finally:
+            if owned:
+                self.free(buf)
+        return st
+
+    def region_apply(self, vox, mask, mode: int = abi.REGION_KEEP, fill: int = 0, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_apply: the volume with the voxels outside (REGION_KEEP) or inside (REGION_REMOVE) the region set to `fill`.
+        Returns a u16 array [nz][ny][nx]; with out_ptr (a device buffer of nx * ny * nz u16, which may be a device `vox` itself) the
+        result stays on the device and out_ptr is returned."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        out = out_ptr if out_ptr is not None else self.malloc(2 * nx * ny * nz)
+        try:
+            self.check(self.lib.svr_region_apply(src, nx, ny, nz, on_dev, C.c_void_p(buf), int(mode), int(fill), C.c_void_p(out)))
+            if out_ptr is not None:
+                self.synchronize()
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint16)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def _region_mask(self, mask, shape):
+        """(device pointer, owned) of a bool array (uploaded as the bit mask) or of a device pointer."""
+        if isinstance(mask, np.ndarray):
+            words = region_mask_pack(mask.reshape(shape))
+            buf = self.malloc(4 * max(len(words), 1))
+            self.to_device(buf, words)
+            return buf, True
+        return int(mask), False
+
+    def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
+        """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
+        m = abi.RegionMeasurement()
+        sp = (C.c_double * 3)(*[float(t) for t in spacing])
+        self.check(self.lib.svr_region_measure(C.byref(stats), sp, C.byref(m)))
+        return m
+
+
+def region_mask_words(shape) -> int:
+    """svr_region_mask_words of a [nz][ny][nx] volume."""
+    nz, ny, nx = shape
+    return ((nx + 31) // 32) * ny * nz
+
+
+def region_mask_unpack(words: np.ndarray, shape) -> np.ndarray:
+    """The bit mask of svr_region_grow (uint32 words) as a bool array [nz][ny][nx]."""
+    nz, ny, nx = shape
+    wx = (nx + 31) // 32
+    b = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8).reshape(nz, ny, wx * 4), axis=-1, bitorder="little")
+    return b[:, :, :nx].astype(bool)
+
+
+def region_mask_pack(mask: np.ndarray) -> np.ndarray:
+    """A bool array [nz][ny][nx] as the bit mask of the region calls: uint32 words, padding bits 0."""
+    nz, ny, nx = mask.shape
+    wx = (nx + 31) // 32
+    padded = np.zeros((nz, ny, wx * 32), dtype=np.uint8)
+    padded[:, :, :nx] = mask
+    return np.ascontiguousarray(np.packbits(padded, axis=-1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32))
+
+
+def region_seed_from_world(lib, volume: cudaVolume, dim, point):
+    """svr_region_seed_from_world: the voxel (x, y, z) whose cell contains a world point (e.g. a svr_hit position); dim = (nx, ny, nz).
+    Host code of the library: no device is needed."""
+    ijk = (C.c_int32 * 3)()
+    pt = _to_vec3(point)
+    if lib.svr_region_seed_from_world(C.byref(volume), int(dim[0]), int(dim[1]), int(dim[2]), C.byref(pt), ijk) != 0:
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise SvrError(msg)
+    return (int(ijk[0]), int(ijk[1]), int(ijk[2]))
+
 
 def slice_params_axis(lib, volume: cudaVolume, axis: int, position: float, w: int, h: int) -> abi.SliceParams:
     """svr_slice_params_axis: the plane perpendicular to world axis 0 / 1 / 2 at `position` in [0, 1] across the clipped box of

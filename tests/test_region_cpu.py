@@ -1,0 +1,380 @@
+"""The region calls without a GPU: the ABI of the new structs and symbols, the defaults, every refusal (arguments are checked before the
+device is touched), the host helpers svr_region_seed_from_world and svr_region_measure, the test-side reference (tests/region_ref.py)
+against scipy.ndimage.label, and the conditions the fixtures of tests/test_region_gpu.py have to meet, asserted on the reference."""
+import ctypes as C
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from sunvolumerender_amd import abi, host, scenes
+from tests import region_ref as rr
+
+ROOT = Path(__file__).resolve().parents[1]
+HEADER = (ROOT / "include" / "svr_abi.h").read_text()
+
+# the named cases on tiny_head (48^3): (window lo, hi, seed, {connectivity: voxels}, candidates)
+BRAIN = (23593, 28835, (24, 24, 24), {6: 13709, 18: 13709, 26: 13709}, 14709)
+BONE = (39321, 65535, None, {6: 5410, 18: 5410, 26: 5410}, 5410)
+THIN = (13107, 24903, (26, 44, 23), {6: 54, 18: 54, 26: 2382}, None)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    lib = abi.load()
+    lib.svr_set_error_mode(0)
+    lib.svr_clear_error()
+    return lib
+
+
+def head():
+    return scenes.make_scene("tiny_head").vox
+
+
+def bone_seed(vox):
+    z, y, x = np.argwhere(vox >= BONE[0])[0]
+    return (int(x), int(y), int(z))
+
+
+# ---------------------------------------------------------------- ABI
+def test_symbols_structs_and_constants(lib):
+    names = ["svr_region_params_default", "svr_region_mask_words", "svr_region_default_max_sweeps", "svr_region_grow", "svr_region_stats_of",
+             "svr_region_apply", "svr_region_seed_from_world", "svr_region_measure", "svr_region_last_ms"]
+    raw = C.CDLL(str(abi.library_path()))
+    for n in names:
+        assert n in abi.PROTOTYPES and hasattr(raw, n), n
+        assert re.search(rf"\b{n}\s*\(", HEADER), n
+
+    def define(name):
+        m = re.search(rf"#define\s+{name}\s+\(?(-?\d+)\)?", HEADER)
+        assert m, name
+        return int(m.group(1))
+
+    assert abi.REGION_MAX_SEEDS == define("SVR_REGION_MAX_SEEDS") == 64
+    assert (abi.REGION_KEEP, abi.REGION_REMOVE) == (define("SVR_REGION_KEEP"), define("SVR_REGION_REMOVE")) == (rr.KEEP, rr.REMOVE)
+    assert (abi.REGION_STATUS_OK, abi.REGION_STATUS_EMPTY) == (define("SVR_REGION_STATUS_OK"), define("SVR_REGION_STATUS_EMPTY")) == (rr.OK, rr.EMPTY)
+    assert abi.REGION_ERR_SWEEPS == define("SVR_REGION_ERR_SWEEPS") < 0
+    S = abi.RegionStats
+    assert C.sizeof(S) == 112 and S.voxels.offset == 0 and S.faces_z.offset == 64 and S.vmin.offset == 72 and S.bbox_min.offset == 80
+    assert S.bbox_max.offset == 92 and S.sweeps.offset == 104 and S.status.offset == 108
+    P = abi.RegionParams
+    assert C.sizeof(P) == 40 and P.connectivity.offset == 8 and P.box_min.offset == 12 and P.box_max.offset == 24 and P.max_sweeps.offset == 36
+    assert C.sizeof(abi.RegionMeasurement) == 56 and abi.RegionMeasurement.surface_area.offset == 48
+
+
+def test_defaults_and_mask_words(lib):
+    p = abi.RegionParams(5, 4, 7, (1, 1, 1), (0, 0, 0), 9)
+    assert lib.svr_region_params_default(C.byref(p)) == 0                      # plain host code: no GPU needed
+    assert p.as_dict() == {"lo": 0, "hi": 65535, "connectivity": 6, "box_min": [0, 0, 0], "box_max": [2**31 - 1] * 3, "max_sweeps": 0}
+    assert lib.svr_region_params_default(None) == -4
+    lib.svr_clear_error()
+    for nx, ny, nz in ((1, 1, 1), (31, 2, 3), (32, 2, 3), (33, 7, 5), (64, 1, 1), (65, 9, 3), (512, 512, 512), (2048, 1024, 1024)):
+        want = ((nx + 31) // 32) * ny * nz
+        assert lib.svr_region_mask_words(nx, ny, nz) == want == host.region_mask_words((nz, ny, nx))
+    assert lib.svr_region_mask_words(0, 4, 4) == 0 and lib.svr_region_mask_words(4, -1, 4) == 0
+    # the default cap: min(64 + 2 T, 65536) with T tiles of 128 x 8 x 8
+    assert rr.TILE == (128, 8, 8)
+    assert lib.svr_region_default_max_sweeps(40, 24, 17) == 64 + 2 * (1 * 3 * 3)
+    assert lib.svr_region_default_max_sweeps(129, 9, 8) == 64 + 2 * (2 * 2 * 1)
+    assert lib.svr_region_default_max_sweeps(1024, 1024, 1024) == 65536
+    m = np.zeros((3, 5, 70), dtype=bool)
+    m[2, 4, 69] = m[0, 0, 0] = m[1, 2, 32] = True
+    w = host.region_mask_pack(m)
+    assert w.dtype == np.uint32 and len(w) == 3 * 5 * 3 and w[0] == 1 and w[(1 * 5 + 2) * 3 + 1] == 1 and w[-1] == 1 << 5
+    assert np.array_equal(w, rr.pack(m)) and np.array_equal(host.region_mask_unpack(w, m.shape), m) and np.array_equal(rr.unpack(w, m.shape), m)
+
+
+# ---------------------------------------------------------------- refusals: all are decided before the device is touched
+def _grow(lib, vox=1, dims=(4, 4, 4), seeds=((0, 0, 0),), nseeds=None, mask=1, stats=True, params=True, **kw):
+    p = abi.RegionParams()
+    lib.svr_region_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k in ("box_min", "box_max"):
+            for a in range(3):
+                getattr(p, k)[a] = v[a]
+        else:
+            setattr(p, k, v)
+    xyz = (C.c_int32 * (3 * max(len(seeds or ()), 1)))(*[c for s in seeds or () for c in s])
+    st = abi.RegionStats()
+    st.voxels = 12345
+    lib.svr_clear_error()
+    rc = lib.svr_region_grow(C.c_void_p(vox), dims[0], dims[1], dims[2], 1, xyz if seeds is not None else None,
+                             len(seeds or ()) if nseeds is None else nseeds, C.byref(p) if params else None, C.c_void_p(mask),
+                             C.byref(st) if stats else None)
+    msg = lib.svr_last_error().decode()
+    code = lib.svr_last_error_code()
+    lib.svr_clear_error()
+    assert st.voxels == 12345                                                  # nothing is written on a refusal
+    return rc, code, msg
+
+
+@pytest.mark.parametrize("kw, code, word", [
+    (dict(vox=None), -4, "null"), (dict(mask=None), -4, "null"), (dict(stats=False), -4, "null"), (dict(params=False), -4, "null"),
+    (dict(dims=(0, 4, 4)), -6, "dimensions"), (dict(dims=(4, -1, 4)), -6, "dimensions"), (dict(dims=(4, 4, 0)), -6, "dimensions"),
+    (dict(dims=(2048, 1024, 1025)), -6, "2^31"), (dict(dims=(2**31 - 1, 2, 1)), -6, "2^31"),
+    (dict(lo=10, hi=9), -3, "window"), (dict(hi=65536), -3, "window"),
+    (dict(connectivity=4), -3, "connectivity"), (dict(connectivity=0), -3, "connectivity"), (dict(connectivity=27), -3, "connectivity"),
+    (dict(nseeds=0), -3, "nseeds"), (dict(seeds=((0, 0, 0),) * 65), -3, "nseeds"),
+    (dict(seeds=((4, 0, 0),)), -3, "seed"), (dict(seeds=((0, -1, 0),)), -3, "seed"), (dict(seeds=((1, 1, 1), (0, 0, 4))), -3, "seed"),
+    (dict(box_min=(2, 0, 0), box_max=(1, 3, 3)), -3, "box"), (dict(box_min=(0, 4, 0)), -3, "box"), (dict(box_max=(3, 3, -1)), -3, "box"),
+])
+def test_grow_refusals(lib, kw, code, word):
+    rc, last, msg = _grow(lib, **kw)
+    assert rc == last == code and "svr_region_grow" in msg and word in msg, (rc, last, msg)
+
+
+def test_null_seeds_and_other_calls_refuse(lib):
+    assert _grow(lib, seeds=None, nseeds=1)[0] == -4
+    st = abi.RegionStats()
+    one = C.c_void_p(1)
+    for args, code in (((None, 4, 4, 4, 1, one, C.byref(st)), -4), ((one, 4, 4, 4, 1, None, C.byref(st)), -4), ((one, 4, 4, 4, 1, one, None), -4),
+                       ((one, 4, 0, 4, 1, one, C.byref(st)), -6), ((one, 2**16, 2**16, 1, 1, one, C.byref(st)), -6)):
+        assert lib.svr_region_stats_of(*args) == code
+        assert b"svr_region_stats_of" in lib.svr_last_error()
+        lib.svr_clear_error()
+    for args, code in (((None, 4, 4, 4, 1, one, abi.REGION_KEEP, 0, one), -4), ((one, 4, 4, 4, 1, None, abi.REGION_KEEP, 0, one), -4),
+                       ((one, 4, 4, 4, 1, one, abi.REGION_KEEP, 0, None), -4), ((one, 4, 4, -4, 1, one, abi.REGION_KEEP, 0, one), -6),
+                       ((one, 4, 4, 4, 1, one, 0, 0, one), -3), ((one, 4, 4, 4, 1, one, 3, 0, one), -3),
+                       ((one, 4, 4, 4, 1, one, abi.REGION_REMOVE, 65536, one), -3)):
+        assert lib.svr_region_apply(*args) == code
+        assert b"svr_region_apply" in lib.svr_last_error()
+        lib.svr_clear_error()
+
+
+# ---------------------------------------------------------------- svr_region_seed_from_world
+def _volume(dim, spacing):
+    return host.create_device_volume(0, dim, spacing, 1.0)
+
+
+@pytest.mark.parametrize("dim, spacing", [((48, 48, 48), (1.0, 1.0, 1.0)), ((33, 7, 5), (0.7, 1.3, 2.5)), ((1, 1, 1), (1.0, 1.0, 1.0)),
+                                          ((512, 300, 17), (0.4, 0.4, 3.0))])
+def test_seed_from_world(lib, dim, spacing):
+    vol = _volume(dim, spacing)
+    lo = np.array([vol.bbox.vmin.x, vol.bbox.vmin.y, vol.bbox.vmin.z], dtype=np.float32)
+    hi = np.array([vol.bbox.vmax.x, vol.bbox.vmax.y, vol.bbox.vmax.z], dtype=np.float32)
+    n = np.array(dim)
+    # voxel centres: the sampler's texel i is centred at texture coordinate (i + 0.5) / n (oracle/svr_oracle.c, svo_tex3d: u n - 0.5 = i)
+    rng = np.random.default_rng(1)
+    picks = [np.zeros(3, dtype=int), n - 1] + [rng.integers(0, n) for _ in range(20)]
+    for ijk in picks:
+        p = lo.astype(np.float64) + (ijk + 0.5) / n * (hi.astype(np.float64) - lo)
+        assert host.region_seed_from_world(lib, vol, dim, p) == tuple(int(t) for t in ijk)
+    # both faces of the box: the near face is voxel 0, the far face belongs to the last voxel
+    assert host.region_seed_from_world(lib, vol, dim, lo) == (0, 0, 0)
+    assert host.region_seed_from_world(lib, vol, dim, hi) == tuple(int(t) - 1 for t in n)
+    # outside, on every axis and side, and non-finite
+    ext = hi - lo
+    mid = (lo + hi) / 2
+    for a in range(3):
+        for off in (-0.01, 1.01):
+            p = mid.copy()
+            p[a] = lo[a] + off * ext[a]
+            with pytest.raises(host.SvrError, match="outside"):
+                host.region_seed_from_world(lib, vol, dim, p)
+    with pytest.raises(host.SvrError, match="outside"):
+        host.region_seed_from_world(lib, vol, dim, (float("nan"), 0.0, 0.0))
+    ijk = (C.c_int32 * 3)(7, 7, 7)
+    pt = abi.vec3(0, 0, 0)
+    assert lib.svr_region_seed_from_world(None, 4, 4, 4, C.byref(pt), ijk) == -4
+    assert lib.svr_region_seed_from_world(C.byref(vol), 4, 0, 4, C.byref(pt), ijk) == -6
+    assert list(ijk) == [7, 7, 7]
+    lib.svr_clear_error()
+
+
+def test_seed_from_world_is_the_samplers_cell(lib, oracle):
+    """Against the oracle's sampler itself (svo_volume_intensity: (p - vmin) * invSize, then svo_tex3d).  With one voxel set to V and the
+    rest 0, the sampler returns V times the trilinear weight of that voxel: at a point on the centre lines of two axes and d cells off
+    the centre on the third, |d| < 0.5, that is V (1 - |d|) > V / 2 for the voxel whose cell holds the point and < V / 2 for any other."""
+    from oracle.binding import OracleScene
+
+    dim = (6, 5, 4)
+    sc = scenes.make_scene("tiny")
+    sc.vox, sc.spacing, sc.max_magnitude = np.zeros(dim[::-1], dtype=np.uint16), (0.5, 1.0, 2.0), 1.0
+    S = OracleScene(sc)
+    vol = _volume(dim, sc.spacing)
+    lo = np.array([vol.bbox.vmin.x, vol.bbox.vmin.y, vol.bbox.vmin.z], dtype=np.float64)
+    hi = np.array([vol.bbox.vmax.x, vol.bbox.vmax.y, vol.bbox.vmax.z], dtype=np.float64)
+    n = np.array(dim)
+    V = 60000
+    rng = np.random.default_rng(3)
+    checked = 0
+    for _ in range(60):
+        ijk = rng.integers(0, n)
+        axis = int(rng.integers(0, 3))
+        off = np.zeros(3)
+        off[axis] = rng.choice([-0.45, -0.2, 0.0, 0.3, 0.45])
+        p = (lo + (ijk + 0.5 + off) / n * (hi - lo)).astype(np.float32)
+        got = host.region_seed_from_world(lib, vol, dim, p)
+        assert got == tuple(int(t) for t in ijk)
+        S._vox[...] = 0
+        S._vox[got[2], got[1], got[0]] = V
+        val = S.lib.svo_volume_intensity(S.ptr, (C.c_float * 3)(*p)) * 65535.0
+        assert val > 0.5 * V and val == pytest.approx(V * (1 - abs(off[axis])), rel=1e-3)
+        checked += 1
+    assert checked == 60
+
+
+# ---------------------------------------------------------------- svr_region_measure
+@pytest.mark.parametrize("spacing", [(1.0, 1.0, 1.0), (0.7, 1.3, 2.5)])
+def test_measure_against_numpy(lib, spacing):
+    vox = head()
+    region, st = rr.reference("brain", vox, [BRAIN[2]], BRAIN[0], BRAIN[1], 6)
+    s = abi.RegionStats()
+    for k in ("voxels", "sum", "sum_sq", "sum_x", "sum_y", "sum_z", "faces_x", "faces_y", "faces_z", "vmin", "vmax", "status"):
+        setattr(s, k, st[k])
+    m = abi.RegionMeasurement()
+    sp = (C.c_double * 3)(*spacing)
+    assert lib.svr_region_measure(C.byref(s), sp, C.byref(m)) == 0
+    want = rr.measure(vox, region, spacing)
+    # float64 on both sides; the sums of ~1.4e4 terms differ by a few ulp, the standard deviation (a root of a difference) by more
+    assert m.volume == pytest.approx(want["volume"], rel=1e-13) and m.surface_area == pytest.approx(want["surface_area"], rel=1e-13)
+    assert m.mean == pytest.approx(want["mean"], rel=1e-12) and m.stddev == pytest.approx(want["stddev"], rel=1e-9)
+    assert list(m.centroid) == pytest.approx(want["centroid"], rel=1e-12)
+    # an empty region: zeros
+    e = abi.RegionStats()
+    assert lib.svr_region_measure(C.byref(e), sp, C.byref(m)) == 0
+    assert m.as_dict() == {"volume": 0.0, "mean": 0.0, "stddev": 0.0, "centroid": [0.0, 0.0, 0.0], "surface_area": 0.0}
+    # large sums: 2^31 voxels of 65535 and 65534 alternating -- the exact radicand keeps the deviation of 0.5
+    big = abi.RegionStats()
+    half = 2**30
+    big.voxels, big.sum, big.sum_sq = 2 * half, half * (65535 + 65534), half * (65535**2 + 65534**2)
+    assert lib.svr_region_measure(C.byref(big), sp, C.byref(m)) == 0
+    assert m.stddev == 0.5 and m.mean == 65534.5
+    for bad in ((0.0, 1.0, 1.0), (1.0, -1.0, 1.0), (1.0, 1.0, float("inf"))):
+        assert lib.svr_region_measure(C.byref(s), (C.c_double * 3)(*bad), C.byref(m)) == -3
+    assert lib.svr_region_measure(None, sp, C.byref(m)) == -4
+    lib.svr_clear_error()
+
+
+# ---------------------------------------------------------------- the reference itself
+STRUCTURES = {6: 1, 18: 2, 26: 3}
+
+
+def _scipy_region(vox, seeds, lo, hi, conn, box=None):
+    ndi = pytest.importorskip("scipy.ndimage")
+    cand = rr.candidates(vox, lo, hi, box)
+    lab, _ = ndi.label(cand, structure=ndi.generate_binary_structure(3, STRUCTURES[conn]))
+    ids = {int(lab[z, y, x]) for x, y, z in seeds} - {0}
+    return np.isin(lab, sorted(ids)) if ids else np.zeros_like(cand)
+
+
+@pytest.mark.parametrize("conn", [6, 18, 26])
+def test_reference_against_scipy(conn):
+    vox = head()
+    for lo, hi, seeds in ((BRAIN[0], BRAIN[1], [BRAIN[2]]), (BONE[0], BONE[1], [bone_seed(vox)]), (THIN[0], THIN[1], [THIN[2]]),
+                          (0, 0, [(0, 0, 0)]), (0, 0, [(24, 24, 24)]), (13107, 24903, [(26, 44, 23), (24, 24, 24), (5, 5, 5)])):
+        assert np.array_equal(rr.grow(vox, seeds, lo, hi, conn), _scipy_region(vox, seeds, lo, hi, conn))
+    nv = rr.noise_volume((9, 10, 37))
+    seeds = rr.spread_seeds(nv)
+    box = ((2, 1, 0), (30, 8, 7))
+    assert np.array_equal(rr.grow(nv, seeds, rr.NOISE_LO, rr.NOISE_HI, conn, box), _scipy_region(nv, seeds, rr.NOISE_LO, rr.NOISE_HI, conn, box))
+    sv, seed = rr.serpentine()
+    assert np.array_equal(rr.grow(sv, [seed], 1000, 1000, conn), _scipy_region(sv, [seed], 1000, 1000, conn))
+
+
+def test_reference_stats_by_hand():
+    vox = np.arange(2 * 3 * 4, dtype=np.uint16).reshape(2, 3, 4) * 1000
+    region = np.zeros((2, 3, 4), dtype=bool)
+    region[0, 0, 0] = region[0, 0, 1] = region[1, 0, 1] = region[1, 2, 3] = True
+    st = rr.stats(vox, region)
+    vals = [0, 1000, 13000, 23000]
+    assert st["voxels"] == 4 and st["sum"] == sum(vals) and st["sum_sq"] == sum(v * v for v in vals)
+    assert (st["sum_x"], st["sum_y"], st["sum_z"]) == (0 + 1 + 1 + 3, 2, 2)
+    assert (st["faces_x"], st["faces_y"], st["faces_z"]) == (8 - 2, 8, 8 - 2)
+    assert (st["vmin"], st["vmax"], st["bbox_min"], st["bbox_max"], st["status"]) == (0, 23000, [0, 0, 0], [3, 2, 1], rr.OK)
+    e = rr.stats(vox, np.zeros_like(region))
+    assert (e["voxels"], e["vmin"], e["vmax"], e["bbox_min"], e["bbox_max"], e["status"]) == (0, 65535, 0, [4, 3, 2], [-1, -1, -1], rr.EMPTY)
+    assert np.array_equal(rr.apply(vox, region, rr.KEEP, 7)[region], vox[region]) and (rr.apply(vox, region, rr.KEEP, 7)[~region] == 7).all()
+    assert (rr.apply(vox, region, rr.REMOVE, 9)[region] == 9).all() and np.array_equal(rr.apply(vox, region, rr.REMOVE, 9)[~region], vox[~region])
+
+
+# ---------------------------------------------------------------- conditions on the fixtures of the GPU tests
+def test_head_cases_have_the_stated_sizes():
+    vox = head()
+    assert vox.shape == (48, 48, 48)
+    for lo, hi, seed, sizes, cands in (BRAIN, BONE, THIN):
+        seed = bone_seed(vox) if seed is None else seed
+        for conn, n in sizes.items():
+            region, st = rr.reference("head", vox, [seed], lo, hi, conn)
+            assert st["voxels"] == n == int(region.sum())
+            if cands is not None:
+                assert int(rr.candidates(vox, lo, hi).sum()) == cands
+    # brain: a proper sub-component (a thresholded answer is wrong); bone: one shell that wraps the volume; the thin window separates 26
+    assert BRAIN[3][6] < BRAIN[4]
+    _, st = rr.reference("head", vox, [bone_seed(vox)], BONE[0], BONE[1], 6)
+    assert all(b - a >= 30 for a, b in zip(st["bbox_min"], st["bbox_max"]))
+    assert THIN[3][6] == THIN[3][18] < THIN[3][26]
+    _, air = rr.reference("head", vox, [(0, 0, 0)], 0, 0, 6)
+    assert air["voxels"] == 74800 and air["bbox_min"] == [0, 0, 0] and air["bbox_max"] == [47, 47, 47] and air["voxels"] < vox.size
+    assert int((vox == 0).sum()) >= air["voxels"]
+    _, whole = rr.reference("head", vox, [(7, 8, 9)], 0, 65535, 6)
+    assert whole["voxels"] == vox.size
+    noisy = scenes.make_scene("tiny_head_noisy").vox
+    _, st = rr.reference("noisy", noisy, [(0, 0, 0)], 0, 300, 6)
+    assert st["voxels"] == 76205
+
+
+def test_edge_fixtures_are_not_degenerate():
+    tx, ty, tz = rr.TILE
+    for shape in rr.EDGE_SHAPES:
+        vox = rr.noise_volume(shape)
+        seeds = rr.spread_seeds(vox)
+        for conn in (6, 18, 26):
+            region, st = rr.reference("noise", vox, seeds, rr.NOISE_LO, rr.NOISE_HI, conn)
+            assert 1 <= st["voxels"] <= vox.size
+            if vox.size > 1:
+                assert 1 < st["voxels"] < vox.size, (shape, conn)
+    for name, a, b in rr.PAIRS:
+        # the two voxels lie in different words or tiles
+        assert (a[0] // rr.WORD, a[1] // ty, a[2] // tz) != (b[0] // rr.WORD, b[1] // ty, b[2] // tz), name
+        vox = rr.pair_volume(a, b)
+        for conn in (6, 18, 26):
+            for s, o in ((a, b), (b, a)):
+                region, st = rr.reference("pair" + name, vox, [s], 1000, 1000, conn)
+                assert st["voxels"] == rr.pair_expected(s, o, conn)
+    got = {conn: [rr.pair_expected(a, b, conn) for _, a, b in rr.PAIRS] for conn in (6, 18, 26)}
+    assert set(got[6]) == {1} and set(got[18]) == {1, 2} and set(got[26]) == {2}
+    # the serpentine: one corridor, about a quarter of the volume, across three tiles on two axes
+    sv, seed = rr.serpentine()
+    region, st = rr.reference("serpentine", sv, [seed], 1000, 1000, 6)
+    assert st["voxels"] == int((sv == 1000).sum()) and 0.2 < st["voxels"] / sv.size < 0.3
+    spans = [(st["bbox_max"][a] // t) - (st["bbox_min"][a] // t) + 1 for a, t in enumerate(rr.TILE)]
+    assert sum(1 for s in spans if s >= 3) >= 2, spans
+    # the bridge: the box leaves the seed's bar, the whole volume the two bars and the bridge
+    bv, bseed, box = rr.bridge_volume()
+    whole, _ = rr.reference("bridge", bv, [bseed], 500, 500, 6)
+    cut, _ = rr.reference("bridge", bv, [bseed], 500, 500, 6, box)
+    assert whole.sum() == (bv == 500).sum() and 0 < cut.sum() < (rr.candidates(bv, 500, 500, box)).sum() and not cut[:, :, 30:].any()
+
+
+# ---------------------------------------------------------------- examples/render_mhd.cpp -grow: the arguments
+@pytest.fixture(scope="module")
+def render_mhd(tmp_path_factory):
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = tmp_path_factory.mktemp("render_mhd") / "render_mhd"
+    libdir = abi.library_path().parent
+    res = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"),
+                          "-o", str(exe), f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    return exe
+
+
+@pytest.mark.parametrize("args", [["-grow", "-1", "2", "0", "10"], ["-grow", "1", "2", "10", "9"], ["-grow", "1", "2", "0", "65536"], ["-grow", "1", "2", "3"],
+                                  ["-grow", "1", "2", "0", "10", "-conn", "8"]])
+def test_render_mhd_rejects_bad_grow_arguments(render_mhd, tmp_path, args):
+    import subprocess
+
+    res = subprocess.run([str(render_mhd), str(tmp_path / "missing.mhd"), *args], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 2 and res.stderr.strip(), (res.returncode, res.stderr)
+
+
+def test_render_mhd_usage_names_grow(render_mhd):
+    import subprocess
+
+    err = subprocess.run([str(render_mhd)], capture_output=True, text=True, timeout=60).stderr
+    assert "-grow X Y LO HI" in err and "-conn 6|18|26" in err and "-keep | -remove" in err
