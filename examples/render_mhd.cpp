@@ -13,9 +13,12 @@
 // -grow X Y LO HI picks at pixel (X, Y) with the -hit mode in force, grows the connected region of the voxels with raw value LO .. HI
 // (0 .. 65535) around the picked voxel (svr_region_grow; -conn 6|18|26, default 6), prints its voxel count, volume, mean +- standard
 // deviation, bounding box and surface area, and renders the volume with everything else removed (-keep, the default) or with the
-// region removed (-remove) into the output image.
+// region removed (-remove) into the output image.  After -grow, -detach R, -fillholes, -open R, -close R, -dilate R and -erode R clean the
+// region up, in command-line order (Canvas::DetachRegion, FillRegionHoles, MorphRegion; R = 1 .. 32 applications of the unit element
+// -element 6|18|26, default 6): -detach cuts off what hangs on the picked structure by connections thinner than the element,
+// -fillholes adds what the region encloses.  The measurements are printed once more after the last step, and that region is shown.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +31,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -42,8 +45,32 @@ int main(int argc, char** argv)
     svr_hit_params hitParams = {SVR_HIT_OPACITY, 0.5f, 0.5f};
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
+    struct CleanStep { const char* name; int op; uint32_t radius; };       // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach
+    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode, in order
+    int cleanElement = 6;
     for (int i = 2; i < argc; ++i) {
-        if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
+        int cleanOp = -2;
+        if (!strcmp(argv[i], "-detach")) cleanOp = -1;
+        else if (!strcmp(argv[i], "-open")) cleanOp = SVR_MORPH_OPEN;
+        else if (!strcmp(argv[i], "-close")) cleanOp = SVR_MORPH_CLOSE;
+        else if (!strcmp(argv[i], "-dilate")) cleanOp = SVR_MORPH_DILATE;
+        else if (!strcmp(argv[i], "-erode")) cleanOp = SVR_MORPH_ERODE;
+        if (cleanOp != -2) {
+            char* end = nullptr;
+            const long r = i + 1 < argc ? strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || r < 1 || r > SVR_MORPH_MAX_RADIUS) {
+                fprintf(stderr, "%s needs a radius R in 1 .. %d (got %s)\n", argv[i], SVR_MORPH_MAX_RADIUS, i + 1 < argc ? argv[i + 1] : "nothing");
+                return 2;
+            }
+            cleanSteps.push_back(CleanStep{argv[i], cleanOp, (uint32_t)r});
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-fillholes")) cleanSteps.push_back(CleanStep{argv[i], 0, 0u});
+        else if (!strcmp(argv[i], "-element") && i + 1 < argc) {
+            cleanElement = atoi(argv[++i]);
+            if (cleanElement != 6 && cleanElement != 18 && cleanElement != 26) { fprintf(stderr, "-element needs 6, 18 or 26 (got %s)\n", argv[i]); return 2; }
+        }
+        else if (!strcmp(argv[i], "-tf") && i + 1 < argc) tfFile = argv[++i];
         else if (!strcmp(argv[i], "-env") && i + 1 < argc) envFile = argv[++i];
         else if (!strcmp(argv[i], "-frames") && i + 1 < argc) frames = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-depth") && i + 1 < argc) depth = atoi(argv[++i]);
@@ -112,6 +139,7 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if ((slabMode || stack) && sliceAxis < 0) { fprintf(stderr, "-slab and -stack need -slice\n"); return 2; }
+    if (!cleanSteps.empty() && !grow) { fprintf(stderr, "%s needs -grow X Y LO HI\n", cleanSteps[0].name); return 2; }
     if (svr_init(0)) return 1;
     {
         Canvas canvas(W, H);
@@ -195,6 +223,24 @@ int main(int argc, char** argv)
                 printf("grow %d %d window %d..%d conn %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %u sweeps\n",
                        growX, growY, growLo, growHi, growConn, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
                        st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
+            if (!cleanSteps.empty()) {
+                std::string done;
+                for (const CleanStep& c : cleanSteps) {
+                    const int rc = c.op == -1 ? canvas.DetachRegion(cleanElement, c.radius, &st)
+                                 : c.op == 0 ? canvas.FillRegionHoles(6, &st)
+                                             : canvas.MorphRegion(c.op, cleanElement, c.radius, &st);
+                    if (rc != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    done += std::string(done.empty() ? "" : " ") + (c.name + 1);
+                    if (c.op != 0) done += " " + std::to_string(c.radius);
+                }
+                if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (st.status == SVR_REGION_STATUS_EMPTY)
+                    printf("cleaned (%s, element %d): the region is empty\n", done.c_str(), cleanElement);
+                else
+                    printf("cleaned (%s, element %d): %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
+                           done.c_str(), cleanElement, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                           st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+            }
             if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         }
 

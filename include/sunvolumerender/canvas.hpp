@@ -15,6 +15,7 @@
 #define SUNVOLUMERENDER_CANVAS_HPP
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "host_api.hpp"
@@ -454,8 +455,37 @@ public:
         svr_region_stats st = {};
         rc = svr_region_grow(vox, dim[0], dim[1], dim[2], 1, seed, 1u, &p, regionMask, &st);
         haveRegion = rc == 0;
+        for (int a = 0; a < 3; ++a) regionSeed[a] = seed[a];     // DetachRegion starts from the same voxel, with the same connectivity
+        regionConnectivity = connectivity;
         if (stats) *stats = st;
         return rc;
+    }
+    // Clean-up of the grown region (svr_region_morph / _fill_holes / _detach; include/svr_abi.h, "operations on region masks").  Each
+    // replaces the Canvas's region mask by its result -- on failure the mask stays as it was -- and *stats (may be null) gets the
+    // statistics of the new mask (svr_region_stats_of); ShowRegion then shows the cleaned region.
+    // MorphRegion: SVR_MORPH_DILATE / _ERODE / _OPEN / _CLOSE by the unit element 6 / 18 / 26 applied `radius` times
+    int MorphRegion(int op, int element, uint32_t radius, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask()) return -4;
+        const int* dim = volumeReader->dim;
+        return ReplaceRegion(svr_region_morph(regionMask, dim[0], dim[1], dim[2], op, element, radius, regionWork), stats);
+    }
+    // FillRegionHoles: the region and every voxel outside it that cannot reach a face of the volume through the background
+    int FillRegionHoles(int background_connectivity = 6, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask()) return -4;
+        const int* dim = volumeReader->dim;
+        return ReplaceRegion(svr_region_fill_holes(regionMask, dim[0], dim[1], dim[2], background_connectivity, 0u, regionWork), stats);
+    }
+    // DetachRegion: what the region keeps around GrowRegion's seed voxel when connections thinner than the element (applied `radius`
+    // times) are cut; a seed outside the region's opening leaves an empty region (stats->status == SVR_REGION_STATUS_EMPTY), return 0
+    int DetachRegion(int element, uint32_t radius, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask()) return -4;
+        const int* dim = volumeReader->dim;
+        int32_t status = SVR_REGION_STATUS_OK;
+        return ReplaceRegion(svr_region_detach(regionMask, dim[0], dim[1], dim[2], regionSeed, 1u, element, radius, regionConnectivity, 0u, regionWork, &status),
+                             stats);
     }
     // ShowRegion: every renderer now draws the volume with the voxels outside (SVR_REGION_KEEP) or inside (SVR_REGION_REMOVE) the grown
     // region set to `fill`; ShowAll goes back to the loaded volume.  The Canvas owns the extra texture
@@ -531,7 +561,25 @@ private:
     {
         if (regionTex) svr_destroy_texture(regionTex);
         if (regionMask) svr_device_free(regionMask);
-        regionTex = 0; regionMask = nullptr; haveRegion = false;
+        if (regionWork) svr_device_free(regionWork);
+        regionTex = 0; regionMask = nullptr; regionWork = nullptr; haveRegion = false;
+    }
+    // the second mask buffer, into which the clean-up calls write (their `out` must not overlap their input)
+    bool WorkMask()
+    {
+        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion) return false;
+        const int* dim = volumeReader->dim;
+        if (!regionWork) regionWork = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
+        return regionWork != nullptr;
+    }
+    // after a clean-up call that returned rc: its result becomes the region mask
+    int ReplaceRegion(int rc, svr_region_stats* stats)
+    {
+        if (rc != 0) return rc;
+        std::swap(regionMask, regionWork);
+        if (!stats) return 0;
+        const int* dim = volumeReader->dim;
+        return svr_region_stats_of(volumeReader->DeviceVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats);
     }
     void UpdateCamera()                                                         // canvas.cpp:178-188
     {
@@ -552,6 +600,9 @@ private:
     cudaTransferFunction transferFunction;
     RenderMode renderMode = RENDER_MODE_RAYCASTING;
     uint32_t* regionMask = nullptr;                // GrowRegion's bit mask (device)
+    uint32_t* regionWork = nullptr;                // the other mask buffer of the clean-up calls
+    int32_t regionSeed[3] = {0, 0, 0};             // GrowRegion's seed voxel and connectivity, for DetachRegion
+    int regionConnectivity = 6;
     cudaTextureObject_t regionTex = 0;             // ShowRegion's masked volume
     bool haveRegion = false;
     svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};

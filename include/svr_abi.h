@@ -727,6 +727,55 @@ int svr_region_measure(const svr_region_stats* stats, const double spacing[3], s
 /* HIP-event times of the phases of the last svr_region_grow: classify (with the seeds), grow (all sweeps), stats.  Pointers may be NULL */
 int svr_region_last_ms(float* classify_ms, float* grow_ms, float* stats_ms);
 
+/* ---- operations on region masks: morphology, set operations, regrowth, hole filling, leak cutting (csrc/svr_morph.hip) ----
+ * Every mask is a DEVICE pointer to svr_region_mask_words(nx, ny, nz) words in the layout above.  The calls are stateless: they run on the
+ * library's stream and touch no scene, option or accumulator; results are exact (integers) and feed svr_region_stats_of, _measure, _apply.
+ * PADDING: the bits of a row's last word at x >= nx are ignored on input, whatever they hold, and are 0 on output.
+ * NEIGHBOURS: element / connectivity 6 = the face neighbours of a voxel, 18 = faces and edges, 26 = faces, edges and corners.
+ * MORPH: the unit structuring element is a voxel and its element-neighbours; radius r applies it r times (the iterated definition).
+ *   DILATE: a voxel is set if it or one of its element-neighbours INSIDE the volume is set; nothing enters from outside.
+ *   ERODE is the dual, erode(M) = NOT dilate(NOT M) inside the volume: a voxel stays if it and all its element-neighbours inside the volume
+ *   are set, so a region touching a face of the volume is not eroded from that face.  OPEN = erode then dilate, CLOSE = dilate then erode;
+ *   open(M) is a subset of M, M of close(M), and both are idempotent.  (scipy.ndimage: binary_dilation(border_value=0) and
+ *   binary_erosion(border_value=1), iterations=radius, generate_binary_structure(3, 1 | 2 | 3).)
+ * COMBINE: AND, OR, ANDNOT (a & ~b), XOR, NOT (~a; b must be NULL).  out may alias a or b.
+ * RECONSTRUCT: out = the union of the connected components (connectivity 6 / 18 / 26) of `cand` that contain a voxel of marker & cand;
+ *   empty, with return 0, if there is none.  It is svr_region_grow's fixpoint with masks in place of the window and the seed list, and runs
+ *   on the same kernel and sweeps: max_sweeps = 0 means svr_region_default_max_sweeps, and at the cap the call returns SVR_REGION_ERR_SWEEPS
+ *   with the part grown so far in out.  *sweeps_out (may be NULL) = the passes launched.
+ * FILL HOLES: out = NOT reconstruct(marker = every voxel on the six faces of the volume, cand = NOT in, background_connectivity): `in` and
+ *   every background voxel that cannot reach a face.  background_connectivity 6 is scipy.ndimage.binary_fill_holes' default.  At the sweep
+ *   cap (SVR_REGION_ERR_SWEEPS) out holds the complement of the background reached so far: more than the filled mask.
+ * DETACH: cuts from a grown region what hangs on it by connections thinner than the element: E = erode(in, element, radius); K =
+ *   reconstruct(marker = dilate(the seed voxels, element, radius), cand = E, connectivity); out = dilate(K, element, radius) & in.  The
+ *   marker is the dilated seed, so a seed that the erosion removes still finds its core whenever it lies in the opening of `in`; if it does
+ *   not, the result is empty: *status = SVR_REGION_STATUS_EMPTY, return 0.  Seeds are a HOST array as in svr_region_grow.
+ * The library allocates and frees the temporaries (a morph that takes more than one launch -- open, close, a radius of 3 or above 4: one mask;
+ * reconstruct and fill_holes: one mask; detach: four); a call that used one synchronises the stream before it returns, svr_region_combine
+ * and a one-launch morph (dilate or erode by 1, 2 or 4) are asynchronous.
+ * REFUSED, before the device is touched: a null pointer (-4); a dimension <= 0 or more than 2^31 voxels (-6); an unknown op, an element or
+ * connectivity other than 6 / 18 / 26, a radius outside 1 .. SVR_MORPH_MAX_RADIUS, b != NULL with SVR_MASK_NOT, nseeds == 0 or >
+ * SVR_REGION_MAX_SEEDS, a seed outside the volume, an `out` that overlaps an input of morph, reconstruct, fill_holes or detach (-3). */
+#define SVR_MORPH_DILATE 1
+#define SVR_MORPH_ERODE  2
+#define SVR_MORPH_OPEN   3
+#define SVR_MORPH_CLOSE  4
+#define SVR_MORPH_MAX_RADIUS 32
+#define SVR_MASK_AND    1
+#define SVR_MASK_OR     2
+#define SVR_MASK_ANDNOT 3
+#define SVR_MASK_XOR    4
+#define SVR_MASK_NOT    5
+int svr_region_morph(const uint32_t* in_mask_device, int nx, int ny, int nz, int op, int element, uint32_t radius, uint32_t* out_mask_device);
+int svr_region_combine(const uint32_t* a_device, const uint32_t* b_device, int nx, int ny, int nz, int op, uint32_t* out_device);
+int svr_region_reconstruct(const uint32_t* marker_device, const uint32_t* cand_device, int nx, int ny, int nz, int connectivity, uint32_t max_sweeps,
+                           uint32_t* out_device, uint32_t* sweeps_out);
+int svr_region_fill_holes(const uint32_t* in_device, int nx, int ny, int nz, int background_connectivity, uint32_t max_sweeps, uint32_t* out_device);
+int svr_region_detach(const uint32_t* in_device, int nx, int ny, int nz, const int32_t* seeds_xyz, uint32_t nseeds, int element, uint32_t radius,
+                      int connectivity, uint32_t max_sweeps, uint32_t* out_device, int32_t* status);
+/* HIP-event time of the device work of the last of the five calls above (waits for it) */
+int svr_region_mask_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

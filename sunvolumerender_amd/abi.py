@@ -279,6 +279,9 @@ REGION_MAX_SEEDS = 64
 REGION_KEEP, REGION_REMOVE = 1, 2
 REGION_STATUS_OK, REGION_STATUS_EMPTY = 0, 1
 REGION_ERR_SWEEPS = -9
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 1, 2, 3, 4
+MORPH_MAX_RADIUS = 32
+MASK_AND, MASK_OR, MASK_ANDNOT, MASK_XOR, MASK_NOT = 1, 2, 3, 4, 5
 
 
 EXPECTED_SIZES = {
@@ -441,6 +444,13 @@ PROTOTYPES = {
     "svr_region_seed_from_world": (C.c_int, [_P(cudaVolume), C.c_int, C.c_int, C.c_int, _P(vec3), _P(C.c_int32)]),
     "svr_region_measure": (C.c_int, [_P(RegionStats), _P(C.c_double), _P(RegionMeasurement)]),
     "svr_region_last_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "svr_region_morph": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "svr_region_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "svr_region_reconstruct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, _P(C.c_uint32)]),
+    "svr_region_fill_holes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "svr_region_detach": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_int32), C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32,
+                                    C.c_void_p, _P(C.c_int32)]),
+    "svr_region_mask_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

@@ -6,7 +6,7 @@
 //   reads V voxels of a row (V = 8: one 16-byte load, when nx % 8 == 0 and the rows are 16-byte aligned; else V = 1) and the lanes of a
 //   word OR their bits together (a wave64 ballot for V = 1, two xor shuffles for V = 8).  k_region_seed then sets the seeds that are
 //   candidates and marks the 27 tiles around every seed dirty.
-// GROW (k_region_grow<CONN>): tiles of TWX x TY x TZ = 4 words x 8 rows x 8 slices (128 x 8 x 8 voxels), one 256-thread block per tile,
+// GROW (k_region_grow<CONN> and the sweep loop, in svr_region_grow.hpp: svr_morph.hip runs the same code): tiles of TWX x TY x TZ = 4 words x 8 rows x 8 slices (128 x 8 x 8 voxels), one 256-thread block per tile,
 //   one thread per word.  The block copies the region words of the tile and of a one-word / one-row halo into LDS (2.4 KB), keeps its
 //   candidate word in a register and iterates: new = fill(r | (neighbours & c), c), where `neighbours` ORs the words of the 3 x 3 rows
 //   around it that the connectivity admits -- shifted by one bit to either side, across the word boundary, where a step in x is part of
@@ -41,21 +41,15 @@
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
 
-#ifndef SVR_REGION_BATCH
-#define SVR_REGION_BATCH 16         // sweeps launched per read of the `added` counters (measured against 1 and 4: DESIGN.md 8h)
-#endif
+#include "svr_region_grow.hpp"      // k_region_grow<CONN>, its tiles and the sweep loop (shared with svr_morph.hip)
 
 using svr::failf;
 
 namespace {
 
-constexpr int TWX = 4, TY = 8, TZ = 8;                  // tile: words in x, rows, slices
-constexpr int GROW_THREADS = TWX * TY * TZ;             // one thread per word
 constexpr int THREADS = 256;
 constexpr int ACC_SLOTS = 64;                           // k_region_stats spreads its atomics over this many accumulators
-static_assert(GROW_THREADS == 256, "the halo load and the 27 marker threads assume 256 threads");
 
-struct RegionDims { int nx, ny, nz, wx; };
 struct RegionBox { int x0, y0, z0, x1, y1, z1; };        // inclusive
 struct RegionSeeds { int n; int xyz[SVR_REGION_MAX_SEEDS][3]; };
 struct RegionAcc {                                       // device accumulators of k_region_stats
@@ -139,99 +133,6 @@ __global__ void k_region_seed(RegionSeeds s, RegionDims d, int ntx, int nty, int
                 const int ax = tx + dx, ay = ty + dy, az = tz + dz;
                 if (ax >= 0 && ax < ntx && ay >= 0 && ay < nty && az >= 0 && az < ntz) dirty[((size_t)az * nty + ay) * ntx + ax] = 1u;
             }
-}
-
-// the bits of g extended along the runs of p, both ways (g is a subset of p)
-__device__ inline uint32_t fill_runs(uint32_t g, uint32_t p)
-{
-    uint32_t a = g, q = p;
-    a |= q & (a << 1); q &= q << 1;
-    a |= q & (a << 2); q &= q << 2;
-    a |= q & (a << 4); q &= q << 4;
-    a |= q & (a << 8); q &= q << 8;
-    a |= q & (a << 16);
-    q = p;
-    a |= q & (a >> 1); q &= q >> 1;
-    a |= q & (a >> 2); q &= q >> 2;
-    a |= q & (a >> 4); q &= q >> 4;
-    a |= q & (a >> 8); q &= q >> 8;
-    a |= q & (a >> 16);
-    return a;
-}
-
-template <int CONN>
-__global__ __launch_bounds__(GROW_THREADS) void k_region_grow(const uint32_t* __restrict__ cand, uint32_t* region, RegionDims d, int ntx, int nty,
-                                                              int ntz, uint32_t* dirty_cur, uint32_t* dirty_next, uint32_t* added)
-{
-    const size_t tile = blockIdx.x;
-#ifndef SVR_REGION_ALL_TILES                             // (the A/B build of tools/region_time.py sweeps every tile every pass)
-    if (!dirty_cur[tile]) return;
-#endif
-    __shared__ uint32_t R[TZ + 2][TY + 2][TWX + 2];
-    __shared__ uint32_t s_flags;
-    const int tid = threadIdx.x;
-    const int tx = (int)(tile % ntx), ty = (int)((tile / ntx) % nty), tz = (int)(tile / ((size_t)ntx * nty));
-    for (int i = tid; i < (TZ + 2) * (TY + 2) * (TWX + 2); i += GROW_THREADS) {
-        const int hx = i % (TWX + 2), hy = (i / (TWX + 2)) % (TY + 2), hz = i / ((TWX + 2) * (TY + 2));
-        const int gw = tx * TWX + hx - 1, gy = ty * TY + hy - 1, gz = tz * TZ + hz - 1;
-        uint32_t r = 0u;
-        if (gw >= 0 && gw < d.wx && gy >= 0 && gy < d.ny && gz >= 0 && gz < d.nz) r = region[((size_t)gz * d.ny + gy) * d.wx + gw];
-        R[hz][hy][hx] = r;
-    }
-    const int lx = tid % TWX, ly = (tid / TWX) % TY, lz = tid / (TWX * TY);
-    const int gw = tx * TWX + lx, gy = ty * TY + ly, gz = tz * TZ + lz;
-    const bool valid = gw < d.wx && gy < d.ny && gz < d.nz;
-    const size_t at = valid ? ((size_t)gz * d.ny + gy) * d.wx + gw : 0;
-    const uint32_t c = valid ? cand[at] : 0u;
-    if (tid == 0) s_flags = 0u;
-    __syncthreads();
-    if (tid == 0) dirty_cur[tile] = 0u;                  // (every thread has read the flag: this buffer is the sweep after next's)
-    const uint32_t r0 = R[lz + 1][ly + 1][lx + 1];
-    uint32_t r = r0;
-    for (;;) {
-        uint32_t n = 0u;
-#pragma unroll
-        for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int k = (dz != 0) + (dy != 0);                                 // steps of the move besides the one in x
-                const bool plain = k == 0 ? false : k == 1 ? true : CONN >= 18;      // (dx = 0; the centre word itself is r)
-                const bool shifted = k == 0 ? true : k == 1 ? CONN >= 18 : CONN == 26;   // dx = +-1
-                if (!plain && !shifted) continue;
-                const uint32_t m = R[lz + 1 + dz][ly + 1 + dy][lx + 1];
-                if (plain) n |= m;
-                if (shifted) n |= (m << 1) | (m >> 1) | (R[lz + 1 + dz][ly + 1 + dy][lx] >> 31) | (R[lz + 1 + dz][ly + 1 + dy][lx + 2] << 31);
-            }
-        const uint32_t nr = fill_runs(r | (n & c), c);
-        const int changed = nr != r;
-        if (changed) { R[lz + 1][ly + 1][lx + 1] = nr; r = nr; }
-        if (!__syncthreads_or(changed)) break;
-    }
-    const uint32_t nb = r & ~r0;
-    if (nb) {
-        atomicOr(&region[at], nb);
-        uint32_t f = 64u;
-        if (lx == 0 && (nb & 1u)) f |= 1u;
-        if (lx == TWX - 1 && (nb >> 31)) f |= 2u;
-        if (ly == 0) f |= 4u;
-        if (ly == TY - 1) f |= 8u;
-        if (lz == 0) f |= 16u;
-        if (lz == TZ - 1) f |= 32u;
-        atomicOr(&s_flags, f);
-    }
-    __syncthreads();
-    const uint32_t flags = s_flags;
-    if (tid == 0 && (flags & 64u)) atomicAdd(added, 1u);
-    if (tid < 27) {
-        // the neighbour tile in direction (dx, dy, dz) sees the layers of this tile that lie on all the faces the direction names
-        const int dx = tid % 3 - 1, dy = (tid / 3) % 3 - 1, dz = tid / 9 - 1;
-        const int k = (dx != 0) + (dy != 0) + (dz != 0);
-        if (k == 0 || k > (CONN == 6 ? 1 : CONN == 18 ? 2 : 3)) return;
-        const uint32_t need = (dx < 0 ? 1u : dx > 0 ? 2u : 0u) | (dy < 0 ? 4u : dy > 0 ? 8u : 0u) | (dz < 0 ? 16u : dz > 0 ? 32u : 0u);
-        const int ax = tx + dx, ay = ty + dy, az = tz + dz;
-        if ((flags & need) == need && ax >= 0 && ax < ntx && ay >= 0 && ay < nty && az >= 0 && az < ntz)
-            dirty_next[((size_t)az * nty + ay) * ntx + ax] = 1u;
-    }
 }
 
 __device__ inline unsigned long long wave_sum(unsigned long long v)
@@ -488,8 +389,9 @@ int svr_region_grow(const uint16_t* voxels, int nx, int ny, int nz, int src_is_d
 
     const RegionDims d = make_dims(nx, ny, nz);
     const size_t n = (size_t)nx * ny * nz, words = (size_t)svr_region_mask_words(nx, ny, nz);
-    const int ntx = (d.wx + TWX - 1) / TWX, nty = (ny + TY - 1) / TY, ntz = (nz + TZ - 1) / TZ;
-    const size_t tiles = (size_t)ntx * nty * ntz;
+    RegionSweep sw(d);
+    const int ntx = sw.ntx, nty = sw.nty, ntz = sw.ntz;
+    const size_t tiles = sw.tiles;
     DeviceVoxels dv;
     uint32_t *d_cand = nullptr, *d_dirty = nullptr, *d_added = nullptr;
     RegionAcc* d_acc = nullptr;
@@ -524,23 +426,8 @@ int svr_region_grow(const uint16_t* voxels, int nx, int ny, int nz, int src_is_d
 
     uint32_t sweeps = 0u;
     bool done = false;
-    while (!done && sweeps < cap) {
-        const uint32_t nb = cap - sweeps < (uint32_t)SVR_REGION_BATCH ? cap - sweeps : (uint32_t)SVR_REGION_BATCH;
-        REGION_TRY(hipMemsetAsync(d_added, 0, SVR_REGION_BATCH * sizeof(uint32_t), st));
-        for (uint32_t i = 0; i < nb; ++i) {
-            uint32_t *cur = dirty[(sweeps + i) & 1u], *next = dirty[(sweeps + i + 1u) & 1u];
-            const dim3 g((uint32_t)tiles), b(GROW_THREADS);
-            if (params->connectivity == 6) hipLaunchKernelGGL((k_region_grow<6>), g, b, 0, st, d_cand, mask_device, d, ntx, nty, ntz, cur, next, d_added + i);
-            else if (params->connectivity == 18) hipLaunchKernelGGL((k_region_grow<18>), g, b, 0, st, d_cand, mask_device, d, ntx, nty, ntz, cur, next, d_added + i);
-            else hipLaunchKernelGGL((k_region_grow<26>), g, b, 0, st, d_cand, mask_device, d, ntx, nty, ntz, cur, next, d_added + i);
-        }
-        REGION_TRY(hipGetLastError());
-        sweeps += nb;
-        uint32_t added[SVR_REGION_BATCH];
-        REGION_TRY(hipMemcpyAsync(added, d_added, sizeof added, hipMemcpyDeviceToHost, st));
-        REGION_TRY(hipStreamSynchronize(st));
-        for (uint32_t i = 0; i < nb; ++i) if (added[i] == 0u) done = true;
-    }
+    sw.dirty = d_dirty; sw.added = d_added;
+    REGION_TRY(region_sweep_to_fixpoint(st, (int)params->connectivity, d_cand, mask_device, d, sw, cap, &sweeps, &done));
     REGION_TRY(hipEventRecord(ev[2], st));
     stats_host->sweeps = sweeps;
     if (!done) {

@@ -363,6 +363,72 @@ class Device:
             return buf, True
         return int(mask), False
 
+    # ---- operations on region masks (svr_region_morph / _combine / _reconstruct / _fill_holes / _detach) ----
+    def _mask_call(self, masks, shape, out_ptr, call):
+        """Runs call(device pointers of `masks` (None stays None), shape, out) and returns the result mask as a bool array [nz][ny][nx].
+        masks: bool arrays [nz][ny][nx] (uploaded) or device pointers with shape=(nz, ny, nx); out_ptr: a device buffer of
+        region_mask_words(shape) uint32 that receives the bit mask (else a temporary one is used)."""
+        arrays = [m for m in masks if isinstance(m, np.ndarray)]
+        if arrays:
+            shape = arrays[0].shape
+        if shape is None:
+            raise ValueError("device masks need shape=(nz, ny, nx)")
+        shape = tuple(int(n) for n in shape)
+        if len(shape) != 3:
+            raise ValueError("a mask must be [nz][ny][nx]")
+        bufs = [None if m is None else self._region_mask(m, shape) for m in masks]
+        words = region_mask_words(shape)
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(words, 1))
+        try:
+            extra = call([None if b is None else C.c_void_p(b[0]) for b in bufs], shape, C.c_void_p(out))
+            mask = region_mask_unpack(self.to_host(out, (words,), np.uint32), shape)
+        finally:
+            for b in bufs:
+                if b is not None and b[1]:
+                    self.free(b[0])
+            if out_ptr is None:
+                self.free(out)
+        return mask if extra is None else (mask, extra)
+
+    def region_morph(self, mask, op: int, element: int = 6, radius: int = 1, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_morph: MORPH_DILATE / _ERODE / _OPEN / _CLOSE of a mask by the unit element 6 / 18 / 26 applied `radius` times."""
+        def call(p, s, out):
+            self.check(self.lib.svr_region_morph(p[0], s[2], s[1], s[0], int(op), int(element), int(radius), out))
+        return self._mask_call([mask], shape, out_ptr, call)
+
+    def region_combine(self, a, b, op: int, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_combine: MASK_AND / _OR / _ANDNOT (a & ~b) / _XOR of two masks, or MASK_NOT of a (b = None).  out_ptr may be a or b."""
+        def call(p, s, out):
+            self.check(self.lib.svr_region_combine(p[0], p[1], s[2], s[1], s[0], int(op), out))
+        return self._mask_call([a, b], shape, out_ptr, call)
+
+    def region_reconstruct(self, marker, cand, connectivity: int = 6, max_sweeps: int = 0, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_reconstruct: the components of `cand` that hold a voxel of marker & cand.  Returns (mask, sweeps)."""
+        def call(p, s, out):
+            sweeps = C.c_uint32(0)
+            self.check(self.lib.svr_region_reconstruct(p[0], p[1], s[2], s[1], s[0], int(connectivity), int(max_sweeps), out, C.byref(sweeps)))
+            return int(sweeps.value)
+        return self._mask_call([marker, cand], shape, out_ptr, call)
+
+    def region_fill_holes(self, mask, background_connectivity: int = 6, max_sweeps: int = 0, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_fill_holes: the mask and every background voxel that cannot reach a face of the volume."""
+        def call(p, s, out):
+            self.check(self.lib.svr_region_fill_holes(p[0], s[2], s[1], s[0], int(background_connectivity), int(max_sweeps), out))
+        return self._mask_call([mask], shape, out_ptr, call)
+
+    def region_detach(self, mask, seeds, element: int = 6, radius: int = 1, connectivity: int = 6, max_sweeps: int = 0, shape=None,
+                      out_ptr: Optional[int] = None):
+        """svr_region_detach: the part of a grown region around the seed voxels (x, y, z) that survives an opening by `element` applied
+        `radius` times -- what hangs on it by thinner connections is cut off.  Returns (mask, status): REGION_STATUS_OK or _EMPTY."""
+        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+
+        def call(p, s, out):
+            status = C.c_int32(0)
+            self.check(self.lib.svr_region_detach(p[0], s[2], s[1], s[0], xyz.ctypes.data_as(C.POINTER(C.c_int32)), len(xyz), int(element),
+                                                  int(radius), int(connectivity), int(max_sweeps), out, C.byref(status)))
+            return int(status.value)
+        return self._mask_call([mask], shape, out_ptr, call)
+
     def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
         """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
         m = abi.RegionMeasurement()
