@@ -17,8 +17,13 @@
 // region up, in command-line order (Canvas::DetachRegion, FillRegionHoles, MorphRegion; R = 1 .. 32 applications of the unit element
 // -element 6|18|26, default 6): -detach cuts off what hangs on the picked structure by connections thinner than the element,
 // -fillholes adds what the region encloses.  The measurements are printed once more after the last step, and that region is shown.
+// -threshold LO HI is the alternative to -grow: the region is every voxel with raw value LO .. HI, with no pick (Canvas::ThresholdRegion);
+// the line it prints gives the number of connected parts (-conn) next to the measurements.  -largest K keeps the K largest parts and
+// -minsize N those of at least N voxels (Canvas::KeepLargestRegion, RemoveSmallRegions; connectivity -conn): clean-up steps taken in
+// command-line order with the others, each printing the parts it found and kept and the measurements of what is left.  -detach starts
+// from the picked voxel and is therefore not available after -threshold.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,7 +36,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -45,8 +50,9 @@ int main(int argc, char** argv)
     svr_hit_params hitParams = {SVR_HIT_OPACITY, 0.5f, 0.5f};
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
-    struct CleanStep { const char* name; int op; uint32_t radius; };       // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach
-    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode, in order
+    bool threshold = false;                                         // -threshold: the whole window growLo .. growHi, no pick
+    struct CleanStep { const char* name; int op; uint32_t radius; };       // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N)
+    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize, in order
     int cleanElement = 6;
     for (int i = 2; i < argc; ++i) {
         int cleanOp = -2;
@@ -64,6 +70,28 @@ int main(int argc, char** argv)
             }
             cleanSteps.push_back(CleanStep{argv[i], cleanOp, (uint32_t)r});
             ++i;
+        }
+        else if (!strcmp(argv[i], "-largest") || !strcmp(argv[i], "-minsize")) {
+            const bool largest = argv[i][1] == 'l';
+            char* end = nullptr;
+            const long long v = i + 1 < argc ? strtoll(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || v < 1 || v > 0x7fffffffLL) {
+                fprintf(stderr, "%s needs a %s >= 1 (got %s)\n", argv[i], largest ? "number of parts K" : "voxel count N", i + 1 < argc ? argv[i + 1] : "nothing");
+                return 2;
+            }
+            cleanSteps.push_back(CleanStep{argv[i], largest ? -3 : -4, (uint32_t)v});
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-threshold")) {
+            char *e0 = nullptr, *e1 = nullptr;
+            const long lo = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : 0, hi = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : 0;
+            if (i + 2 >= argc || e0 == argv[i + 1] || *e0 != '\0' || e1 == argv[i + 2] || *e1 != '\0' || lo < 0 || hi > 65535 || lo > hi) {
+                fprintf(stderr, "-threshold needs a raw window 0 <= LO <= HI <= 65535 (got %s %s)\n", i + 1 < argc ? argv[i + 1] : "nothing", i + 2 < argc ? argv[i + 2] : "nothing");
+                return 2;
+            }
+            growLo = (int)lo; growHi = (int)hi;
+            threshold = true;
+            i += 2;
         }
         else if (!strcmp(argv[i], "-fillholes")) cleanSteps.push_back(CleanStep{argv[i], 0, 0u});
         else if (!strcmp(argv[i], "-element") && i + 1 < argc) {
@@ -139,7 +167,15 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if ((slabMode || stack) && sliceAxis < 0) { fprintf(stderr, "-slab and -stack need -slice\n"); return 2; }
-    if (!cleanSteps.empty() && !grow) { fprintf(stderr, "%s needs -grow X Y LO HI\n", cleanSteps[0].name); return 2; }
+    if (grow && threshold) { fprintf(stderr, "-grow and -threshold exclude each other\n"); return 2; }
+    if (!cleanSteps.empty() && !grow && !threshold) {
+        if (cleanSteps[0].op <= -3) fprintf(stderr, "%s needs -grow X Y LO HI or -threshold LO HI\n", cleanSteps[0].name);
+        else fprintf(stderr, "%s needs -grow X Y LO HI\n", cleanSteps[0].name);
+        return 2;
+    }
+    if (threshold)
+        for (const CleanStep& c : cleanSteps)
+            if (c.op == -1) { fprintf(stderr, "-detach starts from the picked voxel: it needs -grow X Y LO HI, not -threshold\n"); return 2; }
     if (svr_init(0)) return 1;
     {
         Canvas canvas(W, H);
@@ -161,7 +197,7 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
-        canvas.volumeReader->KeepVoxels(grow);                         // the region calls work on the plain voxels
+        canvas.volumeReader->KeepVoxels(grow || threshold);                         // the region calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%s: %d x %d x %d, range %.0f..%.0f, max gradient magnitude %.0f, %zu histogram bins\n", volume.c_str(),
@@ -207,17 +243,27 @@ int main(int argc, char** argv)
             return 0;
         }
 
-        if (grow) {
+        if (grow || threshold) {
             // pick, segment, measure; what follows renders the kept (or the remaining) volume
-            svr_hit hit;
-            if (canvas.Pick((uint32_t)growX, (uint32_t)growY, &hit, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-            if (hit.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-grow: %s at pixel %d %d\n", hit.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", growX, growY); return 1; }
+            svr_hit hit = svr_hit();
+            if (grow && canvas.Pick((uint32_t)growX, (uint32_t)growY, &hit, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            if (grow && hit.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-grow: %s at pixel %d %d\n", hit.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", growX, growY); return 1; }
             svr_region_stats st;
-            if (canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            if ((grow ? canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) : canvas.ThresholdRegion((uint32_t)growLo, (uint32_t)growHi, &st)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
             const double sp[3] = {canvas.Volume().spacing.x, canvas.Volume().spacing.y, canvas.Volume().spacing.z};
             svr_region_measurement m;
             if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-            if (st.status == SVR_REGION_STATUS_EMPTY)
+            if (threshold) {
+                uint32_t parts = 0u;
+                if (canvas.CountRegionParts(growConn, &parts) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (st.status == SVR_REGION_STATUS_EMPTY)
+                    printf("threshold window %d..%d: no voxel lies in the window; the region is empty\n", growLo, growHi);
+                else
+                    printf("threshold window %d..%d conn %d: %u parts, %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
+                           growLo, growHi, growConn, parts, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                           st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+            }
+            else if (st.status == SVR_REGION_STATUS_EMPTY)
                 printf("grow %d %d window %d..%d: the picked voxel (value %g) is outside the window; the region is empty\n", growX, growY, growLo, growHi, hit.value);
             else
                 printf("grow %d %d window %d..%d conn %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %u sweeps\n",
@@ -225,7 +271,25 @@ int main(int argc, char** argv)
                        st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
             if (!cleanSteps.empty()) {
                 std::string done;
+                bool plainSteps = false;                           // a step other than -largest / -minsize: those print their own lines
                 for (const CleanStep& c : cleanSteps) {
+                    if (c.op <= -3) {
+                        uint32_t before = 0u, after = 0u;
+                        int rc = canvas.CountRegionParts(growConn, &before);
+                        if (rc == 0) rc = c.op == -3 ? canvas.KeepLargestRegion((int)c.radius, growConn, &st) : canvas.RemoveSmallRegions(c.radius, growConn, &st);
+                        if (rc == 0) rc = canvas.CountRegionParts(growConn, &after);
+                        if (rc == 0) rc = svr_region_measure(&st, sp, &m);
+                        if (rc != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                        if (st.status == SVR_REGION_STATUS_EMPTY)
+                            printf("%s %u conn %d: %u of %u parts kept; the region is empty\n", c.name + 1, c.radius, growConn, after, before);
+                        else
+                            printf("%s %u conn %d: %u of %u parts kept, %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
+                                   c.name + 1, c.radius, growConn, after, before, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0],
+                                   st.bbox_min[1], st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+                        done += std::string(done.empty() ? "" : " ") + (c.name + 1) + " " + std::to_string(c.radius);
+                        continue;
+                    }
+                    plainSteps = true;
                     const int rc = c.op == -1 ? canvas.DetachRegion(cleanElement, c.radius, &st)
                                  : c.op == 0 ? canvas.FillRegionHoles(6, &st)
                                              : canvas.MorphRegion(c.op, cleanElement, c.radius, &st);
@@ -234,7 +298,9 @@ int main(int argc, char** argv)
                     if (c.op != 0) done += " " + std::to_string(c.radius);
                 }
                 if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-                if (st.status == SVR_REGION_STATUS_EMPTY)
+                if (!plainSteps)
+                    ;                                              // (-largest / -minsize alone: their own lines say it all)
+                else if (st.status == SVR_REGION_STATUS_EMPTY)
                     printf("cleaned (%s, element %d): the region is empty\n", done.c_str(), cleanElement);
                 else
                     printf("cleaned (%s, element %d): %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",

@@ -457,6 +457,7 @@ public:
         haveRegion = rc == 0;
         for (int a = 0; a < 3; ++a) regionSeed[a] = seed[a];     // DetachRegion starts from the same voxel, with the same connectivity
         regionConnectivity = connectivity;
+        haveSeed = haveRegion;
         if (stats) *stats = st;
         return rc;
     }
@@ -481,11 +482,51 @@ public:
     // times) are cut; a seed outside the region's opening leaves an empty region (stats->status == SVR_REGION_STATUS_EMPTY), return 0
     int DetachRegion(int element, uint32_t radius, svr_region_stats* stats = nullptr)
     {
-        if (!WorkMask()) return -4;
+        if (!WorkMask() || !haveSeed) return -4;
         const int* dim = volumeReader->dim;
         int32_t status = SVR_REGION_STATUS_OK;
         return ReplaceRegion(svr_region_detach(regionMask, dim[0], dim[1], dim[2], regionSeed, 1u, element, radius, regionConnectivity, 0u, regionWork, &status),
                              stats);
+    }
+    // The components of the region (svr_region_threshold / _label / _label_table / _select_by_size; include/svr_abi.h, "connected
+    // components of region masks").
+    // ThresholdRegion: the current region becomes every voxel with lo <= raw value <= hi -- the whole window, with no pick.  There is no
+    // seed voxel then, so DetachRegion is refused (-4) until the next GrowRegion
+    int ThresholdRegion(uint32_t lo, uint32_t hi, svr_region_stats* stats = nullptr)
+    {
+        const uint16_t* vox = volumeReader->DeviceVoxels();
+        if (!ready || !vox) return -4;
+        const int* dim = volumeReader->dim;
+        if (!regionMask) regionMask = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
+        if (!regionMask) return -4;
+        const int rc = svr_region_threshold(vox, dim[0], dim[1], dim[2], 1, lo, hi, nullptr, nullptr, regionMask);
+        haveRegion = rc == 0;
+        haveSeed = false;
+        if (rc != 0 || !stats) return rc;
+        return svr_region_stats_of(vox, dim[0], dim[1], dim[2], 1, regionMask, stats);
+    }
+    // KeepLargestRegion: the k largest connected components (connectivity 6, 18 or 26) of the region, ties in size to the one that
+    // starts first; RemoveSmallRegions: the components of at least min_voxels voxels.  An empty result is not an error
+    // (stats->status == SVR_REGION_STATUS_EMPTY)
+    int KeepLargestRegion(int k, int connectivity, svr_region_stats* stats = nullptr)
+    {
+        if (k < 1) return -3;
+        return SelectRegionParts(0u, (uint32_t)k, connectivity, stats);
+    }
+    int RemoveSmallRegions(uint32_t min_voxels, int connectivity, svr_region_stats* stats = nullptr)
+    {
+        return SelectRegionParts(min_voxels, 0u, connectivity, stats);
+    }
+    // CountRegionParts: *count = the number of connected components of the region; the region stays as it is
+    int CountRegionParts(int connectivity, uint32_t* count)
+    {
+        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion || !count) return -4;
+        const int* dim = volumeReader->dim;
+        uint32_t* labels = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
+        if (!labels) return -4;
+        const int rc = svr_region_label(regionMask, dim[0], dim[1], dim[2], connectivity, labels, count);
+        svr_device_free(labels);
+        return rc;
     }
     // ShowRegion: every renderer now draws the volume with the voxels outside (SVR_REGION_KEEP) or inside (SVR_REGION_REMOVE) the grown
     // region set to `fill`; ShowAll goes back to the loaded volume.  The Canvas owns the extra texture
@@ -562,7 +603,7 @@ private:
         if (regionTex) svr_destroy_texture(regionTex);
         if (regionMask) svr_device_free(regionMask);
         if (regionWork) svr_device_free(regionWork);
-        regionTex = 0; regionMask = nullptr; regionWork = nullptr; haveRegion = false;
+        regionTex = 0; regionMask = nullptr; regionWork = nullptr; haveRegion = false; haveSeed = false;
     }
     // the second mask buffer, into which the clean-up calls write (their `out` must not overlap their input)
     bool WorkMask()
@@ -580,6 +621,27 @@ private:
         if (!stats) return 0;
         const int* dim = volumeReader->dim;
         return svr_region_stats_of(volumeReader->DeviceVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats);
+    }
+    // label the region, tabulate its components, keep those of at least min_voxels voxels among the largest_k largest (0 = no limit)
+    int SelectRegionParts(uint32_t min_voxels, uint32_t largest_k, int connectivity, svr_region_stats* stats)
+    {
+        if (!WorkMask()) return -4;
+        const int* dim = volumeReader->dim;
+        uint32_t* labels = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
+        if (!labels) return -4;
+        uint32_t count = 0u, kept = 0u;
+        int rc = svr_region_label(regionMask, dim[0], dim[1], dim[2], connectivity, labels, &count);
+        if (rc == 0 && count == 0u) {                                           // an empty region has no component: it stays empty
+            svr_device_free(labels);
+            return stats ? svr_region_stats_of(volumeReader->DeviceVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats) : 0;
+        }
+        svr_region_component* table = rc == 0 ? (svr_region_component*)svr_device_malloc((size_t)count * sizeof(svr_region_component)) : nullptr;
+        if (rc == 0 && !table) rc = -4;
+        if (rc == 0) rc = svr_region_label_table(labels, nullptr, dim[0], dim[1], dim[2], 1, count, table);
+        if (rc == 0) rc = svr_region_select_by_size(labels, dim[0], dim[1], dim[2], count, table, min_voxels, largest_k, regionWork, &kept);
+        if (table) svr_device_free(table);                                      // (select_by_size synchronised the stream)
+        svr_device_free(labels);
+        return ReplaceRegion(rc, stats);
     }
     void UpdateCamera()                                                         // canvas.cpp:178-188
     {
@@ -603,6 +665,7 @@ private:
     uint32_t* regionWork = nullptr;                // the other mask buffer of the clean-up calls
     int32_t regionSeed[3] = {0, 0, 0};             // GrowRegion's seed voxel and connectivity, for DetachRegion
     int regionConnectivity = 6;
+    bool haveSeed = false;                         // false after ThresholdRegion: the region then comes from no pick
     cudaTextureObject_t regionTex = 0;             // ShowRegion's masked volume
     bool haveRegion = false;
     svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};

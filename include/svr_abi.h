@@ -776,6 +776,53 @@ int svr_region_detach(const uint32_t* in_device, int nx, int ny, int nz, const i
 /* HIP-event time of the device work of the last of the five calls above (waits for it) */
 int svr_region_mask_last_ms(float* ms);
 
+/* ---- connected components of region masks: label, measure per component, keep the largest, drop the small (csrc/svr_label.hip;
+ *      DESIGN.md 8j) ----
+ * Masks are DEVICE pointers in the layout above; the calls are stateless: they run on the library's stream and touch no scene, option
+ * or accumulator; results are exact (integers) and unique, whatever order the GPU works in.  Input padding bits are ignored, output
+ * padding bits are 0.
+ * THRESHOLD: out = the candidate mask of svr_region_grow without any seed, {voxel in the box : lo <= v <= hi}.  box_min / box_max are
+ *   HOST arrays of 3 int32 (x, y, z), inclusive, intersected with the volume; both NULL = the whole volume.  The volume is a u16 array
+ *   [nz][ny][nx], host or device (src_is_device), as in svr_region_grow.  Asynchronous for a device source.
+ * LABEL: labels_device is a dense uint32 array [nz][ny][nx] (4 nx ny nz bytes).  0 = background; the connected components of the mask
+ *   under connectivity 6 / 18 / 26 are numbered 1 .. K in ascending order of their smallest linear voxel index (z ny + y) nx + x, which
+ *   makes the array unique (it is scipy.ndimage.label's numbering with generate_binary_structure(3, 1 | 2 | 3)).  *count_out = K.  An
+ *   empty mask gives K = 0, all labels 0 and return 0.  The call allocates and frees its temporaries (about 1 / 32 of the label array)
+ *   and synchronises the stream.  The work is union-find with walks that only ever move to smaller indices; every walk also counts its
+ *   steps against the voxel count, and a walk that reached that cap -- which no valid state can -- makes the call return
+ *   SVR_REGION_ERR_LABEL with the labels invalid; it does not go on.
+ * TABLE (svr_region_component[count], indexed by label - 1): voxels = the component's size; first = its smallest linear voxel index;
+ *   bbox_min, bbox_max = its inclusive bounds in x, y, z; sum = the sum of the raw values over it (0 when voxels_or_null is NULL).
+ *   Labels above `count` are ignored.  Asynchronous for a device source or none.
+ * SELECT: out = the voxels whose label has a non-zero entry in keep_device (uint8 [count + 1], indexed by label; entry 0 is ignored:
+ *   background never enters; labels above count are dropped).  Asynchronous.
+ * SELECT BY SIZE: keeps the components with at least min_voxels voxels that are among the largest_k largest (0 = no limit); ties in size
+ *   go to the lower label.  The sizes are read back and ranked in host code, so the call synchronises.  *kept_out = the components
+ *   kept; 0 of them is an empty mask and return 0.
+ * K = 0: a caller whose mask has no component has nothing to tabulate or select; count == 0 is refused.
+ * REFUSED, before the device is touched: a null pointer (-4); a dimension <= 0 or more than 2^31 voxels (-6); lo > hi or hi > 65535, a box
+ *   with one pointer NULL, with box_min > box_max on an axis or with no voxel of the volume in it, a connectivity other than 6 / 18 / 26,
+ *   count == 0 (-3). */
+#define SVR_REGION_ERR_LABEL (-10)   /* a union-find walk reached its iteration cap: the labels are not valid */
+
+typedef struct svr_region_component {   /* 40 bytes */
+    uint32_t voxels;
+    uint32_t first;
+    int32_t  bbox_min[3], bbox_max[3];
+    uint64_t sum;
+} svr_region_component;
+
+int svr_region_threshold(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, uint32_t lo, uint32_t hi, const int32_t* box_min,
+                         const int32_t* box_max, uint32_t* out_mask_device);
+int svr_region_label(const uint32_t* in_mask_device, int nx, int ny, int nz, int connectivity, uint32_t* labels_device, uint32_t* count_out);
+int svr_region_label_table(const uint32_t* labels_device, const uint16_t* voxels_or_null, int nx, int ny, int nz, int src_is_device, uint32_t count,
+                           svr_region_component* table_device);
+int svr_region_select(const uint32_t* labels_device, int nx, int ny, int nz, uint32_t count, const uint8_t* keep_device, uint32_t* out_mask_device);
+int svr_region_select_by_size(const uint32_t* labels_device, int nx, int ny, int nz, uint32_t count, const svr_region_component* table_device,
+                              uint32_t min_voxels, uint32_t largest_k, uint32_t* out_mask_device, uint32_t* kept_out);
+/* HIP-event time of the device work of the last of the five calls above (waits for it) */
+int svr_region_label_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

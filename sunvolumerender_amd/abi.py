@@ -274,7 +274,17 @@ class RegionMeasurement(C.Structure):  # svr_region_measurement
         return {n: (list(getattr(self, n)) if n == "centroid" else getattr(self, n)) for n, _ in self._fields_}
 
 
+class RegionComponent(C.Structure):  # svr_region_component
+    _fields_ = [("voxels", C.c_uint32), ("first", C.c_uint32), ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("sum", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n.startswith("bbox") else int(getattr(self, n))) for n, _ in self._fields_}
+
+
 svr_region_params, svr_region_stats, svr_region_measurement = RegionParams, RegionStats, RegionMeasurement
+svr_region_component = RegionComponent
+REGION_ERR_LABEL = -10
+LABEL_SCAN_BLOCK = 256      # SVR_LABEL_SCAN_BLOCK of csrc/svr_label.hip: the words one block of a level of the renumbering scan covers
 REGION_MAX_SEEDS = 64
 REGION_KEEP, REGION_REMOVE = 1, 2
 REGION_STATUS_OK, REGION_STATUS_EMPTY = 0, 1
@@ -305,6 +315,7 @@ EXPECTED_SIZES = {
     RegionParams: 40,
     RegionStats: 112,
     RegionMeasurement: 56,
+    RegionComponent: 40,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -451,6 +462,14 @@ PROTOTYPES = {
     "svr_region_detach": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_int32), C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32,
                                     C.c_void_p, _P(C.c_int32)]),
     "svr_region_mask_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_region_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(C.c_int32), _P(C.c_int32),
+                                       C.c_void_p]),
+    "svr_region_label": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _P(C.c_uint32)]),
+    "svr_region_label_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "svr_region_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "svr_region_select_by_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                            _P(C.c_uint32)]),
+    "svr_region_label_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

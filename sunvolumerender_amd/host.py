@@ -429,12 +429,151 @@ class Device:
             return int(status.value)
         return self._mask_call([mask], shape, out_ptr, call)
 
+    # ---- connected components of region masks (svr_region_threshold / _label / _label_table / _select / _select_by_size) ----
+    def region_threshold(self, vox, lo: int, hi: int, box=None, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_threshold: the mask {voxel in `box` : lo <= v <= hi} of a host [nz][ny][nx] u16 array or a device pointer with
+        shape=(nz, ny, nx); box = ((x0, y0, z0), (x1, y1, z1)), inclusive, or None for the whole volume.  Returns the bool array."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        b0 = b1 = None
+        if box is not None:
+            b0, b1 = (C.c_int32 * 3)(*[int(t) for t in box[0]]), (C.c_int32 * 3)(*[int(t) for t in box[1]])
+
+        def call(p, s, out):
+            self.check(self.lib.svr_region_threshold(src, nx, ny, nz, on_dev, int(lo), int(hi), b0, b1, out))
+        return self._mask_call([], (nz, ny, nx), out_ptr, call)
+
+    def _region_labels(self, labels, shape):
+        """(device pointer, (nz, ny, nx), owned) of a uint32 label array [nz][ny][nx] (uploaded) or of a device pointer with `shape`."""
+        if isinstance(labels, np.ndarray):
+            a = np.ascontiguousarray(labels, dtype=np.uint32)
+            if a.ndim != 3:
+                raise ValueError("the labels must be [nz][ny][nx]")
+            buf = self.malloc(max(a.nbytes, 4))
+            self.to_device(buf, a)
+            return buf, a.shape, True
+        if shape is None:
+            raise ValueError("device labels need shape=(nz, ny, nx)")
+        return int(labels), tuple(int(n) for n in shape), False
+
+    def region_label(self, mask, connectivity: int = 6, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_label: the connected components of a mask (a bool array [nz][ny][nx], or a device pointer with shape=) under
+        connectivity 6 / 18 / 26, numbered 1 .. K by their first voxel.  Returns (labels, K): a uint32 array [nz][ny][nx], or out_ptr
+        itself when a device buffer of 4 nx ny nz bytes is given."""
+        if isinstance(mask, np.ndarray):
+            shape = mask.shape
+        if shape is None:
+            raise ValueError("a device mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = (int(n) for n in shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
+        k = C.c_uint32(0)
+        try:
+            self.check(self.lib.svr_region_label(C.c_void_p(buf), nx, ny, nz, int(connectivity), C.c_void_p(out), C.byref(k)))
+            if out_ptr is not None:
+                return out_ptr, int(k.value)
+            return self.to_host(out, (nz, ny, nx), np.uint32), int(k.value)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_label_table(self, labels, count: int, vox=None, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_label_table: the svr_region_component of the labels 1 .. count as a numpy structured array (COMPONENT_DTYPE),
+        indexed by label - 1.  labels: a uint32 array [nz][ny][nx] or a device pointer with shape=; vox (optional, for `sum`): a host
+        u16 array or a device pointer of the same shape.  out_ptr: a device buffer of 40 * count bytes that receives the table."""
+        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, shape)
+        src, on_dev = None, 0
+        if vox is not None:
+            src, vshape, on_dev, _keep = self._region_source(vox, (nz, ny, nx))
+            if tuple(vshape) != (nz, ny, nx):
+                raise ValueError("the volume and the labels differ in shape")
+        out = out_ptr if out_ptr is not None else self.malloc(40 * max(int(count), 1))
+        try:
+            self.check(self.lib.svr_region_label_table(C.c_void_p(lbuf), src, nx, ny, nz, on_dev, int(count), C.c_void_p(out)))
+            self.synchronize()
+            return self.to_host(out, (int(count),), COMPONENT_DTYPE)
+        finally:
+            if lowned:
+                self.free(lbuf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_select(self, labels, count: int, keep, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_select: the mask of the voxels whose label has a non-zero entry in keep (count + 1 entries, indexed by label; entry
+        0 is ignored)."""
+        lbuf, lshape, lowned = self._region_labels(labels, shape)
+        k = np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1)
+        if len(k) != int(count) + 1:
+            raise ValueError("keep must have count + 1 entries")
+        kbuf = self.malloc(len(k))
+        self.to_device(kbuf, k)
+
+        def call(p, s, out):
+            self.check(self.lib.svr_region_select(C.c_void_p(lbuf), s[2], s[1], s[0], int(count), C.c_void_p(kbuf), out))
+        try:
+            return self._mask_call([], lshape, out_ptr, call)
+        finally:
+            self.free(kbuf)
+            if lowned:
+                self.free(lbuf)
+
+    def region_select_by_size(self, labels, count: int, table=None, min_voxels: int = 0, largest_k: int = 0, shape=None,
+                              out_ptr: Optional[int] = None):
+        """svr_region_select_by_size: the components with at least min_voxels voxels among the largest_k largest (0 = no limit; ties go
+        to the lower label).  table: the structured array of region_label_table, a device pointer to it, or None (it is computed).
+        Returns (mask, kept)."""
+        lbuf, lshape, lowned = self._region_labels(labels, shape)
+        tbuf, towned = None, True
+        try:
+            if table is None:
+                tbuf = self.malloc(40 * max(int(count), 1))
+                self.region_label_table(lbuf, count, shape=lshape, out_ptr=tbuf)
+            elif isinstance(table, np.ndarray):
+                t = np.ascontiguousarray(table, dtype=COMPONENT_DTYPE)
+                tbuf = self.malloc(max(t.nbytes, 40))
+                self.to_device(tbuf, t)
+            else:
+                tbuf, towned = int(table), False
+
+            def call(p, s, out):
+                kept = C.c_uint32(0)
+                self.check(self.lib.svr_region_select_by_size(C.c_void_p(lbuf), s[2], s[1], s[0], int(count), C.c_void_p(tbuf), int(min_voxels),
+                                                              int(largest_k), out, C.byref(kept)))
+                return int(kept.value)
+            return self._mask_call([], lshape, out_ptr, call)
+        finally:
+            if towned and tbuf is not None:
+                self.free(tbuf)
+            if lowned:
+                self.free(lbuf)
+
+    def region_label_last_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_region_label_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
         """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
         m = abi.RegionMeasurement()
         sp = (C.c_double * 3)(*[float(t) for t in spacing])
         self.check(self.lib.svr_region_measure(C.byref(stats), sp, C.byref(m)))
         return m
+
+
+# svr_region_component as a numpy record (40 bytes); LABEL_SCAN_BLOCK mirrors SVR_LABEL_SCAN_BLOCK of csrc/svr_label.hip
+COMPONENT_DTYPE = np.dtype([("voxels", "<u4"), ("first", "<u4"), ("bbox_min", "<i4", (3,)), ("bbox_max", "<i4", (3,)), ("sum", "<u8")])
+assert COMPONENT_DTYPE.itemsize == 40
+LABEL_SCAN_BLOCK = abi.LABEL_SCAN_BLOCK
+
+
+def region_label_scan_levels(shape) -> int:
+    """The levels of svr_region_label's renumbering scan for a [nz][ny][nx] volume: 1 while one block covers the mask words, 2 up to
+    a block of blocks, and so on."""
+    n, levels = region_mask_words(shape), 1
+    while n > LABEL_SCAN_BLOCK:
+        n, levels = (n + LABEL_SCAN_BLOCK - 1) // LABEL_SCAN_BLOCK, levels + 1
+    return levels
 
 
 def region_mask_words(shape) -> int:
