@@ -22,8 +22,11 @@
 // -minsize N those of at least N voxels (Canvas::KeepLargestRegion, RemoveSmallRegions; connectivity -conn): clean-up steps taken in
 // command-line order with the others, each printing the parts it found and kept and the measurements of what is left.  -detach starts
 // from the picked voxel and is therefore not available after -threshold.
+// -ball-dilate L, -ball-erode L, -ball-open L and -ball-close L are clean-up steps too, by a true ball of radius L > 0 in the units of the
+// volume's spacing (Canvas::BallMorphRegion: the exact Euclidean distance map, any radius at the same cost); each prints the measurements
+// of what is left.  -thickness prints, after the last step, the largest ball inscribed in the region and its centre voxel.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,7 +39,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N]... [-element 6|18|26] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -51,9 +54,10 @@ int main(int argc, char** argv)
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
     bool threshold = false;                                         // -threshold: the whole window growLo .. growHi, no pick
-    struct CleanStep { const char* name; int op; uint32_t radius; };       // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N)
-    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize, in order
+    struct CleanStep { const char* name; int op; uint32_t radius; double length; };   // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N), -10 - SVR_MORPH_* = -ball-* (length: L)
+    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize / -ball-*, in order
     int cleanElement = 6;
+    bool thickness = false;                                         // -thickness: the largest inscribed ball of the final region
     for (int i = 2; i < argc; ++i) {
         int cleanOp = -2;
         if (!strcmp(argv[i], "-detach")) cleanOp = -1;
@@ -68,7 +72,7 @@ int main(int argc, char** argv)
                 fprintf(stderr, "%s needs a radius R in 1 .. %d (got %s)\n", argv[i], SVR_MORPH_MAX_RADIUS, i + 1 < argc ? argv[i + 1] : "nothing");
                 return 2;
             }
-            cleanSteps.push_back(CleanStep{argv[i], cleanOp, (uint32_t)r});
+            cleanSteps.push_back(CleanStep{argv[i], cleanOp, (uint32_t)r, 0.0});
             ++i;
         }
         else if (!strcmp(argv[i], "-largest") || !strcmp(argv[i], "-minsize")) {
@@ -79,9 +83,24 @@ int main(int argc, char** argv)
                 fprintf(stderr, "%s needs a %s >= 1 (got %s)\n", argv[i], largest ? "number of parts K" : "voxel count N", i + 1 < argc ? argv[i + 1] : "nothing");
                 return 2;
             }
-            cleanSteps.push_back(CleanStep{argv[i], largest ? -3 : -4, (uint32_t)v});
+            cleanSteps.push_back(CleanStep{argv[i], largest ? -3 : -4, (uint32_t)v, 0.0});
             ++i;
         }
+        else if (!strncmp(argv[i], "-ball-", 6)) {
+            const char* what = argv[i] + 6;
+            const int op = !strcmp(what, "dilate") ? SVR_MORPH_DILATE : !strcmp(what, "erode") ? SVR_MORPH_ERODE : !strcmp(what, "open") ? SVR_MORPH_OPEN
+                         : !strcmp(what, "close") ? SVR_MORPH_CLOSE : 0;
+            if (!op) { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+            char* end = nullptr;
+            const double len = i + 1 < argc ? strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(len > 0.0) || !std::isfinite(len)) {
+                fprintf(stderr, "%s needs a radius L > 0 in the units of the spacing (got %s)\n", argv[i], i + 1 < argc ? argv[i + 1] : "nothing");
+                return 2;
+            }
+            cleanSteps.push_back(CleanStep{argv[i], -10 - op, 0u, len});
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-thickness")) thickness = true;
         else if (!strcmp(argv[i], "-threshold")) {
             char *e0 = nullptr, *e1 = nullptr;
             const long lo = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : 0, hi = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : 0;
@@ -93,7 +112,7 @@ int main(int argc, char** argv)
             threshold = true;
             i += 2;
         }
-        else if (!strcmp(argv[i], "-fillholes")) cleanSteps.push_back(CleanStep{argv[i], 0, 0u});
+        else if (!strcmp(argv[i], "-fillholes")) cleanSteps.push_back(CleanStep{argv[i], 0, 0u, 0.0});
         else if (!strcmp(argv[i], "-element") && i + 1 < argc) {
             cleanElement = atoi(argv[++i]);
             if (cleanElement != 6 && cleanElement != 18 && cleanElement != 26) { fprintf(stderr, "-element needs 6, 18 or 26 (got %s)\n", argv[i]); return 2; }
@@ -173,6 +192,7 @@ int main(int argc, char** argv)
         else fprintf(stderr, "%s needs -grow X Y LO HI\n", cleanSteps[0].name);
         return 2;
     }
+    if (thickness && !grow && !threshold) { fprintf(stderr, "-thickness needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (threshold)
         for (const CleanStep& c : cleanSteps)
             if (c.op == -1) { fprintf(stderr, "-detach starts from the picked voxel: it needs -grow X Y LO HI, not -threshold\n"); return 2; }
@@ -273,6 +293,24 @@ int main(int argc, char** argv)
                 std::string done;
                 bool plainSteps = false;                           // a step other than -largest / -minsize: those print their own lines
                 for (const CleanStep& c : cleanSteps) {
+                    if (c.op <= -10) {
+                        uint32_t w[3] = {0u, 0u, 0u};
+                        double unit = 0.0;
+                        int rc = canvas.RegionDistanceUnits(w, &unit);
+                        if (rc == 0) rc = canvas.BallMorphRegion(-10 - c.op, c.length, &st);
+                        if (rc == 0) rc = svr_region_measure(&st, sp, &m);
+                        if (rc != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                        if (st.status == SVR_REGION_STATUS_EMPTY)
+                            printf("%s %g (unit %g, weights %u %u %u): the region is empty\n", c.name + 1, c.length, unit, w[0], w[1], w[2]);
+                        else
+                            printf("%s %g (unit %g, weights %u %u %u): %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
+                                   c.name + 1, c.length, unit, w[0], w[1], w[2], (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0],
+                                   st.bbox_min[1], st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+                        char len[32];
+                        snprintf(len, sizeof len, "%g", c.length);
+                        done += std::string(done.empty() ? "" : " ") + (c.name + 1) + " " + len;
+                        continue;
+                    }
                     if (c.op <= -3) {
                         uint32_t before = 0u, after = 0u;
                         int rc = canvas.CountRegionParts(growConn, &before);
@@ -306,6 +344,14 @@ int main(int argc, char** argv)
                     printf("cleaned (%s, element %d): %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
                            done.c_str(), cleanElement, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
                            st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+            }
+            if (thickness) {
+                double radius = 0.0;
+                int32_t at[3] = {-1, -1, -1};
+                const int rc = canvas.RegionThickness(&radius, at);
+                if (rc < 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (rc == SVR_REGION_STATUS_EMPTY) printf("largest inscribed ball: none (the region is empty or fills the volume)\n");
+                else printf("largest inscribed ball: radius %g at voxel %d %d %d\n", radius, at[0], at[1], at[2]);
             }
             if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         }

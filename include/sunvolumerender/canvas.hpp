@@ -14,6 +14,7 @@
 #ifndef SUNVOLUMERENDER_CANVAS_HPP
 #define SUNVOLUMERENDER_CANVAS_HPP
 
+#include <cmath>
 #include <string>
 #include <utility>
 #include <vector>
@@ -488,6 +489,74 @@ public:
         return ReplaceRegion(svr_region_detach(regionMask, dim[0], dim[1], dim[2], regionSeed, 1u, element, radius, regionConnectivity, 0u, regionWork, &status),
                              stats);
     }
+    // Euclidean clean-up and measures of the region (svr_region_ball / _distance / _distance_max / _distance_volume; include/svr_abi.h,
+    // "exact Euclidean distance maps").  Lengths are in the units of the loaded volume's spacing: svr_region_distance_weights turns the
+    // spacing into integer weights and a unit, a length L is r2 = floor((L / unit)^2) and a map value d2 means sqrt(d2) * unit.
+    // RegionDistanceUnits: those weights and that unit
+    int RegionDistanceUnits(uint32_t weights[3], double* unit) const
+    {
+        const int* dim = volumeReader->dim;
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        return svr_region_distance_weights(sp, dim[0], dim[1], dim[2], weights, unit);
+    }
+    // BallMorphRegion: SVR_MORPH_DILATE / _ERODE / _OPEN / _CLOSE by the ball of `radius` (>= 0, finite); replaces the region like MorphRegion
+    int BallMorphRegion(int op, double radius, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask()) return -4;
+        if (!(radius >= 0.0) || !std::isfinite(radius)) return -3;
+        uint32_t w[3];
+        double unit = 0.0;
+        if (int rc = RegionDistanceUnits(w, &unit)) return rc;
+        const int* dim = volumeReader->dim;
+        return ReplaceRegion(svr_region_ball(regionMask, dim[0], dim[1], dim[2], op, w, LengthToR2(radius, unit), regionWork), stats);
+    }
+    // RegionThickness: the largest ball inscribed in the region -- *radius = sqrt(max d2) * unit of the distance to the nearest voxel of the
+    // volume outside the region, ijk = the first voxel (x, y, z) that attains it.  Returns SVR_REGION_STATUS_OK, or SVR_REGION_STATUS_EMPTY
+    // (radius 0, ijk -1) for an empty region and for one that fills the volume; negative on an error.  The region stays as it is
+    int RegionThickness(double* radius, int32_t ijk[3])
+    {
+        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion || !radius || !ijk) return -4;
+        uint32_t w[3];
+        double unit = 0.0;
+        if (int rc = RegionDistanceUnits(w, &unit)) return rc;
+        const int* dim = volumeReader->dim;
+        uint32_t* map = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
+        if (!map) return -4;
+        uint32_t max_d2 = 0u, first = 0u;
+        int32_t status = SVR_REGION_STATUS_EMPTY;
+        int rc = svr_region_distance(regionMask, dim[0], dim[1], dim[2], w, SVR_DIST_TO_UNSET, map);
+        if (rc == 0) rc = svr_region_distance_max(map, regionMask, dim[0], dim[1], dim[2], &max_d2, &first, &status);
+        svr_device_free(map);
+        if (rc != 0) return rc;
+        *radius = 0.0;
+        ijk[0] = ijk[1] = ijk[2] = -1;
+        if (status == SVR_REGION_STATUS_EMPTY) return SVR_REGION_STATUS_EMPTY;
+        *radius = std::sqrt((double)max_d2) * unit;
+        ijk[0] = (int32_t)(first % (uint32_t)dim[0]);
+        ijk[1] = (int32_t)(first / (uint32_t)dim[0] % (uint32_t)dim[1]);
+        ijk[2] = (int32_t)(first / (uint32_t)dim[0] / (uint32_t)dim[1]);
+        return SVR_REGION_STATUS_OK;
+    }
+    // ShowRegionDistance: every renderer now draws the distance map of the region -- to the region (SVR_DIST_TO_SET) or, inside it, to its
+    // outside (SVR_DIST_TO_UNSET) -- as the volume min(65535, floor(sqrt(d2) * scale)), until ShowAll or the next volume
+    int ShowRegionDistance(int target, uint32_t scale)
+    {
+        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion) return -4;
+        uint32_t w[3];
+        double unit = 0.0;
+        if (int rc = RegionDistanceUnits(w, &unit)) return rc;
+        const int* dim = volumeReader->dim;
+        const size_t n = (size_t)dim[0] * dim[1] * dim[2];
+        uint32_t* map = (uint32_t*)svr_device_malloc(n * sizeof(uint32_t));
+        uint16_t* shown = (uint16_t*)svr_device_malloc(n * sizeof(uint16_t));
+        int rc = map && shown ? 0 : -4;
+        if (rc == 0) rc = svr_region_distance(regionMask, dim[0], dim[1], dim[2], w, target, map);
+        if (rc == 0) rc = svr_region_distance_volume(map, dim[0], dim[1], dim[2], scale, shown);
+        if (rc == 0) rc = ShowVoxels(shown);
+        if (map) svr_device_free(map);
+        if (shown) svr_device_free(shown);
+        return rc;
+    }
     // The components of the region (svr_region_threshold / _label / _label_table / _select_by_size; include/svr_abi.h, "connected
     // components of region masks").
     // ThresholdRegion: the current region becomes every voxel with lo <= raw value <= hi -- the whole window, with no pick.  There is no
@@ -538,20 +607,9 @@ public:
         uint16_t* shown = (uint16_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint16_t));
         if (!shown) return -4;
         int rc = svr_region_apply(vox, dim[0], dim[1], dim[2], 1, regionMask, mode, fill, shown);
-        cudaTextureObject_t tex = 0;
-        if (rc == 0) {
-            tex = svr_create_volume_texture(shown, dim[0], dim[1], dim[2], 1, SVR_LAYOUT_AUTO);    // (copies: `shown` is free afterwards)
-            if (!tex) rc = svr_last_error_code() ? svr_last_error_code() : -4;
-        }
+        if (rc == 0) rc = ShowVoxels(shown);
         svr_device_free(shown);
-        if (rc != 0) return rc;
-        svr_device_synchronize();                      // no frame in flight still reads the texture that goes
-        if (regionTex) svr_destroy_texture(regionTex);
-        regionTex = tex;
-        deviceVolume.tex = tex;
-        setup_volume(deviceVolume);
-        ReStartRender();
-        return 0;
+        return rc;
     }
     void ShowAll()
     {
@@ -604,6 +662,26 @@ private:
         if (regionMask) svr_device_free(regionMask);
         if (regionWork) svr_device_free(regionWork);
         regionTex = 0; regionMask = nullptr; regionWork = nullptr; haveRegion = false; haveSeed = false;
+    }
+    // a device u16 volume of the loaded dimensions becomes the texture every renderer draws (ShowRegion, ShowRegionDistance)
+    int ShowVoxels(const uint16_t* shown)
+    {
+        const int* dim = volumeReader->dim;
+        const cudaTextureObject_t tex = svr_create_volume_texture(shown, dim[0], dim[1], dim[2], 1, SVR_LAYOUT_AUTO);    // (copies: `shown` is free afterwards)
+        if (!tex) return svr_last_error_code() ? svr_last_error_code() : -4;
+        svr_device_synchronize();                      // no frame in flight still reads the texture that goes
+        if (regionTex) svr_destroy_texture(regionTex);
+        regionTex = tex;
+        deviceVolume.tex = tex;
+        setup_volume(deviceVolume);
+        ReStartRender();
+        return 0;
+    }
+    // a length in the spacing's units as the r2 of svr_region_ball
+    static uint32_t LengthToR2(double length, double unit)
+    {
+        const double q = length / unit, r2 = std::floor(q * q);
+        return r2 >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)r2;
     }
     // the second mask buffer, into which the clean-up calls write (their `out` must not overlap their input)
     bool WorkMask()

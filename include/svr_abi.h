@@ -823,6 +823,55 @@ int svr_region_select_by_size(const uint32_t* labels_device, int nx, int ny, int
 /* HIP-event time of the device work of the last of the five calls above (waits for it) */
 int svr_region_label_last_ms(float* ms);
 
+/* ---- exact Euclidean distance maps of region masks and ball morphology (csrc/svr_distance.hip) ----
+ * Masks are DEVICE pointers in the layout above; input padding bits are ignored whatever they hold, output padding bits are 0.  The calls
+ * are stateless: they run on the library's stream and touch no scene, option or accumulator.  Integers only; every result is exact and
+ * unique, whatever order the GPU works in.
+ * WEIGHTS AND THE MEASURE: `weights` is a HOST array of three uint32 (x, y, z), each >= 1; NULL means 1, 1, 1.  The squared distance between
+ *   voxels p and q is wx (px - qx)^2 + wy (py - qy)^2 + wz (pz - qz)^2.  A map is a dense uint32 array [nz][ny][nx] on the device;
+ *   SVR_DIST_NONE means "there is no target voxel at all".  A call is refused when wx (nx - 1)^2 + wy (ny - 1)^2 + wz (nz - 1)^2, taken in
+ *   64-bit host arithmetic, exceeds 0xFFFFFFFE -- which also bounds every axis at 65536.
+ * DISTANCE: target SVR_DIST_TO_SET: every voxel gets the smallest squared distance to a set voxel (set voxels get 0); SVR_DIST_TO_UNSET:
+ *   to an unset voxel OF THE VOLUME (unset voxels get 0) -- nothing outside the volume counts as background and padding bits are not
+ *   voxels: scipy.ndimage.distance_transform_edt(mask, sampling=sqrt(w)) squared, and the border rule of svr_region_morph's ERODE.  With
+ *   no target voxel every entry is SVR_DIST_NONE and the return is 0.  The call allocates and frees its workspace -- 8 bytes per voxel: a
+ *   second map and the envelope stacks of the column passes -- and synchronises the stream.
+ * SELECT: out = the voxels with lo2 <= d2 <= hi2, so SVR_DIST_NONE is selected only by hi2 == 0xFFFFFFFF.  Margins are 0 .. r2 of a TO_SET
+ *   map, shells a2 .. b2.  Asynchronous.
+ * BALL: svr_region_morph's ops with the ball {offset : weighted d^2 <= r2} as the element.  DILATE = d2_to_set <= r2 (an empty mask stays
+ *   empty whatever r2); ERODE = d2_to_unset > r2, so a region touching a face of the volume is not eroded from that face, and a full mask
+ *   stays full; OPEN = erode then dilate, CLOSE = dilate then erode.  r2 = 0 is the identity with the padding cleared.  With weights 1, 1,
+ *   1 the ball of r2 = 1 / 2 / 3 is the unit element 6 / 18 / 26.  The cost does not depend on r2.  The last pass of each transform compares
+ *   with r2 and writes mask words: no map is stored.  Workspace 12 bytes per voxel (and one mask for open / close); the call synchronises
+ *   unless r2 = 0.  out may not overlap in.
+ * MAX: looks at the voxels of the mask, or at all voxels when the mask is NULL: *max_d2 = the largest value other than SVR_DIST_NONE among
+ *   them, *first_index = the smallest linear voxel index (z ny + y) nx + x that attains it -- on a TO_UNSET map the centre of the largest
+ *   inscribed ball.  When there is no such voxel *status = SVR_REGION_STATUS_EMPTY (both outputs 0) and the return is 0.  Synchronises.
+ * VOLUME: out = min(65535, isqrt(d2 scale^2)) as u16 [nz][ny][nx], isqrt the exact integer floor square root of the 64-bit product;
+ *   SVR_DIST_NONE becomes 65535; scale in 1 .. 65535.  The result is ready for svr_create_volume_texture.  Asynchronous.
+ * WEIGHTS FROM A SPACING (plain host code): unit = min(spacing) / 2^k for the largest k in 4, 3, 2, 1, 0 for which the weights
+ *   w[a] = max(1, llround((spacing[a] / unit)^2)) pass the overflow bound; a length L in the spacing's units is then r2 = floor((L / unit)^2)
+ *   and a map value d2 means sqrt(d2) unit.
+ * REFUSED, before the device is touched: a null pointer (-4); a dimension <= 0 or more than 2^31 voxels (-6); a weight of 0, the overflow
+ *   bound, an unknown target or op, lo2 > hi2, a scale outside 1 .. 65535, an `out` that overlaps `in` of svr_region_ball, a spacing that
+ *   is not positive and finite or that no k fits (-3). */
+#define SVR_DIST_NONE     0xFFFFFFFFu
+#define SVR_DIST_TO_SET   1
+#define SVR_DIST_TO_UNSET 2
+int svr_region_distance(const uint32_t* in_mask_device, int nx, int ny, int nz, const uint32_t* weights_or_null, int target, uint32_t* d2_device);
+int svr_region_distance_select(const uint32_t* d2_device, int nx, int ny, int nz, uint32_t lo2, uint32_t hi2, uint32_t* out_mask_device);
+int svr_region_ball(const uint32_t* in_mask_device, int nx, int ny, int nz, int op, const uint32_t* weights_or_null, uint32_t r2,
+                    uint32_t* out_mask_device);
+int svr_region_distance_max(const uint32_t* d2_device, const uint32_t* mask_device_or_null, int nx, int ny, int nz, uint32_t* max_d2,
+                            uint32_t* first_index, int32_t* status);
+int svr_region_distance_volume(const uint32_t* d2_device, int nx, int ny, int nz, uint32_t scale, uint16_t* out_u16_device);
+int svr_region_distance_weights(const double spacing[3], int nx, int ny, int nz, uint32_t weights[3], double* unit_out);
+/* HIP-event time of the device work of the last of the calls above (waits for it) */
+int svr_region_distance_last_ms(float* ms);
+/* HIP-event times of the row, y and z pass of the last transform run (svr_region_distance, or the second half of an open / close).
+ * Pointers may be NULL */
+int svr_region_distance_pass_ms(float* rows_ms, float* y_ms, float* z_ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

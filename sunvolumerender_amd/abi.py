@@ -292,6 +292,9 @@ REGION_ERR_SWEEPS = -9
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 1, 2, 3, 4
 MORPH_MAX_RADIUS = 32
 MASK_AND, MASK_OR, MASK_ANDNOT, MASK_XOR, MASK_NOT = 1, 2, 3, 4, 5
+DIST_NONE = 0xFFFFFFFF
+DIST_TO_SET, DIST_TO_UNSET = 1, 2
+DISTANCE_COLUMN_BLOCK = 256  # SVR_DISTANCE_COLUMN_BLOCK of csrc/svr_distance.hip: the columns of a column pass that one block covers
 
 
 EXPECTED_SIZES = {
@@ -470,6 +473,14 @@ PROTOTYPES = {
     "svr_region_select_by_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                             _P(C.c_uint32)]),
     "svr_region_label_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_region_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_int, C.c_void_p]),
+    "svr_region_distance_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "svr_region_ball": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_uint32, C.c_void_p]),
+    "svr_region_distance_max": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_int32)]),
+    "svr_region_distance_volume": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "svr_region_distance_weights": (C.c_int, [_P(C.c_double), C.c_int, C.c_int, C.c_int, _P(C.c_uint32), _P(C.c_double)]),
+    "svr_region_distance_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_region_distance_pass_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

@@ -1,0 +1,535 @@
+// svr_distance.hip -- exact squared Euclidean distance maps of region masks with per-axis integer weights, and what is one cheap pass
+// away from them: selection by distance, ball morphology, the largest inscribed ball, the map as a u16 volume (svr_region_distance,
+// _distance_select, _ball, _distance_max, _distance_volume, _distance_weights; the contract is in include/svr_abi.h, the design in
+// DESIGN.md 8k).  Integers only, on the mask layout of svr_region.hip: voxel (x, y, z) = bit x & 31 of word (z * ny + y) * wx + (x >> 5).
+// Input padding is ignored, output padding is 0.
+//
+// The transform is separable: D(x, y, z) = min over (i, j, k) targets of wx (x - i)^2 + wy (y - j)^2 + wz (z - k)^2
+//   = min_k [ wz (z - k)^2 + min_j [ wy (y - j)^2 + min_i wx (x - i)^2 ] ], and every min is over exact integers, so any correct
+//   evaluation gives the same array.  SVR_DIST_NONE marks "no target on this row / in this slice / at all"; it is never added to.
+//   k_dist_rows     one lane per voxel, 32 lanes per mask word: the nearest target bit at or left of the lane's bit and at or right of it,
+//     by __clz / __ffs on the word and, where the word has none on that side, on the nearest non-zero word of the row on that side (a
+//     scan of at most wx - 1 words that stops as soon as it cannot beat the other side).  TO_UNSET works on the complemented words with
+//     the padding of the row's last word forced to "not a target".  Writes wx d^2 (4 B per voxel, coalesced rows).
+//   k_dist_columns<MODE>  one thread per column of the axis (y, then z), lanes along x: the lower envelope of the parabolas
+//     g(i) + w (u - i)^2 by Meijster's two scans.  The forward scan keeps a stack of (site s, first coordinate t at which s is the
+//     minimiser), packed t << 16 | s in a GLOBAL workspace laid out [k][column] -- a site pushed has t < n <= 65536, so both fit 16 bits --
+//     with the top entry and its g in registers; g of an entry uncovered by a pop is read back from the pass's input, which is why a pass
+//     never writes the array it reads (rows -> A, y: A -> B, z: B -> A or the mask).  The separator of sites i < u,
+//     floor((g(u) - g(i) + w (u^2 - i^2)) / (2 w (u - i))), is only ever taken when site i wins at its own t >= 0, which makes the
+//     numerator non-negative: it is computed in double (both terms are below 2^50, so the quotient is within one of the floor) and fixed
+//     up in 64-bit integers.  The backward scan walks u = n - 1 .. 0, evaluates the top site and pops at u == t.
+//     MODE 0 writes the map; MODE 1 / 2 (the last pass of svr_region_ball) compare with r2 and write mask WORDS by ballot: d2 <= r2
+//     (dilate, on the TO_SET map) or d2 > r2 (erode, on the TO_UNSET map) -- no 4 B per voxel map is written for a select to read back.
+//     With SVR_DISTANCE_BRUTE the kernel is the literal O(n^2) min-plus product instead: the A/B build of tools/distance_time.py.
+//   k_dist_select, k_dist_volume, k_dist_max: one lane per voxel.  k_dist_max reduces (d2 << 32) | ~index in the lane, then in the wave,
+//     and issues one 64-bit atomicMax per wave: the largest d2 and, among equals, the smallest index.
+// TERMINATION: no lane or block waits for another.  Every for loop runs to an axis length or a word count; the pop loop of the forward
+//   scan removes one entry per turn from a stack that has received at most one entry per turn of the outer loop, so its turns total at
+//   most n per column, and it is also counted against n.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/svr_abi.h"
+#include "svr_internal.hpp"
+
+using svr::failf;
+
+#define SVR_DISTANCE_COLUMN_BLOCK 256   // columns of a column pass that one block covers (= its threads); sunvolumerender_amd/abi.py mirrors it
+
+namespace {
+
+constexpr int THREADS = 256;
+static_assert(SVR_DISTANCE_COLUMN_BLOCK == THREADS, "k_dist_columns runs one column per thread");
+constexpr uint32_t NONE = SVR_DIST_NONE;
+constexpr int OUT_MAP = 0, OUT_LE = 1, OUT_GT = 2;
+
+struct DistDims { int nx, ny, nz, wx; };
+
+// one column pass: `rows` groups of nx columns; column (r, x) starts at r * row_stride + x and has n entries `stride` apart.  The
+// mask word of level u of the columns of word gw of group r is r * mask_row + u * mask_level + gw.
+struct ColPass {
+    uint32_t n, rows, nx, wx, w;
+    size_t stride, row_stride, mask_row, mask_level, cols;   // cols = rows * nx, the stack's second dimension
+};
+
+__device__ inline uint32_t valid_bits(int gw, int nx)
+{
+    const int rem = nx - gw * 32;
+    return rem >= 32 ? 0xffffffffu : (1u << rem) - 1u;
+}
+
+// the 32 bits of this lane's half of the wave
+__device__ inline uint32_t half_ballot(bool p)
+{
+    const unsigned long long b = __ballot(p);
+    return (threadIdx.x & 32) ? (uint32_t)(b >> 32) : (uint32_t)b;
+}
+
+__device__ inline uint64_t sq_diff(uint32_t a, uint32_t b)
+{
+    const uint32_t d = a > b ? a - b : b - a;              // below 65536
+    return (uint64_t)(d * d);
+}
+
+// a lane of the one-lane-per-voxel kernels: bit `bit` of mask word i
+struct LaneAt { size_t i, v; int bit, gw; bool word_ok, inside; };
+__device__ inline LaneAt lane_at(size_t t, const DistDims& d, size_t words)
+{
+    LaneAt a;
+    a.i = t >> 5;
+    a.bit = (int)(t & 31u);
+    a.word_ok = a.i < words;
+    const size_t i = a.word_ok ? a.i : 0;
+    a.gw = (int)(i % (unsigned)d.wx);
+    const size_t row = i / (unsigned)d.wx;
+    const int x = a.gw * 32 + a.bit;
+    a.inside = a.word_ok && x < d.nx;
+    a.v = row * (size_t)d.nx + (size_t)x;
+    return a;
+}
+
+// the target bits of mask word i (word gw of its row): the set voxels, or the unset voxels of the volume
+__device__ inline uint32_t target_word(const uint32_t* __restrict__ mask, size_t i, int gw, int nx, bool unset)
+{
+    const uint32_t m = mask[i];
+    return (unset ? ~m : m) & valid_bits(gw, nx);
+}
+
+__global__ __launch_bounds__(THREADS) void k_dist_rows(const uint32_t* __restrict__ mask, uint32_t* __restrict__ out, DistDims d, size_t words, uint32_t w,
+                                                       int unset)
+{
+    const LaneAt a = lane_at((size_t)blockIdx.x * THREADS + threadIdx.x, d, words);
+    if (!a.word_ok) return;
+    const uint32_t m = target_word(mask, a.i, a.gw, d.nx, unset != 0);
+    uint32_t best = 0xffffffffu;                          // the distance in voxels to the nearest target of the row
+    const uint32_t left = m & (0xffffffffu >> (31 - a.bit)), right = m & (0xffffffffu << a.bit);
+    if (left) best = (uint32_t)(a.bit - (31 - __clz(left)));
+    if (right) best = min(best, (uint32_t)(__ffs(right) - 1 - a.bit));
+    if (!left)                                            // the nearest non-zero word to the left, while it can still be nearer
+        for (int j = a.gw - 1; j >= 0 && (uint32_t)((a.gw - j) * 32 + a.bit - 31) < best; --j) {
+            const uint32_t mm = target_word(mask, a.i - (size_t)(a.gw - j), j, d.nx, unset != 0);
+            if (mm) { best = min(best, (uint32_t)((a.gw - j) * 32 + a.bit - (31 - __clz(mm)))); break; }
+        }
+    if (!right)
+        for (int j = a.gw + 1; j < d.wx && (uint32_t)((j - a.gw) * 32 - a.bit) < best; ++j) {
+            const uint32_t mm = target_word(mask, a.i + (size_t)(j - a.gw), j, d.nx, unset != 0);
+            if (mm) { best = min(best, (uint32_t)((j - a.gw) * 32 + __ffs(mm) - 1 - a.bit)); break; }
+        }
+    if (a.inside) out[a.v] = best == 0xffffffffu ? NONE : w * best * best;
+}
+
+// what a column pass does with the value of entry u of its column
+template <int MODE>
+__device__ inline void emit(uint32_t v, uint32_t u, bool active, size_t at, uint32_t* __restrict__ out, const ColPass& p, uint32_t r2, uint32_t r,
+                            uint32_t gw, int bit)
+{
+    if (MODE == OUT_MAP) {
+        if (active) out[at] = v;
+    } else {
+        const bool on = active && (MODE == OUT_LE ? (v != NONE && v <= r2) : (v == NONE || v > r2));
+        const uint32_t word = half_ballot(on);
+        if (bit == 0 && r < p.rows) out[(size_t)r * p.mask_row + (size_t)u * p.mask_level + gw] = word;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(THREADS) void k_dist_columns(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t* __restrict__ stack, ColPass p,
+                                                          uint32_t r2)
+{
+    const size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t wi = t >> 5;
+    const int bit = (int)(t & 31u);
+    const uint32_t gw = (uint32_t)(wi % p.wx);
+    const size_t rr = wi / p.wx;
+    const uint32_t r = rr < p.rows ? (uint32_t)rr : p.rows;
+    const uint32_t x = gw * 32u + (uint32_t)bit;
+    const bool active = r < p.rows && x < p.nx;           // (the other lanes of the wave run the loops too: the ballots need them)
+    const size_t base = active ? (size_t)r * p.row_stride + x : 0;
+    const uint64_t w = p.w;
+#ifdef SVR_DISTANCE_BRUTE
+    (void)stack;
+    for (uint32_t u = 0; u < p.n; ++u) {
+        uint64_t best = NONE;
+        if (active)
+            for (uint32_t i = 0; i < p.n; ++i) {
+                const uint32_t g = in[base + (size_t)i * p.stride];
+                if (g != NONE) best = min(best, (uint64_t)g + w * sq_diff(u, i));
+            }
+        emit<MODE>((uint32_t)best, u, active, base + (size_t)u * p.stride, out, p, r2, r, gw, bit);
+    }
+#else
+    uint32_t* const st = stack + (active ? (size_t)r * p.nx + x : 0);       // entry k of this column: st[k * cols]
+    int q = -1;                                           // the top of the stack; its entry and its g are kept in registers
+    uint32_t s_top = 0u, t_top = 0u, g_top = 0u;
+    uint32_t g_next = active ? in[base] : NONE;
+    for (uint32_t u = 0; u < p.n; ++u) {
+        const uint32_t gu = g_next;
+        if (active && u + 1u < p.n) g_next = in[base + (size_t)(u + 1u) * p.stride];
+        if (gu == NONE) continue;                         // no parabola here (and none in a lane without a column)
+        for (uint32_t pops = 0; q >= 0 && pops <= p.n; ++pops) {
+            if ((uint64_t)g_top + w * sq_diff(t_top, s_top) <= (uint64_t)gu + w * sq_diff(t_top, u)) break;   // the top holds its own start
+            if (--q >= 0) {
+                const uint32_t e = st[(size_t)q * p.cols];
+                s_top = e & 0xffffu;
+                t_top = e >> 16;
+                g_top = in[base + (size_t)s_top * p.stride];
+            }
+        }
+        if (q < 0) {
+            q = 0; s_top = u; t_top = 0u; g_top = gu;
+            st[0] = u;
+        } else {
+            // the last coordinate at which s_top is still at least as good as u; s_top wins at t_top >= 0, so the numerator is >= 0
+            const uint64_t num = (uint64_t)gu + w * (uint64_t)(u * u - s_top * s_top) - (uint64_t)g_top, den = 2ull * w * (uint64_t)(u - s_top);
+            uint64_t sep = (uint64_t)((double)num / (double)den);
+            if (sep * den > num) --sep;
+            else if ((sep + 1ull) * den <= num) ++sep;
+            if (sep + 1ull < (uint64_t)p.n) {
+                ++q; s_top = u; t_top = (uint32_t)sep + 1u; g_top = gu;
+                st[(size_t)q * p.cols] = (t_top << 16) | u;
+            }
+        }
+    }
+    for (uint32_t u = p.n; u-- > 0u;) {
+        uint32_t v = NONE;
+        if (q >= 0) {
+            v = (uint32_t)((uint64_t)g_top + w * sq_diff(u, s_top));
+            if (u == t_top && q > 0) {
+                const uint32_t e = st[(size_t)(--q) * p.cols];
+                s_top = e & 0xffffu;
+                t_top = e >> 16;
+                g_top = in[base + (size_t)s_top * p.stride];
+            }
+        }
+        emit<MODE>(v, u, active, base + (size_t)u * p.stride, out, p, r2, r, gw, bit);
+    }
+#endif
+}
+
+__global__ __launch_bounds__(THREADS) void k_dist_select(const uint32_t* __restrict__ d2, DistDims d, size_t words, uint32_t lo2, uint32_t hi2,
+                                                         uint32_t* __restrict__ out)
+{
+    const LaneAt a = lane_at((size_t)blockIdx.x * THREADS + threadIdx.x, d, words);
+    bool on = false;
+    if (a.inside) {
+        const uint32_t v = d2[a.v];
+        on = v >= lo2 && v <= hi2;
+    }
+    const uint32_t word = half_ballot(on);
+    if (a.bit == 0 && a.word_ok) out[a.i] = word;
+}
+
+__global__ __launch_bounds__(THREADS) void k_mask_clean(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, DistDims d, size_t words)
+{
+    const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i < words) out[i] = in[i] & valid_bits((int)(i % (unsigned)d.wx), d.nx);
+}
+
+__global__ __launch_bounds__(THREADS) void k_dist_volume(const uint32_t* __restrict__ d2, size_t n, uint32_t scale, uint16_t* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = d2[i];
+    uint32_t res = 65535u;
+    const uint64_t prod = (uint64_t)v * (uint64_t)(scale * scale);       // below 2^64: v < 2^32, scale^2 < 2^32
+    if (v != NONE && prod < 65535ull * 65535ull) {        // the floor square root of a value below 2^32
+        const uint32_t pv = (uint32_t)prod;
+        uint32_t s = (uint32_t)sqrt((double)pv);
+        if ((uint64_t)s * s > pv) --s;
+        else if ((uint64_t)(s + 1u) * (s + 1u) <= pv) ++s;
+        res = s;
+    }
+    out[i] = (uint16_t)res;
+}
+
+__global__ __launch_bounds__(THREADS) void k_dist_max(const uint32_t* __restrict__ d2, const uint32_t* __restrict__ mask, DistDims d, size_t words,
+                                                      unsigned long long* best)
+{
+    unsigned long long key = 0ull;                        // (d2 << 32) | ~index; 0 = none: ~index is never 0 for an index below 2^31
+    const size_t total = words * 32u, step = (size_t)gridDim.x * THREADS;
+    for (size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x; t < total; t += step) {
+        const LaneAt a = lane_at(t, d, words);
+        if (!a.inside || (mask && !((mask[a.i] >> a.bit) & 1u))) continue;
+        const uint32_t v = d2[a.v];
+        if (v == NONE) continue;
+        const unsigned long long k = ((unsigned long long)v << 32) | (unsigned long long)(uint32_t)~(uint32_t)a.v;
+        key = k > key ? k : key;
+    }
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)key, lane ^ off), hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), lane ^ off);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        key = o > key ? o : key;
+    }
+    if (lane == 0 && key) atomicMax(best, key);
+}
+
+// ---------------- host side ----------------
+#define DIST_TRY(call)                                                                                                           \
+    do {                                                                                                                          \
+        hipError_t _e = (call);                                                                                                   \
+        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
+    } while (0)
+
+int check_dims(const char* who, int nx, int ny, int nz)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
+    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
+        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
+    return 0;
+}
+
+// wx (nx - 1)^2 + wy (ny - 1)^2 + wz (nz - 1)^2 <= 0xFFFFFFFE, in 64-bit arithmetic that cannot wrap
+bool weights_fit(const uint64_t w[3], int nx, int ny, int nz)
+{
+    const int dims[3] = {nx, ny, nz};
+    uint64_t total = 0;
+    for (int a = 0; a < 3; ++a) {
+        const uint64_t e = (uint64_t)(dims[a] - 1), s = e * e;           // below 2^62
+        if (s == 0) continue;
+        if (w[a] > 0xFFFFFFFEull / s) return false;
+        total += w[a] * s;                                // each term and the running sum stay below 2^34
+        if (total > 0xFFFFFFFEull) return false;
+    }
+    return true;
+}
+
+int check_weights(const char* who, const uint32_t* weights_or_null, int nx, int ny, int nz, uint32_t w[3])
+{
+    for (int a = 0; a < 3; ++a) w[a] = weights_or_null ? weights_or_null[a] : 1u;
+    if (!w[0] || !w[1] || !w[2]) return failf(-3, "%s: every weight must be at least 1 (got %u, %u, %u)", who, w[0], w[1], w[2]);
+    const uint64_t w64[3] = {w[0], w[1], w[2]};
+    if (!weights_fit(w64, nx, ny, nz))
+        return failf(-3, "%s: the largest squared distance of %d x %d x %d under weights %u, %u, %u would overflow 32 bits", who, nx, ny, nz, w[0], w[1], w[2]);
+    return 0;
+}
+
+bool overlap(const void* a, const void* b, size_t bytes)
+{
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return p < q + bytes && q < p + bytes;
+}
+
+DistDims make_dims(int nx, int ny, int nz) { return DistDims{nx, ny, nz, (nx + 31) / 32}; }
+size_t mask_words(const DistDims& d) { return (size_t)d.wx * d.ny * d.nz; }
+dim3 grid_for(size_t n) { return dim3((uint32_t)((n + THREADS - 1) / THREADS)); }      // at most 2^31 items: 2^23 blocks
+
+// HIP events: [0], [1] around the device work of the last call of this file; [2] .. [5] around the three passes of its last transform
+hipEvent_t g_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+bool g_passes = false;                                    // [2] .. [5] have been recorded
+bool events_ready()
+{
+    if (g_ev[0]) return true;
+    for (auto& e : g_ev)
+        if (hipEventCreate(&e) != hipSuccess) { g_ev[0] = nullptr; return false; }
+    return true;
+}
+struct CallTimer {
+    hipStream_t st;
+    bool on;
+    explicit CallTimer(hipStream_t s) : st(s), on(false) { if (events_ready()) on = hipEventRecord(g_ev[0], st) == hipSuccess; }
+    void stop() { if (on) hipEventRecord(g_ev[1], st); on = false; }
+    ~CallTimer() { stop(); }
+};
+
+// one transform: mask -> rows into a -> y pass into b -> z pass into a (MODE OUT_MAP; a is then the map) or into out_mask (OUT_LE / OUT_GT)
+hipError_t transform(hipStream_t st, const uint32_t* mask, const DistDims& d, const uint32_t w[3], bool unset, int mode, uint32_t r2, uint32_t* a,
+                     uint32_t* b, uint32_t* stack, uint32_t* out_mask)
+{
+    const size_t words = mask_words(d), plane = (size_t)d.nx * d.ny;
+    const bool ev = events_ready();
+    if (ev) hipEventRecord(g_ev[2], st);
+    hipLaunchKernelGGL(k_dist_rows, grid_for(words * 32), dim3(THREADS), 0, st, mask, a, d, words, w[0], unset ? 1 : 0);
+    if (ev) hipEventRecord(g_ev[3], st);
+    ColPass py = {(uint32_t)d.ny, (uint32_t)d.nz, (uint32_t)d.nx, (uint32_t)d.wx, w[1], (size_t)d.nx, plane, (size_t)d.ny * d.wx, (size_t)d.wx,
+                  (size_t)d.nz * d.nx};
+    hipLaunchKernelGGL((k_dist_columns<OUT_MAP>), grid_for((size_t)d.nz * d.wx * 32), dim3(THREADS), 0, st, a, b, stack, py, 0u);
+    if (ev) hipEventRecord(g_ev[4], st);
+    ColPass pz = {(uint32_t)d.nz, (uint32_t)d.ny, (uint32_t)d.nx, (uint32_t)d.wx, w[2], plane, (size_t)d.nx, (size_t)d.wx, (size_t)d.ny * d.wx,
+                  (size_t)d.ny * d.nx};
+    const dim3 gz = grid_for((size_t)d.ny * d.wx * 32);
+    if (mode == OUT_MAP) hipLaunchKernelGGL((k_dist_columns<OUT_MAP>), gz, dim3(THREADS), 0, st, b, a, stack, pz, 0u);
+    else if (mode == OUT_LE) hipLaunchKernelGGL((k_dist_columns<OUT_LE>), gz, dim3(THREADS), 0, st, b, out_mask, stack, pz, r2);
+    else hipLaunchKernelGGL((k_dist_columns<OUT_GT>), gz, dim3(THREADS), 0, st, b, out_mask, stack, pz, r2);
+    if (ev) { hipEventRecord(g_ev[5], st); g_passes = true; }
+    return hipGetLastError();
+}
+
+float elapsed(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    if (hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; }
+    return ms;
+}
+
+} // namespace
+
+extern "C" {
+
+int svr_region_distance(const uint32_t* in_mask_device, int nx, int ny, int nz, const uint32_t* weights_or_null, int target, uint32_t* d2_device)
+{
+    const char* who = "svr_region_distance";
+    if (!in_mask_device || !d2_device) return failf(-4, "%s: null argument", who);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    uint32_t w[3];
+    if (int e = check_weights(who, weights_or_null, nx, ny, nz, w)) return e;
+    if (target != SVR_DIST_TO_SET && target != SVR_DIST_TO_UNSET) return failf(-3, "%s: unknown target %d", who, target);
+    if (svr::ensure_ready()) return svr_last_error_code();
+    hipStream_t st = svr::current_stream();
+    const DistDims d = make_dims(nx, ny, nz);
+    const size_t n = (size_t)nx * ny * nz;
+    uint32_t* buf = nullptr;                              // the second map and the stacks: 8 bytes per voxel
+    auto cleanup = [&]() { if (buf) hipFree(buf); };
+    DIST_TRY(hipMalloc((void**)&buf, 2 * n * sizeof(uint32_t)));
+    CallTimer timer(st);                                  // (the launches, not the allocation)
+    DIST_TRY(transform(st, in_mask_device, d, w, target == SVR_DIST_TO_UNSET, OUT_MAP, 0u, d2_device, buf, buf + n, nullptr));
+    timer.stop();
+    DIST_TRY(hipStreamSynchronize(st));
+    cleanup();
+    return 0;
+}
+
+int svr_region_distance_select(const uint32_t* d2_device, int nx, int ny, int nz, uint32_t lo2, uint32_t hi2, uint32_t* out_mask_device)
+{
+    const char* who = "svr_region_distance_select";
+    if (!d2_device || !out_mask_device) return failf(-4, "%s: null argument", who);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (lo2 > hi2) return failf(-3, "%s: the range must satisfy lo2 <= hi2 (got %u .. %u)", who, lo2, hi2);
+    if (svr::ensure_ready()) return svr_last_error_code();
+    hipStream_t st = svr::current_stream();
+    CallTimer timer(st);
+    auto cleanup = []() {};
+    const DistDims d = make_dims(nx, ny, nz);
+    const size_t words = mask_words(d);
+    hipLaunchKernelGGL(k_dist_select, grid_for(words * 32), dim3(THREADS), 0, st, d2_device, d, words, lo2, hi2, out_mask_device);
+    DIST_TRY(hipGetLastError());
+    return 0;
+}
+
+int svr_region_ball(const uint32_t* in_mask_device, int nx, int ny, int nz, int op, const uint32_t* weights_or_null, uint32_t r2, uint32_t* out_mask_device)
+{
+    const char* who = "svr_region_ball";
+    if (!in_mask_device || !out_mask_device) return failf(-4, "%s: null argument", who);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (op != SVR_MORPH_DILATE && op != SVR_MORPH_ERODE && op != SVR_MORPH_OPEN && op != SVR_MORPH_CLOSE) return failf(-3, "%s: unknown op %d", who, op);
+    uint32_t w[3];
+    if (int e = check_weights(who, weights_or_null, nx, ny, nz, w)) return e;
+    const DistDims d = make_dims(nx, ny, nz);
+    const size_t words = mask_words(d), n = (size_t)nx * ny * nz;
+    if (overlap(in_mask_device, out_mask_device, words * sizeof(uint32_t))) return failf(-3, "%s: out must not overlap in", who);
+    if (svr::ensure_ready()) return svr_last_error_code();
+    hipStream_t st = svr::current_stream();
+    uint32_t* buf = nullptr;                              // two maps, the stacks, and the mask between the two halves of open / close
+    auto cleanup = [&]() { if (buf) hipFree(buf); };
+    if (r2 == 0u) {                                       // the ball is the voxel itself: the identity, padding cleared
+        CallTimer timer(st);
+        hipLaunchKernelGGL(k_mask_clean, grid_for(words), dim3(THREADS), 0, st, in_mask_device, out_mask_device, d, words);
+        DIST_TRY(hipGetLastError());
+        return 0;
+    }
+    const bool two = op == SVR_MORPH_OPEN || op == SVR_MORPH_CLOSE;
+    DIST_TRY(hipMalloc((void**)&buf, (3 * n + (two ? words : 0)) * sizeof(uint32_t)));
+    uint32_t *a = buf, *b = buf + n, *stack = buf + 2 * n, *mid = buf + 3 * n;
+    CallTimer timer(st);
+    const bool erode_first = op == SVR_MORPH_ERODE || op == SVR_MORPH_OPEN;
+    // dilate: d2 to the set voxels <= r2; erode: d2 to the unset voxels of the volume > r2
+    DIST_TRY(transform(st, in_mask_device, d, w, erode_first, erode_first ? OUT_GT : OUT_LE, r2, a, b, stack, two ? mid : out_mask_device));
+    if (two) DIST_TRY(transform(st, mid, d, w, !erode_first, erode_first ? OUT_LE : OUT_GT, r2, a, b, stack, out_mask_device));
+    timer.stop();
+    DIST_TRY(hipStreamSynchronize(st));
+    cleanup();
+    return 0;
+}
+
+int svr_region_distance_max(const uint32_t* d2_device, const uint32_t* mask_device_or_null, int nx, int ny, int nz, uint32_t* max_d2, uint32_t* first_index,
+                            int32_t* status)
+{
+    const char* who = "svr_region_distance_max";
+    if (!d2_device || !max_d2 || !first_index || !status) return failf(-4, "%s: null argument", who);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (svr::ensure_ready()) return svr_last_error_code();
+    hipStream_t st = svr::current_stream();
+    unsigned long long* d_best = nullptr;
+    auto cleanup = [&]() { if (d_best) hipFree(d_best); };
+    DIST_TRY(hipMalloc((void**)&d_best, sizeof(unsigned long long)));
+    CallTimer timer(st);
+    DIST_TRY(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), st));
+    const DistDims d = make_dims(nx, ny, nz);
+    const size_t words = mask_words(d);
+    const size_t blocks = std::min<size_t>((words * 32 + THREADS - 1) / THREADS, 2048);       // the rest by the grid-stride loop
+    hipLaunchKernelGGL(k_dist_max, dim3((uint32_t)blocks), dim3(THREADS), 0, st, d2_device, mask_device_or_null, d, words, d_best);
+    DIST_TRY(hipGetLastError());
+    timer.stop();
+    unsigned long long best = 0ull;
+    DIST_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, st));
+    DIST_TRY(hipStreamSynchronize(st));
+    cleanup();
+    *max_d2 = (uint32_t)(best >> 32);
+    *first_index = best ? ~(uint32_t)best : 0u;
+    *status = best ? SVR_REGION_STATUS_OK : SVR_REGION_STATUS_EMPTY;
+    return 0;
+}
+
+int svr_region_distance_volume(const uint32_t* d2_device, int nx, int ny, int nz, uint32_t scale, uint16_t* out_u16_device)
+{
+    const char* who = "svr_region_distance_volume";
+    if (!d2_device || !out_u16_device) return failf(-4, "%s: null argument", who);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (scale < 1u || scale > 65535u) return failf(-3, "%s: the scale must lie in 1 .. 65535 (got %u)", who, scale);
+    if (svr::ensure_ready()) return svr_last_error_code();
+    hipStream_t st = svr::current_stream();
+    CallTimer timer(st);
+    auto cleanup = []() {};
+    const size_t n = (size_t)nx * ny * nz;
+    hipLaunchKernelGGL(k_dist_volume, grid_for(n), dim3(THREADS), 0, st, d2_device, n, scale, out_u16_device);
+    DIST_TRY(hipGetLastError());
+    return 0;
+}
+
+int svr_region_distance_weights(const double spacing[3], int nx, int ny, int nz, uint32_t weights[3], double* unit_out)
+{
+    const char* who = "svr_region_distance_weights";
+    if (!spacing || !weights || !unit_out) return failf(-4, "%s: null argument", who);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    for (int a = 0; a < 3; ++a)
+        if (!(spacing[a] > 0.0) || !std::isfinite(spacing[a])) return failf(-3, "%s: the spacing must be positive and finite (got %g, %g, %g)", who, spacing[0], spacing[1], spacing[2]);
+    const double smin = std::fmin(spacing[0], std::fmin(spacing[1], spacing[2]));
+    for (int k = 4; k >= 0; --k) {
+        const double unit = smin / (double)(1 << k);
+        uint64_t w[3];
+        bool ok = unit > 0.0;
+        for (int a = 0; a < 3 && ok; ++a) {
+            const double r = spacing[a] / unit, x = r * r;
+            if (!(x < 4294967295.5)) { ok = false; break; }
+            const long long v = std::llround(x);
+            w[a] = v < 1 ? 1ull : (uint64_t)v;
+        }
+        if (!ok || !weights_fit(w, nx, ny, nz)) continue;
+        for (int a = 0; a < 3; ++a) weights[a] = (uint32_t)w[a];
+        *unit_out = unit;
+        return 0;
+    }
+    return failf(-3, "%s: no unit of min(spacing) / 2^k, k = 4 .. 0, keeps the squared distances of %d x %d x %d at spacing %g, %g, %g inside 32 bits", who, nx, ny,
+                 nz, spacing[0], spacing[1], spacing[2]);
+}
+
+int svr_region_distance_last_ms(float* ms)
+{
+    if (!ms) return failf(-4, "svr_region_distance_last_ms: null argument");
+    *ms = g_ev[0] ? elapsed(g_ev[0], g_ev[1]) : 0.f;
+    return 0;
+}
+
+int svr_region_distance_pass_ms(float* rows_ms, float* y_ms, float* z_ms)
+{
+    float* const out[3] = {rows_ms, y_ms, z_ms};
+    for (int i = 0; i < 3; ++i)
+        if (out[i]) *out[i] = g_passes ? elapsed(g_ev[2 + i], g_ev[3 + i]) : 0.f;
+    return 0;
+}
+
+} // extern "C"

@@ -553,6 +553,102 @@ class Device:
         self.check(self.lib.svr_region_label_last_ms(C.byref(ms)))
         return float(ms.value)
 
+    # ---- exact Euclidean distance maps and ball morphology (svr_region_distance / _distance_select / _ball / _distance_max / _distance_volume) ----
+    @staticmethod
+    def _weights(weights):
+        return None if weights is None else (C.c_uint32 * 3)(*[int(t) for t in weights])
+
+    def _region_map(self, d2, shape):
+        """(device pointer, (nz, ny, nx), owned) of a uint32 map [nz][ny][nx] (uploaded) or of a device pointer with `shape`."""
+        return self._region_labels(d2, shape)
+
+    def region_distance(self, mask, shape=None, weights=None, target: int = abi.DIST_TO_SET, out_ptr: Optional[int] = None):
+        """svr_region_distance: the exact squared distance, under the integer weights (wx, wy, wz) (None = 1, 1, 1), of every voxel to the
+        nearest set voxel (DIST_TO_SET) or to the nearest unset voxel of the volume (DIST_TO_UNSET); DIST_NONE everywhere when there is
+        none.  mask: a bool array [nz][ny][nx], or a device pointer with shape=.  Returns a uint32 array [nz][ny][nx], or out_ptr itself
+        when a device buffer of 4 nx ny nz bytes is given."""
+        if isinstance(mask, np.ndarray):
+            shape = mask.shape
+        if shape is None:
+            raise ValueError("a device mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = (int(n) for n in shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
+        try:
+            self.check(self.lib.svr_region_distance(C.c_void_p(buf), nx, ny, nz, self._weights(weights), int(target), C.c_void_p(out)))
+            if out_ptr is not None:
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint32)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_distance_select(self, d2, lo2: int, hi2: int, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_distance_select: the mask of the voxels with lo2 <= d2 <= hi2.  d2: a uint32 array [nz][ny][nx] or a device pointer
+        with shape=."""
+        dbuf, dshape, downed = self._region_map(d2, shape)
+
+        def call(p, s, out):
+            self.check(self.lib.svr_region_distance_select(C.c_void_p(dbuf), s[2], s[1], s[0], int(lo2), int(hi2), out))
+        try:
+            return self._mask_call([], dshape, out_ptr, call)
+        finally:
+            if downed:
+                self.free(dbuf)
+
+    def region_ball(self, mask, op: int, r2: int, weights=None, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_ball: MORPH_DILATE / _ERODE / _OPEN / _CLOSE of a mask by the ball {offset : weighted d^2 <= r2}."""
+        def call(p, s, out):
+            self.check(self.lib.svr_region_ball(p[0], s[2], s[1], s[0], int(op), self._weights(weights), int(r2), out))
+        return self._mask_call([mask], shape, out_ptr, call)
+
+    def region_distance_max(self, d2, mask=None, shape=None):
+        """svr_region_distance_max: (max_d2, first_index, status) over the voxels of `mask` (a bool array or a device pointer; None = all
+        voxels): the largest value other than DIST_NONE and the smallest linear voxel index that attains it; status REGION_STATUS_EMPTY
+        when there is no such voxel."""
+        dbuf, (nz, ny, nx), downed = self._region_map(d2, shape)
+        mbuf, mowned = (None, False) if mask is None else self._region_mask(mask, (nz, ny, nx))
+        m, first, status = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+        try:
+            self.check(self.lib.svr_region_distance_max(C.c_void_p(dbuf), C.c_void_p(mbuf) if mbuf is not None else None, nx, ny, nz, C.byref(m),
+                                                        C.byref(first), C.byref(status)))
+        finally:
+            if downed:
+                self.free(dbuf)
+            if mowned:
+                self.free(mbuf)
+        return int(m.value), int(first.value), int(status.value)
+
+    def region_distance_volume(self, d2, scale: int = 1, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_distance_volume: min(65535, isqrt(d2 scale^2)) as a u16 array [nz][ny][nx] (DIST_NONE gives 65535); with out_ptr (a
+        device buffer of nx * ny * nz u16) the result stays on the device and out_ptr is returned."""
+        dbuf, (nz, ny, nx), downed = self._region_map(d2, shape)
+        out = out_ptr if out_ptr is not None else self.malloc(2 * max(nx * ny * nz, 1))
+        try:
+            self.check(self.lib.svr_region_distance_volume(C.c_void_p(dbuf), nx, ny, nz, int(scale), C.c_void_p(out)))
+            self.synchronize()
+            if out_ptr is not None:
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint16)
+        finally:
+            if downed:
+                self.free(dbuf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_distance_last_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_region_distance_last_ms(C.byref(ms)))
+        return float(ms.value)
+
+    def region_distance_pass_ms(self):
+        """(rows, y, z) HIP-event times of the passes of the last transform."""
+        ms = [C.c_float(0.0) for _ in range(3)]
+        self.check(self.lib.svr_region_distance_pass_ms(*[C.byref(t) for t in ms]))
+        return tuple(float(t.value) for t in ms)
+
     def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
         """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
         m = abi.RegionMeasurement()
@@ -574,6 +670,22 @@ def region_label_scan_levels(shape) -> int:
     while n > LABEL_SCAN_BLOCK:
         n, levels = (n + LABEL_SCAN_BLOCK - 1) // LABEL_SCAN_BLOCK, levels + 1
     return levels
+
+
+def distance_weights(spacing, shape, lib=None):
+    """svr_region_distance_weights: ((wx, wy, wz), unit) for a spacing (sx, sy, sz) and a [nz][ny][nx] shape: the integer weights of the
+    squared distance in units of `unit` = min(spacing) / 2^k.  A length L is r2 = floor((L / unit)^2); a map value d2 means sqrt(d2) unit.
+    Host code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    nz, ny, nx = (int(n) for n in shape)
+    sp = (C.c_double * 3)(*[float(t) for t in spacing])
+    w, unit = (C.c_uint32 * 3)(), C.c_double(0.0)
+    rc = lib.svr_region_distance_weights(sp, nx, ny, nz, w, C.byref(unit))
+    if rc != 0:
+        msg = lib.svr_last_error().decode()
+        lib.svr_clear_error()
+        raise SvrError(f"svr_region_distance_weights failed ({rc}): {msg}")
+    return (int(w[0]), int(w[1]), int(w[2])), float(unit.value)
 
 
 def region_mask_words(shape) -> int:
