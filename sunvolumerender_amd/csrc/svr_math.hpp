@@ -43,6 +43,17 @@ SVR_DEV float logf_(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599
 SVR_DEV float logf_unit(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 
 #else
+// Range reduction of the Cephes logarithm, x = 2^e * m with m in (sqrt(1/2), sqrt(2)], in integers: no compare, no select.
+//     iy = ix - SVR_LOG_SPLIT;   e = (int)iy >> 23;   m = bits((iy & 0x7fffff) + SVR_LOG_SPLIT)
+// 1.41421356f is 0x3fb504f3; SVR_LOG_SPLIT = 0x3f3504f4 is the smallest float above it, halved.  Modulo 2^32 the subtraction removes
+// the exponent bias less one (0x3f000000) and adds 0x800000 - 0x3504f4 to the mantissa field, which carries into the exponent field
+// exactly when the mantissa bits exceed 0x3504f3, i.e. when 1.m > 1.41421356f.  The shift therefore gives the exponent, incremented
+// above the threshold, and the low 23 bits plus SVR_LOG_SPLIT are the bits of 1.m * 0.5f above it and of 1.m itself up to it:
+// the same e and the same bits of m as `m = 1.m; if (m > 1.41421356f) { m = m * 0.5f; e += 1; }`, the form the CPU checker keeps,
+// for every normal float (all 2 130 706 432 of them compared; tests/test_log_reduction_gpu.py).  The domain of logf_ includes x > 1: up to ix = 0x7f7fffff (FLT_MAX)
+// the difference stays below 2^31, so the shift is that of a non-negative int; for x below sqrt(1/2) the difference is a negative
+// int and the ARITHMETIC shift rounds the exponent down, as the split requires.
+#define SVR_LOG_SPLIT 0x3f3504f4u
 SVR_DEV float logf_(float x)
 {
     if (x != x) return x;
@@ -56,9 +67,9 @@ SVR_DEV float logf_(float x)
         ix = f2u(x);
         e = -23;
     }
-    e += (int)(ix >> 23) - 127;
-    float m = u2f((ix & 0x007fffffu) | 0x3f800000u);
-    if (m > 1.41421356f) { m = m * 0.5f; e += 1; }
+    const uint32_t iy = ix - SVR_LOG_SPLIT;
+    e += (int)iy >> 23;
+    float m = u2f((iy & 0x007fffffu) + SVR_LOG_SPLIT);
     float y = m - 1.f;
     float z = y * y;
     float p = 7.0376836292E-2f;
@@ -83,12 +94,9 @@ SVR_DEV float logf_(float x)
 // unless it is exactly 0.  Same value as logf_ on that domain, fewer branches.
 SVR_DEV float logf_unit(float x)
 {
-    uint32_t ix = f2u(x);
-    int e = (int)(ix >> 23) - 127;
-    float m = u2f((ix & 0x007fffffu) | 0x3f800000u);
-    bool hi = m > 1.41421356f;
-    m = hi ? m * 0.5f : m;
-    e = hi ? e + 1 : e;
+    const uint32_t iy = f2u(x) - SVR_LOG_SPLIT;
+    int e = (int)iy >> 23;
+    float m = u2f((iy & 0x007fffffu) + SVR_LOG_SPLIT);
     float y = m - 1.f;
     float z = y * y;
     float p = 7.0376836292E-2f;
