@@ -25,8 +25,12 @@
 // -ball-dilate L, -ball-erode L, -ball-open L and -ball-close L are clean-up steps too, by a true ball of radius L > 0 in the units of the
 // volume's spacing (Canvas::BallMorphRegion: the exact Euclidean distance map, any radius at the same cost); each prints the measurements
 // of what is left.  -thickness prints, after the last step, the largest ball inscribed in the region and its centre voxel.
+// -median E N and -smooth SIGMA filter the voxels BEFORE they are segmented, in command-line order (Canvas::MedianVolume: the median over
+// the unit element E = 6|18|26, N = 1 .. 64 times; Canvas::SmoothVolume: binomial smoothing of SIGMA > 0 in the units of the volume's
+// spacing): -grow and -threshold then work on the filtered copy, and so does what they show.  -show-filtered draws the filtered copy
+// in place of the loaded volume.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -39,7 +43,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -58,6 +62,9 @@ int main(int argc, char** argv)
     std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize / -ball-*, in order
     int cleanElement = 6;
     bool thickness = false;                                         // -thickness: the largest inscribed ball of the final region
+    struct FilterStep { int element; uint32_t iterations; double sigma; };     // -median E N (element != 0) or -smooth SIGMA
+    std::vector<FilterStep> filterSteps;                            // in command-line order
+    bool showFiltered = false;                                      // -show-filtered
     for (int i = 2; i < argc; ++i) {
         int cleanOp = -2;
         if (!strcmp(argv[i], "-detach")) cleanOp = -1;
@@ -100,6 +107,28 @@ int main(int argc, char** argv)
             cleanSteps.push_back(CleanStep{argv[i], -10 - op, 0u, len});
             ++i;
         }
+        else if (!strcmp(argv[i], "-median")) {
+            char *e0 = nullptr, *e1 = nullptr;
+            const long e = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : 0, n = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : 0;
+            if (i + 2 >= argc || e0 == argv[i + 1] || *e0 != '\0' || e1 == argv[i + 2] || *e1 != '\0' || (e != 6 && e != 18 && e != 26) || n < 1 || n > SVR_FILTER_MAX_ITERATIONS) {
+                fprintf(stderr, "-median needs an element E of 6, 18 or 26 and a number of passes N in 1 .. %d (got %s %s)\n", SVR_FILTER_MAX_ITERATIONS,
+                        i + 1 < argc ? argv[i + 1] : "nothing", i + 2 < argc ? argv[i + 2] : "nothing");
+                return 2;
+            }
+            filterSteps.push_back(FilterStep{(int)e, (uint32_t)n, 0.0});
+            i += 2;
+        }
+        else if (!strcmp(argv[i], "-smooth")) {
+            char* end = nullptr;
+            const double sigma = i + 1 < argc ? strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(sigma > 0.0) || !std::isfinite(sigma)) {
+                fprintf(stderr, "-smooth needs a SIGMA > 0 in the units of the spacing (got %s)\n", i + 1 < argc ? argv[i + 1] : "nothing");
+                return 2;
+            }
+            filterSteps.push_back(FilterStep{0, 0u, sigma});
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-show-filtered")) showFiltered = true;
         else if (!strcmp(argv[i], "-thickness")) thickness = true;
         else if (!strcmp(argv[i], "-threshold")) {
             char *e0 = nullptr, *e1 = nullptr;
@@ -196,6 +225,7 @@ int main(int argc, char** argv)
     if (threshold)
         for (const CleanStep& c : cleanSteps)
             if (c.op == -1) { fprintf(stderr, "-detach starts from the picked voxel: it needs -grow X Y LO HI, not -threshold\n"); return 2; }
+    if (showFiltered && filterSteps.empty()) { fprintf(stderr, "-show-filtered needs -median E N or -smooth SIGMA\n"); return 2; }
     if (svr_init(0)) return 1;
     {
         Canvas canvas(W, H);
@@ -217,7 +247,7 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
-        canvas.volumeReader->KeepVoxels(grow || threshold);                         // the region calls work on the plain voxels
+        canvas.volumeReader->KeepVoxels(grow || threshold || !filterSteps.empty());  // the region and filter calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%s: %d x %d x %d, range %.0f..%.0f, max gradient magnitude %.0f, %zu histogram bins\n", volume.c_str(),
@@ -239,6 +269,24 @@ int main(int argc, char** argv)
         canvas.SetProjection(proj);
         raycast = raycast || project;                                  // one deterministic image either way
         canvas.SetDenoisePreview(denoisePreview);
+
+        for (const FilterStep& f : filterSteps) {
+            // filter the voxels that -grow / -threshold will segment
+            float ms = 0.f;
+            if (f.element) {
+                if (canvas.MedianVolume(f.element, f.iterations) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                svr_volume_filter_last_ms(&ms);
+                printf("median element %d x %u: %.3f ms\n", f.element, f.iterations, ms);
+            } else {
+                const double sp[3] = {canvas.Volume().spacing.x, canvas.Volume().spacing.y, canvas.Volume().spacing.z};
+                uint32_t radii[3] = {0u, 0u, 0u};
+                double applied[3] = {0.0, 0.0, 0.0};
+                if (svr_volume_smooth_radii(sp, f.sigma, radii, applied) != 0 || canvas.SmoothVolume(f.sigma) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                svr_volume_filter_last_ms(&ms);
+                printf("smooth sigma %g: radii %u %u %u (sigma %g %g %g), %.3f ms\n", f.sigma, radii[0], radii[1], radii[2], applied[0], applied[1], applied[2], ms);
+            }
+        }
+        if (showFiltered && canvas.ShowFiltered() != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
 
         if (!picks.empty()) {
             // point picks instead of a rendering: one line per pick

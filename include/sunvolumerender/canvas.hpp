@@ -442,7 +442,7 @@ public:
     // (svr_region_measure turns them into volume, mean, deviation, centroid, surface area).  Returns the call's status (0 = ok)
     int GrowRegion(const svr_hit& hit, uint32_t lo, uint32_t hi, int connectivity, svr_region_stats* stats = nullptr)
     {
-        const uint16_t* vox = volumeReader->DeviceVoxels();
+        const uint16_t* vox = SegVoxels();
         if (!ready || !vox || hit.status != SVR_HIT_STATUS_FOUND) return -4;
         const int* dim = volumeReader->dim;
         int32_t seed[3];
@@ -515,7 +515,7 @@ public:
     // (radius 0, ijk -1) for an empty region and for one that fills the volume; negative on an error.  The region stays as it is
     int RegionThickness(double* radius, int32_t ijk[3])
     {
-        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion || !radius || !ijk) return -4;
+        if (!ready || !SegVoxels() || !haveRegion || !radius || !ijk) return -4;
         uint32_t w[3];
         double unit = 0.0;
         if (int rc = RegionDistanceUnits(w, &unit)) return rc;
@@ -541,7 +541,7 @@ public:
     // outside (SVR_DIST_TO_UNSET) -- as the volume min(65535, floor(sqrt(d2) * scale)), until ShowAll or the next volume
     int ShowRegionDistance(int target, uint32_t scale)
     {
-        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion) return -4;
+        if (!ready || !SegVoxels() || !haveRegion) return -4;
         uint32_t w[3];
         double unit = 0.0;
         if (int rc = RegionDistanceUnits(w, &unit)) return rc;
@@ -563,7 +563,7 @@ public:
     // seed voxel then, so DetachRegion is refused (-4) until the next GrowRegion
     int ThresholdRegion(uint32_t lo, uint32_t hi, svr_region_stats* stats = nullptr)
     {
-        const uint16_t* vox = volumeReader->DeviceVoxels();
+        const uint16_t* vox = SegVoxels();
         if (!ready || !vox) return -4;
         const int* dim = volumeReader->dim;
         if (!regionMask) regionMask = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
@@ -589,7 +589,7 @@ public:
     // CountRegionParts: *count = the number of connected components of the region; the region stays as it is
     int CountRegionParts(int connectivity, uint32_t* count)
     {
-        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion || !count) return -4;
+        if (!ready || !SegVoxels() || !haveRegion || !count) return -4;
         const int* dim = volumeReader->dim;
         uint32_t* labels = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
         if (!labels) return -4;
@@ -601,7 +601,7 @@ public:
     // region set to `fill`; ShowAll goes back to the loaded volume.  The Canvas owns the extra texture
     int ShowRegion(int mode, uint32_t fill)
     {
-        const uint16_t* vox = volumeReader->DeviceVoxels();
+        const uint16_t* vox = SegVoxels();
         if (!ready || !vox || !haveRegion) return -4;
         const int* dim = volumeReader->dim;
         uint16_t* shown = (uint16_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint16_t));
@@ -610,6 +610,44 @@ public:
         if (rc == 0) rc = ShowVoxels(shown);
         svr_device_free(shown);
         return rc;
+    }
+    // extension: filter the voxels before they are segmented (svr_volume_rank / _smooth; include/svr_abi.h, "exact volume filters").  The
+    // result is a device copy that the Canvas owns; while one exists GrowRegion, ThresholdRegion, ShowRegion and the other region methods
+    // read it in place of the loaded voxels.  Repeated calls stack: each filters the copy the last one left.  The loaded volume and
+    // what is drawn do not change (ShowFiltered draws the copy).  Needs the plain voxels: volumeReader->KeepVoxels(true) before LoadVolume.
+    // MedianVolume: the median over the unit element 6 / 18 / 26, `iterations` times
+    int MedianVolume(int element, uint32_t iterations)
+    {
+        const int* dim = volumeReader->dim;
+        const uint16_t* vox = SegVoxels();
+        return ReplaceFiltered([&](uint16_t* out) { return svr_volume_rank(vox, dim[0], dim[1], dim[2], 1, SVR_FILTER_MEDIAN, element, iterations, out); });
+    }
+    // SmoothVolume: binomial smoothing of `sigma` in the units of the volume's spacing, the same length on every axis: the radii are
+    // those of svr_volume_smooth_radii, so an axis with a coarse spacing gets a smaller radius (0 = it is left alone)
+    int SmoothVolume(double sigma)
+    {
+        const int* dim = volumeReader->dim;
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        uint32_t radii[3];
+        if (int rc = svr_volume_smooth_radii(sp, sigma, radii, nullptr)) return rc;
+        const uint16_t* vox = SegVoxels();
+        return ReplaceFiltered([&](uint16_t* out) { return svr_volume_smooth(vox, dim[0], dim[1], dim[2], 1, radii, out); });
+    }
+    // UnfilterVolume: drops the copy; the region methods read the loaded voxels again.  A region made from the copy stays as it is
+    void UnfilterVolume()
+    {
+        if (!filtered) return;
+        svr_device_synchronize();
+        svr_device_free(filtered);
+        filtered = nullptr;
+    }
+    bool HasFiltered() const { return filtered != nullptr; }
+    const uint16_t* FilteredVoxels() const { return filtered; }     // device, [nz][ny][nx]; null without a filter
+    // ShowFiltered: every renderer now draws the filtered copy, until ShowAll or the next volume
+    int ShowFiltered()
+    {
+        if (!ready || !filtered) return -4;
+        return ShowVoxels(filtered);
     }
     void ShowAll()
     {
@@ -656,8 +694,27 @@ private:
         maxSpan *= 1.5f;
         eyeDist = maxSpan / (2 * tan((fov * 0.5f) * 0.01745329251994329576923690768489f));
     }
+    // the voxels that are segmented: the filtered copy when there is one, else the loaded ones (null unless KeepVoxels(true) was set)
+    const uint16_t* SegVoxels() const { return filtered ? filtered : volumeReader->DeviceVoxels(); }
+    // run a filter from SegVoxels() into a fresh buffer; on success that buffer becomes the filtered copy
+    template <typename Call>
+    int ReplaceFiltered(Call call)
+    {
+        if (!ready || !SegVoxels()) return -4;
+        const int* dim = volumeReader->dim;
+        uint16_t* out = (uint16_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint16_t));
+        if (!out) return -4;
+        const int rc = call(out);
+        svr_device_synchronize();
+        if (rc != 0) { svr_device_free(out); return rc; }
+        if (filtered) svr_device_free(filtered);
+        filtered = out;
+        return 0;
+    }
     void ClearRegion()
     {
+        if (filtered) svr_device_free(filtered);
+        filtered = nullptr;
         if (regionTex) svr_destroy_texture(regionTex);
         if (regionMask) svr_device_free(regionMask);
         if (regionWork) svr_device_free(regionWork);
@@ -686,7 +743,7 @@ private:
     // the second mask buffer, into which the clean-up calls write (their `out` must not overlap their input)
     bool WorkMask()
     {
-        if (!ready || !volumeReader->DeviceVoxels() || !haveRegion) return false;
+        if (!ready || !SegVoxels() || !haveRegion) return false;
         const int* dim = volumeReader->dim;
         if (!regionWork) regionWork = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
         return regionWork != nullptr;
@@ -698,7 +755,7 @@ private:
         std::swap(regionMask, regionWork);
         if (!stats) return 0;
         const int* dim = volumeReader->dim;
-        return svr_region_stats_of(volumeReader->DeviceVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats);
+        return svr_region_stats_of(SegVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats);
     }
     // label the region, tabulate its components, keep those of at least min_voxels voxels among the largest_k largest (0 = no limit)
     int SelectRegionParts(uint32_t min_voxels, uint32_t largest_k, int connectivity, svr_region_stats* stats)
@@ -711,7 +768,7 @@ private:
         int rc = svr_region_label(regionMask, dim[0], dim[1], dim[2], connectivity, labels, &count);
         if (rc == 0 && count == 0u) {                                           // an empty region has no component: it stays empty
             svr_device_free(labels);
-            return stats ? svr_region_stats_of(volumeReader->DeviceVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats) : 0;
+            return stats ? svr_region_stats_of(SegVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats) : 0;
         }
         svr_region_component* table = rc == 0 ? (svr_region_component*)svr_device_malloc((size_t)count * sizeof(svr_region_component)) : nullptr;
         if (rc == 0 && !table) rc = -4;
@@ -746,6 +803,7 @@ private:
     bool haveSeed = false;                         // false after ThresholdRegion: the region then comes from no pick
     cudaTextureObject_t regionTex = 0;             // ShowRegion's masked volume
     bool haveRegion = false;
+    uint16_t* filtered = nullptr;                  // MedianVolume / SmoothVolume's copy of the voxels (device)
     svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
     svr_slice_params slice = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, 0.f, 1.f, SVR_SLAB_MIP, 0u, 0.f, 1.f};
 };

@@ -872,6 +872,46 @@ int svr_region_distance_last_ms(float* ms);
  * Pointers may be NULL */
 int svr_region_distance_pass_ms(float* rows_ms, float* y_ms, float* z_ms);
 
+/* ---- exact volume filters: median / min / max and binomial smoothing of the raw voxels, before they are segmented
+ *      (csrc/svr_filter.hip) ----
+ * A volume is a u16 array [nz][ny][nx], host or device (src_is_device), as in svr_region_grow; `out` is DEVICE memory of nx ny nz u16
+ * and is ready for svr_create_volume_texture and for every svr_region_* call.  The calls are stateless: they run on the library's
+ * stream and touch no scene, option or accumulator.  Integers only; every result is exact and unique, whatever order the GPU works in.
+ * BORDER: it replicates.  A neighbour index outside the volume is clamped per axis, so a window always holds its full count of values
+ *   (with repeats) and a binomial sum all its taps: numpy's pad mode 'edge', scipy's mode='nearest'.
+ * RANK: the window of a voxel is the voxel and its neighbours under the unit element 6 / 18 / 26 of svr_region_morph: 7 / 19 / 27 values.
+ *   SVR_FILTER_MEDIAN = the value of rank 3 / 9 / 13 (0-based) of the sorted window, SVR_FILTER_MIN = rank 0, SVR_FILTER_MAX = the last
+ *   rank; values are compared as unsigned 16-bit numbers.  `iterations` in 1 .. SVR_FILTER_MAX_ITERATIONS applies the filter that many
+ *   times to its own output.  This is scipy.ndimage.median_filter / minimum_filter / maximum_filter with
+ *   footprint=generate_binary_structure(3, 1 | 2 | 3) and mode='nearest'.
+ * SMOOTH: separable binomial smoothing.  radii_xyz is a HOST array of three uint32 (x, y, z), each in 0 .. SVR_SMOOTH_MAX_RADIUS; the
+ *   passes run in the order x, y, z, and a pass of radius r > 0 along an axis replaces v[i] by
+ *     (sum_{k = 0 .. 2r} C(2r, k) v[clamp(i - r + k)] + 2^(2r - 1)) >> 2r
+ *   -- the binomial kernel of order 2r, rounded half up ONCE PER AXIS, so the result of a pass is a u16 volume again and the whole is
+ *   defined by the passes alone.  The sum is at most 65535 * 4^8 + 2^15 < 2^32: it fits an unsigned 32-bit integer exactly, which is what
+ *   caps the radius at 8.  Radius 0 is the identity on its axis; (0, 0, 0) is a copy.  The variance of a pass is r / 2 voxels^2, so
+ *   radius 8 is sigma = 2 voxels.
+ * RADII FROM A SIGMA (plain host code): radii[a] = llround(2 (sigma / spacing[a])^2), the radius whose variance is nearest to sigma^2 in
+ *   the spacing's units; sigma_out[a] (may be NULL) = sqrt(radii[a] / 2) spacing[a], the sigma actually applied.  sigma = 0 gives 0, 0, 0.
+ * WORKSPACE AND SYNCHRONISATION: a call with more than one pass (iterations > 1; more than one radius > 0) allocates one temporary
+ *   volume of nx ny nz u16 and frees it, and a host source is uploaded to a temporary; such calls synchronise the stream before they
+ *   return.  A one-pass call on a device source, and the (0, 0, 0) copy of one, are asynchronous.  `voxels` is never written.
+ * REFUSED, before the device is touched and with nothing written: a null pointer (-4); a dimension <= 0 or more than 2^31 voxels (-6);
+ *   an unknown op, an element other than 6 / 18 / 26, iterations of 0 or above the cap, a radius above 8, an `out` that overlaps a device
+ *   `voxels`; for svr_volume_smooth_radii a spacing that is not positive and finite, a sigma that is negative or not finite, or one that
+ *   needs a radius above 8 on some axis (-3). */
+#define SVR_FILTER_MEDIAN 1
+#define SVR_FILTER_MIN    2
+#define SVR_FILTER_MAX    3
+#define SVR_FILTER_MAX_ITERATIONS 64
+#define SVR_SMOOTH_MAX_RADIUS 8
+int svr_volume_rank(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, int op, int element, uint32_t iterations,
+                    uint16_t* out_u16_device);
+int svr_volume_smooth(const uint16_t* voxels, int nx, int ny, int nz, int src_is_device, const uint32_t* radii_xyz, uint16_t* out_u16_device);
+int svr_volume_smooth_radii(const double spacing[3], double sigma, uint32_t radii[3], double sigma_out[3]);
+/* HIP-event time of the device work of the last svr_volume_rank / svr_volume_smooth call (waits for it) */
+int svr_volume_filter_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

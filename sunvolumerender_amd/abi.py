@@ -295,6 +295,9 @@ MASK_AND, MASK_OR, MASK_ANDNOT, MASK_XOR, MASK_NOT = 1, 2, 3, 4, 5
 DIST_NONE = 0xFFFFFFFF
 DIST_TO_SET, DIST_TO_UNSET = 1, 2
 DISTANCE_COLUMN_BLOCK = 256  # SVR_DISTANCE_COLUMN_BLOCK of csrc/svr_distance.hip: the columns of a column pass that one block covers
+FILTER_MEDIAN, FILTER_MIN, FILTER_MAX = 1, 2, 3
+FILTER_MAX_ITERATIONS = 64
+SMOOTH_MAX_RADIUS = 8
 
 
 EXPECTED_SIZES = {
@@ -481,6 +484,10 @@ PROTOTYPES = {
     "svr_region_distance_weights": (C.c_int, [_P(C.c_double), C.c_int, C.c_int, C.c_int, _P(C.c_uint32), _P(C.c_double)]),
     "svr_region_distance_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_region_distance_pass_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "svr_volume_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "svr_volume_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_void_p]),
+    "svr_volume_smooth_radii": (C.c_int, [_P(C.c_double), C.c_double, _P(C.c_uint32), _P(C.c_double)]),
+    "svr_volume_filter_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

@@ -649,6 +649,46 @@ class Device:
         self.check(self.lib.svr_region_distance_pass_ms(*[C.byref(t) for t in ms]))
         return tuple(float(t.value) for t in ms)
 
+    # ---- exact volume filters (svr_volume_*): median / min / max and binomial smoothing of the raw voxels ----
+    def volume_rank(self, vox, op: int, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
+        """svr_volume_rank: the median (FILTER_MEDIAN), minimum (FILTER_MIN) or maximum (FILTER_MAX) of every voxel's window under the
+        unit element 6 / 18 / 26 with a replicated border, applied `iterations` times.  vox is a host [nz][ny][nx] u16 array, or a device
+        pointer with shape=(nz, ny, nx).  Returns a u16 array [nz][ny][nx]; with out_ptr (a device buffer of nx * ny * nz u16 that does
+        not overlap a device `vox`) the result stays on the device and out_ptr is returned."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        return self._volume_filter((nz, ny, nx), out_ptr, lambda out: self.lib.svr_volume_rank(
+            src, nx, ny, nz, on_dev, int(op), int(element), int(iterations), C.c_void_p(out)))
+
+    def volume_median(self, vox, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
+        """volume_rank with FILTER_MEDIAN."""
+        return self.volume_rank(vox, abi.FILTER_MEDIAN, element, iterations, shape, out_ptr)
+
+    def volume_smooth(self, vox, radii, shape=None, out_ptr: Optional[int] = None):
+        """svr_volume_smooth: separable binomial smoothing with the per-axis radii (rx, ry, rz), each 0 .. SMOOTH_MAX_RADIUS, one
+        rounding per axis, a replicated border.  vox, the return value and out_ptr as in volume_rank."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        r = (C.c_uint32 * 3)(*[int(t) for t in radii])
+        return self._volume_filter((nz, ny, nx), out_ptr, lambda out: self.lib.svr_volume_smooth(src, nx, ny, nz, on_dev, r, C.c_void_p(out)))
+
+    def _volume_filter(self, shape, out_ptr, call):
+        nz, ny, nx = shape
+        out = out_ptr if out_ptr is not None else self.malloc(2 * max(nx * ny * nz, 1))
+        try:
+            self.check(call(out))
+            self.synchronize()
+            if out_ptr is not None:
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint16)
+        finally:
+            if out_ptr is None:
+                self.free(out)
+
+    def volume_filter_last_ms(self) -> float:
+        """HIP-event time of the device work of the last volume_rank / volume_smooth call."""
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_volume_filter_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
         """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
         m = abi.RegionMeasurement()
@@ -686,6 +726,21 @@ def distance_weights(spacing, shape, lib=None):
         lib.svr_clear_error()
         raise SvrError(f"svr_region_distance_weights failed ({rc}): {msg}")
     return (int(w[0]), int(w[1]), int(w[2])), float(unit.value)
+
+
+def smooth_radii(spacing, sigma, lib=None):
+    """svr_volume_smooth_radii: ((rx, ry, rz), (sx, sy, sz)) for a spacing and a sigma in the spacing's units: the binomial radii
+    llround(2 (sigma / spacing[a])^2) and the sigma each one applies, sqrt(r / 2) spacing[a].  Host code of the library: no device is
+    needed."""
+    lib = lib if lib is not None else abi.load()
+    sp = (C.c_double * 3)(*[float(t) for t in spacing])
+    r, so = (C.c_uint32 * 3)(), (C.c_double * 3)()
+    rc = lib.svr_volume_smooth_radii(sp, float(sigma), r, so)
+    if rc != 0:
+        msg = lib.svr_last_error().decode()
+        lib.svr_clear_error()
+        raise SvrError(f"svr_volume_smooth_radii failed ({rc}): {msg}")
+    return (int(r[0]), int(r[1]), int(r[2])), (float(so[0]), float(so[1]), float(so[2]))
 
 
 def region_mask_words(shape) -> int:
