@@ -2625,8 +2625,8 @@ int svr_set_option(int key, int value)
 #ifdef SVR_TEST_HOOKS
     // experiment builds only (tools/exp.py; `SVR_EXTRA_HIPCC_FLAGS=-DSVR_TEST_HOOKS python -m sunvolumerender_amd._build --force`)
     case 100: g.opt_debug_stop = value; return 0;      // timing ablation: stop every path after a phase (wrong images)
-    case 101: g.opt_unit = value; return 0;            // tasks per ticket of the tile kernel
 #endif
+    case 101: g.opt_unit = value; return 0;            // tasks per ticket of the tile kernel (0: one; placement only -- tests/test_task_loop_gpu.py)
     case SVR_OPT_FRAME_AHEAD: g.opt_frame_ahead = value ? 1 : 0; g.ahead[0].valid = g.ahead[1].valid = false; return 0;
     case SVR_OPT_RAYCAST_LANES_LOG2:
         if (value < 0 || value > 5) return fail(-6, "SVR_OPT_RAYCAST_LANES_LOG2: bad value %d (0..5)", value);

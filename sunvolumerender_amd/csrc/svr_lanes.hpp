@@ -30,7 +30,9 @@ namespace svr {
 // Phase profile of experiment builds (-DSVR_TEST_HOOKS): per phase, shader cycles the waves spent in it and the same
 // weighted by the lanes that had work there (-> lane utilisation per phase); read with svr_debug_phase_profile.
 enum { PH_PRIMARY = 0, PH_REFILL, PH_SHADE, PH_CHEAP, PH_FETCH, PH_MARCH, PH_END, PH_FOLD, PH_N };
-constexpr uint32_t PROF_WORDS = 2 * PH_N + 2;     // + cheap-loop iterations, + walking lanes summed over them
+// the tile kernel's task loop, behind the words above (tools/phase_prof.py): the wait for a ticket's value, and a wave's whole loop over the tickets
+enum { PH_TICKET = PH_N + 1, PH_LOOP, PH_END_ALL };
+constexpr uint32_t PROF_WORDS = 2 * PH_END_ALL;   // 2 * PH_N: cheap-loop iterations, 2 * PH_N + 1: walking lanes summed over them
 #ifdef SVR_TEST_HOOKS
 #define SVR_PROF 1
 struct ProfScope {

@@ -140,6 +140,15 @@ inline hipError_t task_launch_setup(const DevWork& w, const LaunchCfg& cfg, uint
 // order as nframes calls of the reference -- and the accumulator is read and written once per launch (12 B per
 // pixel) instead of once per frame.  clear_hdr_buffer (pathtracer.cu:86-94) is the frame0 == 0 case.
 // rows: [task * 3 + channel] rows of `row` floats (this wave's), tasks: their task numbers
+// AHEAD (SVR_FOLD_LOAD_AHEAD; rows in GLOBAL memory: the traceDepth-1 QUEUE builds of the tile kernel, the local-majorant pools): the chain of divisions had
+// one exposed load round trip in front of every link (global_load, s_waitcnt vmcnt(0), 13 dependent instructions; 2 x 64 links per 32 tasks
+// of the headline launch).  The samples of FOLD_CHUNK frames are loaded together, then folded in frame order: c3 + 1.4 % ... + 2.3 % (two boxes)
+// (profiles/r06_notes_experiments.txt).  Rows in LDS (the straight-line builds, 4 pending tasks) keep the plain loop: they lost 0.9 % with it.
+#ifndef SVR_FOLD_LOAD_AHEAD
+#define SVR_FOLD_LOAD_AHEAD 1
+#endif
+constexpr uint32_t FOLD_CHUNK = 8;
+template <bool AHEAD = true>
 SVR_DEV void fold_pending(const DevScene& s, const DevWork& w, const float* rows, uint32_t row, const uint32_t* tasks, uint32_t npend)
 {
     const TaskShape ts = task_shape(w);
@@ -169,7 +178,20 @@ SVR_DEV void fold_pending(const DevScene& s, const DevWork& w, const float* rows
                 acc = acc + (Lf - acc) / n1;
             }
         } else {
-            for (uint32_t f = 0; f < nfr; ++f) {
+            uint32_t f = 0;
+            if constexpr (AHEAD && SVR_FOLD_LOAD_AHEAD) {
+                for (; f + FOLD_CHUNK <= nfr; f += FOLD_CHUNK) {
+                    float Lv[FOLD_CHUNK];
+#pragma unroll
+                    for (uint32_t j = 0; j < FOLD_CHUNK; ++j) Lv[j] = rp[(f + j) << ts.P2];
+#pragma unroll
+                    for (uint32_t j = 0; j < FOLD_CHUNK; ++j) {
+                        const float n1 = (float)(w.frame0 + f + j) + 1.f;
+                        acc = acc + (Lv[j] - acc) / n1;
+                    }
+                }
+            }
+            for (; f < nfr; ++f) {
                 const float Lf = rp[f << ts.P2];
                 const float n1 = (float)(w.frame0 + f) + 1.f;
                 acc = acc + (Lf - acc) / n1;

@@ -34,6 +34,12 @@ for setting in a.settings:
         cyc, lc = float(out[2 * i]), float(out[2 * i + 1])
         if cyc:
             print(f"   {n:8s} {cyc / tot * 100:6.2f} %   util {lc / cyc / 64 * 100:5.1f} %")
+    # the tile kernel's task loop (svr_lanes.hpp: PH_TICKET = 9, PH_LOOP = 10): the waves' whole loops, and their waits for a ticket's value
+    loop, ticket = float(out[20]), float(out[18])
+    if loop:
+        print(f"   task loop {loop:.4g} wave-cycles = 100 %: ticket wait {ticket / loop * 100:.2f} %, " +
+              ", ".join(f"{n} {float(out[2 * i]) / loop * 100:.2f} %" for i, n in enumerate(names) if out[2 * i]) +
+              f", unstamped {(loop - ticket - tot) / loop * 100:.2f} %")
     if out[16]:
         if a.depth > 1:
             print(f"   cheap-loop iterations {int(out[16])}, mean walking lanes {float(out[17]) / float(out[16]):.1f}")
