@@ -25,12 +25,15 @@
 // -ball-dilate L, -ball-erode L, -ball-open L and -ball-close L are clean-up steps too, by a true ball of radius L > 0 in the units of the
 // volume's spacing (Canvas::BallMorphRegion: the exact Euclidean distance map, any radius at the same cost); each prints the measurements
 // of what is left.  -thickness prints, after the last step, the largest ball inscribed in the region and its centre voxel.
+// -split L is the step that separates objects which touch: necks thinner than a ball of radius L > 0 are cut (Canvas::SplitRegion: erode
+// by the ball, label the cores under -conn, give every voxel to the core nearest inside the region, take a cut of one voxel between the
+// parts); it prints the number of parts, and -largest / -minsize after it choose among them.
 // -median E N and -smooth SIGMA filter the voxels BEFORE they are segmented, in command-line order (Canvas::MedianVolume: the median over
 // the unit element E = 6|18|26, N = 1 .. 64 times; Canvas::SmoothVolume: binomial smoothing of SIGMA > 0 in the units of the volume's
 // spacing): -grow and -threshold then work on the filtered copy, and so does what they show.  -show-filtered draws the filtered copy
 // in place of the loaded volume.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -43,7 +46,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -58,8 +61,8 @@ int main(int argc, char** argv)
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
     bool threshold = false;                                         // -threshold: the whole window growLo .. growHi, no pick
-    struct CleanStep { const char* name; int op; uint32_t radius; double length; };   // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N), -10 - SVR_MORPH_* = -ball-* (length: L)
-    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize / -ball-*, in order
+    struct CleanStep { const char* name; int op; uint32_t radius; double length; };   // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N), -5 = -split (length: L), -10 - SVR_MORPH_* = -ball-* (length: L)
+    std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize / -ball-* / -split, in order
     int cleanElement = 6;
     bool thickness = false;                                         // -thickness: the largest inscribed ball of the final region
     struct FilterStep { int element; uint32_t iterations; double sigma; };     // -median E N (element != 0) or -smooth SIGMA
@@ -105,6 +108,16 @@ int main(int argc, char** argv)
                 return 2;
             }
             cleanSteps.push_back(CleanStep{argv[i], -10 - op, 0u, len});
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-split")) {
+            char* end = nullptr;
+            const double len = i + 1 < argc ? strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(len > 0.0) || !std::isfinite(len)) {
+                fprintf(stderr, "-split needs a neck radius L > 0 in the units of the spacing (got %s)\n", i + 1 < argc ? argv[i + 1] : "nothing");
+                return 2;
+            }
+            cleanSteps.push_back(CleanStep{argv[i], -5, 0u, len});
             ++i;
         }
         else if (!strcmp(argv[i], "-median")) {
@@ -339,7 +352,7 @@ int main(int argc, char** argv)
                        st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
             if (!cleanSteps.empty()) {
                 std::string done;
-                bool plainSteps = false;                           // a step other than -largest / -minsize: those print their own lines
+                bool plainSteps = false;                           // a step other than -largest / -minsize / -ball-* / -split: those print their own lines
                 for (const CleanStep& c : cleanSteps) {
                     if (c.op <= -10) {
                         uint32_t w[3] = {0u, 0u, 0u};
@@ -357,6 +370,22 @@ int main(int argc, char** argv)
                         char len[32];
                         snprintf(len, sizeof len, "%g", c.length);
                         done += std::string(done.empty() ? "" : " ") + (c.name + 1) + " " + len;
+                        continue;
+                    }
+                    if (c.op == -5) {
+                        uint32_t parts = 0u;
+                        int rc = canvas.SplitRegion(c.length, growConn, &parts, &st);
+                        if (rc == 0) rc = svr_region_measure(&st, sp, &m);
+                        if (rc != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                        if (st.status == SVR_REGION_STATUS_EMPTY)
+                            printf("split %g conn %d: %u parts; the region is empty\n", c.length, growConn, parts);
+                        else
+                            printf("split %g conn %d: %u parts, %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
+                                   c.length, growConn, parts, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                                   st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+                        char len[32];
+                        snprintf(len, sizeof len, "%g", c.length);
+                        done += std::string(done.empty() ? "" : " ") + "split " + len;
                         continue;
                     }
                     if (c.op <= -3) {

@@ -597,6 +597,62 @@ public:
         svr_device_free(labels);
         return rc;
     }
+    // Splitting and path lengths (svr_region_split / _zone_cut / _geodesic; include/svr_abi.h, "geodesic distances and influence zones").
+    // SplitRegion: separates objects of the region that touch through necks thinner than a ball of neck_radius (> 0, finite, in the
+    // spacing's units): the region is eroded by that ball, the cores are labelled under `connectivity`, every voxel goes to the core
+    // nearest inside the region (moves weighted by their Euclidean length: svr_region_geodesic_weights) and a cut of one voxel is taken
+    // between different parts.  *parts = the number of cores; the cut mask replaces the region like MorphRegion, so CountRegionParts,
+    // KeepLargestRegion, RemoveSmallRegions and ShowRegion follow.  No core (*parts = 0) leaves an empty region, return 0
+    int SplitRegion(double neck_radius, int connectivity, uint32_t* parts, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask() || !parts) return -4;
+        if (!(neck_radius > 0.0) || !std::isfinite(neck_radius)) return -3;
+        uint32_t w[3], steps[7];
+        double unit = 0.0, step_unit = 0.0;
+        if (int rc = RegionDistanceUnits(w, &unit)) return rc;
+        const int* dim = volumeReader->dim;
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        if (int rc = svr_region_geodesic_weights(sp, connectivity, dim[0], dim[1], dim[2], steps, &step_unit)) return rc;
+        uint32_t* zones = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
+        if (!zones) return -4;
+        uint32_t count = 0u, unreached = 0u;
+        int rc = svr_region_split(regionMask, dim[0], dim[1], dim[2], w, LengthToR2(neck_radius, unit), connectivity, steps, 0u, zones, &count, &unreached,
+                                  nullptr);
+        if (rc == 0) rc = svr_region_zone_cut(zones, dim[0], dim[1], dim[2], connectivity, regionWork);
+        svr_device_free(zones);                                                 // (waits for the cut, which is asynchronous)
+        if (rc == 0) *parts = count;
+        return ReplaceRegion(rc, stats);
+    }
+    // RegionPathLength: *length = the length, in the spacing's units, of the shortest way inside the region between the voxels of two
+    // picks (FOUND records of Pick / HitMap), by 26-moves weighted with their Euclidean lengths (about *length = d * unit; the chamfer
+    // error is stated in include/svr_abi.h).  Returns SVR_REGION_STATUS_OK, or SVR_REGION_STATUS_EMPTY (length 0) when there is no way --
+    // one of the voxels lies outside the region, or they lie in different parts of it; negative on an error.  The region stays as it is
+    int RegionPathLength(const svr_hit& from, const svr_hit& to, double* length)
+    {
+        if (!ready || !SegVoxels() || !haveRegion || !length) return -4;
+        if (from.status != SVR_HIT_STATUS_FOUND || to.status != SVR_HIT_STATUS_FOUND) return -4;
+        const int* dim = volumeReader->dim;
+        int32_t a[3], b[3];
+        if (int rc = svr_region_seed_from_world(&deviceVolume, dim[0], dim[1], dim[2], &from.position, a)) return rc;
+        if (int rc = svr_region_seed_from_world(&deviceVolume, dim[0], dim[1], dim[2], &to.position, b)) return rc;
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        uint32_t steps[7];
+        double unit = 0.0;
+        if (int rc = svr_region_geodesic_weights(sp, 26, dim[0], dim[1], dim[2], steps, &unit)) return rc;
+        const size_t n = (size_t)dim[0] * dim[1] * dim[2];
+        uint32_t* labels = (uint32_t*)svr_device_malloc(n * sizeof(uint32_t));
+        uint32_t* dist = (uint32_t*)svr_device_malloc(n * sizeof(uint32_t));
+        int rc = labels && dist ? 0 : -4;
+        if (rc == 0) rc = svr_region_seed_labels(a, 1u, dim[0], dim[1], dim[2], labels);
+        if (rc == 0) rc = svr_region_geodesic(labels, regionMask, dim[0], dim[1], dim[2], steps, 0u, dist, nullptr, nullptr);
+        uint32_t d = SVR_GEO_NONE;
+        if (rc == 0) rc = svr_memcpy_d2h(&d, dist + (((size_t)b[2] * dim[1] + b[1]) * dim[0] + b[0]), sizeof d);
+        if (labels) svr_device_free(labels);
+        if (dist) svr_device_free(dist);
+        if (rc != 0) return rc;
+        *length = d == SVR_GEO_NONE ? 0.0 : (double)d * unit;
+        return d == SVR_GEO_NONE ? SVR_REGION_STATUS_EMPTY : SVR_REGION_STATUS_OK;
+    }
     // ShowRegion: every renderer now draws the volume with the voxels outside (SVR_REGION_KEEP) or inside (SVR_REGION_REMOVE) the grown
     // region set to `fill`; ShowAll goes back to the loaded volume.  The Canvas owns the extra texture
     int ShowRegion(int mode, uint32_t fill)

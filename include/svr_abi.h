@@ -793,7 +793,8 @@ int svr_region_mask_last_ms(float* ms);
  *   SVR_REGION_ERR_LABEL with the labels invalid; it does not go on.
  * TABLE (svr_region_component[count], indexed by label - 1): voxels = the component's size; first = its smallest linear voxel index;
  *   bbox_min, bbox_max = its inclusive bounds in x, y, z; sum = the sum of the raw values over it (0 when voxels_or_null is NULL).
- *   Labels above `count` are ignored.  Asynchronous for a device source or none.
+ *   Labels above `count` are ignored.  Any label array will do, not only svr_region_label's: a voxel counts for the entry of its label,
+ *   whatever its neighbours hold (the zones of svr_region_split).  Asynchronous for a device source or none.
  * SELECT: out = the voxels whose label has a non-zero entry in keep_device (uint8 [count + 1], indexed by label; entry 0 is ignored:
  *   background never enters; labels above count are dropped).  Asynchronous.
  * SELECT BY SIZE: keeps the components with at least min_voxels voxels that are among the largest_k largest (0 = no limit); ties in size
@@ -911,6 +912,69 @@ int svr_volume_smooth(const uint16_t* voxels, int nx, int ny, int nz, int src_is
 int svr_volume_smooth_radii(const double spacing[3], double sigma, uint32_t radii[3], double sigma_out[3]);
 /* HIP-event time of the device work of the last svr_volume_rank / svr_volume_smooth call (waits for it) */
 int svr_volume_filter_last_ms(float* ms);
+
+/* ---- geodesic distances and influence zones inside region masks; splitting a region at its necks (csrc/svr_geodesic.hip;
+ *      DESIGN.md 8m) ----
+ * Masks are DEVICE pointers in the layout above; input padding bits are ignored whatever they hold, output padding bits are 0.  Label,
+ * distance and zone arrays are dense uint32 [nz][ny][nx] on the device.  The calls are stateless: they run on the library's stream and
+ * touch no scene, option or accumulator.  Integers only; every result is exact and unique, whatever order the GPU works in.
+ * MOVES AND WEIGHTS: a move changes one, two or three coordinates of a voxel by +-1; its class is the set of coordinates it changes.
+ *   `step_weights` is a HOST array of seven uint32, one per class in the order x, y, z, xy, xz, yz, xyz: the cost of a move of the class.
+ *   A weight of 0 forbids the class (6-connectivity is w, w, w, 0, 0, 0, 0; 18-connectivity has the last weight 0); NULL means the chamfer
+ *   weights 3, 3, 3, 4, 4, 4, 5.  A shortest path visits no voxel twice, and since a voxel has one writer and its value only falls, every
+ *   value that is ever stored is the cost of such a path: at most wmax (nx ny nz - 1).  A call is refused when that product, taken in
+ *   64-bit host arithmetic, exceeds 0xFFFFFFFE, and the device needs no overflow check.
+ * GEODESIC: the sources are the voxels of the domain mask whose marker label is non-zero (0 = no marker; any other 32-bit value is a
+ *   label, e.g. what svr_region_label writes; a label outside the domain is ignored).  dist(v) = the cost of the cheapest path of allowed
+ *   moves from any source to v that stays inside the domain; zone(v) = the SMALLEST label among the sources that attain dist(v).
+ *   Equivalently key = (dist, zone) is (0, label) on a source and elsewhere in the domain the lexicographic minimum over the allowed
+ *   neighbours u in the domain of (dist(u) + w(u -> v), zone(u)); weights >= 1 make that system's solution unique.  dist is
+ *   SVR_GEO_NONE and zone 0 outside the domain and where no source reaches.  Either output may be NULL, not both; zones_device may be
+ *   marker_labels_device itself.  With no source at all every dist is SVR_GEO_NONE, every zone 0, and the return is 0.
+ *   The work is chaotic relaxation of packed 64-bit keys in tiles of 32 x 8 x 8 voxels, swept until a sweep lowers nothing; workspace
+ *   8 bytes per voxel, allocated and freed by the call, which synchronises the stream.  *sweeps_out (may be NULL) = the sweeps launched.
+ * SWEEPS: a sweep finishes every voxel whose shortest path crosses one tile face more than those finished before, so C + 2 sweeps are
+ *   enough when no shortest path needs more than C crossings; 968 T + 2 (T tiles, 968 voxels on the faces of each) always is, and is no
+ *   use as a guard.  max_sweeps = 0 means svr_region_geodesic_default_max_sweeps = min(64 + 16 T, 65536): shortest paths that enter a
+ *   tile 16 times on average, e.g. one-voxel corridors between one-voxel walls along x.  A domain that winds more needs max_sweeps from
+ *   the caller.  At the cap the call returns SVR_REGION_ERR_SWEEPS; the outputs then hold upper bounds and are NOT valid, *sweeps_out
+ *   holds the launches, and the call does not go on.
+ * SEED LABELS: zero-fills labels_device and gives the voxel of seed i (a HOST array of (x, y, z), as in svr_region_grow) the label i + 1;
+ *   of several seeds on one voxel the lowest i wins.  Asynchronous.
+ * WEIGHTS FROM A SPACING (plain host code): unit = min(spacing) / 2^k for the largest k in 3, 2, 1, 0 whose weights
+ *   w = max(1, llround(len / unit)), len the Euclidean length of a move of the class in the spacing's units, pass the overflow bound; the
+ *   classes beyond `connectivity` (6: one coordinate, 18: up to two, 26: all) get 0.  An isotropic spacing gives 8, 11, 14 at k = 3.  A map
+ *   value d then means about d unit.  CHAMFER ERROR: a path of moves is never shorter than the straight line; with exact move lengths and
+ *   no obstacle it is longer by at most 12.8 % (26), 22.5 % (18: sqrt(1.5)) or 73.2 % (6: sqrt(3)) in the worst direction, and the rounding
+ *   of a weight moves it by at most 0.5 / w (6 % at k = 3).  The chamfer weights 3, 4, 5 give between 5.7 % less
+ *   and 10.6 % more than three times the Euclidean length.
+ * SPLIT: E = svr_region_ball(in, SVR_MORPH_ERODE, dist_weights, r2); (labels, K) = svr_region_label(E, connectivity); zones = the zones
+ *   of those labels inside `in`.  NULL step weights mean the chamfer weights with the classes beyond `connectivity` set to 0.
+ *   *count_out = K: zone k is the part of `in` around the k-th core in svr_region_label's numbering.  *unreached_out = the voxels of `in`
+ *   with zone 0: pieces too thin to hold a core.  K = 0 gives all zeros, unreached = |in| and return 0.  The zones feed
+ *   svr_region_label_table, svr_region_select and svr_region_select_by_size unchanged.  Workspace: that of the three steps, one after
+ *   the other, and one mask.  count_out, unreached_out are required, sweeps_out may be NULL.  Synchronises.
+ * ZONE CUT: a voxel is kept iff its zone is non-zero and none of its connectivity-neighbours inside the volume has a non-zero zone that
+ *   is SMALLER: of every adjacent pair in different zones the larger label goes, so the cut is one voxel thick and every connected
+ *   component of `out` lies in one zone.  Asynchronous.
+ * REFUSED, before the device is touched and with nothing written: a null pointer where one is required, or both outputs NULL (-4); a
+ *   dimension <= 0 or more than 2^31 voxels (-6); all seven weights 0, the overflow bound, a connectivity other than 6 / 18 / 26, nseeds
+ *   == 0 or > SVR_REGION_MAX_SEEDS, a seed outside the volume, the weight and bound refusals of svr_region_ball for dist_weights, an `out`
+ *   that overlaps an input other than zones over marker labels, a spacing that is not positive and finite or that no k fits (-3). */
+#define SVR_GEO_NONE 0xFFFFFFFFu
+uint32_t svr_region_geodesic_default_max_sweeps(int nx, int ny, int nz);
+int svr_region_geodesic(const uint32_t* marker_labels_device, const uint32_t* domain_mask_device, int nx, int ny, int nz,
+                        const uint32_t* step_weights_or_null, uint32_t max_sweeps, uint32_t* dist_device_or_null, uint32_t* zones_device_or_null,
+                        uint32_t* sweeps_out);
+int svr_region_seed_labels(const int32_t* seeds_xyz, uint32_t nseeds, int nx, int ny, int nz, uint32_t* labels_device);
+int svr_region_geodesic_weights(const double spacing[3], int connectivity, int nx, int ny, int nz, uint32_t weights[7], double* unit_out);
+int svr_region_split(const uint32_t* in_mask_device, int nx, int ny, int nz, const uint32_t* dist_weights_or_null, uint32_t r2, int connectivity,
+                     const uint32_t* step_weights_or_null, uint32_t max_sweeps, uint32_t* zones_device, uint32_t* count_out, uint32_t* unreached_out,
+                     uint32_t* sweeps_out);
+int svr_region_zone_cut(const uint32_t* zones_device, int nx, int ny, int nz, int connectivity, uint32_t* out_mask_device);
+/* HIP-event time of the device work of the last svr_region_geodesic, the zones step of the last svr_region_split, or the last
+ * svr_region_seed_labels / svr_region_zone_cut, whichever came last (waits for it) */
+int svr_region_geodesic_last_ms(float* ms);
 
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);

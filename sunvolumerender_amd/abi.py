@@ -298,6 +298,8 @@ DISTANCE_COLUMN_BLOCK = 256  # SVR_DISTANCE_COLUMN_BLOCK of csrc/svr_distance.hi
 FILTER_MEDIAN, FILTER_MIN, FILTER_MAX = 1, 2, 3
 FILTER_MAX_ITERATIONS = 64
 SMOOTH_MAX_RADIUS = 8
+GEO_NONE = 0xFFFFFFFF
+GEO_TILE = (32, 8, 8)     # the relaxation tile of csrc/svr_geodesic.hip in voxels (x, y, z)
 
 
 EXPECTED_SIZES = {
@@ -488,6 +490,14 @@ PROTOTYPES = {
     "svr_volume_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_void_p]),
     "svr_volume_smooth_radii": (C.c_int, [_P(C.c_double), C.c_double, _P(C.c_uint32), _P(C.c_double)]),
     "svr_volume_filter_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_region_geodesic_default_max_sweeps": (C.c_uint32, [C.c_int, C.c_int, C.c_int]),
+    "svr_region_geodesic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_uint32, C.c_void_p, C.c_void_p, _P(C.c_uint32)]),
+    "svr_region_seed_labels": (C.c_int, [_P(C.c_int32), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "svr_region_geodesic_weights": (C.c_int, [_P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), _P(C.c_double)]),
+    "svr_region_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_uint32, C.c_int, _P(C.c_uint32), C.c_uint32, C.c_void_p,
+                                   _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
+    "svr_region_zone_cut": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "svr_region_geodesic_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

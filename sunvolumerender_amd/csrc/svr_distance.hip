@@ -368,6 +368,11 @@ float elapsed(hipEvent_t a, hipEvent_t b)
 
 } // namespace
 
+int svr::check_distance_weights(const char* who, const unsigned* weights_or_null, int nx, int ny, int nz, unsigned w[3])
+{
+    return check_weights(who, weights_or_null, nx, ny, nz, w);
+}
+
 extern "C" {
 
 int svr_region_distance(const uint32_t* in_mask_device, int nx, int ny, int nz, const uint32_t* weights_or_null, int target, uint32_t* d2_device)

@@ -8,6 +8,8 @@ namespace svr {
 int report_error(int code, const char* msg);   // records (or, in fatal mode, prints and exits); returns code
 int ensure_ready();                            // device selected, context created; 0 on success
 hipStream_t current_stream();                  // the caller's stream (svr_set_stream)
+// svr_distance.hip: w = the three weights of a distance call (NULL = 1, 1, 1); refuses a weight of 0 and the overflow bound (-3)
+int check_distance_weights(const char* who, const unsigned* weights_or_null, int nx, int ny, int nz, unsigned w[3]);
 
 inline int failf(int code, const char* fmt, ...)
 {

@@ -29,7 +29,8 @@
 //   chain is longer -- and at the cap sets an error word and leaves: the host returns SVR_REGION_ERR_LABEL.  A tree's root is the smallest
 //   index in it (induction over the links), two nodes share a root exactly when a chain of unions joins them, so after flatten L[start]
 //   is the component's smallest voxel index whatever order the unions landed in, and the numbering by ascending root is unique.
-// TABLE (k_label_table): one lane per voxel, 32 per mask word; the mask is label != 0.  The first lane of a run collects the run (count
+// TABLE (k_label_table): one lane per voxel, 32 per mask word; a run is a row of adjacent lanes with the same non-zero label (any label array
+//   will do, not only components).  The first lane of a run collects the run (count
 //   from the ballot, sum of the raw values by a segmented shuffle sum) and issues one set of integer atomics on the run's table entry;
 //   when every run a wave holds has the same label the wave reduces them first and one lane issues the atomics, so that a single large
 //   component does not serialise the pass on its entry.
@@ -363,8 +364,11 @@ __global__ __launch_bounds__(THREADS) void k_label_table(const uint32_t* __restr
     if (lab > count) lab = 0u;                            // (a label the table has no entry for is ignored)
     const uint32_t m = half_ballot(lab != 0u);
     const bool set = lab != 0u;
-    const bool head = set && run_start(m, a.bit) == a.bit;
-    const int end = run_end(m, a.bit);                    // (of the run of this lane, if it is set)
+    // a run: adjacent set lanes of a word with ONE label (component labels have one per run of set lanes; the zones of svr_region_split need not)
+    const uint32_t before = shfl_u32(lab, lane > 0 ? lane - 1 : lane);
+    const bool head = set && (a.bit == 0 || before != lab);
+    const uint32_t later = half_ballot(head) & ~((2u << a.bit) - 1u);        // the heads after this lane (bit 31: 2u << 31 = 0, so none)
+    const int end = min(run_end(m, a.bit), later ? __ffs(later) - 1 : 32);  // (of the run of this lane, if it is set)
     uint32_t sum32 = set && vox ? vox[a.v] : 0u;          // the sum over this lane and those after it in the run: at most 32 * 65535
 #pragma unroll
     for (int off = 1; off < 32; off <<= 1) {

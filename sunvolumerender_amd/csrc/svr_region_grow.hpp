@@ -5,9 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#ifndef SVR_REGION_BATCH
-#define SVR_REGION_BATCH 16         // sweeps launched per read of the `added` counters (measured against 1 and 4: DESIGN.md 8h)
-#endif
+#include "svr_sweep.hpp"
 
 namespace {
 
@@ -121,36 +119,16 @@ struct RegionSweep {
         : ntx((d.wx + TWX - 1) / TWX), nty((d.ny + TY - 1) / TY), ntz((d.nz + TZ - 1) / TZ), tiles((size_t)ntx * nty * ntz), dirty(nullptr), added(nullptr) {}
 };
 
-// Sweeps k_region_grow<connectivity> over `region` inside `cand` until a sweep adds nothing or `cap` sweeps are launched: batches of
-// SVR_REGION_BATCH launches, one read of the counters and one stream synchronisation per batch.  *sweeps = the launches (surplus
-// included), *done = the fixpoint was reached.  The stream is idle on return unless a HIP call failed.
+// Sweeps k_region_grow<connectivity> over `region` inside `cand` until a sweep adds nothing or `cap` sweeps are launched.
 inline hipError_t region_sweep_to_fixpoint(hipStream_t st, int connectivity, const uint32_t* cand, uint32_t* region, const RegionDims& d,
                                            const RegionSweep& s, uint32_t cap, uint32_t* sweeps_out, bool* done_out)
 {
-    uint32_t* dirty[2] = {s.dirty, s.dirty + s.tiles};
-    uint32_t sweeps = 0u;
-    bool done = false;
-    hipError_t e = hipSuccess;
-    while (!done && sweeps < cap) {
-        const uint32_t nb = cap - sweeps < (uint32_t)SVR_REGION_BATCH ? cap - sweeps : (uint32_t)SVR_REGION_BATCH;
-        if ((e = hipMemsetAsync(s.added, 0, SVR_REGION_BATCH * sizeof(uint32_t), st)) != hipSuccess) break;
-        for (uint32_t i = 0; i < nb; ++i) {
-            uint32_t *cur = dirty[(sweeps + i) & 1u], *next = dirty[(sweeps + i + 1u) & 1u];
-            const dim3 g((uint32_t)s.tiles), b(GROW_THREADS);
-            if (connectivity == 6) hipLaunchKernelGGL((k_region_grow<6>), g, b, 0, st, cand, region, d, s.ntx, s.nty, s.ntz, cur, next, s.added + i);
-            else if (connectivity == 18) hipLaunchKernelGGL((k_region_grow<18>), g, b, 0, st, cand, region, d, s.ntx, s.nty, s.ntz, cur, next, s.added + i);
-            else hipLaunchKernelGGL((k_region_grow<26>), g, b, 0, st, cand, region, d, s.ntx, s.nty, s.ntz, cur, next, s.added + i);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        sweeps += nb;
-        uint32_t added[SVR_REGION_BATCH];
-        if ((e = hipMemcpyAsync(added, s.added, sizeof added, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
-        for (uint32_t i = 0; i < nb; ++i) if (added[i] == 0u) done = true;
-    }
-    *sweeps_out = sweeps;
-    *done_out = done;
-    return e;
+    return sweep_to_fixpoint(st, s.tiles, s.dirty, s.added, cap, sweeps_out, done_out, [&](uint32_t* cur, uint32_t* next, uint32_t* added) {
+        const dim3 g((uint32_t)s.tiles), b(GROW_THREADS);
+        if (connectivity == 6) hipLaunchKernelGGL((k_region_grow<6>), g, b, 0, st, cand, region, d, s.ntx, s.nty, s.ntz, cur, next, added);
+        else if (connectivity == 18) hipLaunchKernelGGL((k_region_grow<18>), g, b, 0, st, cand, region, d, s.ntx, s.nty, s.ntz, cur, next, added);
+        else hipLaunchKernelGGL((k_region_grow<26>), g, b, 0, st, cand, region, d, s.ntx, s.nty, s.ntz, cur, next, added);
+    });
 }
 
 } // namespace

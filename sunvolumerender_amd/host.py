@@ -649,6 +649,101 @@ class Device:
         self.check(self.lib.svr_region_distance_pass_ms(*[C.byref(t) for t in ms]))
         return tuple(float(t.value) for t in ms)
 
+    # ---- geodesic distances, influence zones and splitting (svr_region_geodesic / _seed_labels / _split / _zone_cut) ----
+    @staticmethod
+    def _step_weights(weights):
+        return None if weights is None else (C.c_uint32 * 7)(*[int(t) for t in weights])
+
+    def region_geodesic(self, labels, domain, shape=None, step_weights=None, max_sweeps: int = 0, want_dist: bool = True, want_zones: bool = True,
+                        dist_ptr: Optional[int] = None, zones_ptr: Optional[int] = None):
+        """svr_region_geodesic: (dist, zones, sweeps) inside `domain` (a bool array [nz][ny][nx], or a device pointer with shape=) from the
+        voxels whose entry in `labels` (a uint32 array or a device pointer) is non-zero: the cost of the cheapest path of moves with the
+        seven step weights (x, y, z, xy, xz, yz, xyz; 0 forbids a class; None = 3, 3, 3, 4, 4, 4, 5) and the smallest label that attains it.
+        GEO_NONE / 0 where no marker reaches.  An output that is not wanted is None; with dist_ptr / zones_ptr (device buffers of
+        4 nx ny nz bytes; zones_ptr may be the labels' own pointer) the result stays on the device and the pointer is returned."""
+        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, domain.shape if isinstance(domain, np.ndarray) else shape)
+        mbuf, mowned = self._region_mask(domain, (nz, ny, nx))
+        nbytes = 4 * max(nx * ny * nz, 1)
+        dout = dist_ptr if dist_ptr is not None else (self.malloc(nbytes) if want_dist else None)
+        zout = zones_ptr if zones_ptr is not None else (self.malloc(nbytes) if want_zones else None)
+        sweeps = C.c_uint32(0)
+        try:
+            self.check(self.lib.svr_region_geodesic(C.c_void_p(lbuf), C.c_void_p(mbuf), nx, ny, nz, self._step_weights(step_weights), int(max_sweeps),
+                                                    None if dout is None else C.c_void_p(dout), None if zout is None else C.c_void_p(zout),
+                                                    C.byref(sweeps)))
+            dist = dist_ptr if dist_ptr is not None else (self.to_host(dout, (nz, ny, nx), np.uint32) if dout is not None else None)
+            zones = zones_ptr if zones_ptr is not None else (self.to_host(zout, (nz, ny, nx), np.uint32) if zout is not None else None)
+            return dist, zones, int(sweeps.value)
+        finally:
+            if lowned:
+                self.free(lbuf)
+            if mowned:
+                self.free(mbuf)
+            if dist_ptr is None and dout is not None:
+                self.free(dout)
+            if zones_ptr is None and zout is not None:
+                self.free(zout)
+
+    def region_seed_labels(self, seeds, shape, out_ptr: Optional[int] = None):
+        """svr_region_seed_labels: a zero uint32 array [nz][ny][nx] with the label i + 1 on the voxel (x, y, z) of seed i (the lowest i of
+        several on a voxel).  Returns the array, or out_ptr itself when a device buffer of 4 nx ny nz bytes is given."""
+        nz, ny, nx = (int(n) for n in shape)
+        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
+        try:
+            self.check(self.lib.svr_region_seed_labels(xyz.ctypes.data_as(C.POINTER(C.c_int32)), len(xyz), nx, ny, nz, C.c_void_p(out)))
+            self.synchronize()
+            if out_ptr is not None:
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint32)
+        finally:
+            if out_ptr is None:
+                self.free(out)
+
+    def region_split(self, mask, r2: int, connectivity: int = 26, dist_weights=None, step_weights=None, max_sweeps: int = 0, shape=None,
+                     out_ptr: Optional[int] = None):
+        """svr_region_split: erodes the mask by the ball of squared radius r2 (dist_weights as in region_ball), labels the cores under
+        `connectivity` and gives every voxel of the mask to the core that is nearest inside the mask (step_weights as in
+        region_geodesic; None = the chamfer weights of the connectivity).  Returns (zones, count, unreached, sweeps): a uint32 array
+        [nz][ny][nx] (or out_ptr itself), the number of cores, the voxels of the mask that no core reaches, the sweeps launched."""
+        if isinstance(mask, np.ndarray):
+            shape = mask.shape
+        if shape is None:
+            raise ValueError("a device mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = (int(n) for n in shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
+        count, lost, sweeps = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        try:
+            self.check(self.lib.svr_region_split(C.c_void_p(buf), nx, ny, nz, self._weights(dist_weights), int(r2), int(connectivity),
+                                                 self._step_weights(step_weights), int(max_sweeps), C.c_void_p(out), C.byref(count), C.byref(lost),
+                                                 C.byref(sweeps)))
+            zones = out_ptr if out_ptr is not None else self.to_host(out, (nz, ny, nx), np.uint32)
+            return zones, int(count.value), int(lost.value), int(sweeps.value)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_zone_cut(self, zones, connectivity: int = 26, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_zone_cut: the mask of the voxels with a zone and no connectivity-neighbour in a smaller non-zero zone: the zones with a
+        cut of one voxel between them.  zones: a uint32 array [nz][ny][nx] or a device pointer with shape=."""
+        zbuf, zshape, zowned = self._region_labels(zones, shape)
+
+        def call(p, s, out):
+            self.check(self.lib.svr_region_zone_cut(C.c_void_p(zbuf), s[2], s[1], s[0], int(connectivity), out))
+        try:
+            return self._mask_call([], zshape, out_ptr, call)
+        finally:
+            if zowned:
+                self.free(zbuf)
+
+    def region_geodesic_last_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_region_geodesic_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     # ---- exact volume filters (svr_volume_*): median / min / max and binomial smoothing of the raw voxels ----
     def volume_rank(self, vox, op: int, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
         """svr_volume_rank: the median (FILTER_MEDIAN), minimum (FILTER_MIN) or maximum (FILTER_MAX) of every voxel's window under the
@@ -726,6 +821,22 @@ def distance_weights(spacing, shape, lib=None):
         lib.svr_clear_error()
         raise SvrError(f"svr_region_distance_weights failed ({rc}): {msg}")
     return (int(w[0]), int(w[1]), int(w[2])), float(unit.value)
+
+
+def geodesic_weights(spacing, connectivity, shape, lib=None):
+    """svr_region_geodesic_weights: ((w_x, w_y, w_z, w_xy, w_xz, w_yz, w_xyz), unit) for a spacing (sx, sy, sz), a connectivity 6 / 18 / 26
+    and a [nz][ny][nx] shape: the Euclidean lengths of the moves in units of `unit` = min(spacing) / 2^k, rounded, 0 for the classes
+    beyond the connectivity.  A geodesic map value d means about d unit.  Host code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    nz, ny, nx = (int(n) for n in shape)
+    sp = (C.c_double * 3)(*[float(t) for t in spacing])
+    w, unit = (C.c_uint32 * 7)(), C.c_double(0.0)
+    rc = lib.svr_region_geodesic_weights(sp, int(connectivity), nx, ny, nz, w, C.byref(unit))
+    if rc != 0:
+        msg = lib.svr_last_error().decode()
+        lib.svr_clear_error()
+        raise SvrError(f"svr_region_geodesic_weights failed ({rc}): {msg}")
+    return tuple(int(t) for t in w), float(unit.value)
 
 
 def smooth_radii(spacing, sigma, lib=None):
