@@ -10,6 +10,9 @@
 //   traceDepth 1   record C1 = a shaded event's prepared next-event estimate, waiting for its shadow walk.  After
 //                  QUEUE_TASKS tasks (2048 paths) the wave drains its records with all 64 lanes:
 //                  IDLE -> (pop) -> WALK -> END -> (radiance = estimate x transmittance) -> IDLE
+//                  In the skipping builds without pooled primary walks the walk's first iteration runs in place, behind the shading
+//                  (SVR_SHADOW_FIRST): three walks in four end there and are settled, the others are queued as R records = C1 + the
+//                  state of the walk, which the machine resumes.
 //   deeper         the first shadow walk and its estimate run in place too; record A = a path waiting for its BSDF
 //                  sampling.  In the machine a lane holds a path only while it WALKs; a finished walk is settled and the
 //                  path waits on the stack of the service it needs -- A (BSDF sampling, throughput, roulette, next walk's
@@ -31,8 +34,12 @@ namespace svr {
 // weighted by the lanes that had work there (-> lane utilisation per phase); read with svr_debug_phase_profile.
 enum { PH_PRIMARY = 0, PH_REFILL, PH_SHADE, PH_CHEAP, PH_FETCH, PH_MARCH, PH_END, PH_FOLD, PH_N };
 // the tile kernel's task loop, behind the words above (tools/phase_prof.py): the wait for a ticket's value, and a wave's whole loop over the tickets
-enum { PH_TICKET = PH_N + 1, PH_LOOP, PH_END_ALL };
-constexpr uint32_t PROF_WORDS = 2 * PH_END_ALL;   // 2 * PH_N: cheap-loop iterations, 2 * PH_N + 1: walking lanes summed over them
+// ... and the iterations of a shadow walk that run in place in the task loop (SVR_SHADOW_FIRST), apart from the machine's PH_CHEAP
+enum { PH_TICKET = PH_N + 1, PH_LOOP, PH_FIRST, PH_END_ALL };
+// 2 * PH_N: cheap-loop iterations, 2 * PH_N + 1: walking lanes summed over them; behind the phases: traceDepth-1 QUEUE builds without pooled walks,
+// shaded events that have a shadow walk, and the records pushed for them
+enum { PROF_SHADOW_WALKS = 2 * PH_END_ALL, PROF_RECORDS };
+constexpr uint32_t PROF_WORDS = 2 * PH_END_ALL + 2;
 #ifdef SVR_TEST_HOOKS
 #define SVR_PROF 1
 struct ProfScope {
@@ -257,6 +264,94 @@ SVR_DEV void queue_push_a(const LaneQueue& Q, uint32_t& nA, bool live, const Sha
     nA += (uint32_t)__popcll(m);
 }
 
+// traceDepth 1, the skipping QUEUE builds without pooled primary walks: the first SVR_SHADOW_FIRST Woodcock iterations of a shadow walk run IN PLACE, right after
+// the shading (svr_trace_tile.hip) -- three quarters of the shadow walks of c3 collide in their first iteration, and the hit lanes of a task are
+// converged there -- and only a walk that is still going is queued, as a resumable record (R, below).  0 = every shaded event is queued before its
+// walk begins (C1 records).  2 is buildable: a lane that asks for a re-march in its second iteration is queued with that request.  The committed
+// tests run the default; the 2 library has passed tests/test_shadow_first_gpu.py, test_task_loop_gpu.py and test_configs_gpu.py once, by hand, and was
+// + 0.7 % in one A/B, below the project's bar (profiles/r07_notes_experiments.txt): not to be adopted on that timing alone.
+#ifndef SVR_SHADOW_FIRST
+#define SVR_SHADOW_FIRST 1
+#endif
+
+// states of a lane of the machine (drain_queue); walk_iterate / walk_fetch move a walking lane between CELL .. END
+struct LaneSt { enum : uint32_t { IDLE = 0u, CELL = 1u, WALK = 2u, FETCH = 3u, MARCH = 4u, END = 5u, WANT_A = 6u, WANT_B = 7u }; };
+
+// One Woodcock iteration of a walking lane without its fetch (woodcock_tracking.h:32-45): FREE / EMPTY / CULLED keep it in WALK, anything else
+// parks it (FETCH: the accept draw xi is kept; MARCH) or ends the walk (END).  A lane in CELL has drawn its distance already (free_iterate).
+// iskip: counting builds, the iteration is one a production build never runs.  Shared by the machine and by the iterations that run in place.
+template <bool COUNT, bool SKIP, typename LDS>
+SVR_DEV void walk_iterate(const DevScene& s, const LDS& L_, v3 orig, v3 dir, Rng& rng, uint32_t& st, float& t, float tMax, float t_occ, uint32_t& clear_run,
+                          uint32_t& guard, float& xi, bool iskip, Cnt& c)
+{
+    if (st != LaneSt::CELL) {
+        if (COUNT) { c.iters++; if (iskip) c.iskip++; }
+        t += -logf_unit(1.f - rng_uniform(rng)) * s.invSigmaMaxSI;
+        if (t > tMax || guard++ >= SVR_WALK_GUARD) { st = LaneSt::END; return; }
+        if (COUNT) c.taps++;
+        if (SKIP && t < t_occ) {
+            if (COUNT && !iskip) c.ipre++;
+            rng_skip(rng);                                  // the accept draw of a FREE iteration
+            return;
+        }
+    }
+    st = LaneSt::WALK;
+    const Cell cell = cell_of(s, orig + dir * t);
+    CellInfo ci;
+    ci.empty = false; ci.deep = false; ci.thr = u2f(SVR_INF_BITS);
+    if (SKIP) ci = cell_info<true>(L_, s, cell);
+    if (ci.empty) {
+        rng_skip(rng);                                  // sigma_t = 0: the draw is consumed, the test fails
+        clear_run = ci.deep ? clear_run + 1u : 0u;
+        if (clear_run == 2u) st = LaneSt::MARCH;
+    } else {
+        clear_run = 0u;
+        xi = rng_uniform(rng);
+        if (xi < ci.thr) st = LaneSt::FETCH;           // else CULLED: xi >= bound >= sigma_t * invSigmaMax
+        else if (COUNT) c.cull++;
+    }
+}
+// the fetch an iteration asked for: 8 voxels + filter + LUT, then the accept test with the draw the lane kept
+template <int LAYOUT, bool COUNT, typename LDS>
+SVR_DEV void walk_fetch(const DevScene& s, const LDS& L_, v3 orig, v3 dir, float t, float xi, uint32_t& st, bool& hit, float& val, Cnt& c)
+{
+    if (COUNT) c.exec++;
+    val = tex_fetch<LAYOUT>(s, cell_of(s, orig + dir * t)) * s.densityScale;
+    const float sigma_t = alpha_of(L_, s, val);
+    if (xi < sigma_t * s.invSigmaMax) { st = LaneSt::END; hit = true; }
+    else st = LaneSt::WALK;
+}
+// END of a SHADOW walk (pathtracer.cu:191-198): transmittance -> direct light.  transmittance.h:15-16 on the walk's result ts (t, or -FLT_MAX), with
+// the box interval of the shadow ray; sample_light returned true: cosTerm > 0
+SVR_DEV v3 nee_settle(v3 L, v3 T, const Nee& ne, bool hit, float t, float tMin, float tMax, uint32_t num_lights, const DevLight& l)
+{
+    const float ts = hit ? t : -SVR_FLT_MAX;
+    const float Tr = ((ts > tMin) && (ts < tMax)) ? 0.f : 1.f;
+    const float kf = Tr * (float)num_lights;
+    const v3 Li = V3(l.radiance[0], l.radiance[1], l.radiance[2]);
+    return L + T * (((ne.B * kf) * Li) / ne.pdf);
+}
+
+// R (traceDepth 1, SVR_SHADOW_FIRST): a shadow walk that is still going after its iterations in place -- the words of a C1 record with the ADVANCED
+// generator and the walk's clear_run in the bounce field of meta, then t, tMin, tMax, t_occ
+// (repeating walk_setup at the pop in place of the last three words measured the same: profiles/r07_notes_experiments.txt)
+constexpr uint32_t REC_R_WORDS = REC_C1_WORDS + 4u;
+static_assert(REC_R_WORDS <= REC_WORDS, "R records fit a wave's queue slice");
+SVR_DEV void queue_push_r(const LaneQueue& Q, uint32_t& nC, bool live, v3 pt, const Nee& ne, const Rng& rng, uint32_t id, uint32_t clear_run, float t, float tMin,
+                          float tMax, float t_occ)
+{
+    const uint64_t m = __ballot(live);
+    if (live) {
+        uint32_t* p = queue_c(Q) + nC + lane_rank(m);
+        const uint32_t cap = Q.cap;
+        rec_c1_store(p, cap, pt, ne, rng, id);
+        p[16 * cap] = rec_meta(id, clear_run, ne.light, 0);
+        p[17 * cap] = f2u(t);
+        p[18 * cap] = f2u(tMin); p[19 * cap] = f2u(tMax); p[20 * cap] = f2u(t_occ);
+    }
+    nC += (uint32_t)__popcll(m);
+}
+
 #ifndef SVR_PARK_CHEAP
 #define SVR_PARK_CHEAP 16
 #endif
@@ -277,14 +372,17 @@ SVR_DEV void queue_push_a(const LaneQueue& Q, uint32_t& nA, bool live, const Sha
 // the nearest light or the environment (the path is over) or a collision, which becomes an H record (nH counts them).
 // OUT: where a finished path's radiance goes.  0: its task's row (pendL).  1 (launches that do not fold: frames traced ahead): straight to its scratch
 // slot, found from the wave's pending task numbers (wk / tasks; svr_tile_tasks.hpp direct_put).
-template <int LAYOUT, bool COUNT, bool SKIP, bool DEPTH1, typename LDS, bool POOL = false, bool HIT_B = false, int OUT = 0, bool LDSL = false>
+// FIRST (traceDepth 1, not POOL): the records are R records -- walks that ran their first FIRST iterations in place
+template <int LAYOUT, bool COUNT, bool SKIP, bool DEPTH1, typename LDS, bool POOL = false, bool HIT_B = false, int OUT = 0, bool LDSL = false, int FIRST = 0>
 SVR_DEV void drain_queue(const DevScene& s, const LDS& L_, const LaneQueue& Q, uint32_t nC, uint32_t nA, uint32_t nB0, uint32_t traceDepth_, float* pendL, uint32_t pend_row, Cnt& c,
                          unsigned long long* c_prof = nullptr, const bool primary = false, uint32_t* nH = nullptr, const DevWork* wk = nullptr, const uint32_t* tasks = nullptr,
                          const DevScene* scp = nullptr, const DevLight* lts = nullptr)
 {
     const DevScene& sc = scp ? *scp : s;
     const DevLight* const LT = LDSL ? lts : sc.lights;
-    enum : uint32_t { IDLE = 0u, CELL = 1u, WALK = 2u, FETCH = 3u, MARCH = 4u, END = 5u, WANT_A = 6u, WANT_B = 7u };
+    static_assert(FIRST == 0 || (DEPTH1 && !POOL), "R records exist at traceDepth 1 without pooled primary walks");
+    enum : uint32_t { IDLE = LaneSt::IDLE, CELL = LaneSt::CELL, WALK = LaneSt::WALK, FETCH = LaneSt::FETCH, MARCH = LaneSt::MARCH, END = LaneSt::END,
+                      WANT_A = LaneSt::WANT_A, WANT_B = LaneSt::WANT_B };
     const float INF = u2f(SVR_INF_BITS);
     const uint32_t traceDepth = DEPTH1 ? 1u : traceDepth_;
     const bool fast_bound = lds_has_bnd8<LDS>::value && s.bnd8 != nullptr;      // (SVR_OPT_FAST_BOUND; media without exactly transparent space)
@@ -316,34 +414,7 @@ SVR_DEV void drain_queue(const DevScene& s, const LDS& L_, const LaneQueue& Q, u
 
     // one Woodcock iteration of a walking lane without a fetch (woodcock_tracking.h:32-45): FREE / EMPTY / CULLED keep it
     // in WALK, anything else parks it (FETCH, MARCH) or ends the walk (END)
-    auto iterate = [&]() {
-        if (st != CELL) {
-            if (COUNT) { c.iters++; if (ray_skippable || tail_counted) c.iskip++; }
-            t += -logf_unit(1.f - rng_uniform(rng)) * s.invSigmaMaxSI;
-            if (t > tMax || guard++ >= SVR_WALK_GUARD) { st = END; return; }
-            if (COUNT) c.taps++;
-            if (SKIP && t < t_occ) {
-                if (COUNT && !(ray_skippable || tail_counted)) c.ipre++;
-                rng_skip(rng);                                  // the accept draw of a FREE iteration
-                return;
-            }
-        }
-        st = WALK;
-        const Cell cell = cell_of(s, orig + dir * t);
-        CellInfo ci;
-        ci.empty = false; ci.deep = false; ci.thr = INF;
-        if (SKIP) ci = cell_info<true>(L_, s, cell);
-        if (ci.empty) {
-            rng_skip(rng);                                  // sigma_t = 0: the draw is consumed, the test fails
-            clear_run = ci.deep ? clear_run + 1u : 0u;
-            if (clear_run == 2u) st = MARCH;
-        } else {
-            clear_run = 0u;
-            xi = rng_uniform(rng);
-            if (xi < ci.thr) st = FETCH;                   // else CULLED: xi >= bound >= sigma_t * invSigmaMax
-            else if (COUNT) c.cull++;
-        }
-    };
+    auto iterate = [&]() { walk_iterate<COUNT, SKIP>(s, L_, orig, dir, rng, st, t, tMax, t_occ, clear_run, guard, xi, ray_skippable || tail_counted, c); };
     // TRIPS (POOL builds: media without exactly transparent space, where a walk is tens of iterations long): five iterations of the
     // walking lanes in a row with the generator as a circular buffer (svr_device.hpp: heads 0 2 4 1 3, no register moves, the
     // Weyl word advanced once), the lanes that leave the WALK state on the way (FETCH / MARCH / END) recording after how many
@@ -444,13 +515,7 @@ SVR_DEV void drain_queue(const DevScene& s, const LDS& L_, const LaneQueue& Q, u
     auto serve_fetch_march = [&]() {
         // FETCH: 8 voxels + filter + LUT, then the accept test with the draw the lane kept
         if (__ballot(st == FETCH) != 0ull) {
-            if (st == FETCH) {
-                if (COUNT) c.exec++;
-                val = tex_fetch<LAYOUT>(s, cell_of(s, orig + dir * t)) * s.densityScale;
-                const float sigma_t = alpha_of(L_, s, val);
-                if (xi < sigma_t * s.invSigmaMax) { st = END; hit = true; }
-                else st = WALK;
-            }
+            if (st == FETCH) walk_fetch<LAYOUT, COUNT>(s, L_, orig, dir, t, xi, st, hit, val, c);
         }
         // MARCH: the walk has left an occupied stretch: where is the next one?
         if (SKIP && __ballot(st == MARCH) != 0ull) {
@@ -474,16 +539,8 @@ SVR_DEV void drain_queue(const DevScene& s, const LDS& L_, const LaneQueue& Q, u
         }
         st = IDLE;
     };
-    // END of a SHADOW walk (pathtracer.cu:191-198): transmittance -> direct light
-    auto nee = [&]() {
-        // transmittance.h:15-16 on the walk's result ts (t, or -FLT_MAX), with the box interval of the shadow ray
-        const float ts = hit ? t : -SVR_FLT_MAX;
-        const float Tr = ((ts > tMin) && (ts < tMax)) ? 0.f : 1.f;
-        const float kf = Tr * (float)sc.num_lights;
-        const DevLight& l = LT[ne.light];
-        const v3 Li = V3(l.radiance[0], l.radiance[1], l.radiance[2]);     // sample_light returned true: cosTerm > 0
-        L = L + T * (((ne.B * kf) * Li) / ne.pdf);
-    };
+    // END of a SHADOW walk: transmittance -> direct light
+    auto nee = [&]() { L = nee_settle(L, T, ne, hit, t, tMin, tMax, sc.num_lights, LT[ne.light]); };
     // the shadow walk of the prepared estimate; the draws of sample_bsdf / roulette follow it unless this is the last bounce
     auto begin_shadow = [&]() {
         orig = vs.pt;
@@ -499,7 +556,8 @@ SVR_DEV void drain_queue(const DevScene& s, const LDS& L_, const LaneQueue& Q, u
         uint32_t next = 0u;
         for (;;) {
             PROF_BEGIN(pw, PH_CHEAP);
-            while (__ballot(st == WALK || st == CELL) != 0ull) {
+            // (FIRST == 2: a popped lane may come with its re-march pending, which serve_fetch_march serves)
+            while (__ballot(st == WALK || st == CELL || (FIRST == 2 && st == MARCH)) != 0ull) {
                 if ((uint32_t)__popcll(__ballot(st == END)) + min((uint32_t)__popcll(__ballot(st == IDLE)), nC - next) >= park_cheap) break;
                 if (SKIP) {
 #pragma nounroll
@@ -566,9 +624,20 @@ SVR_DEV void drain_queue(const DevScene& s, const LDS& L_, const LaneQueue& Q, u
                         if (COUNT && ray_skippable) c.wskip++;
                         st = WALK;
                     } else {
-                        id = meta_id(rec_c1_load(queue_c(Q) + i, Q.cap, vs.pt, ne, rng));
+                        const uint32_t* r = queue_c(Q) + i;
+                        const uint32_t meta = rec_c1_load(r, Q.cap, vs.pt, ne, rng);
+                        id = meta_id(meta);
                         L = V3(0.f, 0.f, 0.f); T = V3(1.f, 1.f, 1.f); k = 0u;
-                        begin_shadow();
+                        if constexpr (FIRST > 0) {
+                            // an R record: the walk goes on behind its iterations in place
+                            orig = vs.pt;
+                            dir = ne.wi;
+                            shadow = true; rng_live = false; hit = false; tail_counted = false;
+                            tMin = u2f(r[18 * Q.cap]); tMax = u2f(r[19 * Q.cap]); t_occ = u2f(r[20 * Q.cap]);
+                            ray_skippable = SKIP && s.ray_skip && t_occ == INF;       // (counting builds: counted as such when the walk began)
+                            t = u2f(r[17 * Q.cap]); clear_run = meta_k(meta); guard = (uint32_t)FIRST;
+                            st = clear_run == 2u ? MARCH : WALK;                      // (2: only behind two iterations in place)
+                        } else begin_shadow();
                     }
                 }
                 next = min(nC, next + (uint32_t)__popcll(idle));

@@ -209,6 +209,10 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     // (traceDepth-1 builds: same-box A/B c3 9 626-9 805 against 9 522-9 526, c3n 2 403 / 2 386, c5 6 549 / 6 489; the deeper build loses 2.5 % with it)
     constexpr bool LDSL = QUEUE && (DEPTH1 || (POOL && SVR_COLD_DEEP_POOL) || SVR_COLD_DEEP_ALL) && SVR_LDS_LIGHTS;
     const DevLight* const lts = lds_lights;
+    // traceDepth 1, no pooled primary walks: iterations of a shadow walk that run in place, in front of the queue (svr_lanes.hpp).  The folding, the
+    // DIRECT and the fast-math form of the skipping build gain 3.5 - 4.2 % with one; the build without empty-space skipping gains nothing
+    // (2 256 / 2 252 against 2 256 / 2 255 Msamples/s: every walk is long there) and keeps every walk in the queue
+    constexpr int FIRST = (QUEUE && DEPTH1 && !POOL && SKIP) ? SVR_SHADOW_FIRST : 0;
     lds_tile_load(lds, s, SKIP);
 
     const uint32_t lane = threadIdx.x & 63u;
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             }
-            drain_queue<LAYOUT, COUNT, SKIP, DEPTH1, LDS, false, false, DIRECT, LDSL>(s, lds, Q, qC, qA, qB, w.traceDepth, gpend, 64u, c, w.counters + CNT_N, false, nullptr, &w, &pend.task[wave][0], cold_scene(), lts);
+            drain_queue<LAYOUT, COUNT, SKIP, DEPTH1, LDS, false, false, DIRECT, LDSL, FIRST>(s, lds, Q, qC, qA, qB, w.traceDepth, gpend, 64u, c, w.counters + CNT_N, false, nullptr, &w, &pend.task[wave][0], cold_scene(), lts);
             qC = qA = qB = 0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -460,7 +464,47 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
                         }
                     }
                     bool over;
-                    if constexpr (DEPTH1) {
+                    if constexpr (FIRST > 0) {
+                        // traceDepth 1: the first iteration(s) of the shadow walk in place (svr_lanes.hpp, SVR_SHADOW_FIRST) -- the operations of the
+                        // machine's begin_shadow / iterate / fetch service / nee on the lane's own generator.  A walk that has ended is settled here and
+                        // the path is over; one that is still going is queued as an R record for the machine to resume.
+                        const bool sh = hit && ne.have;
+                        bool walking = false;
+                        float tMin = (float)1e-6, tMax = SVR_FLT_MAX, t_occ = 0.f, t = 0.f;
+                        uint32_t clear_run = 0u;
+                        if (__ballot(sh) != 0ull) {
+                            PROF_BEGIN(psw, PH_FIRST);
+                            if (sh) {
+                                const DevScene* scp = cold_scene();
+                                const int r = walk_setup<COUNT, SKIP>(s, lds, vs.pt, ne.wi, false, tMin, tMax, t_occ);
+                                t = tMin;
+                                const bool ray_skippable = SKIP && s.ray_skip && t_occ == u2f(SVR_INF_BITS);
+                                if (COUNT && r > 0 && ray_skippable) c.wskip++;
+                                uint32_t wst = r > 0 ? (uint32_t)LaneSt::WALK : (uint32_t)LaneSt::END, guard = 0u;
+                                float xi = 0.f, sval = 0.f;
+                                bool shit = false;
+#pragma unroll
+                                for (int it = 0; it < FIRST; ++it) {
+                                    if (wst == LaneSt::WALK) walk_iterate<COUNT, SKIP>(s, lds, vs.pt, ne.wi, rng, wst, t, tMax, t_occ, clear_run, guard, xi, ray_skippable, c);
+                                    if (wst == LaneSt::FETCH) walk_fetch<LAYOUT, COUNT>(s, lds, vs.pt, ne.wi, t, xi, wst, shit, sval, c);
+                                }
+                                if (wst == LaneSt::END) {
+                                    const DevScene& sc = scp ? *scp : s;
+                                    const DevLight& l = LDSL ? lts[ne.light] : sc.lights[ne.light];
+                                    L = nee_settle(V3(0.f, 0.f, 0.f), V3(1.f, 1.f, 1.f), ne, shit, t, tMin, tMax, sc.num_lights, l);
+                                } else walking = true;                // WALK, or (two iterations) MARCH with clear_run == 2
+                            }
+                            PROF_END(psw, (uint32_t)__popcll(__ballot(sh)));
+                        }
+#if SVR_PROF
+                        {
+                            const unsigned long long n_sh = (unsigned long long)__popcll(__ballot(sh)), n_rec = (unsigned long long)__popcll(__ballot(walking));
+                            if (lane == 0) { atomicAdd(&c_prof[PROF_SHADOW_WALKS], n_sh); atomicAdd(&c_prof[PROF_RECORDS], n_rec); }
+                        }
+#endif
+                        queue_push_r(Q, qC, walking, vs.pt, ne, rng, (npend << 6) | lane, clear_run, t, tMin, tMax, t_occ);
+                        over = !walking;                              // the camera ray's radiance, a first event no light sample reaches (L = 0), or a settled estimate
+                    } else if constexpr (DEPTH1) {
                         queue_push_c1(Q, qC, hit && ne.have, vs.pt, ne, rng, (npend << 6) | lane);
                         over = !(hit && ne.have);                     // the camera ray's radiance, or a first event no light sample reaches (L = 0)
                     } else {

@@ -40,6 +40,12 @@ for setting in a.settings:
         print(f"   task loop {loop:.4g} wave-cycles = 100 %: ticket wait {ticket / loop * 100:.2f} %, " +
               ", ".join(f"{n} {float(out[2 * i]) / loop * 100:.2f} %" for i, n in enumerate(names) if out[2 * i]) +
               f", unstamped {(loop - ticket - tot) / loop * 100:.2f} %")
+    # the shadow-walk iterations that run in place in the task loop (PH_FIRST = 11), stamped apart from the machine's cheap rounds, and behind the
+    # phases (words 24, 25) the shaded events that have a shadow walk and the records pushed for them
+    if out[22]:
+        print(f"   first (in place) {float(out[22]) / (loop or tot) * 100:.2f} % of the {'task loop' if loop else 'stamped phases'}   util {float(out[23]) / float(out[22]) / 64 * 100:5.1f} %")
+    if out[24]:
+        print(f"   shadow walks {int(out[24])}, records pushed {int(out[25])} = {float(out[25]) / float(out[24]) * 100:.2f} %   ({int(out[24]) / a.frames:.0f} / {int(out[25]) / a.frames:.0f} per frame)")
     if out[16]:
         if a.depth > 1:
             print(f"   cheap-loop iterations {int(out[16])}, mean walking lanes {float(out[17]) / float(out[16]):.1f}")
