@@ -1,8 +1,7 @@
 // svr_distance.hip -- exact squared Euclidean distance maps of region masks with per-axis integer weights, and what is one cheap pass
 // away from them: selection by distance, ball morphology, the largest inscribed ball, the map as a u16 volume (svr_region_distance,
 // _distance_select, _ball, _distance_max, _distance_volume, _distance_weights; the contract is in include/svr_abi.h, the design in
-// DESIGN.md 8k).  Integers only, on the mask layout of svr_region.hip: voxel (x, y, z) = bit x & 31 of word (z * ny + y) * wx + (x >> 5).
-// Input padding is ignored, output padding is 0.
+// DESIGN.md 8k).  Integers only, on the mask layout and padding rule of svr_mask.hpp.
 //
 // The transform is separable: D(x, y, z) = min over (i, j, k) targets of wx (x - i)^2 + wy (y - j)^2 + wz (z - k)^2
 //   = min_k [ wz (z - k)^2 + min_j [ wy (y - j)^2 + min_i wx (x - i)^2 ] ], and every min is over exact integers, so any correct
@@ -34,6 +33,8 @@
 
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
+#include "svr_mask.hpp"             // RegionDims, valid_bits, lane_at, half_ballot, the grids
+#include "svr_volume_host.hpp"
 
 using svr::failf;
 
@@ -41,12 +42,10 @@ using svr::failf;
 
 namespace {
 
-constexpr int THREADS = 256;
+constexpr int THREADS = MASK_THREADS;
 static_assert(SVR_DISTANCE_COLUMN_BLOCK == THREADS, "k_dist_columns runs one column per thread");
 constexpr uint32_t NONE = SVR_DIST_NONE;
 constexpr int OUT_MAP = 0, OUT_LE = 1, OUT_GT = 2;
-
-struct DistDims { int nx, ny, nz, wx; };
 
 // one column pass: `rows` groups of nx columns; column (r, x) starts at r * row_stride + x and has n entries `stride` apart.  The
 // mask word of level u of the columns of word gw of group r is r * mask_row + u * mask_level + gw.
@@ -55,67 +54,37 @@ struct ColPass {
     size_t stride, row_stride, mask_row, mask_level, cols;   // cols = rows * nx, the stack's second dimension
 };
 
-__device__ inline uint32_t valid_bits(int gw, int nx)
-{
-    const int rem = nx - gw * 32;
-    return rem >= 32 ? 0xffffffffu : (1u << rem) - 1u;
-}
-
-// the 32 bits of this lane's half of the wave
-__device__ inline uint32_t half_ballot(bool p)
-{
-    const unsigned long long b = __ballot(p);
-    return (threadIdx.x & 32) ? (uint32_t)(b >> 32) : (uint32_t)b;
-}
-
 __device__ inline uint64_t sq_diff(uint32_t a, uint32_t b)
 {
     const uint32_t d = a > b ? a - b : b - a;              // below 65536
     return (uint64_t)(d * d);
 }
 
-// a lane of the one-lane-per-voxel kernels: bit `bit` of mask word i
-struct LaneAt { size_t i, v; int bit, gw; bool word_ok, inside; };
-__device__ inline LaneAt lane_at(size_t t, const DistDims& d, size_t words)
-{
-    LaneAt a;
-    a.i = t >> 5;
-    a.bit = (int)(t & 31u);
-    a.word_ok = a.i < words;
-    const size_t i = a.word_ok ? a.i : 0;
-    a.gw = (int)(i % (unsigned)d.wx);
-    const size_t row = i / (unsigned)d.wx;
-    const int x = a.gw * 32 + a.bit;
-    a.inside = a.word_ok && x < d.nx;
-    a.v = row * (size_t)d.nx + (size_t)x;
-    return a;
-}
-
 // the target bits of mask word i (word gw of its row): the set voxels, or the unset voxels of the volume
-__device__ inline uint32_t target_word(const uint32_t* __restrict__ mask, size_t i, int gw, int nx, bool unset)
+__device__ inline uint32_t target_word(const uint32_t* __restrict__ mask, size_t i, int gw, const RegionDims& d, bool unset)
 {
     const uint32_t m = mask[i];
-    return (unset ? ~m : m) & valid_bits(gw, nx);
+    return (unset ? ~m : m) & valid_bits(gw, d);
 }
 
-__global__ __launch_bounds__(THREADS) void k_dist_rows(const uint32_t* __restrict__ mask, uint32_t* __restrict__ out, DistDims d, size_t words, uint32_t w,
+__global__ __launch_bounds__(THREADS) void k_dist_rows(const uint32_t* __restrict__ mask, uint32_t* __restrict__ out, RegionDims d, size_t words, uint32_t w,
                                                        int unset)
 {
-    const LaneAt a = lane_at((size_t)blockIdx.x * THREADS + threadIdx.x, d, words);
+    const LaneAt a = lane_at(d, words);
     if (!a.word_ok) return;
-    const uint32_t m = target_word(mask, a.i, a.gw, d.nx, unset != 0);
+    const uint32_t m = target_word(mask, a.i, a.gw, d, unset != 0);
     uint32_t best = 0xffffffffu;                          // the distance in voxels to the nearest target of the row
     const uint32_t left = m & (0xffffffffu >> (31 - a.bit)), right = m & (0xffffffffu << a.bit);
     if (left) best = (uint32_t)(a.bit - (31 - __clz(left)));
     if (right) best = min(best, (uint32_t)(__ffs(right) - 1 - a.bit));
     if (!left)                                            // the nearest non-zero word to the left, while it can still be nearer
         for (int j = a.gw - 1; j >= 0 && (uint32_t)((a.gw - j) * 32 + a.bit - 31) < best; --j) {
-            const uint32_t mm = target_word(mask, a.i - (size_t)(a.gw - j), j, d.nx, unset != 0);
+            const uint32_t mm = target_word(mask, a.i - (size_t)(a.gw - j), j, d, unset != 0);
             if (mm) { best = min(best, (uint32_t)((a.gw - j) * 32 + a.bit - (31 - __clz(mm)))); break; }
         }
     if (!right)
         for (int j = a.gw + 1; j < d.wx && (uint32_t)((j - a.gw) * 32 - a.bit) < best; ++j) {
-            const uint32_t mm = target_word(mask, a.i + (size_t)(j - a.gw), j, d.nx, unset != 0);
+            const uint32_t mm = target_word(mask, a.i + (size_t)(j - a.gw), j, d, unset != 0);
             if (mm) { best = min(best, (uint32_t)((j - a.gw) * 32 + __ffs(mm) - 1 - a.bit)); break; }
         }
     if (a.inside) out[a.v] = best == 0xffffffffu ? NONE : w * best * best;
@@ -209,10 +178,10 @@ __global__ __launch_bounds__(THREADS) void k_dist_columns(const uint32_t* __rest
 #endif
 }
 
-__global__ __launch_bounds__(THREADS) void k_dist_select(const uint32_t* __restrict__ d2, DistDims d, size_t words, uint32_t lo2, uint32_t hi2,
+__global__ __launch_bounds__(THREADS) void k_dist_select(const uint32_t* __restrict__ d2, RegionDims d, size_t words, uint32_t lo2, uint32_t hi2,
                                                          uint32_t* __restrict__ out)
 {
-    const LaneAt a = lane_at((size_t)blockIdx.x * THREADS + threadIdx.x, d, words);
+    const LaneAt a = lane_at(d, words);
     bool on = false;
     if (a.inside) {
         const uint32_t v = d2[a.v];
@@ -222,10 +191,10 @@ __global__ __launch_bounds__(THREADS) void k_dist_select(const uint32_t* __restr
     if (a.bit == 0 && a.word_ok) out[a.i] = word;
 }
 
-__global__ __launch_bounds__(THREADS) void k_mask_clean(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, DistDims d, size_t words)
+__global__ __launch_bounds__(THREADS) void k_mask_clean(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, RegionDims d, size_t words)
 {
     const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
-    if (i < words) out[i] = in[i] & valid_bits((int)(i % (unsigned)d.wx), d.nx);
+    if (i < words) out[i] = in[i] & valid_bits((int)(i % (unsigned)d.wx), d);
 }
 
 __global__ __launch_bounds__(THREADS) void k_dist_volume(const uint32_t* __restrict__ d2, size_t n, uint32_t scale, uint16_t* __restrict__ out)
@@ -245,7 +214,7 @@ __global__ __launch_bounds__(THREADS) void k_dist_volume(const uint32_t* __restr
     out[i] = (uint16_t)res;
 }
 
-__global__ __launch_bounds__(THREADS) void k_dist_max(const uint32_t* __restrict__ d2, const uint32_t* __restrict__ mask, DistDims d, size_t words,
+__global__ __launch_bounds__(THREADS) void k_dist_max(const uint32_t* __restrict__ d2, const uint32_t* __restrict__ mask, RegionDims d, size_t words,
                                                       unsigned long long* best)
 {
     unsigned long long key = 0ull;                        // (d2 << 32) | ~index; 0 = none: ~index is never 0 for an index below 2^31
@@ -269,20 +238,6 @@ __global__ __launch_bounds__(THREADS) void k_dist_max(const uint32_t* __restrict
 }
 
 // ---------------- host side ----------------
-#define DIST_TRY(call)                                                                                                           \
-    do {                                                                                                                          \
-        hipError_t _e = (call);                                                                                                   \
-        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
-    } while (0)
-
-int check_dims(const char* who, int nx, int ny, int nz)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
-    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
-        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
-    return 0;
-}
-
 // wx (nx - 1)^2 + wy (ny - 1)^2 + wz (nz - 1)^2 <= 0xFFFFFFFE, in 64-bit arithmetic that cannot wrap
 bool weights_fit(const uint64_t w[3], int nx, int ny, int nz)
 {
@@ -308,62 +263,31 @@ int check_weights(const char* who, const uint32_t* weights_or_null, int nx, int 
     return 0;
 }
 
-bool overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + bytes && q < p + bytes;
-}
-
-DistDims make_dims(int nx, int ny, int nz) { return DistDims{nx, ny, nz, (nx + 31) / 32}; }
-size_t mask_words(const DistDims& d) { return (size_t)d.wx * d.ny * d.nz; }
-dim3 grid_for(size_t n) { return dim3((uint32_t)((n + THREADS - 1) / THREADS)); }      // at most 2^31 items: 2^23 blocks
-
-// HIP events: [0], [1] around the device work of the last call of this file; [2] .. [5] around the three passes of its last transform
-hipEvent_t g_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-bool g_passes = false;                                    // [2] .. [5] have been recorded
-bool events_ready()
-{
-    if (g_ev[0]) return true;
-    for (auto& e : g_ev)
-        if (hipEventCreate(&e) != hipSuccess) { g_ev[0] = nullptr; return false; }
-    return true;
-}
-struct CallTimer {
-    hipStream_t st;
-    bool on;
-    explicit CallTimer(hipStream_t s) : st(s), on(false) { if (events_ready()) on = hipEventRecord(g_ev[0], st) == hipSuccess; }
-    void stop() { if (on) hipEventRecord(g_ev[1], st); on = false; }
-    ~CallTimer() { stop(); }
-};
+CallEvents g_events;                                      // around the device work of the last call of this file (svr_region_distance_last_ms)
+hipEvent_t g_pass_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the three passes of the last transform
+bool g_passes = false;                                    // g_pass_ev have been recorded
 
 // one transform: mask -> rows into a -> y pass into b -> z pass into a (MODE OUT_MAP; a is then the map) or into out_mask (OUT_LE / OUT_GT)
-hipError_t transform(hipStream_t st, const uint32_t* mask, const DistDims& d, const uint32_t w[3], bool unset, int mode, uint32_t r2, uint32_t* a,
+hipError_t transform(hipStream_t st, const uint32_t* mask, const RegionDims& d, const uint32_t w[3], bool unset, int mode, uint32_t r2, uint32_t* a,
                      uint32_t* b, uint32_t* stack, uint32_t* out_mask)
 {
     const size_t words = mask_words(d), plane = (size_t)d.nx * d.ny;
-    const bool ev = events_ready();
-    if (ev) hipEventRecord(g_ev[2], st);
-    hipLaunchKernelGGL(k_dist_rows, grid_for(words * 32), dim3(THREADS), 0, st, mask, a, d, words, w[0], unset ? 1 : 0);
-    if (ev) hipEventRecord(g_ev[3], st);
+    const bool ev = events_ready(g_pass_ev, 4);
+    if (ev) hipEventRecord(g_pass_ev[0], st);
+    hipLaunchKernelGGL(k_dist_rows, lane_grid(words), dim3(THREADS), 0, st, mask, a, d, words, w[0], unset ? 1 : 0);
+    if (ev) hipEventRecord(g_pass_ev[1], st);
     ColPass py = {(uint32_t)d.ny, (uint32_t)d.nz, (uint32_t)d.nx, (uint32_t)d.wx, w[1], (size_t)d.nx, plane, (size_t)d.ny * d.wx, (size_t)d.wx,
                   (size_t)d.nz * d.nx};
-    hipLaunchKernelGGL((k_dist_columns<OUT_MAP>), grid_for((size_t)d.nz * d.wx * 32), dim3(THREADS), 0, st, a, b, stack, py, 0u);
-    if (ev) hipEventRecord(g_ev[4], st);
+    hipLaunchKernelGGL((k_dist_columns<OUT_MAP>), lane_grid((size_t)d.nz * d.wx), dim3(THREADS), 0, st, a, b, stack, py, 0u);
+    if (ev) hipEventRecord(g_pass_ev[2], st);
     ColPass pz = {(uint32_t)d.nz, (uint32_t)d.ny, (uint32_t)d.nx, (uint32_t)d.wx, w[2], plane, (size_t)d.nx, (size_t)d.wx, (size_t)d.ny * d.wx,
                   (size_t)d.ny * d.nx};
-    const dim3 gz = grid_for((size_t)d.ny * d.wx * 32);
+    const dim3 gz = lane_grid((size_t)d.ny * d.wx);
     if (mode == OUT_MAP) hipLaunchKernelGGL((k_dist_columns<OUT_MAP>), gz, dim3(THREADS), 0, st, b, a, stack, pz, 0u);
     else if (mode == OUT_LE) hipLaunchKernelGGL((k_dist_columns<OUT_LE>), gz, dim3(THREADS), 0, st, b, out_mask, stack, pz, r2);
     else hipLaunchKernelGGL((k_dist_columns<OUT_GT>), gz, dim3(THREADS), 0, st, b, out_mask, stack, pz, r2);
-    if (ev) { hipEventRecord(g_ev[5], st); g_passes = true; }
+    if (ev) { hipEventRecord(g_pass_ev[3], st); g_passes = true; }
     return hipGetLastError();
-}
-
-float elapsed(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    if (hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; }
-    return ms;
 }
 
 } // namespace
@@ -385,16 +309,14 @@ int svr_region_distance(const uint32_t* in_mask_device, int nx, int ny, int nz, 
     if (target != SVR_DIST_TO_SET && target != SVR_DIST_TO_UNSET) return failf(-3, "%s: unknown target %d", who, target);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    const DistDims d = make_dims(nx, ny, nz);
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t n = (size_t)nx * ny * nz;
-    uint32_t* buf = nullptr;                              // the second map and the stacks: 8 bytes per voxel
-    auto cleanup = [&]() { if (buf) hipFree(buf); };
-    DIST_TRY(hipMalloc((void**)&buf, 2 * n * sizeof(uint32_t)));
-    CallTimer timer(st);                                  // (the launches, not the allocation)
-    DIST_TRY(transform(st, in_mask_device, d, w, target == SVR_DIST_TO_UNSET, OUT_MAP, 0u, d2_device, buf, buf + n, nullptr));
+    DeviceBuffer buf;                                     // the second map and the stacks: 8 bytes per voxel
+    SVR_HIP_TRY(buf.alloc(2 * n * sizeof(uint32_t)));
+    CallTimer timer(g_events, st);                        // (the launches, not the allocation)
+    SVR_HIP_TRY(transform(st, in_mask_device, d, w, target == SVR_DIST_TO_UNSET, OUT_MAP, 0u, d2_device, buf.as<uint32_t>(), buf.as<uint32_t>() + n, nullptr));
     timer.stop();
-    DIST_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(hipStreamSynchronize(st));                // (buf is freed on return)
     return 0;
 }
 
@@ -406,12 +328,11 @@ int svr_region_distance_select(const uint32_t* d2_device, int nx, int ny, int nz
     if (lo2 > hi2) return failf(-3, "%s: the range must satisfy lo2 <= hi2 (got %u .. %u)", who, lo2, hi2);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    auto cleanup = []() {};
-    const DistDims d = make_dims(nx, ny, nz);
+    CallTimer timer(g_events, st);
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d);
-    hipLaunchKernelGGL(k_dist_select, grid_for(words * 32), dim3(THREADS), 0, st, d2_device, d, words, lo2, hi2, out_mask_device);
-    DIST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_dist_select, lane_grid(words), dim3(THREADS), 0, st, d2_device, d, words, lo2, hi2, out_mask_device);
+    SVR_HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -423,30 +344,28 @@ int svr_region_ball(const uint32_t* in_mask_device, int nx, int ny, int nz, int 
     if (op != SVR_MORPH_DILATE && op != SVR_MORPH_ERODE && op != SVR_MORPH_OPEN && op != SVR_MORPH_CLOSE) return failf(-3, "%s: unknown op %d", who, op);
     uint32_t w[3];
     if (int e = check_weights(who, weights_or_null, nx, ny, nz, w)) return e;
-    const DistDims d = make_dims(nx, ny, nz);
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d), n = (size_t)nx * ny * nz;
-    if (overlap(in_mask_device, out_mask_device, words * sizeof(uint32_t))) return failf(-3, "%s: out must not overlap in", who);
+    if (overlap(in_mask_device, words * sizeof(uint32_t), out_mask_device, words * sizeof(uint32_t))) return failf(-3, "%s: out must not overlap in", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    uint32_t* buf = nullptr;                              // two maps, the stacks, and the mask between the two halves of open / close
-    auto cleanup = [&]() { if (buf) hipFree(buf); };
     if (r2 == 0u) {                                       // the ball is the voxel itself: the identity, padding cleared
-        CallTimer timer(st);
-        hipLaunchKernelGGL(k_mask_clean, grid_for(words), dim3(THREADS), 0, st, in_mask_device, out_mask_device, d, words);
-        DIST_TRY(hipGetLastError());
+        CallTimer timer(g_events, st);
+        hipLaunchKernelGGL(k_mask_clean, word_grid(words), dim3(THREADS), 0, st, in_mask_device, out_mask_device, d, words);
+        SVR_HIP_TRY(hipGetLastError());
         return 0;
     }
     const bool two = op == SVR_MORPH_OPEN || op == SVR_MORPH_CLOSE;
-    DIST_TRY(hipMalloc((void**)&buf, (3 * n + (two ? words : 0)) * sizeof(uint32_t)));
-    uint32_t *a = buf, *b = buf + n, *stack = buf + 2 * n, *mid = buf + 3 * n;
-    CallTimer timer(st);
+    DeviceBuffer buf;                                     // two maps, the stacks, and the mask between the two halves of open / close
+    SVR_HIP_TRY(buf.alloc((3 * n + (two ? words : 0)) * sizeof(uint32_t)));
+    uint32_t *a = buf.as<uint32_t>(), *b = a + n, *stack = a + 2 * n, *mid = a + 3 * n;
+    CallTimer timer(g_events, st);
     const bool erode_first = op == SVR_MORPH_ERODE || op == SVR_MORPH_OPEN;
     // dilate: d2 to the set voxels <= r2; erode: d2 to the unset voxels of the volume > r2
-    DIST_TRY(transform(st, in_mask_device, d, w, erode_first, erode_first ? OUT_GT : OUT_LE, r2, a, b, stack, two ? mid : out_mask_device));
-    if (two) DIST_TRY(transform(st, mid, d, w, !erode_first, erode_first ? OUT_LE : OUT_GT, r2, a, b, stack, out_mask_device));
+    SVR_HIP_TRY(transform(st, in_mask_device, d, w, erode_first, erode_first ? OUT_GT : OUT_LE, r2, a, b, stack, two ? mid : out_mask_device));
+    if (two) SVR_HIP_TRY(transform(st, mid, d, w, !erode_first, erode_first ? OUT_LE : OUT_GT, r2, a, b, stack, out_mask_device));
     timer.stop();
-    DIST_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(hipStreamSynchronize(st));                // (buf is freed on return)
     return 0;
 }
 
@@ -458,21 +377,20 @@ int svr_region_distance_max(const uint32_t* d2_device, const uint32_t* mask_devi
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    unsigned long long* d_best = nullptr;
-    auto cleanup = [&]() { if (d_best) hipFree(d_best); };
-    DIST_TRY(hipMalloc((void**)&d_best, sizeof(unsigned long long)));
-    CallTimer timer(st);
-    DIST_TRY(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), st));
-    const DistDims d = make_dims(nx, ny, nz);
+    DeviceBuffer best_buf;
+    SVR_HIP_TRY(best_buf.alloc(sizeof(unsigned long long)));
+    unsigned long long* const d_best = best_buf.as<unsigned long long>();
+    CallTimer timer(g_events, st);
+    SVR_HIP_TRY(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), st));
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d);
     const size_t blocks = std::min<size_t>((words * 32 + THREADS - 1) / THREADS, 2048);       // the rest by the grid-stride loop
     hipLaunchKernelGGL(k_dist_max, dim3((uint32_t)blocks), dim3(THREADS), 0, st, d2_device, mask_device_or_null, d, words, d_best);
-    DIST_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
     unsigned long long best = 0ull;
-    DIST_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, st));
-    DIST_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipStreamSynchronize(st));
     *max_d2 = (uint32_t)(best >> 32);
     *first_index = best ? ~(uint32_t)best : 0u;
     *status = best ? SVR_REGION_STATUS_OK : SVR_REGION_STATUS_EMPTY;
@@ -487,11 +405,10 @@ int svr_region_distance_volume(const uint32_t* d2_device, int nx, int ny, int nz
     if (scale < 1u || scale > 65535u) return failf(-3, "%s: the scale must lie in 1 .. 65535 (got %u)", who, scale);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    auto cleanup = []() {};
+    CallTimer timer(g_events, st);
     const size_t n = (size_t)nx * ny * nz;
-    hipLaunchKernelGGL(k_dist_volume, grid_for(n), dim3(THREADS), 0, st, d2_device, n, scale, out_u16_device);
-    DIST_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_dist_volume, word_grid(n), dim3(THREADS), 0, st, d2_device, n, scale, out_u16_device);
+    SVR_HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -525,7 +442,7 @@ int svr_region_distance_weights(const double spacing[3], int nx, int ny, int nz,
 int svr_region_distance_last_ms(float* ms)
 {
     if (!ms) return failf(-4, "svr_region_distance_last_ms: null argument");
-    *ms = g_ev[0] ? elapsed(g_ev[0], g_ev[1]) : 0.f;
+    *ms = g_events.last_ms();
     return 0;
 }
 
@@ -533,7 +450,7 @@ int svr_region_distance_pass_ms(float* rows_ms, float* y_ms, float* z_ms)
 {
     float* const out[3] = {rows_ms, y_ms, z_ms};
     for (int i = 0; i < 3; ++i)
-        if (out[i]) *out[i] = g_passes ? elapsed(g_ev[2 + i], g_ev[3 + i]) : 0.f;
+        if (out[i]) *out[i] = g_passes ? elapsed_ms(g_pass_ev[i], g_pass_ev[i + 1]) : 0.f;
     return 0;
 }
 

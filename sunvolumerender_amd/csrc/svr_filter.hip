@@ -28,6 +28,7 @@
 #include "svr_internal.hpp"
 
 #include "svr_rank_select.hpp"
+#include "svr_volume_host.hpp"      // (no mask here: FilterDims is this file's own)
 
 using svr::failf;
 
@@ -176,57 +177,7 @@ __global__ __launch_bounds__(THREADS) void k_smooth(const uint16_t* __restrict__
 }
 
 // ---------------- host side ----------------
-#define FILTER_TRY(call)                                                                                                         \
-    do {                                                                                                                          \
-        hipError_t _e = (call);                                                                                                   \
-        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
-    } while (0)
-
-int check_dims(const char* who, int nx, int ny, int nz)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
-    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
-        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
-    return 0;
-}
-
-bool overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + bytes && q < p + bytes;
-}
-
-// HIP events around the device work of the last rank / smooth call
-hipEvent_t g_ev[2] = {nullptr, nullptr};
-bool events_ready()
-{
-    if (g_ev[0]) return true;
-    for (auto& e : g_ev)
-        if (hipEventCreate(&e) != hipSuccess) { g_ev[0] = nullptr; return false; }
-    return true;
-}
-struct CallTimer {
-    hipStream_t st;
-    bool on;
-    explicit CallTimer(hipStream_t s) : st(s), on(false) { if (events_ready()) on = hipEventRecord(g_ev[0], st) == hipSuccess; }
-    void stop() { if (on) hipEventRecord(g_ev[1], st); on = false; }
-    ~CallTimer() { stop(); }
-};
-
-// the volume on the device: the caller's pointer, or an upload of the host array on the library's stream
-struct DeviceVoxels {
-    const uint16_t* p = nullptr;
-    uint16_t* owned = nullptr;
-    hipError_t get(const uint16_t* voxels, size_t n, int src_is_device, hipStream_t st)
-    {
-        if (src_is_device) { p = voxels; return hipSuccess; }
-        hipError_t e = hipMalloc((void**)&owned, n * sizeof(uint16_t));
-        if (e != hipSuccess) return e;
-        p = owned;
-        return hipMemcpyAsync(owned, voxels, n * sizeof(uint16_t), hipMemcpyHostToDevice, st);
-    }
-    void release() { if (owned) hipFree(owned); owned = nullptr; }
-};
+CallEvents g_events;                                      // around the device work of the last rank / smooth call (svr_volume_filter_last_ms)
 
 FilterDims make_dims(int nx, int ny, int nz)
 {
@@ -280,30 +231,28 @@ int svr_volume_rank(const uint16_t* voxels, int nx, int ny, int nz, int src_is_d
     if (!voxels || !out_u16_device) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (op != SVR_FILTER_MEDIAN && op != SVR_FILTER_MIN && op != SVR_FILTER_MAX) return failf(-3, "%s: unknown op %d", who, op);
-    if (element != 6 && element != 18 && element != 26) return failf(-3, "%s: the element must be 6, 18 or 26 (got %d)", who, element);
+    if (int e = check_connectivity(who, "element", element)) return e;
     if (iterations < 1u || iterations > SVR_FILTER_MAX_ITERATIONS)
         return failf(-3, "%s: iterations must lie in 1 .. %d (got %u)", who, SVR_FILTER_MAX_ITERATIONS, iterations);
-    const size_t n = (size_t)nx * ny * nz;
-    if (src_is_device && overlap(voxels, out_u16_device, n * sizeof(uint16_t))) return failf(-3, "%s: out must not overlap voxels", who);
+    const size_t n = (size_t)nx * ny * nz, bytes = n * sizeof(uint16_t);
+    if (src_is_device && overlap(voxels, bytes, out_u16_device, bytes)) return failf(-3, "%s: out must not overlap voxels", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
     const FilterDims d = make_dims(nx, ny, nz);
     DeviceVoxels dv;
-    uint16_t* tmp = nullptr;
-    auto cleanup = [&]() { dv.release(); if (tmp) hipFree(tmp); };
-    FILTER_TRY(dv.get(voxels, n, src_is_device, st));
-    if (iterations > 1u) FILTER_TRY(hipMalloc((void**)&tmp, n * sizeof(uint16_t)));
-    CallTimer timer(st);
+    DeviceBuffer tmp;
+    SVR_HIP_TRY(dv.get(voxels, n, src_is_device, st));
+    if (iterations > 1u) SVR_HIP_TRY(tmp.alloc(bytes));
+    CallTimer timer(g_events, st);
     const uint16_t* src = dv.p;
     for (uint32_t i = 0; i < iterations; ++i) {
-        uint16_t* dst = (iterations - 1u - i) % 2u == 0u ? out_u16_device : tmp;       // the last pass writes `out`
+        uint16_t* dst = (iterations - 1u - i) % 2u == 0u ? out_u16_device : tmp.as<uint16_t>();    // the last pass writes `out`
         launch_rank(op, element, st, src, dst, d);
         src = dst;
     }
-    FILTER_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
-    if (dv.owned || tmp) FILTER_TRY(hipStreamSynchronize(st));       // the upload and the temporary are freed below
-    cleanup();
+    if (dv.owned() || tmp) SVR_HIP_TRY(hipStreamSynchronize(st));     // the upload and the temporary are freed on return
     return 0;
 }
 
@@ -315,37 +264,35 @@ int svr_volume_smooth(const uint16_t* voxels, int nx, int ny, int nz, int src_is
     for (int a = 0; a < 3; ++a)
         if (radii_xyz[a] > SVR_SMOOTH_MAX_RADIUS)
             return failf(-3, "%s: a radius must be at most %d (got %u, %u, %u)", who, SVR_SMOOTH_MAX_RADIUS, radii_xyz[0], radii_xyz[1], radii_xyz[2]);
-    const size_t n = (size_t)nx * ny * nz;
-    if (src_is_device && overlap(voxels, out_u16_device, n * sizeof(uint16_t))) return failf(-3, "%s: out must not overlap voxels", who);
+    const size_t n = (size_t)nx * ny * nz, bytes = n * sizeof(uint16_t);
+    if (src_is_device && overlap(voxels, bytes, out_u16_device, bytes)) return failf(-3, "%s: out must not overlap voxels", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
     const FilterDims d = make_dims(nx, ny, nz);
     int axes[3], passes = 0;
     for (int a = 0; a < 3; ++a)
         if (radii_xyz[a] > 0u) axes[passes++] = a;
-    DeviceVoxels dv;
-    uint16_t* tmp = nullptr;
-    auto cleanup = [&]() { dv.release(); if (tmp) hipFree(tmp); };
     if (passes == 0) {                                    // a copy
-        CallTimer timer(st);
-        FILTER_TRY(hipMemcpyAsync(out_u16_device, voxels, n * sizeof(uint16_t), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        CallTimer timer(g_events, st);
+        SVR_HIP_TRY(hipMemcpyAsync(out_u16_device, voxels, bytes, src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         timer.stop();
-        if (!src_is_device) FILTER_TRY(hipStreamSynchronize(st));    // the host array is the caller's again on return
+        if (!src_is_device) SVR_HIP_TRY(hipStreamSynchronize(st));    // the host array is the caller's again on return
         return 0;
     }
-    FILTER_TRY(dv.get(voxels, n, src_is_device, st));
-    if (passes > 1) FILTER_TRY(hipMalloc((void**)&tmp, n * sizeof(uint16_t)));
-    CallTimer timer(st);
+    DeviceVoxels dv;
+    DeviceBuffer tmp;
+    SVR_HIP_TRY(dv.get(voxels, n, src_is_device, st));
+    if (passes > 1) SVR_HIP_TRY(tmp.alloc(bytes));
+    CallTimer timer(g_events, st);
     const uint16_t* src = dv.p;
     for (int i = 0; i < passes; ++i) {
-        uint16_t* dst = (passes - 1 - i) % 2 == 0 ? out_u16_device : tmp;
+        uint16_t* dst = (passes - 1 - i) % 2 == 0 ? out_u16_device : tmp.as<uint16_t>();
         launch_smooth(axes[i], radii_xyz[axes[i]], st, src, dst, d);
         src = dst;
     }
-    FILTER_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
-    if (dv.owned || tmp) FILTER_TRY(hipStreamSynchronize(st));
-    cleanup();
+    if (dv.owned() || tmp) SVR_HIP_TRY(hipStreamSynchronize(st));     // the upload and the temporary are freed on return
     return 0;
 }
 
@@ -374,11 +321,7 @@ int svr_volume_smooth_radii(const double spacing[3], double sigma, uint32_t radi
 int svr_volume_filter_last_ms(float* ms)
 {
     if (!ms) return failf(-4, "svr_volume_filter_last_ms: null argument");
-    *ms = 0.f;
-    if (g_ev[0] && (hipEventSynchronize(g_ev[1]) != hipSuccess || hipEventElapsedTime(ms, g_ev[0], g_ev[1]) != hipSuccess)) {
-        (void)hipGetLastError();
-        *ms = 0.f;
-    }
+    *ms = g_events.last_ms();
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // svr_geodesic.hip -- geodesic distances and influence zones inside region masks, and the splitting of a region at its necks that they
 // make possible (svr_region_geodesic, _seed_labels, _geodesic_weights, _split, _zone_cut; the contract is in include/svr_abi.h, the design
-// in DESIGN.md 8m).  Integers only, on the mask layout of svr_region.hip: voxel (x, y, z) = bit x & 31 of word (z * ny + y) * wx + (x >> 5).
+// in DESIGN.md 8m).  Integers only, on the mask layout of svr_mask.hpp.
 //
 // Every voxel has one packed key (dist << 32) | zone in a workspace of 8 bytes per voxel; ~0 = "outside the domain or not reached".  A
 // source has (0, label); every other voxel of the domain wants the lexicographic minimum over its allowed neighbours u of
@@ -32,7 +32,9 @@
 
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
+#include "svr_mask.hpp"             // RegionDims, lane_at, half_ballot, the grids
 #include "svr_sweep.hpp"
+#include "svr_volume_host.hpp"
 
 using svr::failf;
 
@@ -42,9 +44,8 @@ constexpr int GX = 32, GY = 8, GZ = 8;                   // tile in voxels; GX =
 constexpr int GEO_THREADS = GX * GY;                     // one thread per column of GZ voxels
 static_assert(GEO_THREADS == 256 && GX == 32, "the lane mapping assumes a tile one mask word wide and 256 threads");
 constexpr uint64_t KEY_NONE = ~0ull;
-constexpr int LANE_THREADS = 256;                        // the one-lane-per-voxel kernels
+constexpr int LANE_THREADS = MASK_THREADS;               // the one-lane-per-voxel kernels
 
-struct GeoDims { int nx, ny, nz, wx; };
 // w[c]: the weight of move class c (x, y, z, xy, xz, yz, xyz); reach bit c: a tile in a direction of class c can see this tile's keys
 struct GeoWeights { uint32_t w[7]; uint32_t reach; };
 struct GeoSeeds { uint32_t n; uint32_t at[SVR_REGION_MAX_SEEDS]; };   // at[i] = the voxel of seed i, or ~0 if a lower seed has it
@@ -61,37 +62,10 @@ __device__ inline void lds_put(uint64_t* p, uint64_t v) { __hip_atomic_store(p, 
 __device__ inline uint64_t key_get(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void key_put(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// a lane of the one-lane-per-voxel kernels: bit `bit` of mask word i, voxel v = (x, y, z)
-struct GeoLane { size_t i, v; int bit, x, y, z; bool word_ok, inside; };
-__device__ inline GeoLane geo_lane(const GeoDims& d, size_t words)
-{
-    const size_t t = (size_t)blockIdx.x * LANE_THREADS + threadIdx.x;
-    GeoLane a;
-    a.i = t >> 5;
-    a.bit = (int)(t & 31u);
-    a.word_ok = a.i < words;
-    const size_t i = a.word_ok ? a.i : 0;
-    const int gw = (int)(i % (unsigned)d.wx);
-    const size_t row = i / (unsigned)d.wx;
-    a.x = gw * 32 + a.bit;
-    a.y = (int)(row % (unsigned)d.ny);
-    a.z = (int)(row / (unsigned)d.ny);
-    a.inside = a.word_ok && a.x < d.nx;
-    a.v = row * (size_t)d.nx + (size_t)a.x;
-    return a;
-}
-
-// the 32 bits of this lane's half of the wave
-__device__ inline uint32_t geo_half_ballot(bool p)
-{
-    const unsigned long long b = __ballot(p);
-    return (threadIdx.x & 32) ? (uint32_t)(b >> 32) : (uint32_t)b;
-}
-
-__global__ __launch_bounds__(LANE_THREADS) void k_geo_init(const uint32_t* labels, const uint32_t* __restrict__ mask, GeoDims d, size_t words, int nty,
+__global__ __launch_bounds__(LANE_THREADS) void k_geo_init(const uint32_t* labels, const uint32_t* __restrict__ mask, RegionDims d, size_t words, int nty,
                                                            uint64_t* __restrict__ keys, uint32_t* __restrict__ dirty)
 {
-    const GeoLane a = geo_lane(d, words);
+    const LaneAt a = lane_at(d, words);
     if (!a.inside) return;
     const uint32_t lab = labels[a.v];
     const bool source = lab != 0u && ((mask[a.i] >> a.bit) & 1u);
@@ -99,7 +73,7 @@ __global__ __launch_bounds__(LANE_THREADS) void k_geo_init(const uint32_t* label
     if (source) dirty[((size_t)(a.z / GZ) * nty + a.y / GY) * d.wx + a.x / GX] = 1u;
 }
 
-__global__ __launch_bounds__(GEO_THREADS) void k_geo_relax(uint64_t* keys, const uint32_t* __restrict__ mask, GeoDims d, GeoWeights gw, int nty, int ntz,
+__global__ __launch_bounds__(GEO_THREADS) void k_geo_relax(uint64_t* keys, const uint32_t* __restrict__ mask, RegionDims d, GeoWeights gw, int nty, int ntz,
                                                            uint32_t* dirty_cur, uint32_t* dirty_next, uint32_t* added)
 {
     const size_t tile = blockIdx.x;
@@ -183,10 +157,10 @@ __global__ __launch_bounds__(GEO_THREADS) void k_geo_relax(uint64_t* keys, const
     }
 }
 
-__global__ __launch_bounds__(LANE_THREADS) void k_geo_finish(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ mask, GeoDims d, size_t words,
+__global__ __launch_bounds__(LANE_THREADS) void k_geo_finish(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ mask, RegionDims d, size_t words,
                                                              uint32_t* dist, uint32_t* zones, uint32_t* unreached)
 {
-    const GeoLane a = geo_lane(d, words);
+    const LaneAt a = lane_at(d, words);
     bool lost = false;
     if (a.inside) {
         const uint64_t k = keys[a.v];
@@ -206,9 +180,9 @@ __global__ void k_geo_seeds(GeoSeeds s, uint32_t* __restrict__ labels)
 }
 
 template <int CONN>
-__global__ __launch_bounds__(LANE_THREADS) void k_zone_cut(const uint32_t* __restrict__ zones, GeoDims d, size_t words, uint32_t* __restrict__ out)
+__global__ __launch_bounds__(LANE_THREADS) void k_zone_cut(const uint32_t* __restrict__ zones, RegionDims d, size_t words, uint32_t* __restrict__ out)
 {
-    const GeoLane a = geo_lane(d, words);
+    const LaneAt a = lane_at(d, words);
     bool keep = false;
     if (a.inside) {
         const uint32_t z = zones[a.v];
@@ -228,32 +202,12 @@ __global__ __launch_bounds__(LANE_THREADS) void k_zone_cut(const uint32_t* __res
                         if (n != 0u && n < z) keep = false;
                     }
     }
-    const uint32_t word = geo_half_ballot(keep);
+    const uint32_t word = half_ballot(keep);
     if (a.bit == 0 && a.word_ok) out[a.i] = word;
 }
 
 // ---------------- host side ----------------
-#define GEO_TRY(call)                                                                                                            \
-    do {                                                                                                                          \
-        hipError_t _e = (call);                                                                                                   \
-        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
-    } while (0)
-
 constexpr uint32_t CHAMFER[7] = {3u, 3u, 3u, 4u, 4u, 4u, 5u};
-
-int geo_check_dims(const char* who, int nx, int ny, int nz)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
-    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
-        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
-    return 0;
-}
-
-int geo_check_connectivity(const char* who, int connectivity)
-{
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26) return failf(-3, "%s: the connectivity must be 6, 18 or 26 (got %d)", who, connectivity);
-    return 0;
-}
 
 int classes_of(int connectivity) { return connectivity == 6 ? 3 : connectivity == 18 ? 6 : 7; }
 
@@ -289,67 +243,43 @@ int check_step_weights(const char* who, const uint32_t* weights_or_null, int con
     return 0;
 }
 
-bool geo_overlap(const void* a, size_t abytes, const void* b, size_t bbytes)
-{
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + bbytes && q < p + abytes;
-}
-
-GeoDims geo_dims(int nx, int ny, int nz) { return GeoDims{nx, ny, nz, (nx + 31) / 32}; }
-size_t geo_words(const GeoDims& d) { return (size_t)d.wx * d.ny * d.nz; }
-dim3 lanes_for(size_t words) { return dim3((uint32_t)((words * 32 + LANE_THREADS - 1) / LANE_THREADS)); }   // at most 2^31 + 2^26 lanes
 uint64_t geo_tiles(int nx, int ny, int nz) { return (uint64_t)((nx + GX - 1) / GX) * (uint64_t)((ny + GY - 1) / GY) * (uint64_t)((nz + GZ - 1) / GZ); }
 
-hipEvent_t g_ev[2] = {nullptr, nullptr};                 // around the device work of the last call of this file
-bool events_ready()
-{
-    if (g_ev[0]) return true;
-    for (auto& e : g_ev)
-        if (hipEventCreate(&e) != hipSuccess) { g_ev[0] = nullptr; return false; }
-    return true;
-}
-struct CallTimer {
-    hipStream_t st;
-    bool on;
-    explicit CallTimer(hipStream_t s) : st(s), on(false) { if (events_ready()) on = hipEventRecord(g_ev[0], st) == hipSuccess; }
-    void stop() { if (on) hipEventRecord(g_ev[1], st); on = false; }
-    ~CallTimer() { stop(); }
-};
+CallEvents g_events;                                     // around the device work of the last call of this file (svr_region_geodesic_last_ms)
 
 // the checked core of svr_region_geodesic and of the zones step of svr_region_split.  *unreached (may be NULL) = the voxels of the
 // domain that no source reaches.  Synchronises the stream.
-int geodesic_run(const char* who, const uint32_t* labels, const uint32_t* mask, const GeoDims& d, const GeoWeights& gw, uint32_t max_sweeps, uint32_t* dist,
+int geodesic_run(const char* who, const uint32_t* labels, const uint32_t* mask, const RegionDims& d, const GeoWeights& gw, uint32_t max_sweeps, uint32_t* dist,
                  uint32_t* zones, uint32_t* unreached, uint32_t* sweeps_out)
 {
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    const size_t n = (size_t)d.nx * d.ny * d.nz, words = geo_words(d);
+    const size_t n = (size_t)d.nx * d.ny * d.nz, words = mask_words(d);
     const int nty = (d.ny + GY - 1) / GY, ntz = (d.nz + GZ - 1) / GZ;
     const size_t tiles = (size_t)d.wx * nty * ntz;
     const uint32_t cap = max_sweeps ? max_sweeps : svr_region_geodesic_default_max_sweeps(d.nx, d.ny, d.nz);
-    uint64_t* keys = nullptr;                            // the keys, then the two dirty maps, the batch counters and the unreached count
-    auto cleanup = [&]() { if (keys) hipFree(keys); };
+    DeviceBuffer buf;                                    // the keys, then the two dirty maps, the batch counters and the unreached count
     const size_t small = 2 * tiles + SVR_REGION_BATCH + 1;
-    GEO_TRY(hipMalloc((void**)&keys, n * sizeof(uint64_t) + small * sizeof(uint32_t)));
+    SVR_HIP_TRY(buf.alloc(n * sizeof(uint64_t) + small * sizeof(uint32_t)));
+    uint64_t* const keys = buf.as<uint64_t>();
     uint32_t* const dirty = (uint32_t*)(keys + n);
     uint32_t* const added = dirty + 2 * tiles;
     uint32_t* const lost = added + SVR_REGION_BATCH;
-    CallTimer timer(st);                                 // (the launches, not the allocation)
-    GEO_TRY(hipMemsetAsync(dirty, 0, small * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_geo_init, lanes_for(words), dim3(LANE_THREADS), 0, st, labels, mask, d, words, nty, keys, dirty);
-    GEO_TRY(hipGetLastError());
+    CallTimer timer(g_events, st);                       // (the launches, not the allocation)
+    SVR_HIP_TRY(hipMemsetAsync(dirty, 0, small * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_geo_init, lane_grid(words), dim3(LANE_THREADS), 0, st, labels, mask, d, words, nty, keys, dirty);
+    SVR_HIP_TRY(hipGetLastError());
     uint32_t sweeps = 0u;
     bool done = false;
-    GEO_TRY(sweep_to_fixpoint(st, tiles, dirty, added, cap, &sweeps, &done, [&](uint32_t* cur, uint32_t* next, uint32_t* add) {
+    SVR_HIP_TRY(sweep_to_fixpoint(st, tiles, dirty, added, cap, &sweeps, &done, [&](uint32_t* cur, uint32_t* next, uint32_t* add) {
         hipLaunchKernelGGL(k_geo_relax, dim3((uint32_t)tiles), dim3(GEO_THREADS), 0, st, keys, mask, d, gw, nty, ntz, cur, next, add);
     }));
-    hipLaunchKernelGGL(k_geo_finish, lanes_for(words), dim3(LANE_THREADS), 0, st, keys, mask, d, words, dist, zones, lost);
-    GEO_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_geo_finish, lane_grid(words), dim3(LANE_THREADS), 0, st, keys, mask, d, words, dist, zones, lost);
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
     uint32_t lost_host = 0u;
-    GEO_TRY(hipMemcpyAsync(&lost_host, lost, sizeof lost_host, hipMemcpyDeviceToHost, st));
-    GEO_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(hipMemcpyAsync(&lost_host, lost, sizeof lost_host, hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipStreamSynchronize(st));               // (buf is freed on return)
     if (sweeps_out) *sweeps_out = sweeps;
     if (unreached) *unreached = lost_host;
     if (!done) return failf(SVR_REGION_ERR_SWEEPS, "%s: keys were still falling after %u sweeps; the outputs are upper bounds, not the map", who, sweeps);
@@ -374,19 +304,19 @@ int svr_region_geodesic(const uint32_t* marker_labels_device, const uint32_t* do
     const char* who = "svr_region_geodesic";
     if (!marker_labels_device || !domain_mask_device) return failf(-4, "%s: null argument", who);
     if (!dist_device_or_null && !zones_device_or_null) return failf(-4, "%s: both outputs are null", who);
-    if (int e = geo_check_dims(who, nx, ny, nz)) return e;
+    if (int e = check_dims(who, nx, ny, nz)) return e;
     GeoWeights gw;
     if (int e = check_step_weights(who, step_weights_or_null, 26, nx, ny, nz, &gw)) return e;
-    const GeoDims d = geo_dims(nx, ny, nz);
-    const size_t map_bytes = (size_t)nx * ny * nz * sizeof(uint32_t), mask_bytes = geo_words(d) * sizeof(uint32_t);
+    const RegionDims d = make_dims(nx, ny, nz);
+    const size_t map_bytes = (size_t)nx * ny * nz * sizeof(uint32_t), mask_bytes = mask_words(d) * sizeof(uint32_t);
     uint32_t* const outs[2] = {dist_device_or_null, zones_device_or_null};
     for (int i = 0; i < 2; ++i) {
         if (!outs[i]) continue;
         const bool alias = i == 1 && outs[i] == marker_labels_device;                 // zones in place over the labels
-        if (geo_overlap(outs[i], map_bytes, domain_mask_device, mask_bytes) || (!alias && geo_overlap(outs[i], map_bytes, marker_labels_device, map_bytes)))
+        if (overlap(outs[i], map_bytes, domain_mask_device, mask_bytes) || (!alias && overlap(outs[i], map_bytes, marker_labels_device, map_bytes)))
             return failf(-3, "%s: an output must not overlap an input (only zones may be the marker labels themselves)", who);
     }
-    if (outs[0] && outs[1] && geo_overlap(outs[0], map_bytes, outs[1], map_bytes)) return failf(-3, "%s: the two outputs must not overlap", who);
+    if (outs[0] && outs[1] && overlap(outs[0], map_bytes, outs[1], map_bytes)) return failf(-3, "%s: the two outputs must not overlap", who);
     return geodesic_run(who, marker_labels_device, domain_mask_device, d, gw, max_sweeps, dist_device_or_null, zones_device_or_null, nullptr, sweeps_out);
 }
 
@@ -394,16 +324,14 @@ int svr_region_seed_labels(const int32_t* seeds_xyz, uint32_t nseeds, int nx, in
 {
     const char* who = "svr_region_seed_labels";
     if (!seeds_xyz || !labels_device) return failf(-4, "%s: null argument", who);
-    if (int e = geo_check_dims(who, nx, ny, nz)) return e;
-    if (nseeds == 0u || nseeds > SVR_REGION_MAX_SEEDS) return failf(-3, "%s: nseeds must lie in 1 .. %d (got %u)", who, SVR_REGION_MAX_SEEDS, nseeds);
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (int e = check_seeds(who, seeds_xyz, nseeds, nx, ny, nz)) return e;
     GeoSeeds seeds;
     memset(&seeds, 0, sizeof seeds);
     seeds.n = nseeds;
     uint32_t at[SVR_REGION_MAX_SEEDS];
     for (uint32_t i = 0; i < nseeds; ++i) {
         const int32_t x = seeds_xyz[3u * i], y = seeds_xyz[3u * i + 1u], z = seeds_xyz[3u * i + 2u];
-        if (x < 0 || x >= nx || y < 0 || y >= ny || z < 0 || z >= nz)
-            return failf(-3, "%s: seed %u (%d, %d, %d) lies outside the %d x %d x %d volume", who, i, x, y, z, nx, ny, nz);
         at[i] = (uint32_t)(((size_t)z * ny + y) * nx + x);                // below 2^31
         seeds.at[i] = at[i];
         for (uint32_t j = 0; j < i; ++j)
@@ -411,11 +339,10 @@ int svr_region_seed_labels(const int32_t* seeds_xyz, uint32_t nseeds, int nx, in
     }
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    auto cleanup = []() {};
-    CallTimer timer(st);
-    GEO_TRY(hipMemsetAsync(labels_device, 0, (size_t)nx * ny * nz * sizeof(uint32_t), st));
+    CallTimer timer(g_events, st);
+    SVR_HIP_TRY(hipMemsetAsync(labels_device, 0, (size_t)nx * ny * nz * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_geo_seeds, dim3(1), dim3(SVR_REGION_MAX_SEEDS), 0, st, seeds, labels_device);
-    GEO_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -423,8 +350,8 @@ int svr_region_geodesic_weights(const double spacing[3], int connectivity, int n
 {
     const char* who = "svr_region_geodesic_weights";
     if (!spacing || !weights || !unit_out) return failf(-4, "%s: null argument", who);
-    if (int e = geo_check_dims(who, nx, ny, nz)) return e;
-    if (int e = geo_check_connectivity(who, connectivity)) return e;
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
     for (int a = 0; a < 3; ++a)
         if (!(spacing[a] > 0.0) || !std::isfinite(spacing[a])) return failf(-3, "%s: the spacing must be positive and finite (got %g, %g, %g)", who, spacing[0], spacing[1], spacing[2]);
     const double sx = spacing[0], sy = spacing[1], sz = spacing[2];
@@ -457,29 +384,28 @@ int svr_region_split(const uint32_t* in_mask_device, int nx, int ny, int nz, con
 {
     const char* who = "svr_region_split";
     if (!in_mask_device || !zones_device || !count_out || !unreached_out) return failf(-4, "%s: null argument", who);
-    if (int e = geo_check_dims(who, nx, ny, nz)) return e;
-    if (int e = geo_check_connectivity(who, connectivity)) return e;
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
     GeoWeights gw;
     if (int e = check_step_weights(who, step_weights_or_null, connectivity, nx, ny, nz, &gw)) return e;
     uint32_t dw[3];
     if (int e = svr::check_distance_weights(who, dist_weights_or_null, nx, ny, nz, dw)) return e;
-    const GeoDims d = geo_dims(nx, ny, nz);
-    const size_t words = geo_words(d);
-    if (geo_overlap(zones_device, (size_t)nx * ny * nz * sizeof(uint32_t), in_mask_device, words * sizeof(uint32_t)))
+    const RegionDims d = make_dims(nx, ny, nz);
+    const size_t words = mask_words(d);
+    if (overlap(zones_device, (size_t)nx * ny * nz * sizeof(uint32_t), in_mask_device, words * sizeof(uint32_t)))
         return failf(-3, "%s: zones must not overlap the input mask", who);
     if (svr::ensure_ready()) return svr_last_error_code();
-    uint32_t* cores = nullptr;                           // the eroded mask
-    auto cleanup = [&]() { if (cores) hipFree(cores); };
-    GEO_TRY(hipMalloc((void**)&cores, words * sizeof(uint32_t)));
     uint32_t count = 0u;
-    int e = svr_region_ball(in_mask_device, nx, ny, nz, SVR_MORPH_ERODE, dw, r2, cores);
-    if (!e) e = svr_region_label(cores, nx, ny, nz, connectivity, zones_device, &count);      // the labels go where the zones will
-    if (e) { cleanup(); return e; }
-    GEO_TRY(hipStreamSynchronize(svr::current_stream()));                                       // (an r2 = 0 ball and the label are done with `cores`)
-    cleanup();
-    cores = nullptr;
+    {
+        DeviceBuffer cores;                              // the eroded mask: freed at the end of this block, before the keys are allocated
+        SVR_HIP_TRY(cores.alloc(words * sizeof(uint32_t)));
+        int e = svr_region_ball(in_mask_device, nx, ny, nz, SVR_MORPH_ERODE, dw, r2, cores.as<uint32_t>());
+        if (!e) e = svr_region_label(cores.as<uint32_t>(), nx, ny, nz, connectivity, zones_device, &count);   // the labels go where the zones will
+        if (e) return e;
+        SVR_HIP_TRY(hipStreamSynchronize(svr::current_stream()));                                 // (an r2 = 0 ball and the label are done with `cores`)
+    }
     uint32_t lost = 0u;
-    e = geodesic_run(who, zones_device, in_mask_device, d, gw, max_sweeps, nullptr, zones_device, &lost, sweeps_out);
+    const int e = geodesic_run(who, zones_device, in_mask_device, d, gw, max_sweeps, nullptr, zones_device, &lost, sweeps_out);
     if (e) return e;
     *count_out = count;
     *unreached_out = lost;
@@ -490,30 +416,27 @@ int svr_region_zone_cut(const uint32_t* zones_device, int nx, int ny, int nz, in
 {
     const char* who = "svr_region_zone_cut";
     if (!zones_device || !out_mask_device) return failf(-4, "%s: null argument", who);
-    if (int e = geo_check_dims(who, nx, ny, nz)) return e;
-    if (int e = geo_check_connectivity(who, connectivity)) return e;
-    const GeoDims d = geo_dims(nx, ny, nz);
-    const size_t words = geo_words(d);
-    if (geo_overlap(out_mask_device, words * sizeof(uint32_t), zones_device, (size_t)nx * ny * nz * sizeof(uint32_t)))
+    if (int e = check_dims(who, nx, ny, nz)) return e;
+    if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
+    const RegionDims d = make_dims(nx, ny, nz);
+    const size_t words = mask_words(d);
+    if (overlap(out_mask_device, words * sizeof(uint32_t), zones_device, (size_t)nx * ny * nz * sizeof(uint32_t)))
         return failf(-3, "%s: out must not overlap the zones", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    auto cleanup = []() {};
-    CallTimer timer(st);
-    const dim3 g = lanes_for(words), b(LANE_THREADS);
+    CallTimer timer(g_events, st);
+    const dim3 g = lane_grid(words), b(LANE_THREADS);
     if (connectivity == 6) hipLaunchKernelGGL((k_zone_cut<6>), g, b, 0, st, zones_device, d, words, out_mask_device);
     else if (connectivity == 18) hipLaunchKernelGGL((k_zone_cut<18>), g, b, 0, st, zones_device, d, words, out_mask_device);
     else hipLaunchKernelGGL((k_zone_cut<26>), g, b, 0, st, zones_device, d, words, out_mask_device);
-    GEO_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int svr_region_geodesic_last_ms(float* ms)
 {
     if (!ms) return failf(-4, "svr_region_geodesic_last_ms: null argument");
-    float v = 0.f;
-    if (g_ev[0] && (hipEventSynchronize(g_ev[1]) != hipSuccess || hipEventElapsedTime(&v, g_ev[0], g_ev[1]) != hipSuccess)) { (void)hipGetLastError(); v = 0.f; }
-    *ms = v;
+    *ms = g_events.last_ms();
     return 0;
 }
 

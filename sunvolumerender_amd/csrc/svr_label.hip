@@ -1,7 +1,6 @@
 // svr_label.hip -- the "islands" operations on region masks: the window's mask without a seed, connected-component labelling, the
 // component table, selection by label and by size (svr_region_threshold, _label, _label_table, _select, _select_by_size; the contract
-// is in include/svr_abi.h, the design in DESIGN.md 8j).  Integers only, on the mask layout of svr_region.hip: voxel (x, y, z) = bit
-// x & 31 of word (z * ny + y) * wx + (x >> 5).  Input padding is ignored, output padding is 0.
+// is in include/svr_abi.h, the design in DESIGN.md 8j).  Integers only, on the mask layout and padding rule of svr_mask.hpp.
 //
 // LABEL: union-find by smallest index, in place in the label array L (uint32 [nz][ny][nx]).
 //   NODES: a run of set bits inside one mask word is one node, named by the linear voxel index of its first voxel -- the smallest
@@ -45,6 +44,8 @@
 
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
+#include "svr_mask.hpp"             // RegionDims, valid_bits, half_ballot, the grids
+#include "svr_volume_host.hpp"
 
 using svr::failf;
 
@@ -52,18 +53,11 @@ using svr::failf;
 
 namespace {
 
-constexpr int THREADS = 256;
+constexpr int THREADS = MASK_THREADS;
 static_assert(SVR_LABEL_SCAN_BLOCK == THREADS, "k_scan_block scans one word per thread");
 static_assert(sizeof(svr_region_component) == 40, "svr_region_component is 40 bytes");
 
-struct LabelDims { int nx, ny, nz, wx; };
 struct LabelBox { int x0, y0, z0, x1, y1, z1; };          // inclusive
-
-__device__ inline uint32_t valid_bits(int gw, const LabelDims& d)
-{
-    const int rem = d.nx - gw * 32;
-    return rem >= 32 ? 0xffffffffu : (1u << rem) - 1u;
-}
 
 // the lowest bit of the run of m that holds bit k
 __device__ inline int run_start(uint32_t m, int k)
@@ -110,7 +104,7 @@ __device__ inline void unite(uint32_t* L, uint32_t a, uint32_t b, uint32_t cap, 
 }
 
 struct WordAt { size_t i; int gw, gy, gz; size_t row; };
-__device__ inline WordAt word_at(size_t i, const LabelDims& d)
+__device__ inline WordAt word_at(size_t i, const RegionDims& d)
 {
     WordAt w;
     w.i = i;
@@ -122,14 +116,14 @@ __device__ inline WordAt word_at(size_t i, const LabelDims& d)
 }
 
 // the mask word (gw, gy, gz) without padding; 0 outside the volume
-__device__ inline uint32_t mask_word(const uint32_t* __restrict__ mask, int gw, int gy, int gz, const LabelDims& d)
+__device__ inline uint32_t mask_word(const uint32_t* __restrict__ mask, int gw, int gy, int gz, const RegionDims& d)
 {
     if (gw < 0 || gw >= d.wx || gy < 0 || gy >= d.ny || gz < 0 || gz >= d.nz) return 0u;
     return mask[((size_t)gz * d.ny + gy) * d.wx + gw] & valid_bits(gw, d);
 }
 
 #ifndef SVR_LABEL_GLOBAL_ONLY
-__global__ __launch_bounds__(THREADS) void k_label_init(const uint32_t* __restrict__ mask, uint32_t* __restrict__ L, LabelDims d, size_t words)
+__global__ __launch_bounds__(THREADS) void k_label_init(const uint32_t* __restrict__ mask, uint32_t* __restrict__ L, RegionDims d, size_t words)
 {
     const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
     if (i >= words) return;
@@ -143,7 +137,7 @@ __global__ __launch_bounds__(THREADS) void k_label_init(const uint32_t* __restri
 }
 
 template <int CONN>
-__global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restrict__ mask, uint32_t* L, LabelDims d, size_t words, uint32_t cap,
+__global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restrict__ mask, uint32_t* L, RegionDims d, size_t words, uint32_t cap,
                                                          uint32_t* err)
 {
     const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
@@ -188,7 +182,7 @@ __global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restr
     }
 }
 
-__global__ __launch_bounds__(THREADS) void k_label_flatten(const uint32_t* __restrict__ mask, uint32_t* L, LabelDims d, size_t words, uint32_t cap,
+__global__ __launch_bounds__(THREADS) void k_label_flatten(const uint32_t* __restrict__ mask, uint32_t* L, RegionDims d, size_t words, uint32_t cap,
                                                            uint32_t* err, uint32_t* __restrict__ roots, uint32_t* __restrict__ counts)
 {
     const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
@@ -210,7 +204,7 @@ __global__ __launch_bounds__(THREADS) void k_label_flatten(const uint32_t* __res
 }
 #else
 // ---- the A/B form: every voxel a node, every backward neighbour a union, no runs ----
-__global__ __launch_bounds__(THREADS) void k_label_init(const uint32_t* __restrict__ mask, uint32_t* __restrict__ L, LabelDims d, size_t words)
+__global__ __launch_bounds__(THREADS) void k_label_init(const uint32_t* __restrict__ mask, uint32_t* __restrict__ L, RegionDims d, size_t words)
 {
     const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
     if (i >= words) return;
@@ -223,7 +217,7 @@ __global__ __launch_bounds__(THREADS) void k_label_init(const uint32_t* __restri
 }
 
 template <int CONN>
-__global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restrict__ mask, uint32_t* L, LabelDims d, size_t words, uint32_t cap,
+__global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restrict__ mask, uint32_t* L, RegionDims d, size_t words, uint32_t cap,
                                                          uint32_t* err)
 {
     const size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x;
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restr
             }
 }
 
-__global__ __launch_bounds__(THREADS) void k_label_flatten(const uint32_t* __restrict__ mask, uint32_t* L, LabelDims d, size_t words, uint32_t cap,
+__global__ __launch_bounds__(THREADS) void k_label_flatten(const uint32_t* __restrict__ mask, uint32_t* L, RegionDims d, size_t words, uint32_t cap,
                                                            uint32_t* err, uint32_t* __restrict__ roots, uint32_t* __restrict__ counts)
 {
     const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
@@ -294,11 +288,13 @@ __global__ __launch_bounds__(THREADS) void k_scan_add(uint32_t* __restrict__ dat
     if (i < n) data[i] += sums[blockIdx.x];
 }
 
-// a lane of the kernels below: bit `bit` of mask word i
-struct LaneAt { size_t i; int bit, x; bool inside; WordAt w; size_t v; };
-__device__ inline LaneAt lane_at(const LabelDims& d, size_t words)
+// A lane of the kernels below: bit `bit` of mask word i.  This file keeps its own form of svr_mask.hpp's lane_at: with the shared one
+// k_label_threshold and k_label_table<> came out with another instruction order (the same instructions and register counts), and the
+// device code of these files is pinned (tools/kernel_asm_digest.py).
+struct LabelLane { size_t i; int bit, x; bool inside; WordAt w; size_t v; };
+__device__ inline LabelLane label_lane(const RegionDims& d, size_t words)
 {
-    LaneAt a;
+    LabelLane a;
     const size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x;
     a.i = t >> 5;
     a.bit = (int)(t & 31u);
@@ -310,17 +306,10 @@ __device__ inline LaneAt lane_at(const LabelDims& d, size_t words)
     return a;
 }
 
-// the 32 bits of this lane's half of the wave
-__device__ inline uint32_t half_ballot(bool p)
-{
-    const unsigned long long b = __ballot(p);
-    return (threadIdx.x & 32) ? (uint32_t)(b >> 32) : (uint32_t)b;
-}
-
-__global__ __launch_bounds__(THREADS) void k_label_renumber(const uint32_t* __restrict__ mask, uint32_t* L, LabelDims d, size_t words,
+__global__ __launch_bounds__(THREADS) void k_label_renumber(const uint32_t* __restrict__ mask, uint32_t* L, RegionDims d, size_t words,
                                                             const uint32_t* __restrict__ roots, const uint32_t* __restrict__ scan)
 {
-    const LaneAt a = lane_at(d, words);
+    const LabelLane a = label_lane(d, words);
     const uint32_t m = a.i < words ? mask[a.i] & valid_bits(a.w.gw, d) : 0u;
     const bool set = (m >> a.bit) & 1u;
     const int s = run_start(m, a.bit);
@@ -355,10 +344,10 @@ __global__ void k_table_init(svr_region_component* t, uint32_t count)
 }
 
 template <bool COMBINE>
-__global__ __launch_bounds__(THREADS) void k_label_table(const uint32_t* __restrict__ labels, const uint16_t* __restrict__ vox, LabelDims d, size_t words,
+__global__ __launch_bounds__(THREADS) void k_label_table(const uint32_t* __restrict__ labels, const uint16_t* __restrict__ vox, RegionDims d, size_t words,
                                                          uint32_t count, svr_region_component* table)
 {
-    const LaneAt a = lane_at(d, words);
+    const LabelLane a = label_lane(d, words);
     const int lane = threadIdx.x & 63;
     uint32_t lab = a.inside ? labels[a.v] : 0u;
     if (lab > count) lab = 0u;                            // (a label the table has no entry for is ignored)
@@ -412,20 +401,20 @@ __global__ __launch_bounds__(THREADS) void k_label_table(const uint32_t* __restr
     if (vox) atomicAdd((unsigned long long*)&e->sum, sum);
 }
 
-__global__ __launch_bounds__(THREADS) void k_label_select(const uint32_t* __restrict__ labels, LabelDims d, size_t words, uint32_t count,
+__global__ __launch_bounds__(THREADS) void k_label_select(const uint32_t* __restrict__ labels, RegionDims d, size_t words, uint32_t count,
                                                           const uint8_t* __restrict__ keep, uint32_t* __restrict__ out)
 {
-    const LaneAt a = lane_at(d, words);
+    const LabelLane a = label_lane(d, words);
     const uint32_t lab = a.inside ? labels[a.v] : 0u;
     const bool on = lab != 0u && lab <= count && keep[lab] != 0;
     const uint32_t wv = half_ballot(on);
     if (a.bit == 0 && a.i < words) out[a.i] = wv;
 }
 
-__global__ __launch_bounds__(THREADS) void k_label_threshold(const uint16_t* __restrict__ vox, LabelDims d, size_t words, uint32_t lo, uint32_t hi, LabelBox b,
+__global__ __launch_bounds__(THREADS) void k_label_threshold(const uint16_t* __restrict__ vox, RegionDims d, size_t words, uint32_t lo, uint32_t hi, LabelBox b,
                                                              uint32_t* __restrict__ out)
 {
-    const LaneAt a = lane_at(d, words);
+    const LabelLane a = label_lane(d, words);
     bool on = false;
     if (a.inside && a.x >= b.x0 && a.x <= b.x1 && a.w.gy >= b.y0 && a.w.gy <= b.y1 && a.w.gz >= b.z0 && a.w.gz <= b.z1) {   // (voxels outside the box are not read)
         const uint32_t v = vox[a.v];
@@ -436,55 +425,9 @@ __global__ __launch_bounds__(THREADS) void k_label_threshold(const uint16_t* __r
 }
 
 // ---------------- host side ----------------
-#define LABEL_TRY(call)                                                                                                          \
-    do {                                                                                                                          \
-        hipError_t _e = (call);                                                                                                   \
-        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
-    } while (0)
+CallEvents g_events;                                      // around the device work of the last call of this file (svr_region_label_last_ms)
 
-int check_dims(const char* who, int nx, int ny, int nz)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
-    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
-        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
-    return 0;
-}
-
-LabelDims make_dims(int nx, int ny, int nz) { return LabelDims{nx, ny, nz, (nx + 31) / 32}; }
-size_t mask_words(const LabelDims& d) { return (size_t)d.wx * d.ny * d.nz; }
-dim3 word_grid(size_t words) { return dim3((uint32_t)((words + THREADS - 1) / THREADS)); }
-dim3 lane_grid(size_t words) { return dim3((uint32_t)((words * 32 + THREADS - 1) / THREADS)); }      // at most 2^26 words: 2^23 blocks
-
-// the volume on the device: the caller's pointer, or an upload of the host array on the library's stream
-struct DeviceVoxels {
-    const uint16_t* p = nullptr;
-    uint16_t* owned = nullptr;
-    hipError_t get(const uint16_t* voxels, size_t n, int src_is_device, hipStream_t st)
-    {
-        if (src_is_device) { p = voxels; return hipSuccess; }
-        hipError_t e = hipMalloc((void**)&owned, n * sizeof(uint16_t));
-        if (e != hipSuccess) return e;
-        p = owned;
-        return hipMemcpyAsync(owned, voxels, n * sizeof(uint16_t), hipMemcpyHostToDevice, st);
-    }
-    void release() { if (owned) hipFree(owned); owned = nullptr; }
-};
-
-// HIP events around the device work of the last call of this file (svr_region_label_last_ms); created once, on first use
-hipEvent_t g_ev[2] = {nullptr, nullptr};
-struct CallTimer {
-    hipStream_t st;
-    bool on;
-    explicit CallTimer(hipStream_t s) : st(s), on(false)
-    {
-        if (!g_ev[0] && (hipEventCreate(&g_ev[0]) != hipSuccess || hipEventCreate(&g_ev[1]) != hipSuccess)) { g_ev[0] = g_ev[1] = nullptr; return; }
-        on = hipEventRecord(g_ev[0], st) == hipSuccess;
-    }
-    void stop() { if (on) hipEventRecord(g_ev[1], st); on = false; }
-    ~CallTimer() { stop(); }
-};
-
-hipError_t launch_select(hipStream_t st, const uint32_t* labels, const LabelDims& d, uint32_t count, const uint8_t* keep, uint32_t* out)
+hipError_t launch_select(hipStream_t st, const uint32_t* labels, const RegionDims& d, uint32_t count, const uint8_t* keep, uint32_t* out)
 {
     const size_t words = mask_words(d);
     hipLaunchKernelGGL(k_label_select, lane_grid(words), dim3(THREADS), 0, st, labels, d, words, count, keep, out);
@@ -503,29 +446,21 @@ int svr_region_threshold(const uint16_t* voxels, int nx, int ny, int nz, int src
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (lo > hi || hi > 65535u) return failf(-3, "%s: the window must satisfy lo <= hi <= 65535 (got %u .. %u)", who, lo, hi);
     if ((box_min == nullptr) != (box_max == nullptr)) return failf(-3, "%s: the box needs both box_min and box_max, or neither", who);
-    const int dims[3] = {nx, ny, nz};
     int b0[3] = {0, 0, 0}, b1[3] = {nx - 1, ny - 1, nz - 1};
     if (box_min)
-        for (int a = 0; a < 3; ++a) {
-            if (box_min[a] > box_max[a] || box_max[a] < 0 || box_min[a] >= dims[a])
-                return failf(-3, "%s: the box %d .. %d on axis %d is empty, inverted or outside the volume", who, (int)box_min[a], (int)box_max[a], a);
-            b0[a] = box_min[a] < 0 ? 0 : box_min[a];
-            b1[a] = box_max[a] >= dims[a] ? dims[a] - 1 : box_max[a];
-        }
+        if (int e = clamp_box(who, box_min, box_max, nx, ny, nz, b0, b1)) return e;
     const LabelBox box = {b0[0], b0[1], b0[2], b1[0], b1[1], b1[2]};
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    const LabelDims d = make_dims(nx, ny, nz);
+    CallTimer timer(g_events, st);
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d);
     DeviceVoxels dv;
-    auto cleanup = [&]() { dv.release(); };
-    LABEL_TRY(dv.get(voxels, (size_t)nx * ny * nz, src_is_device, st));
+    SVR_HIP_TRY(dv.get(voxels, (size_t)nx * ny * nz, src_is_device, st));
     hipLaunchKernelGGL(k_label_threshold, lane_grid(words), dim3(THREADS), 0, st, dv.p, d, words, lo, hi, box, out_mask_device);
-    LABEL_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
-    if (dv.owned) LABEL_TRY(hipStreamSynchronize(st));   // the upload is freed below
-    cleanup();
+    if (dv.owned()) SVR_HIP_TRY(hipStreamSynchronize(st));   // the upload is freed on return
     return 0;
 }
 
@@ -534,10 +469,10 @@ int svr_region_label(const uint32_t* in_mask_device, int nx, int ny, int nz, int
     const char* who = "svr_region_label";
     if (!in_mask_device || !labels_device || !count_out) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26) return failf(-3, "%s: the connectivity must be 6, 18 or 26 (got %d)", who, connectivity);
+    if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    const LabelDims d = make_dims(nx, ny, nz);
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d);
     const uint32_t cap = (uint32_t)((size_t)nx * ny * nz);   // no chain is longer than the voxel count (<= 2^31)
     // the scan's levels: words, blocks of words, blocks of blocks, ... , 1 (the total)
@@ -545,16 +480,15 @@ int svr_region_label(const uint32_t* in_mask_device, int nx, int ny, int nz, int
     do level.push_back((level.back() + SVR_LABEL_SCAN_BLOCK - 1) / SVR_LABEL_SCAN_BLOCK); while (level.back() > 1);
     size_t scan_words = 0;
     for (size_t n : level) scan_words += n;
-    uint32_t* buf = nullptr;                             // the root mask, the scan levels, the error word
-    auto cleanup = [&]() { if (buf) hipFree(buf); };
-    LABEL_TRY(hipMalloc((void**)&buf, (words + scan_words + 1) * sizeof(uint32_t)));
-    CallTimer timer(st);                                  // (the launches, not the allocation)
-    uint32_t* roots = buf;
+    DeviceBuffer buf;                                    // the root mask, the scan levels, the error word
+    SVR_HIP_TRY(buf.alloc((words + scan_words + 1) * sizeof(uint32_t)));
+    CallTimer timer(g_events, st);                        // (the launches, not the allocation)
+    uint32_t* roots = buf.as<uint32_t>();
     std::vector<uint32_t*> lv(level.size());
-    lv[0] = buf + words;
+    lv[0] = roots + words;
     for (size_t j = 1; j < level.size(); ++j) lv[j] = lv[j - 1] + level[j - 1];
     uint32_t* d_err = lv.back() + 1;
-    LABEL_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), st));
+    SVR_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), st));
     const dim3 wg = word_grid(words), b(THREADS);
     hipLaunchKernelGGL(k_label_init, wg, b, 0, st, in_mask_device, labels_device, d, words);
 #ifdef SVR_LABEL_GLOBAL_ONLY
@@ -566,18 +500,17 @@ int svr_region_label(const uint32_t* in_mask_device, int nx, int ny, int nz, int
     else if (connectivity == 18) hipLaunchKernelGGL((k_label_union<18>), ug, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err);
     else hipLaunchKernelGGL((k_label_union<26>), ug, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err);
     hipLaunchKernelGGL(k_label_flatten, wg, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err, roots, lv[0]);
-    LABEL_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     for (size_t j = 0; j + 1 < level.size(); ++j)
         hipLaunchKernelGGL(k_scan_block, word_grid(level[j]), b, 0, st, lv[j], level[j], lv[j + 1]);
     for (size_t j = level.size() - 2; j-- > 0;)          // (the top level that was scanned is one block: nothing to add to it)
         hipLaunchKernelGGL(k_scan_add, word_grid(level[j]), b, 0, st, lv[j], level[j], lv[j + 1]);
     hipLaunchKernelGGL(k_label_renumber, lane_grid(words), b, 0, st, in_mask_device, labels_device, d, words, roots, lv[0]);
-    LABEL_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
     uint32_t back[2] = {0u, 0u};                          // the total, the error word (adjacent)
-    LABEL_TRY(hipMemcpyAsync(back, lv.back(), sizeof back, hipMemcpyDeviceToHost, st));
-    LABEL_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(hipMemcpyAsync(back, lv.back(), sizeof back, hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipStreamSynchronize(st));                // (buf is freed on return)
     if (back[1]) return failf(SVR_REGION_ERR_LABEL, "%s: a union-find walk reached its iteration cap (%u; flags %u); the labels are not valid", who, cap, back[1]);
     *count_out = back[0];
     return 0;
@@ -592,22 +525,20 @@ int svr_region_label_table(const uint32_t* labels_device, const uint16_t* voxels
     if (count == 0u) return failf(-3, "%s: count must be at least 1 (a caller with no component has no table)", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    const LabelDims d = make_dims(nx, ny, nz);
+    CallTimer timer(g_events, st);
+    const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d);
     DeviceVoxels dv;
-    auto cleanup = [&]() { dv.release(); };
-    if (voxels_or_null) LABEL_TRY(dv.get(voxels_or_null, (size_t)nx * ny * nz, src_is_device, st));
+    if (voxels_or_null) SVR_HIP_TRY(dv.get(voxels_or_null, (size_t)nx * ny * nz, src_is_device, st));
     hipLaunchKernelGGL(k_table_init, dim3((count + THREADS - 1) / THREADS), dim3(THREADS), 0, st, table_device, count);
 #ifdef SVR_LABEL_TABLE_PLAIN                               // (the A/B build of tools/label_time.py: every run issues its own atomics)
     hipLaunchKernelGGL((k_label_table<false>), lane_grid(words), dim3(THREADS), 0, st, labels_device, dv.p, d, words, count, table_device);
 #else
     hipLaunchKernelGGL((k_label_table<true>), lane_grid(words), dim3(THREADS), 0, st, labels_device, dv.p, d, words, count, table_device);
 #endif
-    LABEL_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipGetLastError());
     timer.stop();
-    if (dv.owned) LABEL_TRY(hipStreamSynchronize(st));   // the upload is freed below
-    cleanup();
+    if (dv.owned()) SVR_HIP_TRY(hipStreamSynchronize(st));   // the upload is freed on return
     return 0;
 }
 
@@ -619,9 +550,8 @@ int svr_region_select(const uint32_t* labels_device, int nx, int ny, int nz, uin
     if (count == 0u) return failf(-3, "%s: count must be at least 1 (a caller with no component has nothing to select)", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    auto cleanup = []() {};
-    LABEL_TRY(launch_select(st, labels_device, make_dims(nx, ny, nz), count, keep_device, out_mask_device));
+    CallTimer timer(g_events, st);
+    SVR_HIP_TRY(launch_select(st, labels_device, make_dims(nx, ny, nz), count, keep_device, out_mask_device));
     return 0;
 }
 
@@ -634,12 +564,11 @@ int svr_region_select_by_size(const uint32_t* labels_device, int nx, int ny, int
     if (count == 0u) return failf(-3, "%s: count must be at least 1 (a caller with no component has nothing to select)", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    uint8_t* d_keep = nullptr;
-    auto cleanup = [&]() { if (d_keep) hipFree(d_keep); };
+    CallTimer timer(g_events, st);
+    DeviceBuffer d_keep;
     std::vector<svr_region_component> table(count);
-    LABEL_TRY(hipMemcpyAsync(table.data(), table_device, (size_t)count * sizeof(svr_region_component), hipMemcpyDeviceToHost, st));
-    LABEL_TRY(hipStreamSynchronize(st));
+    SVR_HIP_TRY(hipMemcpyAsync(table.data(), table_device, (size_t)count * sizeof(svr_region_component), hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipStreamSynchronize(st));
     std::vector<std::pair<uint32_t, uint32_t>> cand;      // (size, label) of the components that are large enough
     for (uint32_t i = 0; i < count; ++i)
         if (table[i].voxels >= min_voxels && table[i].voxels > 0u) cand.emplace_back(table[i].voxels, i + 1u);
@@ -650,12 +579,11 @@ int svr_region_select_by_size(const uint32_t* labels_device, int nx, int ny, int
     }
     std::vector<uint8_t> keep((size_t)count + 1u, 0);
     for (const auto& c : cand) keep[c.second] = 1;
-    LABEL_TRY(hipMalloc((void**)&d_keep, keep.size()));
-    LABEL_TRY(hipMemcpyAsync(d_keep, keep.data(), keep.size(), hipMemcpyHostToDevice, st));
-    LABEL_TRY(launch_select(st, labels_device, make_dims(nx, ny, nz), count, d_keep, out_mask_device));
+    SVR_HIP_TRY(d_keep.alloc(keep.size()));
+    SVR_HIP_TRY(hipMemcpyAsync(d_keep.p, keep.data(), keep.size(), hipMemcpyHostToDevice, st));
+    SVR_HIP_TRY(launch_select(st, labels_device, make_dims(nx, ny, nz), count, d_keep.as<uint8_t>(), out_mask_device));
     timer.stop();
-    LABEL_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(hipStreamSynchronize(st));                // (d_keep is freed on return)
     *kept_out = (uint32_t)cand.size();
     return 0;
 }
@@ -663,9 +591,7 @@ int svr_region_select_by_size(const uint32_t* labels_device, int nx, int ny, int
 int svr_region_label_last_ms(float* ms)
 {
     if (!ms) return failf(-4, "svr_region_label_last_ms: null argument");
-    *ms = 0.f;
-    if (!g_ev[0]) return 0;
-    if (hipEventSynchronize(g_ev[1]) != hipSuccess || hipEventElapsedTime(ms, g_ev[0], g_ev[1]) != hipSuccess) { (void)hipGetLastError(); *ms = 0.f; }
+    *ms = g_events.last_ms();
     return 0;
 }
 

@@ -1,8 +1,7 @@
 // svr_morph.hip -- what operates on a region mask once it exists: dilate / erode / open / close, set operations, regrowth from a mask
 // inside a mask, hole filling and the cutting of thin leaks (svr_region_morph, _combine, _reconstruct, _fill_holes, _detach; the
-// contract is in include/svr_abi.h, the design in DESIGN.md 8i).  Integers only, on the mask layout of svr_region.hip: voxel (x, y, z) =
-// bit x & 31 of word (z * ny + y) * wx + (x >> 5).  PADDING: the bits of a row's last word at x >= nx are ignored on input, whatever
-// they hold, and are 0 on output -- every kernel here ANDs what it loads and what it stores with the word's valid bits.
+// contract is in include/svr_abi.h, the design in DESIGN.md 8i).  Integers only, on the mask layout and padding rule of svr_mask.hpp:
+// every kernel here ANDs what it loads and what it stores with the word's valid bits.
 //
 // MORPH: radius r = r unit steps (open / close: r of one polarity, then r of the other).  Steps of one polarity are made four at a
 //   time (k_morph_fused<ELEMENT, ERODE, 4>), then two (<.., 2>), then one (k_morph_step<ELEMENT, ERODE>) -- the fused forms measured
@@ -34,22 +33,16 @@
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
 
-#include "svr_region_grow.hpp"
+#include "svr_region_grow.hpp"      // the grow kernel and its sweep loop; svr_mask.hpp
+#include "svr_volume_host.hpp"
 
 using svr::failf;
 
 namespace {
 
-constexpr int THREADS = 256;
+constexpr int THREADS = MASK_THREADS;
 
 struct MorphSeeds { int n; int xyz[SVR_REGION_MAX_SEEDS][3]; };
-
-// the bits of word gw (0 <= gw < wx) that are voxels: all but the padding of a row's last word
-__device__ inline uint32_t valid_bits(int gw, const RegionDims& d)
-{
-    const int rem = d.nx - gw * 32;
-    return rem >= 32 ? 0xffffffffu : (1u << rem) - 1u;
-}
 
 template <int ELEMENT, bool ERODE>
 __global__ __launch_bounds__(THREADS) void k_morph_step(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, RegionDims d, unsigned long long words)
@@ -210,41 +203,11 @@ __global__ void k_mask_points(MorphSeeds s, RegionDims d, uint32_t* mask)
 }
 
 // ---------------- host side ----------------
-#define MORPH_TRY(call)                                                                                                          \
-    do {                                                                                                                          \
-        hipError_t _e = (call);                                                                                                   \
-        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
-    } while (0)
-
-int check_dims(const char* who, int nx, int ny, int nz)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
-    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
-        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
-    return 0;
-}
-
-int check_element(const char* who, const char* what, int e)
-{
-    if (e != 6 && e != 18 && e != 26) return failf(-3, "%s: the %s must be 6, 18 or 26 (got %d)", who, what, e);
-    return 0;
-}
-
 int check_radius(const char* who, uint32_t radius)
 {
     if (radius == 0u || radius > SVR_MORPH_MAX_RADIUS) return failf(-3, "%s: the radius must lie in 1 .. %d (got %u)", who, SVR_MORPH_MAX_RADIUS, radius);
     return 0;
 }
-
-bool overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + bytes && q < p + bytes;
-}
-
-RegionDims make_dims(int nx, int ny, int nz) { return RegionDims{nx, ny, nz, (nx + 31) / 32}; }
-size_t mask_words(const RegionDims& d) { return (size_t)d.wx * d.ny * d.nz; }
-dim3 word_grid(size_t words) { return dim3((uint32_t)((words + THREADS - 1) / THREADS)); }
 
 hipError_t launch_step(hipStream_t st, int element, bool erode, const uint32_t* in, uint32_t* out, const RegionDims& d)
 {
@@ -339,10 +302,11 @@ hipError_t run_reconstruct(hipStream_t st, const uint32_t* marker, const uint32_
                            uint32_t cap, uint32_t* cand, uint32_t* out, Recon* res)
 {
     RegionSweep sw(d);
-    uint32_t* d_small = nullptr;                         // the two dirty maps, the batch's counters, the `seeded` flag
+    DeviceBuffer small_buf;                              // the two dirty maps, the batch's counters, the `seeded` flag
     const size_t small = 2 * sw.tiles + SVR_REGION_BATCH + 1;
-    hipError_t e = hipMalloc((void**)&d_small, small * sizeof(uint32_t));
+    hipError_t e = small_buf.alloc(small * sizeof(uint32_t));
     if (e != hipSuccess) return e;
+    uint32_t* const d_small = small_buf.as<uint32_t>();
     sw.dirty = d_small; sw.added = d_small + 2 * sw.tiles;
     uint32_t* d_seeded = sw.added + SVR_REGION_BATCH;
     e = hipMemsetAsync(d_small, 0, small * sizeof(uint32_t), st);
@@ -356,22 +320,12 @@ hipError_t run_reconstruct(hipStream_t st, const uint32_t* marker, const uint32_
     if (e == hipSuccess) e = hipMemcpyAsync(&seeded, d_seeded, sizeof seeded, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     res->seeded = seeded != 0u;
-    hipFree(d_small);
     return e;
 }
 
-// HIP events around the device work of the last mask call (svr_region_mask_last_ms); created once, on first use
-hipEvent_t g_ev[2] = {nullptr, nullptr};
-struct CallTimer {
-    hipStream_t st;
-    bool on;
-    explicit CallTimer(hipStream_t s) : st(s), on(false)
-    {
-        if (!g_ev[0] && (hipEventCreate(&g_ev[0]) != hipSuccess || hipEventCreate(&g_ev[1]) != hipSuccess)) { g_ev[0] = g_ev[1] = nullptr; return; }
-        on = hipEventRecord(g_ev[0], st) == hipSuccess;
-    }
-    ~CallTimer() { if (on) hipEventRecord(g_ev[1], st); }
-};
+// Around the device work of the last mask call (svr_region_mask_last_ms).  No entry point here stops its timer: it ends when it is
+// destroyed, so every temporary is declared AFTER the timer and its hipFree lies inside the time (tools/morph_time.py relies on it).
+CallEvents g_events;
 
 } // namespace
 
@@ -383,20 +337,18 @@ int svr_region_morph(const uint32_t* in_mask_device, int nx, int ny, int nz, int
     if (!in_mask_device || !out_mask_device) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (op != SVR_MORPH_DILATE && op != SVR_MORPH_ERODE && op != SVR_MORPH_OPEN && op != SVR_MORPH_CLOSE) return failf(-3, "%s: unknown op %d", who, op);
-    if (int e = check_element(who, "element", element)) return e;
+    if (int e = check_connectivity(who, "element", element)) return e;
     if (int e = check_radius(who, radius)) return e;
     const RegionDims d = make_dims(nx, ny, nz);
     const size_t bytes = mask_words(d) * sizeof(uint32_t);
-    if (overlap(in_mask_device, out_mask_device, bytes)) return failf(-3, "%s: out must not overlap in", who);
+    if (overlap(in_mask_device, bytes, out_mask_device, bytes)) return failf(-3, "%s: out must not overlap in", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    uint32_t* tmp = nullptr;
-    auto cleanup = [&]() { if (tmp) hipFree(tmp); };
-    if (morph_launches(op, radius) > 1) MORPH_TRY(hipMalloc((void**)&tmp, bytes));
-    MORPH_TRY(run_morph(st, op, element, radius, in_mask_device, out_mask_device, tmp, d));
-    if (tmp) MORPH_TRY(hipStreamSynchronize(st));        // the temporary is freed below
-    cleanup();
+    CallTimer timer(g_events, st);
+    DeviceBuffer tmp;                                    // (after the timer: see g_events)
+    if (morph_launches(op, radius) > 1) SVR_HIP_TRY(tmp.alloc(bytes));
+    SVR_HIP_TRY(run_morph(st, op, element, radius, in_mask_device, out_mask_device, tmp.as<uint32_t>(), d));
+    if (tmp) SVR_HIP_TRY(hipStreamSynchronize(st));      // the temporary is freed on return
     return 0;
 }
 
@@ -410,9 +362,8 @@ int svr_region_combine(const uint32_t* a_device, const uint32_t* b_device, int n
     if (op == SVR_MASK_NOT && b_device) return failf(-3, "%s: b must be NULL for SVR_MASK_NOT", who);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    auto cleanup = []() {};
-    MORPH_TRY(launch_combine(st, a_device, b_device, op, out_device, make_dims(nx, ny, nz)));
+    CallTimer timer(g_events, st);
+    SVR_HIP_TRY(launch_combine(st, a_device, b_device, op, out_device, make_dims(nx, ny, nz)));
     return 0;
 }
 
@@ -422,20 +373,19 @@ int svr_region_reconstruct(const uint32_t* marker_device, const uint32_t* cand_d
     const char* who = "svr_region_reconstruct";
     if (!marker_device || !cand_device || !out_device) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
-    if (int e = check_element(who, "connectivity", connectivity)) return e;
+    if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
     const RegionDims d = make_dims(nx, ny, nz);
     const size_t bytes = mask_words(d) * sizeof(uint32_t);
-    if (overlap(marker_device, out_device, bytes) || overlap(cand_device, out_device, bytes)) return failf(-3, "%s: out must not overlap marker or cand", who);
+    if (overlap(marker_device, bytes, out_device, bytes) || overlap(cand_device, bytes, out_device, bytes))
+        return failf(-3, "%s: out must not overlap marker or cand", who);
     const uint32_t cap = max_sweeps ? max_sweeps : svr_region_default_max_sweeps(nx, ny, nz);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    uint32_t* d_cand = nullptr;
-    auto cleanup = [&]() { if (d_cand) hipFree(d_cand); };
-    MORPH_TRY(hipMalloc((void**)&d_cand, bytes));
+    CallTimer timer(g_events, st);
+    DeviceBuffer cand;
+    SVR_HIP_TRY(cand.alloc(bytes));
     Recon res;
-    MORPH_TRY(run_reconstruct(st, marker_device, cand_device, false, d, connectivity, cap, d_cand, out_device, &res));
-    cleanup();
+    SVR_HIP_TRY(run_reconstruct(st, marker_device, cand_device, false, d, connectivity, cap, cand.as<uint32_t>(), out_device, &res));
     if (sweeps_out) *sweeps_out = res.sweeps;
     if (!res.done) return failf(SVR_REGION_ERR_SWEEPS, "%s: the region was still growing after %u sweeps (max_sweeps); the mask is incomplete", who, res.sweeps);
     return 0;
@@ -446,21 +396,19 @@ int svr_region_fill_holes(const uint32_t* in_device, int nx, int ny, int nz, int
     const char* who = "svr_region_fill_holes";
     if (!in_device || !out_device) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
-    if (int e = check_element(who, "background connectivity", background_connectivity)) return e;
+    if (int e = check_connectivity(who, "background connectivity", background_connectivity)) return e;
     const RegionDims d = make_dims(nx, ny, nz);
     const size_t bytes = mask_words(d) * sizeof(uint32_t);
-    if (overlap(in_device, out_device, bytes)) return failf(-3, "%s: out must not overlap in", who);
+    if (overlap(in_device, bytes, out_device, bytes)) return failf(-3, "%s: out must not overlap in", who);
     const uint32_t cap = max_sweeps ? max_sweeps : svr_region_default_max_sweeps(nx, ny, nz);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    uint32_t* d_cand = nullptr;
-    auto cleanup = [&]() { if (d_cand) hipFree(d_cand); };
-    MORPH_TRY(hipMalloc((void**)&d_cand, bytes));
+    CallTimer timer(g_events, st);
+    DeviceBuffer cand;
+    SVR_HIP_TRY(cand.alloc(bytes));
     Recon res;
-    MORPH_TRY(run_reconstruct(st, nullptr, in_device, true, d, background_connectivity, cap, d_cand, out_device, &res));
-    MORPH_TRY(launch_combine(st, out_device, nullptr, SVR_MASK_NOT, out_device, d));       // the background reached -> everything else
-    cleanup();
+    SVR_HIP_TRY(run_reconstruct(st, nullptr, in_device, true, d, background_connectivity, cap, cand.as<uint32_t>(), out_device, &res));
+    SVR_HIP_TRY(launch_combine(st, out_device, nullptr, SVR_MASK_NOT, out_device, d));     // the background reached -> everything else
     if (!res.done)
         return failf(SVR_REGION_ERR_SWEEPS, "%s: the background was still growing after %u sweeps (max_sweeps); out holds more than the filled mask", who, res.sweeps);
     return 0;
@@ -472,43 +420,35 @@ int svr_region_detach(const uint32_t* in_device, int nx, int ny, int nz, const i
     const char* who = "svr_region_detach";
     if (!in_device || !seeds_xyz || !out_device || !status) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
-    if (nseeds == 0u || nseeds > SVR_REGION_MAX_SEEDS) return failf(-3, "%s: nseeds must lie in 1 .. %d (got %u)", who, SVR_REGION_MAX_SEEDS, nseeds);
-    const int dims[3] = {nx, ny, nz};
+    if (int e = check_seeds(who, seeds_xyz, nseeds, nx, ny, nz)) return e;
     MorphSeeds seeds;
     memset(&seeds, 0, sizeof seeds);
     seeds.n = (int)nseeds;
     for (uint32_t i = 0; i < nseeds; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const int32_t c = seeds_xyz[3u * i + a];
-            if (c < 0 || c >= dims[a])
-                return failf(-3, "%s: seed %u (%d, %d, %d) lies outside the %d x %d x %d volume", who, i, seeds_xyz[3u * i], seeds_xyz[3u * i + 1u], seeds_xyz[3u * i + 2u], nx, ny, nz);
-            seeds.xyz[i][a] = c;
-        }
-    if (int e = check_element(who, "element", element)) return e;
+        for (int a = 0; a < 3; ++a) seeds.xyz[i][a] = seeds_xyz[3u * i + a];
+    if (int e = check_connectivity(who, "element", element)) return e;
     if (int e = check_radius(who, radius)) return e;
-    if (int e = check_element(who, "connectivity", connectivity)) return e;
+    if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
     const RegionDims d = make_dims(nx, ny, nz);
     const size_t words = mask_words(d), bytes = words * sizeof(uint32_t);
-    if (overlap(in_device, out_device, bytes)) return failf(-3, "%s: out must not overlap in", who);
+    if (overlap(in_device, bytes, out_device, bytes)) return failf(-3, "%s: out must not overlap in", who);
     const uint32_t cap = max_sweeps ? max_sweeps : svr_region_default_max_sweeps(nx, ny, nz);
     if (svr::ensure_ready()) return svr_last_error_code();
     hipStream_t st = svr::current_stream();
-    CallTimer timer(st);
-    uint32_t* buf = nullptr;                             // four masks: the eroded core, two work masks, the temporary of the morph steps
-    auto cleanup = [&]() { if (buf) hipFree(buf); };
-    MORPH_TRY(hipMalloc((void**)&buf, 4 * bytes));
-    uint32_t *core = buf, *a = buf + words, *b = buf + 2 * words, *tmp = buf + 3 * words;
-    MORPH_TRY(run_morph(st, SVR_MORPH_ERODE, element, radius, in_device, core, tmp, d));
-    MORPH_TRY(hipMemsetAsync(a, 0, bytes, st));
+    CallTimer timer(g_events, st);
+    DeviceBuffer buf;                                    // four masks: the eroded core, two work masks, the temporary of the morph steps
+    SVR_HIP_TRY(buf.alloc(4 * bytes));
+    uint32_t *core = buf.as<uint32_t>(), *a = core + words, *b = core + 2 * words, *tmp = core + 3 * words;
+    SVR_HIP_TRY(run_morph(st, SVR_MORPH_ERODE, element, radius, in_device, core, tmp, d));
+    SVR_HIP_TRY(hipMemsetAsync(a, 0, bytes, st));
     hipLaunchKernelGGL(k_mask_points, dim3(1), dim3(64), 0, st, seeds, d, a);
-    MORPH_TRY(hipGetLastError());
-    MORPH_TRY(run_morph(st, SVR_MORPH_DILATE, element, radius, a, b, tmp, d));             // b = the dilated seeds: the marker
+    SVR_HIP_TRY(hipGetLastError());
+    SVR_HIP_TRY(run_morph(st, SVR_MORPH_DILATE, element, radius, a, b, tmp, d));           // b = the dilated seeds: the marker
     Recon res;
-    MORPH_TRY(run_reconstruct(st, b, core, false, d, connectivity, cap, tmp, a, &res));    // a = the core's components under the marker
-    MORPH_TRY(run_morph(st, SVR_MORPH_DILATE, element, radius, a, b, tmp, d));
-    MORPH_TRY(launch_combine(st, b, in_device, SVR_MASK_AND, out_device, d));
-    MORPH_TRY(hipStreamSynchronize(st));
-    cleanup();
+    SVR_HIP_TRY(run_reconstruct(st, b, core, false, d, connectivity, cap, tmp, a, &res));  // a = the core's components under the marker
+    SVR_HIP_TRY(run_morph(st, SVR_MORPH_DILATE, element, radius, a, b, tmp, d));
+    SVR_HIP_TRY(launch_combine(st, b, in_device, SVR_MASK_AND, out_device, d));
+    SVR_HIP_TRY(hipStreamSynchronize(st));               // (the masks are freed on return)
     *status = res.seeded ? SVR_REGION_STATUS_OK : SVR_REGION_STATUS_EMPTY;
     if (!res.done) return failf(SVR_REGION_ERR_SWEEPS, "%s: the core was still growing after %u sweeps (max_sweeps); the mask is incomplete", who, res.sweeps);
     return 0;
@@ -517,9 +457,7 @@ int svr_region_detach(const uint32_t* in_device, int nx, int ny, int nz, const i
 int svr_region_mask_last_ms(float* ms)
 {
     if (!ms) return failf(-4, "svr_region_mask_last_ms: null argument");
-    *ms = 0.f;
-    if (!g_ev[0]) return 0;
-    if (hipEventSynchronize(g_ev[1]) != hipSuccess || hipEventElapsedTime(ms, g_ev[0], g_ev[1]) != hipSuccess) { (void)hipGetLastError(); *ms = 0.f; }
+    *ms = g_events.last_ms();
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // svr_region.hip -- seeded region growing on a plain u16 volume, the statistics of a region and the "keep / remove" copy of the volume
-// (svr_region_*; the contract is in include/svr_abi.h, the design in DESIGN.md 8h).  Integers only: a region is a bit mask, voxel
-// (x, y, z) = bit x & 31 of word (z * ny + y) * wx + (x >> 5), and every result is compared exactly.
+// (svr_region_*; the contract is in include/svr_abi.h, the design in DESIGN.md 8h).  Integers only: a region is a bit mask in the
+// layout of svr_mask.hpp, and every result is compared exactly.  The host scaffolding is svr_volume_host.hpp's.
 //
 // CLASSIFY (k_region_classify): one read of the volume writes the candidate mask (window and box) and zeroes the region mask; a lane
 //   reads V voxels of a row (V = 8: one 16-byte load, when nx % 8 == 0 and the rows are 16-byte aligned; else V = 1) and the lanes of a
@@ -41,7 +41,8 @@
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
 
-#include "svr_region_grow.hpp"      // k_region_grow<CONN>, its tiles and the sweep loop (shared with svr_morph.hip)
+#include "svr_region_grow.hpp"      // k_region_grow<CONN>, its tiles and the sweep loop (shared with svr_morph.hip); svr_mask.hpp
+#include "svr_volume_host.hpp"      // the argument checks, DeviceBuffer / DeviceVoxels, SVR_HIP_TRY
 
 using svr::failf;
 
@@ -247,23 +248,7 @@ __global__ __launch_bounds__(THREADS) void k_region_apply(const uint16_t* vox, c
 }
 
 // ---------------- host side ----------------
-#define REGION_TRY(call)                                                                                                         \
-    do {                                                                                                                          \
-        hipError_t _e = (call);                                                                                                   \
-        if (_e != hipSuccess) { cleanup(); return failf((int)_e, "%s: HIP error %s at line %d", who, hipGetErrorName(_e), __LINE__); } \
-    } while (0)
-
 float g_ms[3] = {0.f, 0.f, 0.f};                         // classify (with the seeds), grow, stats of the last svr_region_grow
-
-int check_dims(const char* who, int nx, int ny, int nz)
-{
-    if (nx <= 0 || ny <= 0 || nz <= 0) return failf(-6, "%s: bad dimensions %d x %d x %d", who, nx, ny, nz);
-    if ((unsigned long long)nx * (unsigned long long)ny * (unsigned long long)nz > (1ull << 31))
-        return failf(-6, "%s: %d x %d x %d is more than 2^31 voxels", who, nx, ny, nz);
-    return 0;
-}
-
-RegionDims make_dims(int nx, int ny, int nz) { return RegionDims{nx, ny, nz, (nx + 31) / 32}; }
 
 int span_blocks(const RegionDims& d, int V)
 {
@@ -276,21 +261,6 @@ bool vec8_ok(const RegionDims& d, const void* a, const void* b = nullptr)
 {
     return d.nx % 8 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0;
 }
-
-// the volume on the device: the caller's pointer, or an upload of the host array on the library's stream
-struct DeviceVoxels {
-    const uint16_t* p = nullptr;
-    uint16_t* owned = nullptr;
-    hipError_t get(const uint16_t* voxels, size_t n, int src_is_device, hipStream_t st)
-    {
-        if (src_is_device) { p = voxels; return hipSuccess; }
-        hipError_t e = hipMalloc((void**)&owned, n * sizeof(uint16_t));
-        if (e != hipSuccess) return e;
-        p = owned;
-        return hipMemcpyAsync(owned, voxels, n * sizeof(uint16_t), hipMemcpyHostToDevice, st);
-    }
-    void release() { if (owned) hipFree(owned); owned = nullptr; }
-};
 
 hipError_t launch_stats(const uint16_t* vox, const uint32_t* mask, const RegionDims& d, RegionAcc* d_acc, hipStream_t st)
 {
@@ -361,27 +331,15 @@ int svr_region_grow(const uint16_t* voxels, int nx, int ny, int nz, int src_is_d
     if (!voxels || !seeds_xyz || !params || !mask_device || !stats_host) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (params->lo > params->hi || params->hi > 65535u) return failf(-3, "%s: the window must satisfy lo <= hi <= 65535 (got %u .. %u)", who, params->lo, params->hi);
-    if (params->connectivity != 6 && params->connectivity != 18 && params->connectivity != 26)
-        return failf(-3, "%s: the connectivity must be 6, 18 or 26 (got %d)", who, (int)params->connectivity);
-    if (nseeds == 0u || nseeds > SVR_REGION_MAX_SEEDS) return failf(-3, "%s: nseeds must lie in 1 .. %d (got %u)", who, SVR_REGION_MAX_SEEDS, nseeds);
-    const int dims[3] = {nx, ny, nz};
+    if (int e = check_connectivity(who, "connectivity", (int)params->connectivity)) return e;
+    if (int e = check_seeds(who, seeds_xyz, nseeds, nx, ny, nz)) return e;
     RegionSeeds seeds;
     memset(&seeds, 0, sizeof seeds);
     seeds.n = (int)nseeds;
     for (uint32_t i = 0; i < nseeds; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const int32_t c = seeds_xyz[3u * i + a];
-            if (c < 0 || c >= dims[a])
-                return failf(-3, "%s: seed %u (%d, %d, %d) lies outside the %d x %d x %d volume", who, i, seeds_xyz[3u * i], seeds_xyz[3u * i + 1u], seeds_xyz[3u * i + 2u], nx, ny, nz);
-            seeds.xyz[i][a] = c;
-        }
+        for (int a = 0; a < 3; ++a) seeds.xyz[i][a] = seeds_xyz[3u * i + a];
     int b0[3], b1[3];
-    for (int a = 0; a < 3; ++a) {
-        if (params->box_min[a] > params->box_max[a] || params->box_max[a] < 0 || params->box_min[a] >= dims[a])
-            return failf(-3, "%s: the box %d .. %d on axis %d is empty, inverted or outside the volume", who, (int)params->box_min[a], (int)params->box_max[a], a);
-        b0[a] = params->box_min[a] < 0 ? 0 : params->box_min[a];
-        b1[a] = params->box_max[a] >= dims[a] ? dims[a] - 1 : params->box_max[a];
-    }
+    if (int e = clamp_box(who, params->box_min, params->box_max, nx, ny, nz, b0, b1)) return e;
     const RegionBox box = {b0[0], b0[1], b0[2], b1[0], b1[1], b1[2]};
     const uint32_t cap = params->max_sweeps ? params->max_sweeps : svr_region_default_max_sweeps(nx, ny, nz);
     if (svr::ensure_ready()) return svr_last_error_code();
@@ -393,57 +351,47 @@ int svr_region_grow(const uint16_t* voxels, int nx, int ny, int nz, int src_is_d
     const int ntx = sw.ntx, nty = sw.nty, ntz = sw.ntz;
     const size_t tiles = sw.tiles;
     DeviceVoxels dv;
-    uint32_t *d_cand = nullptr, *d_dirty = nullptr, *d_added = nullptr;
-    RegionAcc* d_acc = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto cleanup = [&]() {
-        dv.release();
-        if (d_cand) hipFree(d_cand);
-        if (d_dirty) hipFree(d_dirty);
-        if (d_added) hipFree(d_added);
-        if (d_acc) hipFree(d_acc);
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    };
+    DeviceBuffer cand_buf, dirty_buf, added_buf, acc_buf;
+    DeviceEvent ev[4];
     if (tiles > 0x7fffffffull) return failf(-6, "%s: %zu tiles exceed one launch", who, tiles);
-    REGION_TRY(dv.get(voxels, n, src_is_device, st));
-    REGION_TRY(hipMalloc((void**)&d_cand, words * sizeof(uint32_t)));
-    REGION_TRY(hipMalloc((void**)&d_dirty, 2 * tiles * sizeof(uint32_t)));
-    REGION_TRY(hipMalloc((void**)&d_added, SVR_REGION_BATCH * sizeof(uint32_t)));
-    REGION_TRY(hipMalloc((void**)&d_acc, ACC_SLOTS * sizeof(RegionAcc)));
-    for (hipEvent_t& e : ev) REGION_TRY(hipEventCreate(&e));
-    uint32_t* dirty[2] = {d_dirty, d_dirty + tiles};
+    SVR_HIP_TRY(dv.get(voxels, n, src_is_device, st));
+    SVR_HIP_TRY(cand_buf.alloc(words * sizeof(uint32_t)));
+    SVR_HIP_TRY(dirty_buf.alloc(2 * tiles * sizeof(uint32_t)));
+    SVR_HIP_TRY(added_buf.alloc(SVR_REGION_BATCH * sizeof(uint32_t)));
+    SVR_HIP_TRY(acc_buf.alloc(ACC_SLOTS * sizeof(RegionAcc)));
+    for (DeviceEvent& e : ev) SVR_HIP_TRY(e.create());
+    uint32_t *const d_cand = cand_buf.as<uint32_t>(), *const d_dirty = dirty_buf.as<uint32_t>();
+    RegionAcc* const d_acc = acc_buf.as<RegionAcc>();
 
-    REGION_TRY(hipEventRecord(ev[0], st));
-    REGION_TRY(hipMemsetAsync(d_dirty, 0, 2 * tiles * sizeof(uint32_t), st));
+    SVR_HIP_TRY(hipEventRecord(ev[0].e, st));
+    SVR_HIP_TRY(hipMemsetAsync(d_dirty, 0, 2 * tiles * sizeof(uint32_t), st));
     if (vec8_ok(d, dv.p))
         hipLaunchKernelGGL((k_region_classify<8>), dim3(span_blocks(d, 8)), dim3(THREADS), 0, st, dv.p, d, params->lo, params->hi, box, d_cand, mask_device);
     else
         hipLaunchKernelGGL((k_region_classify<1>), dim3(span_blocks(d, 1)), dim3(THREADS), 0, st, dv.p, d, params->lo, params->hi, box, d_cand, mask_device);
-    REGION_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, seeds, d, ntx, nty, ntz, d_cand, mask_device, dirty[0]);
-    REGION_TRY(hipGetLastError());
-    REGION_TRY(hipEventRecord(ev[1], st));
+    SVR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, seeds, d, ntx, nty, ntz, d_cand, mask_device, d_dirty);
+    SVR_HIP_TRY(hipGetLastError());
+    SVR_HIP_TRY(hipEventRecord(ev[1].e, st));
 
     uint32_t sweeps = 0u;
     bool done = false;
-    sw.dirty = d_dirty; sw.added = d_added;
-    REGION_TRY(region_sweep_to_fixpoint(st, (int)params->connectivity, d_cand, mask_device, d, sw, cap, &sweeps, &done));
-    REGION_TRY(hipEventRecord(ev[2], st));
+    sw.dirty = d_dirty; sw.added = added_buf.as<uint32_t>();
+    SVR_HIP_TRY(region_sweep_to_fixpoint(st, (int)params->connectivity, d_cand, mask_device, d, sw, cap, &sweeps, &done));
+    SVR_HIP_TRY(hipEventRecord(ev[2].e, st));
     stats_host->sweeps = sweeps;
     if (!done) {
-        REGION_TRY(hipStreamSynchronize(st));
-        cleanup();
+        SVR_HIP_TRY(hipStreamSynchronize(st));           // (the buffers are freed on return)
         return failf(SVR_REGION_ERR_SWEEPS, "%s: the region was still growing after %u sweeps (max_sweeps); the mask is incomplete", who, sweeps);
     }
-    REGION_TRY(launch_stats(dv.p, mask_device, d, d_acc, st));
-    REGION_TRY(hipEventRecord(ev[3], st));
+    SVR_HIP_TRY(launch_stats(dv.p, mask_device, d, d_acc, st));
+    SVR_HIP_TRY(hipEventRecord(ev[3].e, st));
     RegionAcc acc[ACC_SLOTS];
-    REGION_TRY(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, st));
-    REGION_TRY(hipStreamSynchronize(st));
-    for (int i = 0; i < 3; ++i) REGION_TRY(hipEventElapsedTime(&g_ms[i], ev[i], ev[i + 1]));
+    SVR_HIP_TRY(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) SVR_HIP_TRY(hipEventElapsedTime(&g_ms[i], ev[i].e, ev[i + 1].e));
     stats_from(acc, stats_host);
     stats_host->sweeps = sweeps;
-    cleanup();
     return 0;
 }
 
@@ -464,17 +412,15 @@ int svr_region_stats_of(const uint16_t* voxels, int nx, int ny, int nz, int src_
     hipStream_t st = svr::current_stream();
     const RegionDims d = make_dims(nx, ny, nz);
     DeviceVoxels dv;
-    RegionAcc* d_acc = nullptr;
-    auto cleanup = [&]() { dv.release(); if (d_acc) hipFree(d_acc); };
-    REGION_TRY(dv.get(voxels, (size_t)nx * ny * nz, src_is_device, st));
-    REGION_TRY(hipMalloc((void**)&d_acc, ACC_SLOTS * sizeof(RegionAcc)));
-    REGION_TRY(launch_stats(dv.p, mask_device, d, d_acc, st));
+    DeviceBuffer acc_buf;
+    SVR_HIP_TRY(dv.get(voxels, (size_t)nx * ny * nz, src_is_device, st));
+    SVR_HIP_TRY(acc_buf.alloc(ACC_SLOTS * sizeof(RegionAcc)));
+    SVR_HIP_TRY(launch_stats(dv.p, mask_device, d, acc_buf.as<RegionAcc>(), st));
     RegionAcc acc[ACC_SLOTS];
-    REGION_TRY(hipMemcpyAsync(acc, d_acc, sizeof acc, hipMemcpyDeviceToHost, st));
-    REGION_TRY(hipStreamSynchronize(st));
+    SVR_HIP_TRY(hipMemcpyAsync(acc, acc_buf.p, sizeof acc, hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipStreamSynchronize(st));
     stats_from(acc, stats_host);
     stats_host->sweeps = 0u;
-    cleanup();
     return 0;
 }
 
@@ -490,16 +436,14 @@ int svr_region_apply(const uint16_t* voxels, int nx, int ny, int nz, int src_is_
     hipStream_t st = svr::current_stream();
     const RegionDims d = make_dims(nx, ny, nz);
     DeviceVoxels dv;
-    auto cleanup = [&]() { dv.release(); };
-    REGION_TRY(dv.get(voxels, (size_t)nx * ny * nz, src_is_device, st));
+    SVR_HIP_TRY(dv.get(voxels, (size_t)nx * ny * nz, src_is_device, st));
     const uint32_t keep_inside = mode == SVR_REGION_KEEP ? 1u : 0u;
     if (vec8_ok(d, dv.p, out_u16_device))
         hipLaunchKernelGGL((k_region_apply<8>), dim3(span_blocks(d, 8)), dim3(THREADS), 0, st, dv.p, mask_device, d, keep_inside, fill, out_u16_device);
     else
         hipLaunchKernelGGL((k_region_apply<1>), dim3(span_blocks(d, 1)), dim3(THREADS), 0, st, dv.p, mask_device, d, keep_inside, fill, out_u16_device);
-    REGION_TRY(hipGetLastError());
-    if (dv.owned) REGION_TRY(hipStreamSynchronize(st));  // the upload is freed below
-    cleanup();
+    SVR_HIP_TRY(hipGetLastError());
+    if (dv.owned()) SVR_HIP_TRY(hipStreamSynchronize(st));   // the upload is freed on return
     return 0;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "svr_mask.hpp"        // RegionDims: the mask layout
 #include "svr_sweep.hpp"
 
 namespace {
@@ -12,8 +13,6 @@ namespace {
 constexpr int TWX = 4, TY = 8, TZ = 8;                  // tile: words in x, rows, slices
 constexpr int GROW_THREADS = TWX * TY * TZ;             // one thread per word
 static_assert(GROW_THREADS == 256, "the halo load and the 27 marker threads assume 256 threads");
-
-struct RegionDims { int nx, ny, nz, wx; };
 
 // the bits of g extended along the runs of p, both ways (g is a subset of p)
 __device__ inline uint32_t fill_runs(uint32_t g, uint32_t p)

@@ -80,21 +80,22 @@ def test_product_does_not_reference_the_oracle():
     assert "oracle" not in out
 
 
+def test_every_header_rebuilds_the_objects():
+    """A csrc/*.hpp that _build.HIP_HEADERS does not name could change without the objects that include it being compiled again."""
+    from sunvolumerender_amd import _build
+
+    headers = sorted(p.name for p in _build.CSRC.glob("*.hpp"))
+    assert len(headers) >= 21
+    assert [h for h in headers if h not in _build.HIP_HEADERS and h != "svr_internal.hpp"] == []
+
+
 @pytest.mark.parametrize("example", ["headless_canvas", "render_mhd"])
 def test_cpp_host_headers_compile_and_link(tmp_path, example):
     """include/sunvolumerender/{host_api,canvas}.hpp + the examples build with plain g++ against the C ABI
     (compile + link only; running them needs a GPU: tests/test_io_gpu.py)."""
-    import shutil
-    import subprocess
+    from tests.cpp_example import build_example
 
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / example
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(ROOT / "examples" / f"{example}.cpp"),
-           "-o", str(exe), f"-L{abi.library_path().parent}", "-lsvr_hip"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    assert exe.exists()
+    assert build_example(tmp_path, example, strict=True, link=False).exists()
 
 
 def test_cpp_rccl_assembly_example_compiles(tmp_path):

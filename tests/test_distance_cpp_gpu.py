@@ -4,7 +4,6 @@ numpy references (tests/distance_ref.py, tests/region_ref.py) on the volume svr_
 import ctypes as C
 import math
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -17,6 +16,7 @@ from tests import region_ref as rr
 from tests.io_util import write_mhd
 from tests.test_io_gpu import _preprocess
 from tests.test_label_cpp_gpu import MEASURED, check_measured
+from tests.cpp_example import build_example, cpp_canvas_eye
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
@@ -26,13 +26,7 @@ f32 = np.float32
 def test_render_mhd_ball_open_and_thickness_match_python_and_numpy(hip_dev, tmp_path):
     from tests.test_io_cpu import GUI_COLOR, GUI_OPACITY
 
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"), "-o", str(exe),
-                          f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path)
     v = scenes.make_ct_head_volume(48)[:28, :36, :44].astype(np.float64)
     vol = ((v / 65535.0) * 3000.0 - 1000.0).astype(np.int16)                 # air -1000 .. bone 2000
     spacing = (0.9, 0.9, 1.5)
@@ -51,9 +45,7 @@ def test_render_mhd_ball_open_and_thickness_match_python_and_numpy(hip_dev, tmp_
         canvas.LoadVolumeFile(str(mhd))
         # the C++ Canvas's camera: its eye distance is rounded once from double (see tests/test_region_cpp_gpu.py), the Python Canvas's is
         # float32 throughout
-        span = f32(f32(max(canvas.volumeSize)) * f32(1.5))
-        eye = float(f32(float(span) / (2 * math.tan(float(f32(f32(canvas.fov) * f32(0.5)) * f32(0.01745329251994329576923690768489))))))
-        assert abs(eye - canvas.eyeDist) <= 1e-5 * eye
+        eye = cpp_canvas_eye(canvas)
         canvas.SetCamera(host.camera_setup((0.0, 0.0, eye), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), canvas.fov, canvas.apeture, canvas.focalLength,
                                            canvas.exposure, W, H))
         hit = canvas.pick([px])[0]                                            # a window around what the centre pixel shows

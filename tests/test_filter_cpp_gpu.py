@@ -2,7 +2,6 @@
 then ThresholdRegion and KeepLargestRegion on the filtered copy) as its own process, against the same steps made of the Python layer and
 the numpy references (tests/filter_ref.py, tests/label_ref.py) on the volume svr_volume_preprocess leaves on the device."""
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -15,19 +14,14 @@ from tests import label_ref as lr
 from tests.io_util import write_mhd
 from tests.test_io_gpu import _preprocess
 from tests.test_label_cpp_gpu import MEASURED, check_measured
+from tests.cpp_example import build_example
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
 
 
 def test_render_mhd_median_then_threshold_matches_python_and_numpy(hip_dev, tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"), "-o", str(exe),
-                          f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path)
     v = fr.heads()[1][:28, :36, :43].astype(np.float64)                       # the salted head; an odd nx
     vol = ((v / 65535.0) * 3000.0 - 1000.0).astype(np.int16)                 # air -1000 .. bone 2000, salt at both ends
     spacing = (0.9, 0.9, 1.5)

@@ -15,6 +15,7 @@ from sunvolumerender_amd import abi, host
 from tests import filter_ref as fr
 from tests import label_ref
 from tests.test_region_cpu import BONE
+from tests.cpp_example import build_example
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "svr_abi.h").read_text()
@@ -232,15 +233,7 @@ def test_the_largest_admitted_sigma(lib):
 # ---------------------------------------------------------------- examples/render_mhd.cpp: the filter arguments
 @pytest.fixture(scope="module")
 def render_mhd(tmp_path_factory):
-    import shutil
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("render_mhd_filter") / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"),
-                          "-o", str(exe), f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path_factory.mktemp("render_mhd_filter"), strict=True)
     return exe
 
 

@@ -4,7 +4,6 @@ the Python layer and the numpy references (tests/geodesic_ref.py, tests/label_re
 device."""
 import math
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -18,6 +17,7 @@ from tests import label_ref as lr
 from tests.io_util import write_mhd
 from tests.test_io_gpu import _preprocess
 from tests.test_label_cpp_gpu import MEASURED, check_measured
+from tests.cpp_example import build_example
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
@@ -25,13 +25,7 @@ f32 = np.float32
 
 
 def test_render_mhd_split_matches_python_and_numpy(hip_dev, tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"), "-o", str(exe),
-                          f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path)
     balls = gr.two_ball_phantom()
     vol = np.where(balls, 1200, -1000).astype(np.int16)
     vol[0, 0, 0] = 2000                                                       # (the window below is the balls alone, not the brightest voxel)

@@ -12,6 +12,7 @@ from oracle import binding
 from sunvolumerender_amd import abi, host, io, scenes
 from tests.io_util import float_to_rgbe, write_hdr, write_mhd
 from tests.util import assert_bit_exact
+from tests.cpp_example import build_example
 
 pytestmark = pytest.mark.gpu
 
@@ -238,18 +239,10 @@ def test_cpp_canvas_example_matches_python_canvas(hip_dev, tmp_path):
     """examples/render_mhd.cpp (C++ Canvas / VolumeReader / TransferFunction / Lights of include/sunvolumerender/canvas.hpp)
     run as its own process writes the same TGA as the Python Canvas replaying the same protocol, which the oracle
     confirms."""
-    import shutil
     import subprocess
     from tests.test_io_cpu import GUI_COLOR, GUI_OPACITY
 
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    root = Path(__file__).resolve().parents[1]
-    exe = tmp_path / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", f"-I{root / 'include'}", str(root / "examples" / "render_mhd.cpp"), "-o", str(exe),
-                          f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path)
     vol = _ct_like()
     spacing = (0.9, 0.9, 1.5)
     mhd = write_mhd(tmp_path / "ct.mhd", vol, spacing)

@@ -14,6 +14,7 @@ from sunvolumerender_amd import abi, host, scenes
 from tests import label_ref as lr
 from tests import region_ref as rr
 from tests.test_region_cpu import BONE, BRAIN, THIN
+from tests.cpp_example import build_example
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "svr_abi.h").read_text()
@@ -238,15 +239,7 @@ def test_gpu_shapes_cross_the_blocks_of_the_scan():
 # ---------------------------------------------------------------- examples/render_mhd.cpp: the component arguments
 @pytest.fixture(scope="module")
 def render_mhd(tmp_path_factory):
-    import shutil
-
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("render_mhd_label") / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"),
-                          "-o", str(exe), f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path_factory.mktemp("render_mhd_label"), strict=True)
     return exe
 
 

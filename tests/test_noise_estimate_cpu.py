@@ -2,7 +2,6 @@
 argument of examples/render_mhd.cpp, and the estimator's statistics on simulated samples (numpy restatement)."""
 import ctypes as C
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -11,6 +10,7 @@ import pytest
 
 from sunvolumerender_amd import abi
 from tests.noise_ref import estimate_ref, measured_error
+from tests.cpp_example import build_example
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "svr_abi.h").read_text()
@@ -41,13 +41,7 @@ def test_option_key_and_symbols():
 
 @pytest.fixture(scope="module")
 def render_mhd(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("render_mhd") / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"),
-                          "-o", str(exe), f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path_factory.mktemp("render_mhd"), strict=True)
     return exe
 
 

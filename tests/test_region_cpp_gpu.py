@@ -2,9 +2,7 @@
 GrowRegion, ShowRegion) as its own process, against the same loop made of the Python layer, the numpy reference of the region
 (tests/region_ref.py) on the volume svr_volume_preprocess leaves on the device."""
 import ctypes as C
-import math
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -15,6 +13,7 @@ from sunvolumerender_amd import abi, host, io, scenes
 from tests import region_ref as rr
 from tests.io_util import write_mhd
 from tests.test_io_gpu import _preprocess
+from tests.cpp_example import build_example, cpp_canvas_eye
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
@@ -24,13 +23,7 @@ f32 = np.float32
 def test_render_mhd_grow_matches_python_and_numpy(hip_dev, tmp_path):
     from tests.test_io_cpu import GUI_COLOR, GUI_OPACITY
 
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"), "-o", str(exe),
-                          f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path)
     v = scenes.make_ct_head_volume(48)[:28, :36, :44].astype(np.float64)
     vol = ((v / 65535.0) * 3000.0 - 1000.0).astype(np.int16)                 # air -1000 .. bone 2000
     spacing = (0.9, 0.9, 1.5)
@@ -49,9 +42,7 @@ def test_render_mhd_grow_matches_python_and_numpy(hip_dev, tmp_path):
         # The C++ Canvas's camera.  Its ZoomToExtent (canvas.hpp, from gui/canvas.cpp:191-197) evaluates the tangent and the division in
         # double and rounds once; the Python Canvas works in float32 throughout.  For this volume the two eye distances differ by one ulp
         # (76.0477219 against 76.0477295), which the plain picture does not show and one grazing pixel of the -keep picture does.
-        span = f32(f32(max(canvas.volumeSize)) * f32(1.5))
-        eye = float(f32(float(span) / (2 * math.tan(float(f32(f32(canvas.fov) * f32(0.5)) * f32(0.01745329251994329576923690768489))))))
-        assert abs(eye - canvas.eyeDist) <= 1e-5 * eye
+        eye = cpp_canvas_eye(canvas)
         canvas.SetCamera(host.camera_setup((0.0, 0.0, eye), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), canvas.fov, canvas.apeture, canvas.focalLength,
                                            canvas.exposure, W, H))
         hit = canvas.pick([px])[0]                                            # the default -hit mode: opacity 0.5

@@ -10,6 +10,7 @@ import pytest
 
 from sunvolumerender_amd import abi, host, scenes
 from tests import region_ref as rr
+from tests.cpp_example import build_example
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "svr_abi.h").read_text()
@@ -351,16 +352,9 @@ def test_edge_fixtures_are_not_degenerate():
 # ---------------------------------------------------------------- examples/render_mhd.cpp -grow: the arguments
 @pytest.fixture(scope="module")
 def render_mhd(tmp_path_factory):
-    import shutil
     import subprocess
 
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("render_mhd") / "render_mhd"
-    libdir = abi.library_path().parent
-    res = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(ROOT / "examples" / "render_mhd.cpp"),
-                          "-o", str(exe), f"-L{libdir}", "-lsvr_hip", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
+    exe = build_example(tmp_path_factory.mktemp("render_mhd"), strict=True)
     return exe
 
 
