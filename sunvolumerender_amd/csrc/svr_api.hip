@@ -590,6 +590,10 @@ void collect_timing()
 int ensure_mask(svr::DevScene& s, const svr_volume& vol, const svr_transfer_function& tf)
 {
     s.empty_mask = nullptr;
+    // the lane machine's parking thresholds are not the mask's: a queue build forced on without empty-space skipping (SVR_OPT_QUEUE = 2,
+    // SVR_OPT_EMPTY_SKIP = 0) reads them too, and with 0 its walk loop leaves before every iteration and the drain never ends
+    s.park_end = (uint32_t)g.opt_park_end;
+    s.park_cheap = (uint32_t)g.opt_park_cheap;
     if (!g.opt_empty_skip) return 0;
     Texture* tv = find_tex(vol.tex, TEX_VOLUME);
     Texture* tt = find_tex(tf.tex, TEX_TF);
@@ -679,8 +683,6 @@ int ensure_mask(svr::DevScene& s, const svr_volume& vol, const svr_transfer_func
     s.sub8 = (g.sub8_valid && g.d_sub8 && (g.opt_lm_sub == 2 || (g.opt_lm_sub == 1 && tv->mc_shift >= 4))) ? g.d_sub8 : nullptr;
     s.has_empty = g.mask_has_empty ? 1u : 0u;
     s.bound_cull = (g.opt_bound_cull == 2 || (g.opt_bound_cull == 1 && g.mask_cull_useful)) ? 1u : 0u;
-    s.park_end = (uint32_t)g.opt_park_end;
-    s.park_cheap = (uint32_t)g.opt_park_cheap;
     // pool tuning (same-box sweeps, gpurun_out/r03p_lm_tune.log): on the full-resolution grid (scenes with empty space) one cell per turn
     // (c3 9 920 / c5 8 430 Msamples/s against 9 480 / 7 630 with three), on the half-resolution grid of fog-like media three cells
     // and later refills (c3n 4 860 against 4 290 with one cell)
@@ -730,8 +732,10 @@ int ensure_slots(uint32_t W, uint32_t H, uint32_t nslots)
     return 0;
 }
 
-// per-wave path-record queues (REC_WORDS x QUEUE_CAP words) and pending-radiance rows (QUEUE_TASKS x 3 x 64 floats) of the
-// tile kernel's QUEUE builds (svr_trace_tile.hip, svr_lanes.hpp): 184 KB + 24 KB per wave, 0.85 GB for 256 blocks.
+// per-wave path-record queues (REC_WORDS x QUEUE_CAP_MAX words) and pending-radiance rows (QUEUE_TASKS_MAX x 3 x 64 floats) of the
+// tile kernel's QUEUE builds (svr_trace_tile.hip, svr_lanes.hpp), sized for the largest form (svr_kernels.hpp, DrainShape: 1024 records in
+// every build, 64 tasks in the skipping traceDepth-1 builds): 184 KB + 48 KB per wave, 0.95 GB for 256 blocks.  The builds with 32 tasks
+// and the local-majorant pools use the front of their slices.
 // soft: the caller can do without them (SVR_OPT_QUEUE = 1): running out of device memory is then not an error, the launches
 // use the straight-line kernel and the allocation is not tried again until the option is set anew.
 using svr::QUEUE_WORDS_PER_BLOCK;
@@ -756,7 +760,8 @@ int ensure_record_queues(uint32_t blocks, bool soft, bool& available)
             available = false;
             return 0;
         }
-        return fail((int)e, "HIP error allocating the tile kernel's queue memory (%zu MB): %s", ((QUEUE_WORDS_PER_BLOCK + PEND_FLOATS_PER_BLOCK) * 4 * blocks) >> 20, hipGetErrorName(e));
+        return fail((int)e, "HIP error allocating the tile kernel's queue memory (%zu MB: %u records and %u task rows per wave): %s",
+                    ((QUEUE_WORDS_PER_BLOCK + PEND_FLOATS_PER_BLOCK) * 4 * blocks) >> 20, svr::QUEUE_CAP_MAX, svr::QUEUE_TASKS_MAX, hipGetErrorName(e));
     }
     g.queue_blocks = blocks;
     return 0;
@@ -843,14 +848,15 @@ int plan_launch(LaunchPlan& p, void* img, const svr_render_params* rp, uint32_t 
     // QUEUE builds (the hits of a task are shaded in place, then their paths continue on a per-lane state machine,
     // svr_lanes.hpp) ride on the folding launches.  Auto: with empty-space skipping on (without it every walk is long and the
     // straight-line code wins: c3, 1660 against 1452 Msamples/s), for deep paths and media without exactly transparent space
-    // always (c3 depth 2 / 4: +10 % / +30 %, c3n: +34 %), otherwise when the launch gives every wave at least 4 drains of
-    // QUEUE_TASKS tasks (c3 / c4 / c5: +4 % / +3 % / +12 %; c2, 512^2 pixels: -2 %)
+    // always (c3 depth 2 / 4: +10 % / +30 %, c3n: +34 %), otherwise when the launch gives every wave at least
+    // QUEUE_AUTO_TASKS_PER_WAVE = 128 tasks (c3 / c4 / c5: +4 % / +3 % / +12 %; c2, 512^2 pixels: -2 %).  The threshold was set as 4 drains of
+    // 32 tasks and stays where it was measured now that the traceDepth-1 builds drain 64 at a time (c3 has 256 tasks per wave)
     p.use_queue = p.fold_batch && g.opt_queue == 2;
     if (p.fold_batch && g.opt_queue == 1 && g.opt_empty_skip) {
         svr::DevWork wq;
         fill_work(wq, s.imageW, s.imageH);
         const uint64_t waves = (uint64_t)(cfg.num_cus * cfg.blocks_per_cu) / 4u * svr::TILE_WAVES;    // blocks of 1024 threads
-        p.use_queue = rp->traceDepth >= 2 || s.bound_cull || (uint64_t)wq.n_items >= 4u * svr::QUEUE_TASKS * waves;
+        p.use_queue = rp->traceDepth >= 2 || s.bound_cull || (uint64_t)wq.n_items >= svr::QUEUE_AUTO_TASKS_PER_WAVE * waves;
     }
     // OPT-IN local majorants (svr_trace_lm.hip): needs the class table and whole-ray validity; its folding launches keep the waves'
     // pending radiance in the rows next to the record queues

@@ -14,20 +14,46 @@ constexpr uint32_t TICKET_STRIDE = 32;      // in uint32 words
 constexpr uint32_t MASK_WORDS_MAX = 8192;   // words of the LDS-resident `empty` bitmask (32 KiB): up to 64^3 macro-cells
 constexpr uint32_t DIST_WORDS_MAX = 4096;   // words of the half-resolution 4-bit distance field (16 KiB): up to 32^3 coarse cells
 constexpr int DIST_CAP = 15;
-// QUEUE builds of the tile kernel (svr_trace_tile.hip, svr_lanes.hpp): per wave, up to QUEUE_CAP scatter records of REC_WORDS
-// words and the radiance of QUEUE_TASKS tasks (3 channels x 64 lanes), in global memory; TILE_WAVES waves per block
+// QUEUE builds of the tile kernel (svr_trace_tile.hip, svr_lanes.hpp): per wave, up to DrainShape::CAP scatter records of REC_WORDS
+// words and the radiance of DrainShape::TASKS tasks (3 channels x 64 lanes), in global memory; both depend on the build (DrainShape
+// below: 64 tasks in the skipping traceDepth-1 builds without pooled walks, 32 elsewhere); TILE_WAVES waves per block
 constexpr uint32_t REC_C1_WORDS = 17;   // traceDepth 1, a shaded scatter event waiting for its shadow walk: pt(3) wi(3) B(3) pdf rng(6) id|light
 constexpr uint32_t REC_A_WORDS = 26;    // deeper paths, after a next-event estimate: pt wo gradient colour(3 each) Pbrdf L(3) T(3) rng(6) meta
 constexpr uint32_t REC_B_WORDS = 20;    // deeper paths, at a scatter point: pt(3) wo(3) val L(3) T(3) rng(6) meta
 constexpr uint32_t REC_WORDS = REC_A_WORDS + REC_B_WORDS;   // words per record slot of a wave (the larger of the two uses)
-#ifndef SVR_QUEUE_TASKS
-#define SVR_QUEUE_TASKS 32
-#endif
-constexpr uint32_t QUEUE_TASKS = SVR_QUEUE_TASKS;
+// Tasks per drain and record capacity are properties of a BUILD (DrainShape below).  The base pair: the deeper builds, the POOL builds, the build
+// without empty-space skipping and the local-majorant pools (svr_trace_lm.hip) ...
+constexpr uint32_t QUEUE_TASKS = 32;
 constexpr uint32_t QUEUE_CAP = 32 * QUEUE_TASKS;
+// ... and the pair of the skipping traceDepth-1 builds without pooled walks (folding, DIRECT, fast-math: the builds that run iterations of the shadow
+// walk in place, svr_lanes.hpp).  Only a quarter of their shaded hits become records, so 64 tasks fill the same 1024 records, and 64 one-pixel tasks x 3
+// channels are exactly three full passes of the fold (svr_tile_tasks.hpp) where 32 are one full pass and a half-empty one.
+#ifndef SVR_QUEUE_TASKS_D1
+#define SVR_QUEUE_TASKS_D1 64
+#endif
+#ifndef SVR_QUEUE_CAP_D1
+#define SVR_QUEUE_CAP_D1 1024
+#endif
+constexpr uint32_t QUEUE_TASKS_D1 = SVR_QUEUE_TASKS_D1;
+constexpr uint32_t QUEUE_CAP_D1 = SVR_QUEUE_CAP_D1;
+constexpr uint32_t QUEUE_TASKS_LIMIT = 64;   // a record's id is (pending task << 6 | lane) in the 12 low bits of its meta word (svr_lanes.hpp)
+template <bool QUEUE, bool DEPTH1, bool SKIP, bool POOL>
+struct DrainShape {
+    static constexpr bool WIDE = QUEUE && DEPTH1 && SKIP && !POOL;
+    static constexpr uint32_t TASKS = WIDE ? QUEUE_TASKS_D1 : QUEUE_TASKS;      // tasks whose radiance waits in the wave's rows: a drain at the latest then
+    static constexpr uint32_t CAP = WIDE ? QUEUE_CAP_D1 : QUEUE_CAP;            // records of the wave's queue slice (a drain when the next task might not fit)
+    static_assert(TASKS >= 1u && TASKS <= QUEUE_TASKS_LIMIT, "a pending task's index has 6 bits in a record's id");
+    static_assert(CAP >= 64u, "a task pushes up to 64 records");
+};
+constexpr uint32_t QUEUE_TASKS_MAX = QUEUE_TASKS_D1 > QUEUE_TASKS ? QUEUE_TASKS_D1 : QUEUE_TASKS;
+constexpr uint32_t QUEUE_CAP_MAX = QUEUE_CAP_D1 > QUEUE_CAP ? QUEUE_CAP_D1 : QUEUE_CAP;
 constexpr uint32_t TILE_WAVES = 16;
-constexpr size_t QUEUE_WORDS_PER_BLOCK = (size_t)REC_WORDS * QUEUE_CAP * TILE_WAVES;
-constexpr size_t PEND_FLOATS_PER_BLOCK = (size_t)QUEUE_TASKS * 3 * 64 * TILE_WAVES;
+// the allocation (svr_api.hip, ensure_record_queues) holds the largest form; every kernel strides its waves' slices by its own shape
+constexpr size_t QUEUE_WORDS_PER_BLOCK = (size_t)REC_WORDS * QUEUE_CAP_MAX * TILE_WAVES;
+constexpr size_t PEND_FLOATS_PER_BLOCK = (size_t)QUEUE_TASKS_MAX * 3 * 64 * TILE_WAVES;
+static_assert(QUEUE_TASKS <= QUEUE_TASKS_LIMIT && QUEUE_TASKS_D1 <= QUEUE_TASKS_LIMIT, "a pending task's index has 6 bits in a record's id");
+// AUTO rule of the queue builds (svr_api.hip, plan_launch): tasks per wave from which they pay = 4 drains of the base 32 tasks
+constexpr uint32_t QUEUE_AUTO_TASKS_PER_WAVE = 128;
 // Bound classes (svr_accel.hip, k_bound_class): 4 bits per half-resolution macro-cell = smallest class c whose threshold
 // BOUND_THR(c) is >= (largest transfer-function alpha any fetch in the cell can return) x invSigmaMax.
 constexpr uint32_t BOUND_CLASSES = 16;

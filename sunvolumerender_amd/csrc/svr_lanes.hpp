@@ -8,10 +8,11 @@
 // the wave shades the hits of a task in place and then hands the paths over:
 //
 //   traceDepth 1   record C1 = a shaded event's prepared next-event estimate, waiting for its shadow walk.  After
-//                  QUEUE_TASKS tasks (2048 paths) the wave drains its records with all 64 lanes:
+//                  the build's tasks per drain (DrainShape, svr_kernels.hpp: 32 tasks = 2048 paths, or 64 = 4096) the wave drains its
+//                  records with all 64 lanes:
 //                  IDLE -> (pop) -> WALK -> END -> (radiance = estimate x transmittance) -> IDLE
-//                  In the skipping builds without pooled primary walks the walk's first iteration runs in place, behind the shading
-//                  (SVR_SHADOW_FIRST): three walks in four end there and are settled, the others are queued as R records = C1 + the
+//                  In the skipping builds without pooled primary walks the walk's first two iterations run in place, behind the shading
+//                  (SVR_SHADOW_FIRST): four walks in five end there and are settled, the others are queued as R records = C1 + the
 //                  state of the walk, which the machine resumes.
 //   deeper         the first shadow walk and its estimate run in place too; record A = a path waiting for its BSDF
 //                  sampling.  In the machine a lane holds a path only while it WALKs; a finished walk is settled and the
@@ -145,6 +146,7 @@ SVR_DEV void shade_event(const DevScene& s, Shade& vs, float val, Rng& rng, Nee&
 // ---- records.  meta = id (12 bits: task << 6 | lane) | bounce k (15 bits) | light (4 bits) | shading type (1 bit)
 SVR_DEV uint32_t rec_meta(uint32_t id, uint32_t k, uint32_t light, int st) { return id | (k << 12) | (light << 27) | (st ? 0x80000000u : 0u); }
 SVR_DEV uint32_t meta_id(uint32_t m) { return m & 0xfffu; }
+static_assert((QUEUE_TASKS_LIMIT << 6) == 0x1000u, "the id field of meta holds every (pending task << 6 | lane) a build may form");
 SVR_DEV uint32_t meta_k(uint32_t m) { return (m >> 12) & 0x7fffu; }
 SVR_DEV uint32_t meta_light(uint32_t m) { return (m >> 27) & 0xfu; }
 SVR_DEV void rec_rng_store(uint32_t* p, uint32_t cap, const Rng& rng)
@@ -267,12 +269,13 @@ SVR_DEV void queue_push_a(const LaneQueue& Q, uint32_t& nA, bool live, const Sha
 // traceDepth 1, the skipping QUEUE builds without pooled primary walks: the first SVR_SHADOW_FIRST Woodcock iterations of a shadow walk run IN PLACE, right after
 // the shading (svr_trace_tile.hip) -- three quarters of the shadow walks of c3 collide in their first iteration, and the hit lanes of a task are
 // converged there -- and only a walk that is still going is queued, as a resumable record (R, below).  0 = every shaded event is queued before its
-// walk begins (C1 records).  2 is buildable: a lane that asks for a re-march in its second iteration is queued with that request.  The committed
-// tests run the default; the 2 library has passed tests/test_shadow_first_gpu.py, test_task_loop_gpu.py and test_configs_gpu.py once, by hand, and was
-// + 0.7 % in one A/B, below the project's bar (profiles/r07_notes_experiments.txt): not to be adopted on that timing alone.
+// walk begins (C1 records).  2 (the default since round 8, profiles/r08_notes_experiments.txt): another 4 % of the walks collide in their second iteration;
+// a lane that asks for a re-march in its second iteration is queued with that request (clear_run == 2 in the record: the machine pops it in the MARCH
+// state).  0 and 1 stay buildable (SVR_EXTRA_HIPCC_FLAGS=-DSVR_SHADOW_FIRST=1).
 #ifndef SVR_SHADOW_FIRST
-#define SVR_SHADOW_FIRST 1
+#define SVR_SHADOW_FIRST 2
 #endif
+static_assert(SVR_SHADOW_FIRST >= 0 && SVR_SHADOW_FIRST <= 2, "clear_run == 2 asks for a re-march: a third iteration in place would have to serve it");
 
 // states of a lane of the machine (drain_queue); walk_iterate / walk_fetch move a walking lane between CELL .. END
 struct LaneSt { enum : uint32_t { IDLE = 0u, CELL = 1u, WALK = 2u, FETCH = 3u, MARCH = 4u, END = 5u, WANT_A = 6u, WANT_B = 7u }; };

@@ -118,8 +118,8 @@ struct DevWork {
     uint32_t refill_min_idle;      // persistent kernel: regenerate lanes once this many are idle (64 = tile-synchronous)
     unsigned long long* counters;  // svr_counters on the device, or null
     uint32_t* ticket;              // persistent kernel work counter
-    uint32_t* queue;               // tile kernel, QUEUE builds: scatter-record queues, REC_WORDS * QUEUE_CAP words per wave; null = straight-line paths
-    float* pend;                   // ... and the waves' pending-radiance rows, QUEUE_TASKS * 3 * 64 floats per wave
+    uint32_t* queue;               // tile kernel, QUEUE builds: scatter-record queues, REC_WORDS * (the build's record capacity) words per wave, allocated for QUEUE_CAP_MAX; null = straight-line paths
+    float* pend;                   // ... and the waves' pending-radiance rows, (the build's tasks per drain) * 3 * 64 floats per wave, allocated for QUEUE_TASKS_MAX
     uint32_t queue_blocks;         // blocks the queue memory is sized for
     uint32_t nan_guard;            // SVR_OPT_NAN_GUARD: the running mean skips non-finite samples (default 0 = the reference's behaviour)
     // adaptive sampling (svr_render_pathtracer_adaptive; whole frame, one process): the launch traces only the listed 16 x 16 tiles of the image.

@@ -162,16 +162,18 @@ SVR_DEV v3 trace_path_tile(const DevScene& s, const LDS& L_, uint32_t x, uint32_
 // pixel and channel) read conflict-free.
 constexpr uint32_t PEND_TASKS = 4;
 constexpr uint32_t PEND_ROW = 65;
-// QUEUE builds keep the radiance of the last QUEUE_TASKS tasks in a per-wave buffer in global memory instead (rows of 64
-// floats; written and read back once by the same wave), and up to QUEUE_CAP path records per wave
-// (QUEUE_TASKS = 32 and QUEUE_CAP = 1024: svr_kernels.hpp, shared with the allocation in svr_api.hip)
+// QUEUE builds keep the radiance of the last TASKS tasks in a per-wave buffer in global memory instead (rows of 64
+// floats; written and read back once by the same wave), and up to CAP path records per wave.  TASKS and CAP are the
+// build's DrainShape (svr_kernels.hpp, shared with the allocation in svr_api.hip): 64 tasks and 1024 records in the skipping
+// traceDepth-1 builds without pooled walks, 32 and 1024 in every other build
 static_assert(TILE_WAVES == SVR_TILE_THREADS / 64, "svr_kernels.hpp sizes the queues for 16 waves per block");
 struct LdsPend {
     float L[TILE_WAVES][PEND_TASKS * 3][PEND_ROW];
     uint32_t task[TILE_WAVES][PEND_TASKS];
 };
-struct LdsPendQueue {                              // QUEUE builds: only the task numbers stay in LDS
-    uint32_t task[TILE_WAVES][QUEUE_TASKS];
+template <uint32_t TASKS>
+struct LdsPendQueue {                              // QUEUE builds: only the task numbers stay in LDS (2 KB per block at 32 tasks, 4 KB at 64)
+    uint32_t task[TILE_WAVES][TASKS];
 };
 
 // POOL (QUEUE builds at traceDepth 1, media where the primary walks of a wave are NOT coherent -- fog-like data without exactly
@@ -188,7 +190,11 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     using LDS = typename std::conditional<SKIP, typename std::conditional<POOL, LdsTilePool, LdsTileCull>::type, LdsTileNoMask>::type;
     __shared__ LDS lds;
     __shared__ GroupMapShared gmaps[TILE_WAVES][GROUP_MAPS_PER_WAVE];
-    __shared__ typename std::conditional<QUEUE, LdsPendQueue, LdsPend>::type pend;
+    using Drain = DrainShape<QUEUE, DEPTH1, SKIP, POOL>;
+    constexpr uint32_t DRAIN_TASKS = Drain::TASKS, DRAIN_CAP = Drain::CAP;
+    static_assert((size_t)REC_WORDS * DRAIN_CAP * TILE_WAVES <= QUEUE_WORDS_PER_BLOCK && (size_t)DRAIN_TASKS * 3u * 64u * TILE_WAVES <= PEND_FLOATS_PER_BLOCK,
+                  "the wave's queue slice and rows lie inside the allocation");
+    __shared__ typename std::conditional<QUEUE, LdsPendQueue<DRAIN_TASKS>, LdsPend>::type pend;
     // QUEUE builds: the lights in LDS -- light sampling and the settling of a shadow walk index them PER LANE (a vector load from the kernarg
     // segment otherwise: a dependent memory round trip in every settling round of the lane machine)
 #ifndef SVR_LDS_LIGHTS
@@ -212,7 +218,9 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     // traceDepth 1, no pooled primary walks: iterations of a shadow walk that run in place, in front of the queue (svr_lanes.hpp).  The folding, the
     // DIRECT and the fast-math form of the skipping build gain 3.5 - 4.2 % with one; the build without empty-space skipping gains nothing
     // (2 256 / 2 252 against 2 256 / 2 255 Msamples/s: every walk is long there) and keeps every walk in the queue
-    constexpr int FIRST = (QUEUE && DEPTH1 && !POOL && SKIP) ? SVR_SHADOW_FIRST : 0;
+    // (two iterations since round 8, in the same builds that drain 64 tasks at a time -- DrainShape::WIDE: + 1.6 - 1.9 % together,
+    // profiles/r08_notes_experiments.txt)
+    constexpr int FIRST = Drain::WIDE ? SVR_SHADOW_FIRST : 0;
     lds_tile_load(lds, s, SKIP);
 
     const uint32_t lane = threadIdx.x & 63u;
@@ -255,9 +263,9 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     const bool fold = w.fold != 0u;                               // host guarantees fgroups == 1 then
     uint32_t npend = 0, qC = 0, qA = 0, qB = 0;
     LaneQueue Q;
-    Q.cap = QUEUE_CAP;
-    Q.q = QUEUE ? w.queue + (size_t)(blockIdx.x * TILE_WAVES + wave) * (REC_WORDS * QUEUE_CAP) : nullptr;
-    float* const gpend = QUEUE ? w.pend + (size_t)(blockIdx.x * TILE_WAVES + wave) * (QUEUE_TASKS * 3u * 64u) : nullptr;
+    Q.cap = DRAIN_CAP;
+    Q.q = QUEUE ? w.queue + (size_t)(blockIdx.x * TILE_WAVES + wave) * (REC_WORDS * DRAIN_CAP) : nullptr;
+    float* const gpend = QUEUE ? w.pend + (size_t)(blockIdx.x * TILE_WAVES + wave) * (DRAIN_TASKS * 3u * 64u) : nullptr;
     // hand the pending tasks' radiance on.  QUEUE: first drain the scatter records with all 64 lanes (svr_lanes.hpp)
     auto flush = [&]() {
         if constexpr (QUEUE) {
@@ -400,7 +408,7 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
                         }
                     }
                     if (lane == 0) pend.task[wave][npend] = k;
-                    if (++npend == QUEUE_TASKS || qC + 64u > QUEUE_CAP) flush();
+                    if (++npend == DRAIN_TASKS || qC + 64u > DRAIN_CAP) flush();
                     continue;
                 } else if constexpr (QUEUE) {
                     // primary walk, then the hits' first scatter events are shaded in place -- the lanes are frames of the
@@ -524,7 +532,7 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
                         }
                     }
                     if (lane == 0) pend.task[wave][npend] = k;
-                    if (++npend == QUEUE_TASKS || qC + qA + qB + 64u > QUEUE_CAP) flush();
+                    if (++npend == DRAIN_TASKS || qC + qA + qB + 64u > DRAIN_CAP) flush();
                     continue;
                 } else {
                     v3 L = V3(0.f, 0.f, 0.f);
