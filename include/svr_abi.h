@@ -355,6 +355,12 @@ int svr_selftest_math(int fn, const float* in, uint32_t in_stride, float* out, u
  * accept test forms there (exact cell, fetch, alpha, invSigmaMax).  out[i] = 1 tested | 2 VIOLATION (a draw the byte culls could be accepted)
  * | 4 index outside the table | byte << 8; 0 = the ray misses the box.  Fails (-3) when the look-up is not in use for the scene */
 int svr_selftest_bound8(const float* rays, uint32_t n, uint32_t* out);
+/* test hook: property test of the whole-ray march that neighbouring pixels share (csrc/svr_walk.hpp, walk_setup_shared) on the scene and image size set
+ * up as for render_pathtracer: the set-up of the primary walk for every pixel, row by row from left to right, x the frames frame0 .. frame0 + 63; every
+ * lane that hits the box then walks its ray in steps of 1/8 macro-cell and counts the points that the returned parameter or the map calls clear but
+ * that lie in a macro-cell which is not empty.  out = { VIOLATIONS (must be 0), points tested, marches for a pixel pair, reuses of a kept march,
+ * kept marches refused, marches for a pixel that cannot share, lanes that hit the box, lanes with a valid map }.  Fails (-3) without whole-ray tests */
+int svr_selftest_group_march(uint32_t frame0, uint64_t out[8]);
 /* The macro-cell grid a volume texture of nx x ny x nz voxels gets (plain host code, no GPU needed): the smallest shift >= shift_min whose grid
  * (ceil(n / 2^shift) cells per axis) has at most 64^3 cells AND whose half-resolution grid (ceil(g / 2) per axis: the 4-bit distance and
  * bound-class tables) has at most 32^3 -- a flat or line-like volume is limited by the second.  out = { shift, gx, gy, gz, hgx, hgy, hgz,

@@ -359,6 +359,7 @@ OPT_ENV_NEE = 34
 OPT_FAST_BOUND = 35
 OPT_DENOISE_PREVIEW = 36
 OPT_NOISE_ESTIMATE = 37
+OPT_UNIT = 101                         # tasks per ticket of the tile kernel (0: the launcher's choice); placement only
 KERNEL_AUTO, KERNEL_PIXEL, KERNEL_TILE, KERNEL_ULOOP, KERNEL_WAVEFRONT = 0, 1, 2, 3, 4
 
 ELEM_I8, ELEM_U8, ELEM_I16, ELEM_U16, ELEM_I32, ELEM_U32, ELEM_F32, ELEM_F64 = range(8)
@@ -427,6 +428,7 @@ PROTOTYPES = {
     "svr_selftest_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "svr_selftest_math": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "svr_selftest_bound8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "svr_selftest_group_march": (C.c_int, [C.c_uint32, C.c_void_p]),
     "svr_macro_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int)]),
     "svr_selftest_accel": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, _P(C.c_int32)]),
     "svr_denoise_params_default": (C.c_int, [_P(DenoiseParams)]),

@@ -2686,6 +2686,7 @@ int svr_get_option(int key)
     case SVR_OPT_FRAMES_PER_WAVE_LOG2: return g.opt_frames_log2;
     case SVR_OPT_RAYCAST_LANES_LOG2: return g.opt_rc_lanes;
     case SVR_OPT_FRAME_AHEAD: return g.opt_frame_ahead;
+    case 101: return g.opt_unit;
     default: return -1;
     }
 }
@@ -2744,6 +2745,27 @@ int svr_selftest_bound8(const float* rays, uint32_t n, uint32_t* out)
     hipFree(d_rays);
     if (d_out) hipFree(d_out);
     if (e != hipSuccess) return fail((int)e, "svr_selftest_bound8 failed: %s", hipGetErrorName(e));
+    return 0;
+}
+
+// test hook: property test of the shared whole-ray march on the CURRENT scene and image size: csrc/svr_selftest.hip
+int svr_selftest_group_march(uint32_t frame0, uint64_t out[8])
+{
+    if (ensure_init()) return g.err_code;
+    if (!out) return fail(-4, "svr_selftest_group_march: bad arguments");
+    if (!g.have_vol || !g.have_tf || !g.have_cam) return fail(-4, "svr_selftest_group_march before setup_volume/setup_transferfunction/setup_camera");
+    svr::DevScene s;
+    if (build_scene(g.vol, g.tf, g.cam, s)) return g.err_code;
+    if (ensure_mask(s, g.vol, g.tf)) return g.err_code;
+    if (s.empty_mask == nullptr || !s.ray_skip) return fail(-3, "svr_selftest_group_march: the scene has no whole-ray test (SVR_OPT_EMPTY_SKIP off, or a clip box beyond the volume)");
+    unsigned long long* d_out = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_out, 8 * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d_out, 0, 8 * sizeof(unsigned long long), g.stream);
+    if (e == hipSuccess) e = svr::launch_group_march_selftest(s, frame0, d_out, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (e != hipSuccess) return fail((int)e, "svr_selftest_group_march failed: %s", hipGetErrorName(e));
     return 0;
 }
 

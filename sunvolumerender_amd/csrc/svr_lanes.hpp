@@ -39,8 +39,10 @@ enum { PH_PRIMARY = 0, PH_REFILL, PH_SHADE, PH_CHEAP, PH_FETCH, PH_MARCH, PH_END
 enum { PH_TICKET = PH_N + 1, PH_LOOP, PH_FIRST, PH_END_ALL };
 // 2 * PH_N: cheap-loop iterations, 2 * PH_N + 1: walking lanes summed over them; behind the phases: traceDepth-1 QUEUE builds without pooled walks,
 // shaded events that have a shadow walk, and the records pushed for them
-enum { PROF_SHADOW_WALKS = 2 * PH_END_ALL, PROF_RECORDS };
-constexpr uint32_t PROF_WORDS = 2 * PH_END_ALL + 2;
+// ... and what the shared whole-ray march did for the tasks (svr_walk.hpp, MarchDid): marched for the pair, reused, refused, marched for the pixel alone
+enum { PROF_SHADOW_WALKS = 2 * PH_END_ALL, PROF_RECORDS, PROF_MARCH };
+constexpr uint32_t PROF_WORDS = 2 * PH_END_ALL + 6;
+static_assert(PROF_WORDS <= 32u, "the debug words behind the counters (svr_api.hip, DEBUG_WORDS)");
 #ifdef SVR_TEST_HOOKS
 #define SVR_PROF 1
 struct ProfScope {

@@ -248,6 +248,9 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     const uint32_t fl2 = ts.fl2, P2 = ts.P2, tw2 = ts.tw2, th2 = ts.th2, wv = ts.wv, fgroups = ts.fgroups;
     const uint32_t n_tasks = ts.n_tasks;
     Cnt c = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // neighbouring pixels share their whole-ray march (svr_walk.hpp, walk_setup_shared): the builds that drain wide, full-grid launches
+    constexpr bool SHARE = Drain::WIDE && !SVR_TILE_LIST && SVR_MARCH_BLOCK > 1;
+    if constexpr (SHARE) march_kept_reset(&gmaps[wave][0]);      // the wave keeps no march yet
 
     // Work distribution.  A single returning atomic saturates near 88 dequeues/us chip-wide
     // (MI355X_MICROARCH.md "dequeue"), which capped this kernel at 0.19 ms per 1024^2 frame.  So tasks are handed
@@ -430,10 +433,15 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
 #if SVR_PROF
                     const uint32_t prof_i0 = c.iters - c.iskip;
 #endif
+                    uint32_t march_did = MARCH_NONE;                  // (experiment builds count what the shared march did)
                     if (live) {
                         uint32_t x = w.x0 + px, y = owned_row_to_y(w, r);
-                        hit = trace_primary<LAYOUT, COUNT, SKIP>(s, lds, x, y, wang_hash(w.frame0 + slot), group_march, P2, &gmaps[wave][0], c, rng, L, vs.pt, vs.wo, val, cold_scene());
+                        hit = trace_primary<LAYOUT, COUNT, SKIP, SHARE>(s, lds, x, y, wang_hash(w.frame0 + slot), group_march, P2, &gmaps[wave][0], c, rng, L, vs.pt, vs.wo, val, cold_scene(), fg,
+                                                                              SVR_PROF ? &march_did : nullptr);
                     }
+#if SVR_PROF
+                    if (lane == 0 && march_did != MARCH_NONE) atomicAdd(&c_prof[PROF_MARCH + march_did - 1u], 1ull);
+#endif
                     PROF_END(pa, (uint32_t)__popcll(__ballot(live)));
 #if SVR_PROF
                     if (COUNT && DEPTH1) {
@@ -575,12 +583,17 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
     // grazing rays), so coarser units leave most waves idle behind the last heavy unit: measured 0.183 / 0.189 /
     // 0.208 / 0.230 / 0.279 ms per frame at 1 / 2 / 4 / 8 / 16 tasks per ticket (8-frame groups).  With 8 ticket
     // shards the atomics are not a limit (~130 k per launch).
-    if (cfg.unit_override > 0) w2.unit = (uint32_t)cfg.unit_override;
     const bool skip = s.empty_mask != nullptr, d1 = w.traceDepth == 1u;
     // QUEUE builds need the per-wave record queues (DevWork.queue, sized for `queue_blocks` blocks) and exist for the BRICK layout only
     // (launches that do not fold -- frames traced ahead -- have the queue builds in their DIRECT form, which is not built with counters)
     const bool queue = LAYOUT != LAYOUT_LINEAR && w.queue != nullptr && w.pend != nullptr && blocks <= w.queue_blocks && w.traceDepth < 32768u &&   // a record's bounce counter has 15 bits
                        (w.fold || !COUNT);
+    // ... but where neighbouring pixels share their whole-ray march (svr_walk.hpp, walk_setup_shared: the QUEUE builds that drain wide, one pixel x 64
+    // frames per task in ONE frame group -- with several, consecutive tasks are one pixel's groups, not a pair -- pinhole camera) a ticket is one march
+    // block, so that its tasks run back to back in one wave.  Placement only: any unit is exact.  Every other launch keeps one task per ticket
+    if (SVR_MARCH_BLOCK > 1 && !SVR_TILE_LIST && queue && skip && d1 && !cfg.pool_primary && w2.frames_log2 == 6u && w.nframes <= 64u && s.cam_pinhole && s.ray_skip)
+        w2.unit = SVR_MARCH_BLOCK;
+    if (cfg.unit_override > 0) w2.unit = (uint32_t)cfg.unit_override;
 #define SVR_LAUNCH_TILE(SK, D1, QU) hipLaunchKernelGGL((k_trace_tile<LAYOUT, COUNT, SK, D1, QU>), dim3(blocks), dim3(SVR_TILE_THREADS), 0, st, s, w2)
     if constexpr (LAYOUT != LAYOUT_LINEAR && !COUNT) {
         if (queue && !w.fold) {

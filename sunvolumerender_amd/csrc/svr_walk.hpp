@@ -342,6 +342,57 @@ SVR_DEV float group_map_next(const GroupMap& gm, uint32_t P2, float t)
     return u2f(SVR_INF_BITS);
 }
 
+// first_occupied_group (below) in two halves, for the march that neighbouring pixels share (walk_setup_shared).  first_occupied_group itself keeps both
+// written out: built from these two it computes the same, but the compiler schedules every kernel that calls it differently (tools/kernel_diff.py:
+// all of svr_trace_tile.o and svr_trace_lm.o), and those kernels move +- 3 % with their register allocation.
+// The ADMISSION half: may a lane with origin o and direction d use a march along the reference ray (oc, dc) that ends
+// at parameter hi?  Same origin, and within 0.25 macro-cell of the reference up to hi.
+SVR_DEV bool group_admit(const DevScene& s, v3 o, v3 d, v3 oc, v3 dc, float hi)
+{
+    const float dev = fmax_(__builtin_fabsf((d.x - dc.x) * s.mc_scale[0]),
+                            fmax_(__builtin_fabsf((d.y - dc.y) * s.mc_scale[1]), __builtin_fabsf((d.z - dc.z) * s.mc_scale[2])));
+    return (o.x == oc.x) && (o.y == oc.y) && (o.z == oc.z) && (dev * hi <= 0.25f);
+}
+
+// The MARCH half, for a whole wave (one pixel x 64 frames: first_occupied_group's loop at P2 == 0): the 64 lanes sample the reference ray (oc, dc) over
+// [lo, hi], 64 samples per round, and return the parameter of the first sample that is not deep-empty (+inf: none).  Fills the wave's map (the words in
+// LDS, lo / dt / inv_dt in `map`) and says whether the map reaches hi; map.valid stays false -- whether a lane may use the map is the caller's admission.
+// false: degenerate direction, nothing was sampled.  Samples outside the box are safe (clamped cell indices: they can only call occupied what is
+// empty), samples past hi count as unoccupied.
+template <typename LDS>
+SVR_DEV bool group_march_ray(const DevScene& s, const LDS& L, v3 oc, v3 dc, float lo, float hi, GroupMap& map, float& result, bool& complete)
+{
+    GroupMapShared& ms = *map.g;
+    const float INF = u2f(SVR_INF_BITS);
+    const uint32_t lane = threadIdx.x & 63u;
+    result = INF; complete = false;
+    const float Ax = fma_(oc.x - s.vmin[0], s.mc_scale[0], s.mc_off), Bx = dc.x * s.mc_scale[0];
+    const float Ay = fma_(oc.y - s.vmin[1], s.mc_scale[1], s.mc_off), By = dc.y * s.mc_scale[1];
+    const float Az = fma_(oc.z - s.vmin[2], s.mc_scale[2], s.mc_off), Bz = dc.z * s.mc_scale[2];
+    const float bmax = fmax_(__builtin_fabsf(Bx), fmax_(__builtin_fabsf(By), __builtin_fabsf(Bz)));
+    if (!(bmax > 0.f)) return false;
+    const float dt = 0.7f / bmax;
+    const int gx = s.mc_gx, gy = s.mc_gy, gz = s.mc_gz;
+    bool found = false;
+    uint32_t round = 0;
+    for (uint32_t k0 = 0u; k0 < 4096u; k0 += 64u, ++round) {
+        const float tk = fma_((float)(k0 + lane), dt, lo);
+        const int ix = min(max((int)__builtin_floorf(fma_(Bx, tk, Ax)), 0), gx - 1);
+        const int iy = min(max((int)__builtin_floorf(fma_(By, tk, Ay)), 0), gy - 1);
+        const int iz = min(max((int)__builtin_floorf(fma_(Bz, tk, Az)), 0), gz - 1);
+        const uint32_t q = (uint32_t)(ix + iy * gx + iz * s.mc_gxy);
+        const bool occupied = (tk <= hi) && !((L.mask[q >> 5] >> (q & 31u)) & 1u);
+        const uint64_t b = __ballot(occupied);
+        if (round < GROUP_MAP_ROUNDS) ms.w[round] = b;
+        if (b && !found) { found = true; result = fma_((float)(k0 + (uint32_t)__builtin_ctzll(b)), dt, lo); }
+        const bool at_end = fma_((float)(k0 + 63u), dt, lo) > hi;          // the round reached the end of the segment
+        if (at_end) { complete = round < GROUP_MAP_ROUNDS; break; }
+        if (found && round + 1u >= GROUP_MAP_ROUNDS) break;                // the map cannot be completed: stop at the first hit
+    }
+    map.lo = lo; map.dt = dt; map.inv_dt = bmax * (1.f / 0.7f);
+    return true;
+}
+
 template <typename LDS>
 SVR_DEV float first_occupied_group(const DevScene& s, const LDS& L, uint32_t P2, v3 o, v3 d, bool hit, float tMin, float tMax, bool& ok,
                                    GroupMap& map)
@@ -398,6 +449,139 @@ SVR_DEV float first_occupied_group(const DevScene& s, const LDS& L, uint32_t P2,
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     return result;
+}
+
+// ---- THE SHARED MARCH (SVR_MARCH_BLOCK = 2: pairs of neighbouring pixels of a row).  Launches with one pixel x 64 frames per task (P2 == 0) of the
+// skipping traceDepth-1 QUEUE builds without pooled walks: the march samples ONE reference ray, and what it finds holds for every lane that passes the
+// admission -- whichever pixel the lane belongs to.  A reference ray through the common edge of two neighbouring pixels is within one pixel of every
+// lane of both, which on the headline scene is the margin a pixel's own jitter already uses.  So the wave keeps its last march (reference ray,
+// interval, result; the map words stay in slot 0) in the slots 1 and 2 of its GroupMapShared row, which a P2 == 0 launch does not use, tagged with
+// the pixel pair and the frame group:
+//   tag differs  -> march along the un-jittered camera direction through the mid-point of the pair's common edge, over this pixel's interval widened
+//                   by one sample step on each side (if this pixel's own lanes would not pass against that ray, sharing is hopeless at this pixel
+//                   size: march for the pixel alone as first_occupied_group does);
+//   tag matches  -> admission against the kept march: same origin, within 0.25 macro-cell of the reference up to its far end, and the lane's box
+//                   segment inside the marched interval (before lo there are no samples, past hi they count as unoccupied).  All hit lanes
+//                   admitted: the result and the map are reused.  Otherwise the wave marches for this pixel alone, and that march is kept.
+// A pixel without a hit lane takes no part.  The tag only says when trying is worthwhile; that a lane may use a march is the admission's word alone, so
+// any ticket unit, task order, window or shard stays exact.  The walks stay bit-exact as with first_occupied_group: a t_occ and a map that call
+// empty only what is empty change no path's operations.
+#ifndef SVR_MARCH_BLOCK
+#define SVR_MARCH_BLOCK 2
+#endif
+static_assert(SVR_MARCH_BLOCK == 1 || SVR_MARCH_BLOCK == 2, "march blocks: 1 (every pixel marches) or 2 (2 x 1 pixels)");
+// min (MAX false) or max over the 64 lanes, in every lane.  The offsets are compile-time constants here (first_occupied_group's loop ends at a
+// run-time 2^P2 and pays two ds_bpermute_b32 per trip).  A hand-written DPP form (row_shr 1 2 4 8, row_bcast 15 and 31, v_readlane 63) measured the
+// same as this one: 11 034 against 11 031 Msamples/s on the headline, same box (profiles/r09_notes_experiments.txt)
+template <bool MAX>
+SVR_DEV float wave_minmax(float v)
+{
+    for (int off = 32; off > 0; off >>= 1) { const float o = __shfl_xor(v, off, 64); v = MAX ? fmax_(v, o) : fmin_(v, o); }
+    return v;
+}
+
+struct MarchKept {                      // slots 1 and 2 of the wave's GroupMapShared row, as words
+    enum { TAG = 0, RESULT, LO, HI, DT, INV_DT, OX, OY, OZ, DX, DY, DZ, COMPLETE, WORDS };
+};
+static_assert(MarchKept::WORDS * 4u <= 2u * sizeof(GroupMapShared) && GROUP_MAPS_PER_WAVE >= 3u, "the kept march fits into slots 1 and 2");
+constexpr uint32_t MARCH_TAG_NONE = 0xffffffffu;
+SVR_DEV uint32_t march_tag(uint32_t x, uint32_t y, uint32_t fg) { return (((y << 15) ^ (x >> 1)) + fg * 0x9e3779b1u) & 0x7fffffffu; }
+// every wave, before its first task (lane-uniform store; read back by the same wave only)
+SVR_DEV void march_kept_reset(GroupMapShared* gslot)
+{
+    reinterpret_cast<uint32_t*>(gslot + 1)[MarchKept::TAG] = MARCH_TAG_NONE;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// what the shared march did for a task (SVR_TEST_HOOKS builds count them; svr_selftest_group_march)
+enum MarchDid : uint32_t { MARCH_NONE = 0, MARCH_SHARED, MARCH_REUSED, MARCH_REFUSED, MARCH_ALONE };
+
+// walk_setup_group for such a task.  (x, y): the pixel, fg: the frame group; sc: the scene for the camera constants of the reference direction.
+// Every lane of the wave must call it; gslot = the wave's GroupMapShared row.
+template <bool COUNT, bool SKIP, typename LDS>
+SVR_DEV int walk_setup_shared(const DevScene& s, const DevScene& sc, const LDS& L, uint32_t x, uint32_t y, uint32_t fg, v3 orig, v3 dir, bool rng_live,
+                              float& tMin, float& tMax, float& t_occ, GroupMapShared* gslot, GroupMap& map, uint32_t* did = nullptr)
+{
+    map.g = gslot;
+    map.valid = false; map.lo = 0.f; map.dt = 1.f; map.inv_dt = 1.f;
+    float tNear, tFar;
+    const bool hit = volume_intersect(s, orig, dir, tNear, tFar);
+    tMin = tNear < 0.f ? (float)1e-6 : tNear;
+    tMax = tFar;
+    t_occ = tMin;
+    if (did) *did = MARCH_NONE;
+    if (!(SKIP && s.ray_skip)) return hit ? 1 : -1;
+    if (__ballot(hit) == 0ull) return -1;                          // no lane hits the box: nothing to march for
+    const float INF = u2f(SVR_INF_BITS);
+    uint32_t* kw = reinterpret_cast<uint32_t*>(gslot + 1);
+    const uint32_t tag = march_tag(x, y, fg);
+    float g = INF;
+    bool ok = false, complete = false, have = false;
+    if (kw[MarchKept::TAG] == tag) {
+        const v3 oc = V3(u2f(kw[MarchKept::OX]), u2f(kw[MarchKept::OY]), u2f(kw[MarchKept::OZ]));
+        const v3 dc = V3(u2f(kw[MarchKept::DX]), u2f(kw[MarchKept::DY]), u2f(kw[MarchKept::DZ]));
+        const float lo = u2f(kw[MarchKept::LO]), hi = u2f(kw[MarchKept::HI]);
+        ok = group_admit(s, orig, dir, oc, dc, hi) && tMin >= lo && tMax <= hi;
+        if (__ballot(hit && !ok) == 0ull) {
+            have = true;
+            g = u2f(kw[MarchKept::RESULT]);
+            complete = kw[MarchKept::COMPLETE] != 0u;
+            map.lo = lo; map.dt = u2f(kw[MarchKept::DT]); map.inv_dt = u2f(kw[MarchKept::INV_DT]);
+            if (did) *did = MARCH_REUSED;
+        } else if (did) *did = MARCH_REFUSED;
+    }
+    if (!have) {
+        const bool fresh = kw[MarchKept::TAG] != tag;
+        float lo = wave_minmax<false>(hit ? tMin : INF), hi = wave_minmax<true>(hit ? tMax : -INF);
+        // the reference: the first lane's origin (a pinhole camera's only one) ...
+        // (v_readfirstlane: the same six values broadcast through the wave's LDS row keep the headline kernel's frame empty, but cost 1.8 %)
+        v3 oc = V3(u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(orig.x))), u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(orig.y))),
+                   u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(orig.z))));
+        v3 dc = V3(0.f, 0.f, 0.f);
+        bool shared = false;
+        if (fresh) {
+            // ... and camera_ray's direction through (x | 1, y + 0.5), the mid-point of the pair's common edge, without jitter or lens sample
+            // (any direction will do: a fast reciprocal square root normalises it)
+            float nx = 2.f * ((float)(x | 1u) / sc.wm1) - 1.f, ny = 2.f * (((float)y + 0.5f) / sc.hm1) - 1.f;
+            nx = nx * sc.aspectRatio * sc.tanFovxOverTwo * sc.focalLength;
+            ny = ny * sc.tanFovxOverTwo * sc.focalLength;
+            const v3 v = (V3(sc.cam_u[0], sc.cam_u[1], sc.cam_u[2]) * nx + V3(sc.cam_v[0], sc.cam_v[1], sc.cam_v[2]) * ny) -
+                         V3(sc.cam_w[0], sc.cam_w[1], sc.cam_w[2]) * sc.focalLength;
+            dc = v * __builtin_amdgcn_rsqf(dot(v, v));
+            const float bmax = fmax_(__builtin_fabsf(dc.x * s.mc_scale[0]), fmax_(__builtin_fabsf(dc.y * s.mc_scale[1]), __builtin_fabsf(dc.z * s.mc_scale[2])));
+            const float dt = 0.7f / bmax;                          // (group_march_ray's step; a degenerate direction fails the admission below)
+            const float lo_w = lo - dt, hi_w = hi + dt;
+            ok = group_admit(s, orig, dir, oc, dc, hi_w);
+            shared = __ballot(hit && !ok) == 0ull;
+            if (shared) { lo = lo_w; hi = hi_w; }
+        }
+        if (!shared) {
+            // this pixel alone, as first_occupied_group: the first lane's ray; lanes that fail (thin lens, wide pixels) walk their own DDA
+            dc = V3(u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(dir.x))), u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(dir.y))),
+                    u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(dir.z))));
+            ok = group_admit(s, orig, dir, oc, dc, hi);
+        }
+        if (did && *did == MARCH_NONE) *did = shared ? MARCH_SHARED : MARCH_ALONE;
+        for (uint32_t r = 0; r < GROUP_MAP_ROUNDS; ++r) gslot->w[r] = 0ull;
+        const bool marched = group_march_ray(s, L, oc, dc, lo, hi, map, g, complete);
+        if (!marched) { ok = false; g = INF; }
+        kw[MarchKept::TAG] = marched ? tag : MARCH_TAG_NONE;
+        kw[MarchKept::RESULT] = f2u(g); kw[MarchKept::LO] = f2u(lo); kw[MarchKept::HI] = f2u(hi);
+        kw[MarchKept::DT] = f2u(map.dt); kw[MarchKept::INV_DT] = f2u(map.inv_dt);
+        kw[MarchKept::OX] = f2u(oc.x); kw[MarchKept::OY] = f2u(oc.y); kw[MarchKept::OZ] = f2u(oc.z);
+        kw[MarchKept::DX] = f2u(dc.x); kw[MarchKept::DY] = f2u(dc.y); kw[MarchKept::DZ] = f2u(dc.z);
+        kw[MarchKept::COMPLETE] = complete ? 1u : 0u;
+        // the row was written by every lane (identical values) and is read by all of them: group_map_next, and the next task's admission
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    map.valid = complete && ok;
+    if (hit) {
+        t_occ = ok ? g : first_occupied(s, L, orig, dir, tMin, tMax);
+        if (!COUNT && !rng_live && t_occ == u2f(SVR_INF_BITS)) return 0;
+    }
+    return hit ? 1 : -1;
 }
 
 // sample_distance, woodcock_tracking.h:20-51.  `val` returns the intensity fetched by the accepted

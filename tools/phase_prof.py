@@ -46,6 +46,13 @@ for setting in a.settings:
         print(f"   first (in place) {float(out[22]) / (loop or tot) * 100:.2f} % of the {'task loop' if loop else 'stamped phases'}   util {float(out[23]) / float(out[22]) / 64 * 100:5.1f} %")
     if out[24]:
         print(f"   shadow walks {int(out[24])}, records pushed {int(out[25])} = {float(out[25]) / float(out[24]) * 100:.2f} %   ({int(out[24]) / a.frames:.0f} / {int(out[25]) / a.frames:.0f} per frame)")
+    # the whole-ray march that the pixels of a pair share (svr_walk.hpp, walk_setup_shared; words 26 .. 29): tasks that marched for the pair, reused
+    # the kept march, were refused by it (and marched alone), marched alone because their own lanes would not pass against the pair's reference
+    if any(out[26:30]):
+        sh, re_, rf, al = (int(v) for v in out[26:30])
+        tot_m = sh + re_ + rf + al
+        print(f"   shared march: {tot_m} tasks with a hit lane: marched for the pair {sh}, reused {re_} = {re_ / tot_m * 100:.1f} %, refused {rf}, alone {al}"
+              f"   -> {(sh + rf + al) / tot_m:.3f} marches per task")
     if out[16]:
         if a.depth > 1:
             print(f"   cheap-loop iterations {int(out[16])}, mean walking lanes {float(out[17]) / float(out[16]):.1f}")
