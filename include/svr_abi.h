@@ -246,7 +246,7 @@ int svr_assemble_frame(void* nccl_comm, void* frame_on_root, const void* hdr_loc
                                      Fewer fetches (c5: 3.9 instead of 5.9 per path), same speed: the test costs a dependent cached load */
 #define SVR_OPT_ROW_ORDER 21        /* tile kernel work distribution: 1 = each of the 8 ticket counters (one per XCD group of blocks) owns whole tile
                                      rows, so neighbouring tiles share an XCD's L2; 0 = every 8th task.  Speed only */
-#define SVR_OPT_GROUP_FRAMES 22     /* frames per folding launch of svr_render_pathtracer_frames: 8, 16, 32 or 64 (default: a wave = one pixel x 64 frames).  Speed only */
+#define SVR_OPT_GROUP_FRAMES 22     /* frames per folding launch of svr_render_pathtracer_frames: 8, 16, 32 or 64 (default: a wave = one pixel x 64 frames); 128 or 256: that many frames in one launch, as whole groups of 64, where the call's kernel has the form for it (depth 1, empty-space skipping, pinhole camera, full grid), 64 elsewhere.  Speed only */
 #define SVR_OPT_LOCAL_MAJORANT 23   /* OPT-IN, default 0: "Woodcock max-density acceleration" -- the free-flight sampler tracks against per-macro-cell
                                      * (local) majorants instead of the reference's single global one (core/woodcock_tracking.h:29-31): same law of the
                                      * collision point, far fewer iterations, but a different consumption of random numbers.  NOT bit-identical to

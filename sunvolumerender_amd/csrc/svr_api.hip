@@ -160,7 +160,7 @@ struct Context {
     size_t slot_floats = 0;        // floats per scratch slot currently allocated (3*W*H)
     uint32_t slots_per_set = 0;    // slots currently allocated per set
     int next_set = 0;
-    int opt_pipeline = 1, opt_refill = 16, opt_empty_skip = 1, opt_ray_skip = 1, opt_debug_stop = 0, opt_frames_log2 = -1, opt_unit = 0, opt_rc_lanes = 3, opt_bound_cull = 1, opt_park_end = 32, opt_fold = 1, opt_queue = 1, opt_fast_math = 0, opt_fine_mask = 0, opt_row_order = 0, opt_group_frames = 64, opt_local_majorant = 0, opt_light_cull = 1, opt_lm_tune = 0, opt_lm_sub = 1, opt_park_cheap = 16, opt_pinhole_fast = 1, opt_pool = 1, opt_trips = 1, opt_nan_guard = 0, opt_macro_shift_min = 0, opt_split = 0, opt_env_nee = 0, opt_fast_bound = 1;
+    int opt_pipeline = 1, opt_refill = 16, opt_empty_skip = 1, opt_ray_skip = 1, opt_debug_stop = 0, opt_frames_log2 = -1, opt_unit = 0, opt_rc_lanes = 3, opt_bound_cull = 1, opt_park_end = 32, opt_fold = 1, opt_queue = 1, opt_fast_math = 0, opt_fine_mask = 0, opt_row_order = 0, opt_group_frames = 256, opt_local_majorant = 0, opt_light_cull = 1, opt_lm_tune = 0, opt_lm_sub = 1, opt_park_cheap = 16, opt_pinhole_fast = 1, opt_pool = 1, opt_trips = 1, opt_nan_guard = 0, opt_macro_shift_min = 0, opt_split = 0, opt_env_nee = 0, opt_fast_bound = 1;
     // empty-space bitmask of the current (volume, transfer function, densityScale)
     uint32_t* d_mask = nullptr;
     uint32_t* d_fine_mask = nullptr;   // `empty` bits of the fine level (global memory), sized for the current volume
@@ -800,6 +800,7 @@ struct LaunchPlan {
     const TileList* tiles = nullptr;    // the launches trace these tiles only
     bool fold_batch = false;            // the tile kernel folds the frames of its launches into the accumulator
     bool use_queue = false;             // ... in its QUEUE builds
+    bool fold_groups = false;           // ... and a folding launch may take several groups of 64 frames (fold_group_frames)
     bool local_majorant = false;        // the local-majorant kernel in place of the tile kernel
     bool frame_ahead = false;           // one frame per call, the next ones traced ahead (render_ahead)
 };
@@ -876,7 +877,13 @@ int plan_launch(LaunchPlan& p, void* img, const svr_render_params* rp, uint32_t 
     }
     p.frame_ahead = nframes == 1 && g.opt_frame_ahead && g.opt_pipeline && !g.opt_count && !g.opt_debug_stop && cfg.kernel == svr::KERNEL_TILE &&
                     adaptive == nullptr;
-    const uint32_t tail_frames = nframes % (uint32_t)(p.fold_batch ? g.opt_group_frames : Context::GROUP);
+    // Folding launches of SEVERAL groups of 64 frames (SVR_OPT_GROUP_FRAMES = 128 / 256) exist in one form of the tile kernel: the skipping traceDepth-1
+    // queue builds without pooled walks, one pixel x 64 frames per task, full grid, tickets in units of tasks (launch_tile_t refuses every other launch
+    // of more than 64 frames).  Every other plan keeps at most 64 frames per launch
+    p.fold_groups = p.fold_batch && p.use_queue && !p.local_majorant && !cfg.pool_primary && p.tiles == nullptr && rp->traceDepth == 1 &&
+                    s.empty_mask != nullptr && s.layout != svr::LAYOUT_LINEAR && s.cam_pinhole && s.ray_skip && !g.opt_row_order && !p.frame_ahead;
+    // (whole groups of 64 frames go first: what is left of a call is less than the smaller of 64 and the option)
+    const uint32_t tail_frames = nframes % (uint32_t)(p.fold_batch ? (g.opt_group_frames < 64 ? g.opt_group_frames : 64) : Context::GROUP);
     if ((!p.fold_batch || p.frame_ahead || (tail_frames != 0 && tail_frames < FOLD_MIN)) &&
         ensure_slots(s.imageW, s.imageH, nframes < (uint32_t)Context::GROUP ? nframes : (uint32_t)Context::GROUP)) return g.err_code;
     return 0;
@@ -1059,6 +1066,21 @@ int render_ahead(const LaunchPlan& p, bool want_img)
     return 0;
 }
 
+// frames of the next launch of a folding call with `left` frames to go: SVR_OPT_GROUP_FRAMES of them.  Above 64 that is whole groups of 64 frames in one
+// launch where the plan has the form for it (LaunchPlan.fold_groups) and the ticket unit, if the caller set one, is a multiple of the group count (the
+// groups of a pixel must stay in one wave: launch_tile_t); otherwise 64.  What is left below 64 frames is one launch as ever
+uint32_t fold_group_frames(const LaunchPlan& p, uint32_t left)
+{
+    const uint32_t group = (uint32_t)g.opt_group_frames;
+    if (group <= 64u || left < 128u || !p.fold_groups) {
+        const uint32_t cap = group < 64u ? group : 64u;
+        return left < cap ? left : cap;
+    }
+    const uint32_t n = (left < group ? left : group) & ~63u;
+    if (g.opt_unit > 0 && (uint32_t)g.opt_unit % (n >> 6) != 0u) return 64u;
+    return n;
+}
+
 // nframes frames into rp's accumulator, tone-mapped into img if `tonemap` (adaptive: the launches of an adaptive call, else null)
 int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframes, bool tonemap, const TileList* adaptive)
 {
@@ -1073,9 +1095,8 @@ int render_frames_traced(void* img, const svr_render_params* rp, uint32_t nframe
     const bool want_img = tonemap && !g.opt_skip_tonemap;
     if (p.frame_ahead) return render_ahead(p, want_img);
     // folding launches may take 64 frames (a wave = ONE pixel x 64 frames): half as many launch boundaries
-    const uint32_t group = p.fold_batch ? (uint32_t)g.opt_group_frames : (uint32_t)Context::GROUP;
-    for (uint32_t g0 = 0; g0 < nframes; g0 += group) {
-        const uint32_t n = nframes - g0 < group ? nframes - g0 : group;
+    for (uint32_t g0 = 0, n = 0; g0 < nframes; g0 += n) {
+        n = p.fold_batch ? fold_group_frames(p, nframes - g0) : (nframes - g0 < (uint32_t)Context::GROUP ? nframes - g0 : (uint32_t)Context::GROUP);
         const bool img_now = want_img && g0 + n >= nframes;
         if (p.fold_batch && n >= FOLD_MIN) {
             if (trace_fold(p, rp->frameNo + g0, n, img_now)) return g.err_code;
@@ -2584,7 +2605,8 @@ int svr_set_option(int key, int value)
         g.opt_bound_cull = value; return 0;
     case SVR_OPT_FOLD: g.opt_fold = value ? 1 : 0; return 0;
     case SVR_OPT_GROUP_FRAMES:
-        if (value != 8 && value != 16 && value != 32 && value != 64) return fail(-6, "SVR_OPT_GROUP_FRAMES: bad value %d (8, 16, 32, 64)", value);
+        if (value != 8 && value != 16 && value != 32 && value != 64 && value != 128 && value != 256)
+            return fail(-6, "SVR_OPT_GROUP_FRAMES: bad value %d (8, 16, 32, 64, 128, 256)", value);
         g.opt_group_frames = value; return 0;
     case SVR_OPT_ROW_ORDER: g.opt_row_order = value ? 1 : 0; return 0;
     case SVR_OPT_FINE_MASK:

@@ -16,10 +16,10 @@ namespace svr {
 // builds: returns true if the primary walk collided -- pt / wo / val / rng are then the scatter event the wave shades in place and
 // svr_lanes.hpp continues the path -- and false if the path is over, with its radiance in L.
 // SHARE (the builds that drain wide, DrainShape::WIDE): one pixel x 64 frames per task (P2 == 0) under a pinhole camera shares its whole-ray test with the
-// neighbouring pixel of the row (svr_walk.hpp, walk_setup_shared); fg = the task's frame group, march_did = what the march did (experiment builds).
+// neighbouring pixel of the row (svr_walk.hpp, walk_setup_shared); march_did = what the march did (experiment builds).
 template <int LAYOUT, bool COUNT, bool SKIP, bool SHARE = false, typename LDS>
 SVR_DEV bool trace_primary(const DevScene& s, const LDS& L_, uint32_t x, uint32_t y, uint32_t hashed, bool group_march, uint32_t P2,
-                           GroupMapShared* gslot, Cnt& c, Rng& rng, v3& L, v3& pt, v3& wo, float& val, const DevScene* scp = nullptr, uint32_t fg = 0u,
+                           GroupMapShared* gslot, Cnt& c, Rng& rng, v3& L, v3& pt, v3& wo, float& val, const DevScene* scp = nullptr,
                            uint32_t* march_did = nullptr)
 {
     const DevScene& sc = scp ? *scp : s;                // (set-up constants: camera, lights, environment -- svr_lanes.hpp, shade_event)
@@ -43,7 +43,7 @@ SVR_DEV bool trace_primary(const DevScene& s, const LDS& L_, uint32_t x, uint32_
         bool shared = false;
         if constexpr (SHARE && SVR_MARCH_BLOCK > 1) shared = P2 == 0u && sc.cam_pinhole != 0u;
         if (shared)
-            r = walk_setup_shared<COUNT, SKIP>(s, sc, L_, x, y, fg, orig, dir, false, tMin, tMax, t_occ, gslot, map, march_did);
+            r = walk_setup_shared<COUNT, SKIP>(s, sc, L_, x, y, orig, dir, false, tMin, tMax, t_occ, gslot, map, march_did);
         else
             r = walk_setup_group<COUNT, SKIP>(s, L_, P2, orig, dir, false, tMin, tMax, t_occ, map);
         t = r <= 0 ? -SVR_FLT_MAX

@@ -108,7 +108,7 @@ SVR_DEV TaskLanes task_lanes(const TaskShape& ts, const DevWork& w, uint32_t k, 
 // task count and the grid of a launch, its DevWork (unit = one task per ticket) and the reset of the ticket counters.
 //   frames per wave: the largest power of two <= min(nframes, 64), unless frames_log2 >= 0 asks for fewer; a FOLDING launch (fold:
 //   in-kernel accumulation) keeps every frame of a pixel in ONE wave -- frame lanes 0 .. nframes - 1 of its group; the caller has
-//   checked nframes <= 64
+//   checked nframes <= 64, or (the tile kernel's wide-draining builds) a multiple of 64: then a task is one pixel x one group of 64 frames
 //   grid: one wave per task up to num_cus x blocks_per_cu x 4 waves
 struct TaskGrid { uint32_t n_tasks, blocks; };
 inline hipError_t task_launch_setup(const DevWork& w, const LaunchCfg& cfg, uint32_t waves_per_block, bool fold, int frames_log2, hipStream_t st,
@@ -119,7 +119,7 @@ inline hipError_t task_launch_setup(const DevWork& w, const LaunchCfg& cfg, uint
     if (frames_log2 >= 0 && (uint32_t)frames_log2 < fl2) fl2 = (uint32_t)frames_log2;
     if (fold) {
         fl2 = 0;
-        while ((1u << fl2) < w.nframes) ++fl2;
+        while (fl2 < 6u && (1u << fl2) < w.nframes) ++fl2;          // (more than 64 frames: whole groups of 64, the tile kernel's wide-draining builds)
     }
     const uint32_t P2 = 6u - fl2, tw2 = (P2 + 1u) >> 1, th2 = P2 >> 1;
     const uint32_t fgroups = (w.nframes + (1u << fl2) - 1u) >> fl2;
@@ -195,6 +195,75 @@ SVR_DEV void fold_pending(const DevScene& s, const DevWork& w, const float* rows
                 const float Lf = rp[f << ts.P2];
                 const float n1 = (float)(w.frame0 + f) + 1.f;
                 acc = acc + (Lf - acc) / n1;
+            }
+        }
+        *h = acc;
+    }
+}
+
+// fold_pending for a folding launch of SEVERAL groups of 64 frames (fgroups > 1: one pixel x 64 frames per task, nframes a multiple of 64; the
+// wide-draining builds of svr_trace_tile.hip only -- every other kernel keeps fold_pending, so its text does not move).  The launcher makes a ticket a
+// multiple of fgroups tasks, so the groups 0 .. fgroups - 1 of a pixel are consecutive tasks of ONE wave, in order, and the running mean of a pixel
+// is replayed in frame order across them:
+//   * the groups of a pixel that are pending together are CHAINED in one accumulator: one read of hdr, fgroups x 64 links, one write.  A chain
+//     starts at a pending task that is group 0 or does not follow its predecessor's task number; one lane per (chain, channel);
+//   * a pixel whose groups straddle two drains continues from hdr: the first part writes it, the second part reads it back (fg > 0) even when
+//     frame0 == 0.  This wave wrote that value itself in its previous flush -- no other wave ever touches the pixel -- and the workgroup fences
+//     around flush() order the store before this load;
+//   * the clear (acc = 0) is for absolute frame 0 alone: frame0 == 0 and group 0.
+// The sample number of frame lane f of group fg is frame0 + 64 fg + f.  rows: [task * 3 + channel] rows of 64 floats.
+SVR_DEV void fold_pending_groups(const DevScene& s, const DevWork& w, const float* rows, const uint32_t* tasks, uint32_t npend)
+{
+    const TaskShape ts = task_shape(w);                    // P2 == 0, fl2 == 6: a task is one pixel, tx / ty are its column / row
+    const uint32_t lane = threadIdx.x & 63u;
+    // the chain heads among the (at most 64) pending tasks, and the r-th head's index in lane r
+    const bool mine = lane < npend;
+    const uint32_t k_l = mine ? tasks[lane] : 0u, k_p = (mine && lane != 0u) ? tasks[lane - 1u] : 0u;
+    uint32_t tx_l, ty_l, fg_l;
+    task_decode(ts, k_l, tx_l, ty_l, fg_l);
+    const bool head = mine && (lane == 0u || fg_l == 0u || k_p + 1u != k_l);
+    const uint64_t heads = __ballot(head);
+    const uint32_t nheads = (uint32_t)__popcll(heads);
+    const uint32_t rank = (uint32_t)__popcll(heads & ((1ull << lane) - 1ull));
+    const uint32_t dest = head ? rank : nheads + (lane - rank);                  // a permutation of the lanes: heads first, in order
+    const uint32_t q_of = (uint32_t)__builtin_amdgcn_ds_permute((int)(dest << 2), (int)lane);
+    const uint32_t items = nheads * 3u;
+    for (uint32_t i0 = 0u; i0 < items; i0 += 64u) {
+        const uint32_t i = i0 + lane;
+        const uint32_t j = (i * 0xAAABu) >> 17;            // i / 3 for i < 2^15
+        const uint32_t ch = i - 3u * j;
+        const uint32_t q = (uint32_t)__shfl((int)q_of, (int)(j & 63u), 64);
+        if (i >= items) continue;
+        uint32_t tx, ty, fg;
+        task_decode(ts, tasks[q], tx, ty, fg);
+        if (tx >= ts.wv || ty >= w.n_rows) continue;
+        const uint64_t above = q < 63u ? heads >> (q + 1u) : 0ull;
+        const uint32_t len = above ? (uint32_t)__builtin_ctzll(above) + 1u : npend - q;     // pending groups of this pixel from q on
+        const uint32_t x = w.x0 + tx, y = owned_row_to_y(w, ty);
+        float* h = w.hdr + 3 * ((size_t)y * s.imageW + x) + ch;
+        float acc = (w.frame0 == 0u && fg == 0u) ? 0.f : *h;
+        for (uint32_t gi = 0u; gi < len; ++gi) {
+            const float* rp = rows + (size_t)((q + gi) * 3u + ch) * 64u;
+            const uint32_t n0 = w.frame0 + ((fg + gi) << 6);
+            if (w.nan_guard) {
+                // SVR_OPT_NAN_GUARD, as in fold_pending
+                for (uint32_t f = 0; f < 64u; ++f) {
+                    float Lf = rp[f];
+                    Lf = (f2u(Lf) & 0x7f800000u) == 0x7f800000u ? acc : Lf;
+                    const float n1 = (float)(n0 + f) + 1.f;
+                    acc = acc + (Lf - acc) / n1;
+                }
+            } else {
+                for (uint32_t f = 0; f < 64u; f += FOLD_CHUNK) {
+                    float Lv[FOLD_CHUNK];
+#pragma unroll
+                    for (uint32_t jj = 0; jj < FOLD_CHUNK; ++jj) Lv[jj] = rp[f + jj];
+#pragma unroll
+                    for (uint32_t jj = 0; jj < FOLD_CHUNK; ++jj) {
+                        const float n1 = (float)(n0 + f + jj) + 1.f;
+                        acc = acc + (Lv[jj] - acc) / n1;
+                    }
+                }
             }
         }
         *h = acc;

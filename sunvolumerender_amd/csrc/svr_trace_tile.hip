@@ -263,7 +263,9 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
     const uint32_t unit = w.unit;
     const uint32_t n_units = (n_tasks + unit - 1u) / unit;
     const uint32_t shard0 = blockIdx.x % TICKET_SHARDS;
-    const bool fold = w.fold != 0u;                               // host guarantees fgroups == 1 then
+    const bool fold = w.fold != 0u;                               // host guarantees fgroups == 1 then, but for the wide-draining builds (GROUPS below)
+    // a folding launch of several groups of 64 frames (launch_tile_t: one pixel x 64 frames per task, a ticket = whole pixels x all their groups)
+    constexpr bool GROUPS = Drain::WIDE && !DIRECT && !SVR_TILE_LIST;
     uint32_t npend = 0, qC = 0, qA = 0, qB = 0;
     LaneQueue Q;
     Q.cap = DRAIN_CAP;
@@ -328,7 +330,10 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
 #endif
             PROF_BEGIN(pfo, PH_FOLD);
             // (samples loaded ahead of the division chain in the traceDepth-1 builds only: the deeper builds lose 2.6 % / 2.1 % at depth 2 / 4 with it)
-            if constexpr (!DIRECT) fold_pending<DEPTH1>(s, w, gpend, 64u, &pend.task[wave][0], npend);
+            if constexpr (GROUPS) {
+                if (fgroups > 1u) fold_pending_groups(s, w, gpend, &pend.task[wave][0], npend);
+                else fold_pending<DEPTH1>(s, w, gpend, 64u, &pend.task[wave][0], npend);
+            } else if constexpr (!DIRECT) fold_pending<DEPTH1>(s, w, gpend, 64u, &pend.task[wave][0], npend);
             PROF_END(pfo, min(64u, npend * (3u << ts.P2)));
         } else {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // pend.L / pend.task are written by one lane and read by another lane of this wave
@@ -436,7 +441,7 @@ __global__ __launch_bounds__(SVR_TILE_THREADS, SVR_TILE_WAVES_PER_EU) void k_tra
                     uint32_t march_did = MARCH_NONE;                  // (experiment builds count what the shared march did)
                     if (live) {
                         uint32_t x = w.x0 + px, y = owned_row_to_y(w, r);
-                        hit = trace_primary<LAYOUT, COUNT, SKIP, SHARE>(s, lds, x, y, wang_hash(w.frame0 + slot), group_march, P2, &gmaps[wave][0], c, rng, L, vs.pt, vs.wo, val, cold_scene(), fg,
+                        hit = trace_primary<LAYOUT, COUNT, SKIP, SHARE>(s, lds, x, y, wang_hash(w.frame0 + slot), group_march, P2, &gmaps[wave][0], c, rng, L, vs.pt, vs.wo, val, cold_scene(),
                                                                               SVR_PROF ? &march_did : nullptr);
                     }
 #if SVR_PROF
@@ -573,7 +578,10 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
 {
     uint32_t wv = w.x1 - w.x0;
     if (wv == 0 || w.n_rows == 0) return hipSuccess;
-    if (w.fold && w.nframes > 64u) return hipErrorInvalidValue;         // in-kernel accumulation: every frame of a pixel sits in ONE wave
+    // in-kernel accumulation: every frame of a pixel sits in ONE wave.  Up to 64 frames that is one task; the wide-draining builds also take whole
+    // groups of 64 frames (checked below, once the build is known)
+    const bool many_groups = w.fold && w.nframes > 64u;
+    if (many_groups && ((w.nframes & 63u) != 0u || cfg.frames_log2 >= 0)) return hipErrorInvalidValue;
     DevWork w2;
     TaskGrid g;
     hipError_t e = task_launch_setup(w, cfg, SVR_TILE_THREADS / 64, w.fold != 0u, cfg.frames_log2, st, w2, g);
@@ -591,9 +599,18 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
     // ... but where neighbouring pixels share their whole-ray march (svr_walk.hpp, walk_setup_shared: the QUEUE builds that drain wide, one pixel x 64
     // frames per task in ONE frame group -- with several, consecutive tasks are one pixel's groups, not a pair -- pinhole camera) a ticket is one march
     // block, so that its tasks run back to back in one wave.  Placement only: any unit is exact.  Every other launch keeps one task per ticket
-    if (SVR_MARCH_BLOCK > 1 && !SVR_TILE_LIST && queue && skip && d1 && !cfg.pool_primary && w2.frames_log2 == 6u && w.nframes <= 64u && s.cam_pinhole && s.ray_skip)
-        w2.unit = SVR_MARCH_BLOCK;
+    // A FOLDING launch of that form may carry fgroups > 1 groups of 64 frames (fold_pending_groups, svr_tile_tasks.hpp): the frame group is the innermost
+    // index of the task order, so a ticket of MARCH_BLOCK x fgroups tasks is a pair's pixels with all their groups, in one wave, in frame order -- the
+    // fold needs that, and the kept march (its tag has no frame group) then serves 2 x fgroups tasks.  Any unit that is a multiple of fgroups is exact;
+    // another one would hand the groups of a pixel to different waves, and tickets that own tile rows (row_order) are single tasks: both are refused, as
+    // is every other build, and the host cuts such calls into launches of 64 frames (svr_api.hip, fold_group_frames)
+    const bool wide_form = !SVR_TILE_LIST && queue && skip && d1 && !cfg.pool_primary && w2.frames_log2 == 6u && s.cam_pinhole && s.ray_skip;
+    const uint32_t fgroups = (w.nframes + 63u) >> 6;
+    if (many_groups && !(wide_form && !w.row_order)) return hipErrorInvalidValue;
+    if (wide_form && (many_groups || (SVR_MARCH_BLOCK > 1 && w.nframes <= 64u)))
+        w2.unit = SVR_MARCH_BLOCK * (many_groups ? fgroups : 1u);
     if (cfg.unit_override > 0) w2.unit = (uint32_t)cfg.unit_override;
+    if (many_groups && w2.unit % fgroups != 0u) return hipErrorInvalidValue;
 #define SVR_LAUNCH_TILE(SK, D1, QU) hipLaunchKernelGGL((k_trace_tile<LAYOUT, COUNT, SK, D1, QU>), dim3(blocks), dim3(SVR_TILE_THREADS), 0, st, s, w2)
     if constexpr (LAYOUT != LAYOUT_LINEAR && !COUNT) {
         if (queue && !w.fold) {

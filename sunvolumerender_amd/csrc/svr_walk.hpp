@@ -456,7 +456,8 @@ SVR_DEV float first_occupied_group(const DevScene& s, const LDS& L, uint32_t P2,
 // admission -- whichever pixel the lane belongs to.  A reference ray through the common edge of two neighbouring pixels is within one pixel of every
 // lane of both, which on the headline scene is the margin a pixel's own jitter already uses.  So the wave keeps its last march (reference ray,
 // interval, result; the map words stay in slot 0) in the slots 1 and 2 of its GroupMapShared row, which a P2 == 0 launch does not use, tagged with
-// the pixel pair and the frame group:
+// the pixel pair alone -- the reference ray carries no jitter, so it is the same for every frame group of the pair, and in a launch of several
+// groups of 64 frames (svr_tile_tasks.hpp, fold_pending_groups), where a ticket is the pair x its groups, one march can serve all of them:
 //   tag differs  -> march along the un-jittered camera direction through the mid-point of the pair's common edge, over this pixel's interval widened
 //                   by one sample step on each side (if this pixel's own lanes would not pass against that ray, sharing is hopeless at this pixel
 //                   size: march for the pixel alone as first_occupied_group does);
@@ -485,7 +486,7 @@ struct MarchKept {                      // slots 1 and 2 of the wave's GroupMapS
 };
 static_assert(MarchKept::WORDS * 4u <= 2u * sizeof(GroupMapShared) && GROUP_MAPS_PER_WAVE >= 3u, "the kept march fits into slots 1 and 2");
 constexpr uint32_t MARCH_TAG_NONE = 0xffffffffu;
-SVR_DEV uint32_t march_tag(uint32_t x, uint32_t y, uint32_t fg) { return (((y << 15) ^ (x >> 1)) + fg * 0x9e3779b1u) & 0x7fffffffu; }
+SVR_DEV uint32_t march_tag(uint32_t x, uint32_t y) { return ((y << 15) ^ (x >> 1)) & 0x7fffffffu; }
 // every wave, before its first task (lane-uniform store; read back by the same wave only)
 SVR_DEV void march_kept_reset(GroupMapShared* gslot)
 {
@@ -497,10 +498,10 @@ SVR_DEV void march_kept_reset(GroupMapShared* gslot)
 // what the shared march did for a task (SVR_TEST_HOOKS builds count them; svr_selftest_group_march)
 enum MarchDid : uint32_t { MARCH_NONE = 0, MARCH_SHARED, MARCH_REUSED, MARCH_REFUSED, MARCH_ALONE };
 
-// walk_setup_group for such a task.  (x, y): the pixel, fg: the frame group; sc: the scene for the camera constants of the reference direction.
+// walk_setup_group for such a task.  (x, y): the pixel; sc: the scene for the camera constants of the reference direction.
 // Every lane of the wave must call it; gslot = the wave's GroupMapShared row.
 template <bool COUNT, bool SKIP, typename LDS>
-SVR_DEV int walk_setup_shared(const DevScene& s, const DevScene& sc, const LDS& L, uint32_t x, uint32_t y, uint32_t fg, v3 orig, v3 dir, bool rng_live,
+SVR_DEV int walk_setup_shared(const DevScene& s, const DevScene& sc, const LDS& L, uint32_t x, uint32_t y, v3 orig, v3 dir, bool rng_live,
                               float& tMin, float& tMax, float& t_occ, GroupMapShared* gslot, GroupMap& map, uint32_t* did = nullptr)
 {
     map.g = gslot;
@@ -515,7 +516,7 @@ SVR_DEV int walk_setup_shared(const DevScene& s, const DevScene& sc, const LDS& 
     if (__ballot(hit) == 0ull) return -1;                          // no lane hits the box: nothing to march for
     const float INF = u2f(SVR_INF_BITS);
     uint32_t* kw = reinterpret_cast<uint32_t*>(gslot + 1);
-    const uint32_t tag = march_tag(x, y, fg);
+    const uint32_t tag = march_tag(x, y);
     float g = INF;
     bool ok = false, complete = false, have = false;
     if (kw[MarchKept::TAG] == tag) {
