@@ -17,6 +17,10 @@
 // region up, in command-line order (Canvas::DetachRegion, FillRegionHoles, MorphRegion; R = 1 .. 32 applications of the unit element
 // -element 6|18|26, default 6): -detach cuts off what hangs on the picked structure by connections thinner than the element,
 // -fillholes adds what the region encloses.  The measurements are printed once more after the last step, and that region is shown.
+// -overlay FILL EDGE (opacities 0 .. 255) lays the region over the picture the run writes -- a slice, a stack, the ray caster's image, a MIP
+// or an isosurface -- instead of cutting it out of the volume: the inside tinted with FILL, the outline with EDGE (svr_overlay_slice;
+// svr_render_hits + svr_hit_ids + svr_overlay_ids for the 3D pictures).  -overlay-parts CONN labels the region first, so every
+// connected part gets its own colour (Canvas::LabelRegion).
 // -threshold LO HI is the alternative to -grow: the region is every voxel with raw value LO .. HI, with no pick (Canvas::ThresholdRegion);
 // the line it prints gives the number of connected parts (-conn) next to the measurements.  -largest K keeps the K largest parts and
 // -minsize N those of at least N voxels (Canvas::KeepLargestRegion, RemoveSmallRegions; connectivity -conn): clean-up steps taken in
@@ -33,7 +37,7 @@
 // spacing): -grow and -threshold then work on the filtered copy, and so does what they show.  -show-filtered draws the filtered copy
 // in place of the loaded volume.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +50,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -61,6 +65,8 @@ int main(int argc, char** argv)
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
     bool threshold = false;                                         // -threshold: the whole window growLo .. growHi, no pick
+    bool overlay = false;                                           // -overlay FILL EDGE: tint the picture by the region, which is not cut out of the volume
+    int overlayFill = 96, overlayEdge = 255, overlayParts = 0;      // -overlay-parts CONN: label the region first, one colour per part
     struct CleanStep { const char* name; int op; uint32_t radius; double length; };   // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N), -5 = -split (length: L), -10 - SVR_MORPH_* = -ball-* (length: L)
     std::vector<CleanStep> cleanSteps;                              // -detach / -fillholes / -open / -close / -dilate / -erode / -largest / -minsize / -ball-* / -split, in order
     int cleanElement = 6;
@@ -164,6 +170,16 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-frames") && i + 1 < argc) frames = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-depth") && i + 1 < argc) depth = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-size") && i + 2 < argc) { W = atoi(argv[i + 1]); H = atoi(argv[i + 2]); i += 2; }
+        else if (!strcmp(argv[i], "-overlay") && i + 2 < argc) {
+            overlayFill = atoi(argv[i + 1]); overlayEdge = atoi(argv[i + 2]);
+            if (overlayFill < 0 || overlayFill > 255 || overlayEdge < 0 || overlayEdge > 255) { fprintf(stderr, "-overlay needs two opacities 0 .. 255, of the fill and of the outline (got %s %s)\n", argv[i + 1], argv[i + 2]); return 2; }
+            overlay = true;
+            i += 2;
+        }
+        else if (!strcmp(argv[i], "-overlay-parts") && i + 1 < argc) {
+            overlayParts = atoi(argv[++i]);
+            if (overlayParts != 6 && overlayParts != 18 && overlayParts != 26) { fprintf(stderr, "-overlay-parts needs 6, 18 or 26 (got %s)\n", argv[i]); return 2; }
+        }
         else if (!strcmp(argv[i], "-raycast")) raycast = true;
         else if (!strcmp(argv[i], "-mip")) { project = true; proj.mode = SVR_PROJ_MIP; }
         else if (!strcmp(argv[i], "-mean")) { project = true; proj.mode = SVR_PROJ_MEAN; }
@@ -238,6 +254,9 @@ int main(int argc, char** argv)
     if (threshold)
         for (const CleanStep& c : cleanSteps)
             if (c.op == -1) { fprintf(stderr, "-detach starts from the picked voxel: it needs -grow X Y LO HI, not -threshold\n"); return 2; }
+    if ((overlay || overlayParts) && !grow && !threshold) { fprintf(stderr, "-overlay needs a region: -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if (overlayParts && !overlay) { fprintf(stderr, "-overlay-parts needs -overlay FILL EDGE\n"); return 2; }
+    if (overlay && sliceAxis < 0 && !raycast && !(project && proj.mode != SVR_PROJ_MEAN)) { fprintf(stderr, "-overlay tints a slice or a picture with one hit per pixel: it needs -slice, -stack, -raycast, -mip or -iso L\n"); return 2; }
     if (showFiltered && filterSteps.empty()) { fprintf(stderr, "-show-filtered needs -median E N or -smooth SIGMA\n"); return 2; }
     if (svr_init(0)) return 1;
     {
@@ -430,8 +449,19 @@ int main(int argc, char** argv)
                 if (rc == SVR_REGION_STATUS_EMPTY) printf("largest inscribed ball: none (the region is empty or fills the volume)\n");
                 else printf("largest inscribed ball: radius %g at voxel %d %d %d\n", radius, at[0], at[1], at[2]);
             }
-            if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            if (overlay) {
+                // the volume is drawn as it was loaded, and the region is laid over the picture
+                if (overlayParts) {
+                    uint32_t parts = 0u;
+                    if (canvas.LabelRegion(overlayParts, &parts) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    printf("overlay parts conn %d: %u parts\n", overlayParts, parts);
+                }
+            }
+            else if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         }
+        svr_overlay_style overlayStyle;
+        svr_overlay_style_default(&overlayStyle);
+        overlayStyle.fill_alpha = (uint32_t)overlayFill; overlayStyle.edge_alpha = (uint32_t)overlayEdge;
 
         if (sliceAxis >= 0) {
             // one slice (or a stack of them) instead of a rendering
@@ -445,6 +475,7 @@ int main(int argc, char** argv)
                 canvas.SetRenderMode(RENDER_MODE_SLICE);
                 canvas.paintGL();
                 if (svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (overlay && canvas.OverlayRegionOnSlice(sp, &overlayStyle) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 if (!canvas.SaveImage(out)) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 printf("slice %c at %g on %s -> %s\n", "xyz"[sliceAxis], slicePos, svr_device_info(), out.c_str());
             } else {
@@ -457,7 +488,12 @@ int main(int argc, char** argv)
                 const size_t bytes = (size_t)W * H * 4;
                 void* imgs = svr_device_malloc(bytes * (size_t)stack);
                 if (!imgs) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-                const int rc = svr_render_slice_stack(imgs, &canvas.Volume(), &canvas.TransferFunctionPod(), (uint32_t)W, (uint32_t)H, &sp, (uint32_t)stack, spacing);
+                int rc = svr_render_slice_stack(imgs, &canvas.Volume(), &canvas.TransferFunctionPod(), (uint32_t)W, (uint32_t)H, &sp, (uint32_t)stack, spacing);
+                if (rc == 0 && overlay) {
+                    const svr_overlay_source src = {canvas.RegionLabels() ? nullptr : canvas.RegionMask(), canvas.RegionLabels()};
+                    const int* dim = canvas.volumeReader->dim;
+                    rc = svr_overlay_slice(imgs, &canvas.Volume(), dim[0], dim[1], dim[2], (uint32_t)W, (uint32_t)H, &sp, (uint32_t)stack, spacing, &src, &overlayStyle);
+                }
                 std::vector<uint8_t> host(bytes);
                 const std::string stem = out.size() > 4 && out.compare(out.size() - 4, 4, ".tga") == 0 ? out.substr(0, out.size() - 4) : out;
                 for (int k = 0; rc == 0 && k < stack; ++k) {
@@ -495,6 +531,12 @@ int main(int argc, char** argv)
         } else
             for (int f = 0; f < (raycast ? 1 : frames); ++f) canvas.paintGL();
         if (svr_last_error_code()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+        if (overlay) {
+            // the hit map that belongs to the picture: the ray caster's opacity level, the isosurface point, the MIP sample
+            svr_hit_params hp = hitParams;
+            if (project) { hp.mode = proj.mode == SVR_PROJ_ISO ? SVR_HIT_ISO : SVR_HIT_MAX; hp.iso = proj.iso; }
+            if (canvas.OverlayRegion(hp, &overlayStyle) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+        }
         if (!canvas.SaveImage(out)) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%u frame(s) on %s -> %s\n", canvas.FrameNo(), svr_device_info(), out.c_str());
     }

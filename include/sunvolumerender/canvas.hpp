@@ -456,6 +456,7 @@ public:
         svr_region_stats st = {};
         rc = svr_region_grow(vox, dim[0], dim[1], dim[2], 1, seed, 1u, &p, regionMask, &st);
         haveRegion = rc == 0;
+        haveLabels = false;
         for (int a = 0; a < 3; ++a) regionSeed[a] = seed[a];     // DetachRegion starts from the same voxel, with the same connectivity
         regionConnectivity = connectivity;
         haveSeed = haveRegion;
@@ -571,6 +572,7 @@ public:
         const int rc = svr_region_threshold(vox, dim[0], dim[1], dim[2], 1, lo, hi, nullptr, nullptr, regionMask);
         haveRegion = rc == 0;
         haveSeed = false;
+        haveLabels = false;
         if (rc != 0 || !stats) return rc;
         return svr_region_stats_of(vox, dim[0], dim[1], dim[2], 1, regionMask, stats);
     }
@@ -653,6 +655,54 @@ public:
         *length = d == SVR_GEO_NONE ? 0.0 : (double)d * unit;
         return d == SVR_GEO_NONE ? SVR_REGION_STATUS_EMPTY : SVR_REGION_STATUS_OK;
     }
+    // extension: the region as an overlay on what is drawn (svr_overlay_slice, svr_render_hits + svr_hit_ids + svr_overlay_ids;
+    // include/svr_abi.h, "overlays").  The region itself stays as it is.
+    // LabelRegion: numbers the connected components of the region 1 .. *count (connectivity 6, 18 or 26) and keeps the labels next to the
+    // mask: the overlays then give every part its own colour, until anything replaces the region
+    int LabelRegion(int connectivity, uint32_t* count)
+    {
+        if (!ready || !SegVoxels() || !haveRegion || !count) return -4;
+        const int* dim = volumeReader->dim;
+        if (!regionLabels) regionLabels = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
+        if (!regionLabels) return -4;
+        const int rc = svr_region_label(regionMask, dim[0], dim[1], dim[2], connectivity, regionLabels, count);
+        haveLabels = rc == 0;
+        return rc;
+    }
+    // OverlayRegionOnSlice: tints the slice image in img -- what RENDER_MODE_SLICE drew for `params` -- by the region: the labels when
+    // they are current, else the mask.  style null = svr_overlay_style_default.  Synchronises
+    int OverlayRegionOnSlice(const svr_slice_params& params, const svr_overlay_style* style = nullptr)
+    {
+        if (!ready || !haveRegion) return -4;
+        const int* dim = volumeReader->dim;
+        svr_overlay_style st;
+        svr_overlay_style_default(&st);
+        const svr_overlay_source src = RegionSource();
+        const int rc = svr_overlay_slice(img, &deviceVolume, dim[0], dim[1], dim[2], (uint32_t)WIDTH, (uint32_t)HEIGHT, &params, 1u, 0.f, &src, style ? style : &st);
+        return rc ? rc : svr_device_synchronize();
+    }
+    // OverlayRegion: tints the 3D picture in img (ray caster or projection) by the region: a pixel whose ray meets what the picture
+    // shows -- the hit map of `params` -- in a voxel of the region gets that part's colour.  Synchronises
+    int OverlayRegion(const svr_hit_params& params = svr_hit_params{SVR_HIT_OPACITY, 0.5f, 0.5f}, const svr_overlay_style* style = nullptr)
+    {
+        if (!ready || !haveRegion) return -4;
+        const int* dim = volumeReader->dim;
+        const size_t n = (size_t)WIDTH * HEIGHT;
+        char* d = (char*)svr_device_malloc(n * (sizeof(svr_hit) + sizeof(uint32_t)));
+        if (!d) return -4;
+        uint32_t* ids = (uint32_t*)(d + n * sizeof(svr_hit));
+        svr_overlay_style st;
+        svr_overlay_style_default(&st);
+        const svr_overlay_source src = RegionSource();
+        int rc = svr_memset_device(d, 0, n * sizeof(svr_hit));          // (records outside a row shard or render window in force read as MISS)
+        if (rc == 0) rc = svr_render_hits(d, &deviceVolume, &transferFunction, &camera, volumeReader->GetElementBoundingSphereRadius(), &params);
+        if (rc == 0) rc = svr_hit_ids(ids, d, (uint32_t)WIDTH, (uint32_t)HEIGHT, &deviceVolume, dim[0], dim[1], dim[2], &src);
+        if (rc == 0) rc = svr_overlay_ids(img, ids, (uint32_t)WIDTH, (uint32_t)HEIGHT, 1u, style ? style : &st);
+        if (rc == 0) rc = svr_device_synchronize();
+        svr_device_free(d);
+        return rc;
+    }
+    const uint32_t* RegionLabels() const { return haveLabels ? regionLabels : nullptr; }   // device; one uint32 per voxel
     // ShowRegion: every renderer now draws the volume with the voxels outside (SVR_REGION_KEEP) or inside (SVR_REGION_REMOVE) the grown
     // region set to `fill`; ShowAll goes back to the loaded volume.  The Canvas owns the extra texture
     int ShowRegion(int mode, uint32_t fill)
@@ -774,7 +824,8 @@ private:
         if (regionTex) svr_destroy_texture(regionTex);
         if (regionMask) svr_device_free(regionMask);
         if (regionWork) svr_device_free(regionWork);
-        regionTex = 0; regionMask = nullptr; regionWork = nullptr; haveRegion = false; haveSeed = false;
+        if (regionLabels) svr_device_free(regionLabels);
+        regionTex = 0; regionMask = nullptr; regionWork = nullptr; regionLabels = nullptr; haveRegion = false; haveSeed = false; haveLabels = false;
     }
     // a device u16 volume of the loaded dimensions becomes the texture every renderer draws (ShowRegion, ShowRegionDistance)
     int ShowVoxels(const uint16_t* shown)
@@ -789,6 +840,11 @@ private:
         setup_volume(deviceVolume);
         ReStartRender();
         return 0;
+    }
+    // what the overlays read: the labels when they are current, else the mask
+    svr_overlay_source RegionSource() const
+    {
+        return haveLabels ? svr_overlay_source{nullptr, regionLabels} : svr_overlay_source{regionMask, nullptr};
     }
     // a length in the spacing's units as the r2 of svr_region_ball
     static uint32_t LengthToR2(double length, double unit)
@@ -809,6 +865,7 @@ private:
     {
         if (rc != 0) return rc;
         std::swap(regionMask, regionWork);
+        haveLabels = false;                            // (they were the parts of the mask that went)
         if (!stats) return 0;
         const int* dim = volumeReader->dim;
         return svr_region_stats_of(SegVoxels(), dim[0], dim[1], dim[2], 1, regionMask, stats);
@@ -854,6 +911,8 @@ private:
     RenderMode renderMode = RENDER_MODE_RAYCASTING;
     uint32_t* regionMask = nullptr;                // GrowRegion's bit mask (device)
     uint32_t* regionWork = nullptr;                // the other mask buffer of the clean-up calls
+    uint32_t* regionLabels = nullptr;              // LabelRegion's parts of the region (device, uint32 per voxel); freed with regionMask
+    bool haveLabels = false;                       // false once anything replaces the region
     int32_t regionSeed[3] = {0, 0, 0};             // GrowRegion's seed voxel and connectivity, for DetachRegion
     int regionConnectivity = 6;
     bool haveSeed = false;                         // false after ThresholdRegion: the region then comes from no pick

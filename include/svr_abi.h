@@ -982,6 +982,72 @@ int svr_region_zone_cut(const uint32_t* zones_device, int nx, int ny, int nz, in
  * svr_region_seed_labels / svr_region_zone_cut, whichever came last (waits for it) */
 int svr_region_geodesic_last_ms(float* ms);
 
+/* ---- overlays: region masks and label maps on slices and 3D views (csrc/svr_overlay.hip) ----
+ * Per-pixel region ids, outlines, and a blend onto the RGBA8 images that svr_render_slice, svr_render_slice_stack, render_raycasting and
+ * svr_render_projection write.  Integers only, but for the sample points of a slice, which are the float32 points of the slice section;
+ * every result is exact.
+ * SOURCE: exactly one pointer of svr_overlay_source is non-NULL.  mask_device: a bit mask in the region layout (padding bits ignored,
+ *   whatever they hold); labels_device: the dense uint32 [nz][ny][nx] of svr_region_label / svr_region_split.  The ID of voxel (x, y, z) is
+ *   its mask bit (0 or 1) or its label.
+ * VOXEL OF A POINT p: the mapping of svr_region_seed_from_world, to the letter.  Per axis tc = fl(fl(p - bbox.vmin) * bbox.invSize) on the
+ *   UNCLIPPED box, i = floor(tc * n) with the product taken exactly (a float32 times an int below 2^31 is exact in double), i = n clamped
+ *   to n - 1.  A point with any tc outside [0, 1], or NaN, has id 0: it is not refused.  The linear index is formed in 64 bits.
+ * ID OF A SLICE PIXEL: the samples are those of the slice section (FRAME, SLICE k, PLANE POINT, SLAB SAMPLES, BOX) with the same counting
+ *   rule; the pixel's id is the SMALLEST NON-ZERO id among the voxels of its counting samples, 0 if there is none or no sample counts.
+ *   (Independent of the order of the samples.)  mode, window_lo, window_hi and flags of the params are not looked at; thickness, step,
+ *   count and spacing are checked as svr_render_slice_stack checks them.
+ * ID OF A HIT PIXEL: a record with status SVR_HIT_STATUS_FOUND has the id of the voxel of `position`; any other record has id 0.  Only
+ *   `status` and `position` are read.
+ * EDGE: a pixel with id k != 0 is an edge pixel iff one of its four neighbours (x +- 1, y), (x, y +- 1) INSIDE the image has an id != k.
+ *   Neighbours outside the image are not looked at; in a stack only neighbours in the same slice count.
+ * STYLE: fill_alpha and edge_alpha lie in 0 .. 255, flags must be 0.  palette is a HOST array of palette_count RGBA8 entries (r in the low
+ *   byte, a in the high byte), 1 .. SVR_OVERLAY_MAX_PALETTE, read before the call returns (it travels to the kernel by value).  palette ==
+ *   NULL with palette_count == 0 selects the built-in table of SVR_OVERLAY_DEFAULT_PALETTE fully opaque colours:
+ *     (230, 25, 75) (60, 180, 75) (255, 225, 25) (0, 130, 200) (245, 130, 48) (145, 30, 180)
+ *     (70, 240, 240) (240, 50, 230) (210, 245, 60) (250, 190, 212) (0, 0, 128) (170, 110, 40).
+ * BLEND of a pixel with id k != 0: e = palette[(k - 1) mod palette_count], A = edge ? edge_alpha : fill_alpha, a = (A * e.a + 127) / 255.
+ *   a == 0: the pixel is not written.  Otherwise each of r, g, b becomes (in * (255 - a) + e.c * a + 127) / 255 (integer division); the
+ *   alpha byte stays.  A pixel with id 0 is never written; an entry with e.a == 0 hides its labels.
+ * svr_slice_ids writes `count` id images of w x h uint32, back to back; it honours svr_set_row_shard and svr_set_render_window (ids
+ *   outside stay untouched).  svr_hit_ids writes one id image from a FULL hit map of w x h records and svr_overlay_ids blends `count` id
+ *   images over `count` RGBA8 images in place; both are whole-image post-processes and ignore shard and window.  svr_overlay_slice is
+ *   svr_slice_ids followed by svr_overlay_ids in one kernel, without the id images: it writes the owned pixels only and judges their
+ *   edges from the true ids of their neighbours, owned or not, so a sharded or windowed overlay equals the cut-out of the full one.
+ *   All honour svr_set_stream and are asynchronous.
+ * REFUSED, before the device is touched and with nothing written: a null argument (-4); a dimension <= 0 or more than 2^31 voxels (-6);
+ *   both or neither source pointer, an alpha above 255, flags != 0, palette_count > SVR_OVERLAY_MAX_PALETTE, a palette without a count
+ *   or a count without a palette, w, h or count of 0, a non-finite bbox, and what svr_render_slice_stack refuses about center, u, v,
+ *   thickness, step, count and spacing (-3). */
+#define SVR_OVERLAY_MAX_PALETTE 256
+#define SVR_OVERLAY_DEFAULT_PALETTE 12
+
+typedef struct svr_overlay_source {
+    const uint32_t* mask_device;     /* bit mask in the region layout, or NULL */
+    const uint32_t* labels_device;   /* uint32 [nz][ny][nx], or NULL */
+} svr_overlay_source;
+
+typedef struct svr_overlay_style {
+    uint32_t fill_alpha, edge_alpha; /* 0 .. 255: opacity of the tint inside a part / on its outline */
+    uint32_t palette_count, flags;
+    const uint32_t* palette;         /* HOST array of palette_count RGBA8 entries, or NULL with palette_count 0: the built-in table */
+} svr_overlay_style;
+
+int svr_overlay_style_default(svr_overlay_style* style);             /* fill 96, edge 255, built-in palette.  Plain host code */
+/* the first n <= SVR_OVERLAY_DEFAULT_PALETTE entries of the built-in table.  Plain host code */
+int svr_overlay_palette_default(uint32_t* out, uint32_t n);
+/* (nx, ny, nz: the dimensions of the mask or label array, which the image calls below only index) */
+int svr_slice_ids(uint32_t* ids_device, const svr_volume* volume,
+                  int nx, int ny, int nz, uint32_t w, uint32_t h, const svr_slice_params* p, uint32_t count, float spacing,
+                  const svr_overlay_source* source);
+int svr_hit_ids(uint32_t* ids_device, const void* hits_device, uint32_t w, uint32_t h, const svr_volume* volume,
+                int nx, int ny, int nz, const svr_overlay_source* source);
+int svr_overlay_ids(void* imgs, const uint32_t* ids_device, uint32_t w, uint32_t h, uint32_t count, const svr_overlay_style* style);
+int svr_overlay_slice(void* imgs, const svr_volume* volume,
+                      int nx, int ny, int nz, uint32_t w, uint32_t h, const svr_slice_params* p, uint32_t count, float spacing,
+                      const svr_overlay_source* source, const svr_overlay_style* style);
+/* HIP-event time of the device work of the last of the four device calls above (waits for it) */
+int svr_overlay_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

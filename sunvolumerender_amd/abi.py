@@ -302,6 +302,25 @@ GEO_NONE = 0xFFFFFFFF
 GEO_TILE = (32, 8, 8)     # the relaxation tile of csrc/svr_geodesic.hip in voxels (x, y, z)
 
 
+class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
+    _fields_ = [("mask_device", C.c_void_p), ("labels_device", C.c_void_p)]
+
+
+class OverlayStyle(C.Structure):  # svr_overlay_style
+    _fields_ = [
+        ("fill_alpha", C.c_uint32),
+        ("edge_alpha", C.c_uint32),
+        ("palette_count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("palette", C.POINTER(C.c_uint32)),   # HOST array of palette_count RGBA8 entries; NULL with 0: the built-in table
+    ]
+
+
+svr_overlay_source, svr_overlay_style = OverlaySource, OverlayStyle
+OVERLAY_MAX_PALETTE = 256
+OVERLAY_DEFAULT_PALETTE = 12
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -324,6 +343,8 @@ EXPECTED_SIZES = {
     RegionStats: 112,
     RegionMeasurement: 56,
     RegionComponent: 40,
+    OverlaySource: 16,
+    OverlayStyle: 24,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -500,6 +521,15 @@ PROTOTYPES = {
                                    _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "svr_region_zone_cut": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "svr_region_geodesic_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
+    "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
+    "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,
+                                C.c_float, _P(OverlaySource)]),
+    "svr_hit_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, _P(cudaVolume), C.c_int, C.c_int, C.c_int, _P(OverlaySource)]),
+    "svr_overlay_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _P(OverlayStyle)]),
+    "svr_overlay_slice": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,
+                                    C.c_float, _P(OverlaySource), _P(OverlayStyle)]),
+    "svr_overlay_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),

@@ -1369,6 +1369,8 @@ namespace svr {
 int report_error(int code, const char* msg) { return fail(code, "%s", msg); }
 int ensure_ready() { return ensure_init(); }
 hipStream_t current_stream() { return g.stream; }
+void image_work(DevWork& work, uint32_t W, uint32_t H, bool whole) { if (whole) fill_work_full(work, W, H); else fill_work(work, W, H); }
+int device_cus() { return g.num_cus; }
 }
 
 extern "C" {

@@ -744,6 +744,68 @@ class Device:
         self.check(self.lib.svr_region_geodesic_last_ms(C.byref(ms)))
         return float(ms.value)
 
+    # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
+    def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
+        """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
+        to abi.OVERLAY_MAX_PALETTE RGBA8 entries as uint32 (r in the low byte) or as rows (r, g, b, a); the style keeps the array alive."""
+        st = abi.OverlayStyle()
+        self.check(self.lib.svr_overlay_style_default(C.byref(st)))
+        if fill_alpha is not None:
+            st.fill_alpha = int(fill_alpha)
+        if edge_alpha is not None:
+            st.edge_alpha = int(edge_alpha)
+        if palette is not None:
+            pal = np.asarray(palette)
+            if pal.ndim == 2:
+                pal = np.ascontiguousarray(pal, dtype=np.uint8).view("<u4").reshape(-1)
+            st._palette = np.ascontiguousarray(pal, dtype=np.uint32)
+            st.palette = st._palette.ctypes.data_as(C.POINTER(C.c_uint32))
+            st.palette_count = len(st._palette)
+        return st
+
+    def overlay_palette_default(self, n: int = abi.OVERLAY_DEFAULT_PALETTE) -> np.ndarray:
+        out = np.zeros(int(n), dtype=np.uint32)
+        self.check(self.lib.svr_overlay_palette_default(out.ctypes.data_as(C.POINTER(C.c_uint32)), int(n)))
+        return out
+
+    @staticmethod
+    def _overlay_source(mask: Optional[int], labels: Optional[int]) -> abi.OverlaySource:
+        return abi.OverlaySource(C.c_void_p(int(mask)) if mask else None, C.c_void_p(int(labels)) if labels else None)
+
+    def slice_ids(self, ids: int, volume: cudaVolume, shape, w: int, h: int, params: abi.SliceParams, mask: Optional[int] = None,
+                  labels: Optional[int] = None, count: int = 1, spacing: float = 0.0):
+        """svr_slice_ids: the region id of every owned pixel of `count` slices into the device buffer ids (count x h x w uint32).  mask /
+        labels: the device pointer of a bit mask or of a uint32 label array of the (nz, ny, nx) = shape volume; exactly one is given."""
+        nz, ny, nx = (int(n) for n in shape)
+        src = self._overlay_source(mask, labels)
+        self.check(self.lib.svr_slice_ids(C.c_void_p(int(ids)), C.byref(volume), nx, ny, nz, int(w), int(h), C.byref(params), int(count),
+                                          C.c_float(float(spacing)), C.byref(src)))
+
+    def hit_ids(self, ids: int, hits: int, w: int, h: int, volume: cudaVolume, shape, mask: Optional[int] = None, labels: Optional[int] = None):
+        """svr_hit_ids: the region id of every record of a full w x h hit map (svr_render_hits) into the device buffer ids."""
+        nz, ny, nx = (int(n) for n in shape)
+        src = self._overlay_source(mask, labels)
+        self.check(self.lib.svr_hit_ids(C.c_void_p(int(ids)), C.c_void_p(int(hits)), int(w), int(h), C.byref(volume), nx, ny, nz, C.byref(src)))
+
+    def overlay_ids(self, imgs: int, ids: int, w: int, h: int, count: int = 1, style: Optional[abi.OverlayStyle] = None):
+        """svr_overlay_ids: tints `count` RGBA8 images of w x h in place by their id images: fill inside a part, outline at its edge."""
+        st = style if style is not None else self.overlay_style()
+        self.check(self.lib.svr_overlay_ids(C.c_void_p(int(imgs)), C.c_void_p(int(ids)), int(w), int(h), int(count), C.byref(st)))
+
+    def overlay_slice(self, imgs: int, volume: cudaVolume, shape, w: int, h: int, params: abi.SliceParams, mask: Optional[int] = None,
+                      labels: Optional[int] = None, style: Optional[abi.OverlayStyle] = None, count: int = 1, spacing: float = 0.0):
+        """svr_overlay_slice: slice_ids followed by overlay_ids in one kernel, over the owned pixels of the slice images at imgs."""
+        nz, ny, nx = (int(n) for n in shape)
+        src = self._overlay_source(mask, labels)
+        st = style if style is not None else self.overlay_style()
+        self.check(self.lib.svr_overlay_slice(C.c_void_p(int(imgs)), C.byref(volume), nx, ny, nz, int(w), int(h), C.byref(params), int(count),
+                                              C.c_float(float(spacing)), C.byref(src), C.byref(st)))
+
+    def overlay_last_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_overlay_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     # ---- exact volume filters (svr_volume_*): median / min / max and binomial smoothing of the raw voxels ----
     def volume_rank(self, vox, op: int, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
         """svr_volume_rank: the median (FILTER_MEDIAN), minimum (FILTER_MIN) or maximum (FILTER_MAX) of every voxel's window under the
@@ -993,6 +1055,7 @@ class Canvas:
         self.lib.setup_volume(C.byref(self.deviceVolume)); self.dev.check()
         self.stepSize = element_bounding_sphere_radius(spacing)
         self.volumeSize = volume_size((nx, ny, nz), spacing)
+        self.volumeDim = (nx, ny, nz)
         self.boundingSphereRadius = bounding_sphere_radius((nx, ny, nz), spacing)
         eye = zoom_to_extent_eye_dist(self.volumeSize, self.fov)
         self.eyeDist = eye
@@ -1016,6 +1079,7 @@ class Canvas:
         self.lib.setup_volume(C.byref(self.deviceVolume)); self.dev.check()
         self.stepSize = self.volumeReader.GetElementBoundingSphereRadius()
         self.volumeSize = self.volumeReader.GetVolumeSize()
+        self.volumeDim = tuple(int(d) for d in self.volumeReader.dim)
         self.boundingSphereRadius = self.volumeReader.GetBoundingSphereRadius()
         self.eyeDist = zoom_to_extent_eye_dist(self.volumeSize, self.fov)
         self.camera = camera_setup((0.0, 0.0, self.eyeDist), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), self.fov, self.apeture,
@@ -1229,6 +1293,62 @@ class Canvas:
             return self.dev.to_host(buf, (n,), HIT_DTYPE)
         finally:
             self.dev.free(buf)
+
+    # ---- extension: overlays of region masks and label maps (svr_overlay_slice; svr_render_hits + svr_hit_ids + svr_overlay_ids) ----
+    def _overlay_region(self, mask, labels):
+        """(mask pointer, labels pointer, owned buffer or None, (nz, ny, nx)) of a bool mask / uint32 label array [nz][ny][nx] (uploaded)
+        or of a device pointer to either; exactly one of the two is given."""
+        if (mask is None) == (labels is None):
+            raise SvrError("an overlay needs a mask or a label array, not both")
+        if not self.ready:
+            raise SvrError("an overlay needs a loaded volume")
+        nx, ny, nz = self.volumeDim
+        shape = (nz, ny, nx)
+        if mask is not None:
+            buf, owned = self.dev._region_mask(mask, shape)
+            return buf, None, buf if owned else None, shape
+        buf, lshape, owned = self.dev._region_labels(labels, shape)
+        if tuple(lshape) != shape:
+            if owned:
+                self.dev.free(buf)
+            raise SvrError(f"the labels are {tuple(lshape)}, the volume is {shape}")
+        return None, buf, buf if owned else None, shape
+
+    def paint_slice_overlay(self, params: abi.SliceParams, mask=None, labels=None, style: Optional[abi.OverlayStyle] = None, count: int = 1,
+                            spacing: float = 0.0, imgs: Optional[int] = None, sync: bool = False):
+        """Tints the slice (or, with imgs and count, the stack) that paint_slice / paint_slice_stack drew with the same params by a region:
+        mask (a bool array [nz][ny][nx] or the device pointer of a bit mask) or labels (a uint32 array or device pointer).  Every part
+        gets the colour of its id, filled with style.fill_alpha and outlined with style.edge_alpha."""
+        m, l, owned, shape = self._overlay_region(mask, labels)
+        try:
+            self.dev.overlay_slice(self.img if imgs is None else imgs, self.deviceVolume, shape, self.W, self.H, params, m, l, style, count, spacing)
+            if sync or owned is not None:
+                self.dev.synchronize()
+        finally:
+            if owned is not None:
+                self.dev.free(owned)
+
+    def paint_overlay(self, mask=None, labels=None, style: Optional[abi.OverlayStyle] = None, mode: int = abi.HIT_OPACITY, alpha: float = 0.5,
+                      iso: float = 0.5, sync: bool = False):
+        """Tints the 3D picture in the canvas image (paint with the ray caster, or paint_projection) by a region: every pixel whose ray
+        meets what the picture shows (the hit map of `mode`, alpha, iso; see hit_map) inside a part gets that part's colour.  Pixels
+        outside a row shard or render window in force have no hit record and stay as they are.  Synchronises."""
+        m, l, owned, shape = self._overlay_region(mask, labels)
+        p = abi.HitParams(int(mode), float(alpha), float(iso))
+        n = self.W * self.H
+        buf = self.dev.malloc(n * (HIT_DTYPE.itemsize + 4))
+        ids = buf + n * HIT_DTYPE.itemsize
+        try:
+            self.dev.check(self.lib.svr_memset_device(C.c_void_p(buf), 0, n * HIT_DTYPE.itemsize))
+            self.dev.check(self.lib.svr_render_hits(C.c_void_p(buf), C.byref(self.deviceVolume), C.byref(self.transferFunction),
+                                                    C.byref(self.camera), C.c_float(self.stepSize), C.byref(p)))
+            self.dev.hit_ids(ids, buf, self.W, self.H, self.deviceVolume, shape, m, l)
+            self.dev.overlay_ids(self.img, ids, self.W, self.H, 1, style)
+            self.dev.synchronize()
+        finally:
+            self.dev.free(buf)
+            if owned is not None:
+                self.dev.free(owned)
 
     # ---- extension: denoised preview of the first frames after a restart ----
     def SetDenoisePreview(self, frames: int, params: Optional[abi.DenoiseParams] = None):
