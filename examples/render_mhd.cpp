@@ -36,8 +36,12 @@
 // the unit element E = 6|18|26, N = 1 .. 64 times; Canvas::SmoothVolume: binomial smoothing of SIGMA > 0 in the units of the volume's
 // spacing): -grow and -threshold then work on the filtered copy, and so does what they show.  -show-filtered draws the filtered copy
 // in place of the loaded volume.
+// -mesh FILE.stl|.ply writes the closed surface of the region that is left after all clean-up and selection steps (Canvas::
+// ExtractRegionSurface, SaveSurface: surface nets in world coordinates; -relax N smooths it by N = 0 .. 64 constrained relaxation
+// steps); -mesh-iso RAW FILE.stl|.ply writes the isosurface {raw value >= RAW} of the (filtered) voxels, with or without a region.  Each
+// prints "mesh: V vertices, T triangles, volume ... mm^3, area ... mm^2", the region's line first.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -50,7 +54,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]]] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -74,6 +78,12 @@ int main(int argc, char** argv)
     struct FilterStep { int element; uint32_t iterations; double sigma; };     // -median E N (element != 0) or -smooth SIGMA
     std::vector<FilterStep> filterSteps;                            // in command-line order
     bool showFiltered = false;                                      // -show-filtered
+    std::string meshFile, meshIsoFile;                              // -mesh FILE: the surface of the final region; -mesh-iso RAW FILE: the raw isosurface
+    int meshRelax = -1, meshIsoLevel = 0;                           // -relax N (with -mesh): 0 .. SVR_MESH_MAX_RELAX relaxation steps
+    const auto meshName = [](const char* f) {                       // an export writes .stl or .ply
+        const size_t n = strlen(f);
+        return n > 4 && (!strcmp(f + n - 4, ".stl") || !strcmp(f + n - 4, ".ply"));
+    };
     for (int i = 2; i < argc; ++i) {
         int cleanOp = -2;
         if (!strcmp(argv[i], "-detach")) cleanOp = -1;
@@ -240,6 +250,28 @@ int main(int argc, char** argv)
             adaptiveTarget = strtof(argv[++i], &end);
             if (end == argv[i] || *end != '\0' || !(adaptiveTarget > 0.f)) { fprintf(stderr, "-adaptive needs a tile target RMSE > 0 (got %s)\n", argv[i]); return 2; }
         }
+        else if (!strcmp(argv[i], "-mesh")) {
+            if (i + 1 >= argc || !meshName(argv[i + 1])) { fprintf(stderr, "-mesh needs a file name that ends in .stl or .ply (got %s)\n", i + 1 < argc ? argv[i + 1] : "nothing"); return 2; }
+            meshFile = argv[++i];
+        }
+        else if (!strcmp(argv[i], "-relax")) {
+            char* end = nullptr;
+            const long v = i + 1 < argc ? strtol(argv[i + 1], &end, 10) : -1;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || v < 0 || v > SVR_MESH_MAX_RELAX) { fprintf(stderr, "-relax needs a number of steps N in 0 .. %d (got %s)\n", SVR_MESH_MAX_RELAX, i + 1 < argc ? argv[i + 1] : "nothing"); return 2; }
+            meshRelax = (int)v;
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-mesh-iso")) {
+            char* end = nullptr;
+            const long v = i + 2 < argc ? strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 2 >= argc || end == argv[i + 1] || *end != '\0' || v < 1 || v > 65535 || !meshName(argv[i + 2])) {
+                fprintf(stderr, "-mesh-iso needs a raw level 1 .. 65535 and a file name that ends in .stl or .ply (got %s %s)\n", i + 1 < argc ? argv[i + 1] : "nothing", i + 2 < argc ? argv[i + 2] : "nothing");
+                return 2;
+            }
+            meshIsoLevel = (int)v;
+            meshIsoFile = argv[i + 2];
+            i += 2;
+        }
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -257,6 +289,8 @@ int main(int argc, char** argv)
     if ((overlay || overlayParts) && !grow && !threshold) { fprintf(stderr, "-overlay needs a region: -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (overlayParts && !overlay) { fprintf(stderr, "-overlay-parts needs -overlay FILL EDGE\n"); return 2; }
     if (overlay && sliceAxis < 0 && !raycast && !(project && proj.mode != SVR_PROJ_MEAN)) { fprintf(stderr, "-overlay tints a slice or a picture with one hit per pixel: it needs -slice, -stack, -raycast, -mip or -iso L\n"); return 2; }
+    if (!meshFile.empty() && !grow && !threshold) { fprintf(stderr, "-mesh exports the surface of a region: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if (meshRelax >= 0 && meshFile.empty()) { fprintf(stderr, "-relax needs -mesh FILE\n"); return 2; }
     if (showFiltered && filterSteps.empty()) { fprintf(stderr, "-show-filtered needs -median E N or -smooth SIGMA\n"); return 2; }
     if (svr_init(0)) return 1;
     {
@@ -279,7 +313,7 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
-        canvas.volumeReader->KeepVoxels(grow || threshold || !filterSteps.empty());  // the region and filter calls work on the plain voxels
+        canvas.volumeReader->KeepVoxels(grow || threshold || !filterSteps.empty() || !meshIsoFile.empty());  // the region and filter calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%s: %d x %d x %d, range %.0f..%.0f, max gradient magnitude %.0f, %zu histogram bins\n", volume.c_str(),
@@ -319,6 +353,14 @@ int main(int argc, char** argv)
             }
         }
         if (showFiltered && canvas.ShowFiltered() != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+
+        // an extracted surface goes to its file in world coordinates, with one line of counts and measures in the spacing's units
+        const auto exportSurface = [&](const std::string& file) {
+            double vol = 0.0, area = 0.0;
+            if (canvas.SurfaceMeasure(&vol, &area) != 0 || canvas.SaveSurface(file) != 0) return false;
+            printf("mesh: %zu vertices, %zu triangles, volume %.9g mm^3, area %.9g mm^2\n", canvas.SurfaceVertices().size() / 3, canvas.SurfaceTriangles().size() / 3, vol, area);
+            return true;
+        };
 
         if (!picks.empty()) {
             // point picks instead of a rendering: one line per pick
@@ -449,6 +491,7 @@ int main(int argc, char** argv)
                 if (rc == SVR_REGION_STATUS_EMPTY) printf("largest inscribed ball: none (the region is empty or fills the volume)\n");
                 else printf("largest inscribed ball: radius %g at voxel %d %d %d\n", radius, at[0], at[1], at[2]);
             }
+            if (!meshFile.empty() && (canvas.ExtractRegionSurface((uint32_t)(meshRelax < 0 ? 0 : meshRelax)) != 0 || !exportSurface(meshFile))) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
             if (overlay) {
                 // the volume is drawn as it was loaded, and the region is laid over the picture
                 if (overlayParts) {
@@ -459,6 +502,7 @@ int main(int argc, char** argv)
             }
             else if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         }
+        if (!meshIsoFile.empty() && (canvas.ExtractIsoSurface((uint32_t)meshIsoLevel, 0u) != 0 || !exportSurface(meshIsoFile))) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         svr_overlay_style overlayStyle;
         svr_overlay_style_default(&overlayStyle);
         overlayStyle.fill_alpha = (uint32_t)overlayFill; overlayStyle.edge_alpha = (uint32_t)overlayEdge;

@@ -599,6 +599,62 @@ public:
         svr_device_free(labels);
         return rc;
     }
+    // Surface meshes (svr_mesh_region / _isosurface / _positions / _measure, svr_stl_write / svr_ply_write; include/svr_abi.h, "surface
+    // meshes of region masks and isosurfaces").  ExtractRegionSurface: the closed surface of the current region after `relax` (0 ..
+    // SVR_MESH_MAX_RELAX) constrained relaxation steps; ExtractIsoSurface: the surface {raw value >= level} of the segmented voxels.  The
+    // canvas keeps the mesh on the host (SurfaceVertices: int32 x, y, z in 1/256 voxel on the padded grid; SurfaceTriangles: uint32
+    // triples) until the next extraction.  An empty mesh is not an error (info->status == SVR_REGION_STATUS_EMPTY)
+    int ExtractRegionSurface(uint32_t relax, svr_mesh_info* info = nullptr)
+    {
+        if (!ready || !haveRegion) return -4;
+        const int* dim = volumeReader->dim;
+        const svr_mesh_params p = {1u, relax};
+        const uint32_t* mask = regionMask;
+        return ExtractSurface([&](int32_t* v, uint64_t nv, uint32_t* t, uint64_t nt, svr_mesh_info* i) { return svr_mesh_region(mask, dim[0], dim[1], dim[2], &p, v, nv, t, nt, i); },
+                              info);
+    }
+    int ExtractIsoSurface(uint32_t level, uint32_t relax, svr_mesh_info* info = nullptr)
+    {
+        const uint16_t* vox = SegVoxels();
+        if (!ready || !vox) return -4;
+        const int* dim = volumeReader->dim;
+        const svr_mesh_params p = {level, relax};
+        return ExtractSurface([&](int32_t* v, uint64_t nv, uint32_t* t, uint64_t nt, svr_mesh_info* i) { return svr_mesh_isosurface(vox, dim[0], dim[1], dim[2], 1, &p, v, nv, t, nt, i); },
+                              info);
+    }
+    bool HasSurface() const { return haveSurface; }
+    const std::vector<int32_t>& SurfaceVertices() const { return surfaceVertices; }
+    const std::vector<uint32_t>& SurfaceTriangles() const { return surfaceTriangles; }
+    // SaveSurface: the extracted surface in world coordinates (where the renderers draw the volume) as binary PLY for a name that ends in
+    // ".ply", as binary STL otherwise
+    int SaveSurface(const std::string& filename) const
+    {
+        if (!haveSurface) return -4;
+        const uint64_t nv = surfaceVertices.size() / 3, nt = surfaceTriangles.size() / 3;
+        std::vector<float> xyz(surfaceVertices.size());
+        if (int rc = svr_mesh_positions(surfaceVertices.data(), nv, nullptr, &deviceVolume, xyz.data())) return rc;
+        const bool ply = filename.size() >= 4 && (filename.compare(filename.size() - 4, 4, ".ply") == 0 || filename.compare(filename.size() - 4, 4, ".PLY") == 0);
+        return (ply ? svr_ply_write : svr_stl_write)(filename.c_str(), xyz.data(), nv, surfaceTriangles.data(), nt);
+    }
+    // SurfaceMeasure: the volume the surface encloses (exact but for the last rounding) and its area, in the spacing's units
+    int SurfaceMeasure(double* volume, double* area) const
+    {
+        if (!haveSurface || !volume || !area) return -4;
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        const double scale[3] = {sp[0] / 256.0, sp[1] / 256.0, sp[2] / 256.0};
+        const size_t vbytes = surfaceVertices.size() * sizeof(int32_t), tbytes = surfaceTriangles.size() * sizeof(uint32_t);
+        int64_t vol6 = 0;
+        *volume = *area = 0.0;
+        if (!tbytes) return 0;
+        char* buf = (char*)svr_device_malloc(vbytes + tbytes);
+        if (!buf) return -4;
+        int rc = svr_memcpy_h2d(buf, surfaceVertices.data(), vbytes);
+        if (rc == 0) rc = svr_memcpy_h2d(buf + vbytes, surfaceTriangles.data(), tbytes);
+        if (rc == 0) rc = svr_mesh_measure((const int32_t*)buf, surfaceVertices.size() / 3, (const uint32_t*)(buf + vbytes), surfaceTriangles.size() / 3, scale, &vol6, area);
+        svr_device_free(buf);
+        if (rc == 0) *volume = (double)vol6 / (6.0 * 256.0 * 256.0 * 256.0) * sp[0] * sp[1] * sp[2];
+        return rc;
+    }
     // Splitting and path lengths (svr_region_split / _zone_cut / _geodesic; include/svr_abi.h, "geodesic distances and influence zones").
     // SplitRegion: separates objects of the region that touch through necks thinner than a ball of neck_radius (> 0, finite, in the
     // spacing's units): the region is eroded by that ball, the cores are labelled under `connectivity`, every voxel goes to the core
@@ -817,6 +873,29 @@ private:
         filtered = out;
         return 0;
     }
+    // a counting call, then an extraction into device arrays of the counted sizes, copied to the host
+    template <typename Call>
+    int ExtractSurface(Call call, svr_mesh_info* info_out)
+    {
+        svr_mesh_info info;
+        haveSurface = false;
+        int rc = call(nullptr, 0u, nullptr, 0u, &info);
+        if (rc != 0) return rc;
+        const size_t vbytes = (size_t)info.vertices * 3 * sizeof(int32_t), tbytes = (size_t)info.triangles * 3 * sizeof(uint32_t);
+        surfaceVertices.assign((size_t)info.vertices * 3, 0);
+        surfaceTriangles.assign((size_t)info.triangles * 3, 0u);
+        if (info.vertices) {
+            char* buf = (char*)svr_device_malloc(vbytes + tbytes);
+            if (!buf) return -4;
+            rc = call((int32_t*)buf, info.vertices, (uint32_t*)(buf + vbytes), info.triangles, &info);
+            if (rc == 0) rc = svr_memcpy_d2h(surfaceVertices.data(), buf, vbytes);
+            if (rc == 0 && tbytes) rc = svr_memcpy_d2h(surfaceTriangles.data(), buf + vbytes, tbytes);
+            svr_device_free(buf);
+        }
+        haveSurface = rc == 0;
+        if (info_out) *info_out = info;
+        return rc;
+    }
     void ClearRegion()
     {
         if (filtered) svr_device_free(filtered);
@@ -919,6 +998,9 @@ private:
     cudaTextureObject_t regionTex = 0;             // ShowRegion's masked volume
     bool haveRegion = false;
     uint16_t* filtered = nullptr;                  // MedianVolume / SmoothVolume's copy of the voxels (device)
+    std::vector<int32_t> surfaceVertices;          // ExtractRegionSurface / ExtractIsoSurface's mesh (host)
+    std::vector<uint32_t> surfaceTriangles;
+    bool haveSurface = false;
     svr_projection_params projection = {SVR_PROJ_MIP, 0u, 0.5f, 0.f, 1.f};
     svr_slice_params slice = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, 0.f, 1.f, SVR_SLAB_MIP, 0u, 0.f, 1.f};
 };

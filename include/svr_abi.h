@@ -1048,6 +1048,76 @@ int svr_overlay_slice(void* imgs, const svr_volume* volume,
 /* HIP-event time of the device work of the last of the four device calls above (waits for it) */
 int svr_overlay_last_ms(float* ms);
 
+/* ---- surface meshes of region masks and isosurfaces by surface nets (csrc/svr_mesh.hip) ----
+ * Integers only; the mesh is defined index for index, whatever order the GPU works in.
+ * FIELD: a u16 volume [nz][ny][nx] with a raw level in 1 .. 65535; sample (x, y, z) is INSIDE iff v >= level.  A region mask is the
+ *   field with value 2 inside and 0 outside at level 1 (padding bits ignored, whatever they hold).  The volume is surrounded by one
+ *   layer of virtual samples of value 0, so every mesh is closed, also where the object touches a face of the volume.  Padded sample
+ *   coordinates are x' = x + 1, in 0 .. nx + 1.
+ * CELLS: cell (i, j, k), i in 0 .. nx (likewise j, k), has the eight padded samples i .. i + 1 x j .. j + 1 x k .. k + 1 as corners; it is
+ *   ACTIVE iff its corners are neither all inside nor all outside.
+ * CROSSING POINT: a cell edge crosses the surface when one end is inside (value vi) and the other outside (value vo); the point lies
+ *   q = floor(256 (level - vo) / (vi - vo)) from the outside end, i.e. q from the edge's lower-coordinate end if that end is outside
+ *   and 256 - q otherwise.
+ * VERTEX: non-negative int32 (x, y, z) in units of 1/256 voxel on the padded grid, u = 256 x': real sample x sits at 256 (x + 1).  An
+ *   active cell with m crossing edges (3 .. 12) has per axis the coordinate 256 i + (2 S + m) / (2 m) (integer division), S = the sum
+ *   of the crossing points' cell-relative coordinates (each 0 .. 256).  Vertices are numbered in ascending linear cell index
+ *   (k (ny + 1) + j)(nx + 1) + i.
+ * QUADS: one per crossing edge from padded sample s to s + e_a; (a, b, c) cyclic: x -> (y, z), y -> (z, x), z -> (x, y).  With the
+ *   four cells that contain the edge written by their (b, c) offsets from the cell with index s, the quad is C(-1,-1), C(0,-1),
+ *   C(0,0), C(-1,0) if s is inside and C(-1,-1), C(-1,0), C(0,0), C(0,-1) if s + e_a is: normals point out of the object.  Quads
+ *   are ordered by the key 3 ((z' (ny + 2) + y')(nx + 2) + x') + a; quad n = (q0, q1, q2, q3) is the triangles (q0, q1, q2) at 2 n
+ *   and (q0, q2, q3) at 2 n + 1.  Two objects that touch along an edge or at a corner share vertices there (a non-manifold edge).
+ * RELAXATION (relax = 0 .. SVR_MESH_MAX_RELAX Jacobi steps; meant for masks): two active cells are LINKED iff they share a face whose
+ *   four corners are mixed; every active cell has at least 3 links.  Per step and axis a vertex becomes (2 T + m) / (2 m), T = the
+ *   sum of its m linked neighbours' previous coordinates, then is clamped to its own cell [256 i, 256 i + 256].  Connectivity never
+ *   changes.  It shrinks convex shapes by a few per cent over many steps; nothing compensates for that.
+ * MEASURES (svr_mesh_measure): *volume6_units = the sum of a . (b x c) over the triangles in wrap-around 64-bit arithmetic = 6 * 256^3
+ *   times the enclosed volume in voxels (exact; the same wherever a closed mesh lies); *area = the sum of 1/2 |((b - a) o s) x
+ *   ((c - a) o s)| in double with the per-axis scale s (spacing / 256), summed in a fixed order.
+ * SIZING: both output pointers NULL is a counting call: only *info_host is filled, return 0.  A capacity (in vertices / triangles)
+ *   that is too small returns SVR_MESH_ERR_CAPACITY with *info_host filled and nothing written to the outputs.
+ * INFO: bbox_min / bbox_max = the inclusive bounds of the vertex coordinates after relaxation (256 (n + 2) per axis and -1 for an
+ *   empty mesh, which has status SVR_REGION_STATUS_EMPTY and return 0).
+ * svr_mesh_positions (plain host code): float32 positions of `nv` host vertices.  volume_or_null == NULL: millimetres, (u / 256 - 1 +
+ *   0.5) * spacing.  With a volume: world coordinates by the sampler's mapping that svr_region_seed_from_world documents -- sample x
+ *   sits at texture coordinate (x + 0.5) / nx of the unclipped box, i.e. at bbox.vmin + (u / 256 - 0.5) * volume->spacing; `spacing` is
+ *   then not looked at and may be NULL.  Evaluated in double, rounded once.
+ * All device calls run on the library's stream and synchronise it.  REFUSED, before the device is touched and with nothing written: a
+ *   null pointer (-4); a dimension <= 0 or above SVR_MESH_MAX_DIM, or more than 2^31 cells (-6); level 0 or above 65535, relax above
+ *   SVR_MESH_MAX_RELAX, exactly one output pointer NULL, a spacing or scale that is not positive and finite (-3).  A mesh of more than
+ *   2^32 / 3 vertices or 2^31 quads is refused (-6) after the classify pass; svr_mesh_measure refuses a triangle that names a vertex >= nv (-3). */
+#define SVR_MESH_MAX_RELAX 64
+#define SVR_MESH_MAX_DIM 8388606         /* 256 (n + 2) <= 2^31 */
+#define SVR_MESH_ERR_CAPACITY (-11)      /* an output array is too small: info holds the sizes, nothing was written */
+
+typedef struct svr_mesh_params {     /* 8 bytes */
+    uint32_t level;                  /* 1 .. 65535; ignored for a mask */
+    uint32_t relax;                  /* 0 .. SVR_MESH_MAX_RELAX */
+} svr_mesh_params;
+
+typedef struct svr_mesh_info {       /* 56 bytes */
+    uint64_t vertices, quads, triangles;
+    int32_t  bbox_min[3], bbox_max[3];
+    int32_t  status;                 /* SVR_REGION_STATUS_* */
+    uint32_t _pad;
+} svr_mesh_info;
+
+int svr_mesh_params_default(svr_mesh_params* p);                     /* level 32768, relax 0.  Plain host code */
+/* voxels: host, or device with src_is_device = 1.  vertices_xyz_device: 3 int32 per vertex; triangles_device: 3 uint32 per triangle */
+int svr_mesh_isosurface(const uint16_t* voxels,
+                        int nx, int ny, int nz, int src_is_device, const svr_mesh_params* params, int32_t* vertices_xyz_device,
+                        uint64_t vertex_capacity, uint32_t* triangles_device, uint64_t triangle_capacity, svr_mesh_info* info_host);
+int svr_mesh_region(const uint32_t* mask_device,
+                    int nx, int ny, int nz, const svr_mesh_params* params, int32_t* vertices_xyz_device, uint64_t vertex_capacity,
+                    uint32_t* triangles_device, uint64_t triangle_capacity, svr_mesh_info* info_host);
+int svr_mesh_measure(const int32_t* vertices_device, uint64_t nv, const uint32_t* triangles_device, uint64_t nt, const double scale[3],
+                     int64_t* volume6_units, double* area);
+int svr_mesh_positions(const int32_t* vertices_host, uint64_t nv, const double spacing[3], const svr_volume* volume_or_null, float* xyz_host);
+/* HIP-event times of the phases of the last svr_mesh_isosurface / _region: classify (with the scans), emit, relax (0 for a phase that
+ * did not run).  Pointers may be NULL */
+int svr_mesh_last_ms(float* classify_ms, float* emit_ms, float* relax_ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

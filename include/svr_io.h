@@ -107,6 +107,16 @@ int svr_load_env_map(const char* path, svr_environment_light* env);
 int svr_tga_write(const char* path, int w, int h, const uint8_t* rgba);
 int svr_tga_encode(int w, int h, const uint8_t* rgba, uint8_t* dst, size_t capacity, size_t* size);
 
+/* ---- surface meshes: binary STL and PLY ---------------------------------------------------------- */
+/* Host arrays: xyz = 3 float32 per vertex (svr_mesh_positions), triangles = 3 uint32 per triangle (svr_mesh_isosurface / _region).
+ * svr_stl_write: binary STL -- an 80-byte header, the uint32 triangle count, then per triangle the float32 facet normal (the normalised
+ *   (b - a) x (c - a) in float32, or 0 0 0 for a degenerate facet), the three vertices and a uint16 0: 84 + 50 nt bytes.
+ * svr_ply_write: binary little-endian PLY 1.0 -- "property float x / y / z" vertices and "property list uchar uint vertex_indices"
+ *   faces of 3; it keeps the shared vertices.
+ * Both refuse a null argument (-4) and an index >= nv (-3) before the file is opened, and report I/O failures like svr_tga_write (-20). */
+int svr_stl_write(const char* path, const float* xyz, uint64_t nv, const uint32_t* triangles, uint64_t nt);
+int svr_ply_write(const char* path, const float* xyz, uint64_t nv, const uint32_t* triangles, uint64_t nt);
+
 #ifdef __cplusplus
 }
 #endif

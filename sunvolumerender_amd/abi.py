@@ -321,6 +321,24 @@ OVERLAY_MAX_PALETTE = 256
 OVERLAY_DEFAULT_PALETTE = 12
 
 
+class MeshParams(C.Structure):  # svr_mesh_params
+    _fields_ = [("level", C.c_uint32), ("relax", C.c_uint32)]
+
+
+class MeshInfo(C.Structure):  # svr_mesh_info
+    _fields_ = [("vertices", C.c_uint64), ("quads", C.c_uint64), ("triangles", C.c_uint64), ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3),
+                ("status", C.c_int32), ("_pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n.startswith("bbox") else int(getattr(self, n))) for n, _ in self._fields_ if n != "_pad"}
+
+
+svr_mesh_params, svr_mesh_info = MeshParams, MeshInfo
+MESH_MAX_RELAX = 64
+MESH_MAX_DIM = 8388606
+MESH_ERR_CAPACITY = -11
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -345,6 +363,8 @@ EXPECTED_SIZES = {
     RegionComponent: 40,
     OverlaySource: 16,
     OverlayStyle: 24,
+    MeshParams: 8,
+    MeshInfo: 56,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -530,6 +550,13 @@ PROTOTYPES = {
     "svr_overlay_slice": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,
                                     C.c_float, _P(OverlaySource), _P(OverlayStyle)]),
     "svr_overlay_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_mesh_params_default": (C.c_int, [_P(MeshParams)]),
+    "svr_mesh_isosurface": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(MeshParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                      _P(MeshInfo)]),
+    "svr_mesh_region": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(MeshParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _P(MeshInfo)]),
+    "svr_mesh_measure": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _P(C.c_double), _P(C.c_int64), _P(C.c_double)]),
+    "svr_mesh_positions": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_double), _P(cudaVolume), C.c_void_p]),
+    "svr_mesh_last_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),
@@ -550,6 +577,8 @@ PROTOTYPES = {
     "svr_load_env_map": (C.c_int, [C.c_char_p, _P(cudaEnvironmentLight)]),
     "svr_tga_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p]),
     "svr_tga_encode": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "svr_stl_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "svr_ply_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
 }
 
 _lib = None

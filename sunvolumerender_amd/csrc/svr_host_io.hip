@@ -524,4 +524,66 @@ int svr_tga_write(const char* path, int w, int h, const uint8_t* rgba)
     return ok ? 0 : failf(-20, "short write to %s", path);
 }
 
+// ---- surface meshes: binary STL and PLY ----
+static int check_mesh_arrays(const char* who, const char* path, const float* xyz, uint64_t nv, const uint32_t* triangles, uint64_t nt)
+{
+    if (!path || (nv && !xyz) || (nt && !triangles)) return failf(-4, "%s: null argument", who);
+    if (nt > 0xffffffffull) return failf(-3, "%s: %llu triangles do not fit the format's 32-bit count", who, (unsigned long long)nt);
+    for (uint64_t i = 0; i < 3 * nt; ++i)
+        if (triangles[i] >= nv)
+            return failf(-3, "%s: triangle %llu names vertex %u of %llu", who, (unsigned long long)(i / 3), triangles[i], (unsigned long long)nv);
+    return 0;
+}
+
+static int write_mesh_file(const char* path, const std::vector<uint8_t>& head, const std::vector<uint8_t>& body, const std::vector<uint8_t>& tail)
+{
+    FILE* f = fopen(path, "wb");
+    if (!f) return failf(-20, "unable to open %s for writing (%s)", path, strerror(errno));
+    bool ok = true;
+    for (const std::vector<uint8_t>* part : {&head, &body, &tail})
+        ok = ok && (part->empty() || fwrite(part->data(), 1, part->size(), f) == part->size());
+    ok = (fclose(f) == 0) && ok;
+    return ok ? 0 : failf(-20, "short write to %s", path);
+}
+
+int svr_stl_write(const char* path, const float* xyz, uint64_t nv, const uint32_t* triangles, uint64_t nt)
+{
+    if (int e = check_mesh_arrays("svr_stl_write", path, xyz, nv, triangles, nt)) return e;
+    std::vector<uint8_t> head(84, 0), body((size_t)nt * 50, 0);
+    const char title[] = "binary STL, sunvolumerender surface mesh";     // (must not begin with "solid")
+    memcpy(head.data(), title, sizeof title - 1);
+    const uint32_t count = (uint32_t)nt;
+    memcpy(head.data() + 80, &count, 4);
+    for (uint64_t t = 0; t < nt; ++t) {
+        const float *a = xyz + 3 * (size_t)triangles[3 * t], *b = xyz + 3 * (size_t)triangles[3 * t + 1], *c = xyz + 3 * (size_t)triangles[3 * t + 2];
+        const float u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, w[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        float n[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
+        const float len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        for (int k = 0; k < 3; ++k) n[k] = (len > 0.f && std::isfinite(len)) ? n[k] / len : 0.f;
+        uint8_t* o = body.data() + (size_t)t * 50;
+        memcpy(o, n, 12);
+        memcpy(o + 12, a, 12);
+        memcpy(o + 24, b, 12);
+        memcpy(o + 36, c, 12);
+    }
+    return write_mesh_file(path, head, body, {});
+}
+
+int svr_ply_write(const char* path, const float* xyz, uint64_t nv, const uint32_t* triangles, uint64_t nt)
+{
+    if (int e = check_mesh_arrays("svr_ply_write", path, xyz, nv, triangles, nt)) return e;
+    char text[320];
+    const int n = snprintf(text, sizeof text,
+                           "ply\nformat binary_little_endian 1.0\ncomment sunvolumerender surface mesh\nelement vertex %llu\nproperty float x\nproperty float y\n"
+                           "property float z\nelement face %llu\nproperty list uchar uint vertex_indices\nend_header\n",
+                           (unsigned long long)nv, (unsigned long long)nt);
+    std::vector<uint8_t> head(text, text + n), body((size_t)nv * 12), tail((size_t)nt * 13);
+    if (nv) memcpy(body.data(), xyz, (size_t)nv * 12);
+    for (uint64_t t = 0; t < nt; ++t) {
+        tail[(size_t)t * 13] = 3;
+        memcpy(tail.data() + (size_t)t * 13 + 1, triangles + 3 * t, 12);
+    }
+    return write_mesh_file(path, head, body, tail);
+}
+
 } // extern "C"

@@ -17,7 +17,7 @@
 //     displaced shows that the higher one was no longer a root, go on with (that value, the lower root).
 //   k_label_flatten one thread per mask word: L[start] = root(start) for every run; a start that is its own root sets its bit in the
 //     root mask (mask layout), and the word's popcount goes to the scan array.
-//   k_scan_block / k_scan_add: exclusive scan of the popcounts, SVR_LABEL_SCAN_BLOCK words per block, one launch per level up and one
+//   k_scan_block / k_scan_add (svr_scan.hpp): exclusive scan of the popcounts, SVR_LABEL_SCAN_BLOCK words per block, one launch per level up and one
 //     per level down; the block totals of a level are the next level's input, the top level is one word: K.
 //   k_label_renumber one lane per voxel, 32 lanes per mask word: the lane of a run's start reads the root r and computes the label =
 //     scan[word of r] + popcount(root bits of that word below r's bit) + 1; the other lanes of the run take it by a wave shuffle;
@@ -45,6 +45,7 @@
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
 #include "svr_mask.hpp"             // RegionDims, valid_bits, half_ballot, the grids
+#include "svr_scan.hpp"             // k_scan_block, k_scan_add
 #include "svr_volume_host.hpp"
 
 using svr::failf;
@@ -54,7 +55,7 @@ using svr::failf;
 namespace {
 
 constexpr int THREADS = MASK_THREADS;
-static_assert(SVR_LABEL_SCAN_BLOCK == THREADS, "k_scan_block scans one word per thread");
+static_assert(SVR_LABEL_SCAN_BLOCK == SCAN_BLOCK, "k_scan_block scans one word per thread");
 static_assert(sizeof(svr_region_component) == 40, "svr_region_component is 40 bytes");
 
 struct LabelBox { int x0, y0, z0, x1, y1, z1; };          // inclusive
@@ -262,32 +263,6 @@ __global__ __launch_bounds__(THREADS) void k_label_flatten(const uint32_t* __res
 }
 #endif
 
-// exclusive scan of SVR_LABEL_SCAN_BLOCK words per block, in place; the block's total goes to sums[block]
-__global__ __launch_bounds__(THREADS) void k_scan_block(uint32_t* __restrict__ data, size_t n, uint32_t* __restrict__ sums)
-{
-    __shared__ uint32_t s[2][THREADS];
-    const int tid = threadIdx.x;
-    const size_t i = (size_t)blockIdx.x * THREADS + tid;
-    const uint32_t v = i < n ? data[i] : 0u;
-    s[0][tid] = v;
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (int off = 1; off < THREADS; off <<= 1) {
-        s[cur ^ 1][tid] = s[cur][tid] + (tid >= off ? s[cur][tid - off] : 0u);
-        cur ^= 1;
-        __syncthreads();
-    }
-    if (i < n) data[i] = s[cur][tid] - v;
-    if (tid == THREADS - 1) sums[blockIdx.x] = s[cur][tid];
-}
-
-__global__ __launch_bounds__(THREADS) void k_scan_add(uint32_t* __restrict__ data, size_t n, const uint32_t* __restrict__ sums)
-{
-    const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
-    if (i < n) data[i] += sums[blockIdx.x];
-}
-
 // A lane of the kernels below: bit `bit` of mask word i.  This file keeps its own form of svr_mask.hpp's lane_at: with the shared one
 // k_label_threshold and k_label_table<> came out with another instruction order (the same instructions and register counts), and the
 // device code of these files is pinned (tools/kernel_asm_digest.py).
@@ -476,18 +451,13 @@ int svr_region_label(const uint32_t* in_mask_device, int nx, int ny, int nz, int
     const size_t words = mask_words(d);
     const uint32_t cap = (uint32_t)((size_t)nx * ny * nz);   // no chain is longer than the voxel count (<= 2^31)
     // the scan's levels: words, blocks of words, blocks of blocks, ... , 1 (the total)
-    std::vector<size_t> level{words};
-    do level.push_back((level.back() + SVR_LABEL_SCAN_BLOCK - 1) / SVR_LABEL_SCAN_BLOCK); while (level.back() > 1);
-    size_t scan_words = 0;
-    for (size_t n : level) scan_words += n;
+    ScanLevels scan(words);
     DeviceBuffer buf;                                    // the root mask, the scan levels, the error word
-    SVR_HIP_TRY(buf.alloc((words + scan_words + 1) * sizeof(uint32_t)));
+    SVR_HIP_TRY(buf.alloc((words + scan.words() + 1) * sizeof(uint32_t)));
     CallTimer timer(g_events, st);                        // (the launches, not the allocation)
     uint32_t* roots = buf.as<uint32_t>();
-    std::vector<uint32_t*> lv(level.size());
-    lv[0] = roots + words;
-    for (size_t j = 1; j < level.size(); ++j) lv[j] = lv[j - 1] + level[j - 1];
-    uint32_t* d_err = lv.back() + 1;
+    scan.place(roots + words);
+    uint32_t* d_err = scan.total() + 1;
     SVR_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(uint32_t), st));
     const dim3 wg = word_grid(words), b(THREADS);
     hipLaunchKernelGGL(k_label_init, wg, b, 0, st, in_mask_device, labels_device, d, words);
@@ -499,17 +469,14 @@ int svr_region_label(const uint32_t* in_mask_device, int nx, int ny, int nz, int
     if (connectivity == 6) hipLaunchKernelGGL((k_label_union<6>), ug, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err);
     else if (connectivity == 18) hipLaunchKernelGGL((k_label_union<18>), ug, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err);
     else hipLaunchKernelGGL((k_label_union<26>), ug, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err);
-    hipLaunchKernelGGL(k_label_flatten, wg, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err, roots, lv[0]);
+    hipLaunchKernelGGL(k_label_flatten, wg, b, 0, st, in_mask_device, labels_device, d, words, cap, d_err, roots, scan.at[0]);
     SVR_HIP_TRY(hipGetLastError());
-    for (size_t j = 0; j + 1 < level.size(); ++j)
-        hipLaunchKernelGGL(k_scan_block, word_grid(level[j]), b, 0, st, lv[j], level[j], lv[j + 1]);
-    for (size_t j = level.size() - 2; j-- > 0;)          // (the top level that was scanned is one block: nothing to add to it)
-        hipLaunchKernelGGL(k_scan_add, word_grid(level[j]), b, 0, st, lv[j], level[j], lv[j + 1]);
-    hipLaunchKernelGGL(k_label_renumber, lane_grid(words), b, 0, st, in_mask_device, labels_device, d, words, roots, lv[0]);
+    SVR_HIP_TRY(scan.run(st));
+    hipLaunchKernelGGL(k_label_renumber, lane_grid(words), b, 0, st, in_mask_device, labels_device, d, words, roots, scan.at[0]);
     SVR_HIP_TRY(hipGetLastError());
     timer.stop();
     uint32_t back[2] = {0u, 0u};                          // the total, the error word (adjacent)
-    SVR_HIP_TRY(hipMemcpyAsync(back, lv.back(), sizeof back, hipMemcpyDeviceToHost, st));
+    SVR_HIP_TRY(hipMemcpyAsync(back, scan.total(), sizeof back, hipMemcpyDeviceToHost, st));
     SVR_HIP_TRY(hipStreamSynchronize(st));                // (buf is freed on return)
     if (back[1]) return failf(SVR_REGION_ERR_LABEL, "%s: a union-find walk reached its iteration cap (%u; flags %u); the labels are not valid", who, cap, back[1]);
     *count_out = back[0];

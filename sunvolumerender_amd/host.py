@@ -806,6 +806,80 @@ class Device:
         self.check(self.lib.svr_overlay_last_ms(C.byref(ms)))
         return float(ms.value)
 
+    # ---- surface meshes by surface nets (svr_mesh_isosurface / _region / _measure / _positions) ----
+    def mesh_params(self, level: Optional[int] = None, relax: int = 0) -> abi.MeshParams:
+        p = abi.MeshParams()
+        self.check(self.lib.svr_mesh_params_default(C.byref(p)))
+        if level is not None:
+            p.level = int(level)
+        p.relax = int(relax)
+        return p
+
+    def _mesh_extract(self, call):
+        """A counting call, then an extraction call into buffers of the counted size.  call(vertices pointer, vertex capacity, triangles
+        pointer, triangle capacity, info) runs the C function.  Returns (vertices int32 [nv, 3], triangles uint32 [nt, 3], info)."""
+        info = abi.MeshInfo()
+        self.check(call(None, 0, None, 0, info))
+        nv, nt = int(info.vertices), int(info.triangles)
+        if nv == 0:
+            return np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint32), info
+        buf = self.malloc(12 * (nv + max(nt, 1)))
+        try:
+            self.check(call(C.c_void_p(buf), nv, C.c_void_p(buf + 12 * nv), nt, info))
+            return self.to_host(buf, (nv, 3), np.int32), self.to_host(buf + 12 * nv, (nt, 3), np.uint32), info
+        finally:
+            self.free(buf)
+
+    def mesh_isosurface(self, vox, level: int, relax: int = 0, shape=None):
+        """svr_mesh_isosurface: the surface-nets mesh of {v >= level} of a host [nz][ny][nx] u16 array or a device pointer with
+        shape=(nz, ny, nx), after `relax` constrained relaxation steps.  Returns (vertices, triangles, info): int32 [nv, 3] in units of
+        1/256 voxel on the padded grid (sample x sits at 256 (x + 1)), uint32 [nt, 3], and the svr_mesh_info."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        p = self.mesh_params(level, relax)
+        return self._mesh_extract(lambda v, nv, t, nt, info: self.lib.svr_mesh_isosurface(src, nx, ny, nz, on_dev, C.byref(p), v, nv, t, nt, C.byref(info)))
+
+    def mesh_region(self, mask, relax: int = 0, shape=None):
+        """svr_mesh_region: the same for a region mask (a bool array [nz][ny][nx], or a device pointer to the bit mask with shape=)."""
+        if isinstance(mask, np.ndarray):
+            shape = mask.shape
+        if shape is None:
+            raise ValueError("a device mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = (int(n) for n in shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        p = self.mesh_params(None, relax)
+        try:
+            return self._mesh_extract(lambda v, nv, t, nt, info: self.lib.svr_mesh_region(C.c_void_p(buf), nx, ny, nz, C.byref(p), v, nv, t, nt, C.byref(info)))
+        finally:
+            if owned:
+                self.free(buf)
+
+    def mesh_measure(self, vertices, triangles, scale=(1.0 / 256, 1.0 / 256, 1.0 / 256)):
+        """svr_mesh_measure of host arrays (uploaded): (volume6, area) -- the exact integer 6 * 256^3 * (enclosed volume in voxels) and the
+        surface area under the per-axis scale (spacing / 256)."""
+        v = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        s = (C.c_double * 3)(*[float(x) for x in scale])
+        vol, area = C.c_int64(0), C.c_double(0.0)
+        buf = self.malloc(max(v.nbytes, 4) + max(t.nbytes, 4))
+        try:
+            if len(v):
+                self.to_device(buf, v)
+            if len(t):
+                self.to_device(buf + max(v.nbytes, 4), t)
+            self.check(self.lib.svr_mesh_measure(C.c_void_p(buf), len(v), C.c_void_p(buf + max(v.nbytes, 4)), len(t), s, C.byref(vol), C.byref(area)))
+        finally:
+            self.free(buf)
+        return int(vol.value), float(area.value)
+
+    def mesh_positions(self, vertices, spacing=(1.0, 1.0, 1.0), volume: Optional[cudaVolume] = None) -> np.ndarray:
+        return mesh_positions(self.lib, vertices, spacing, volume)
+
+    def mesh_last_ms(self):
+        """(classify, emit, relax) HIP-event milliseconds of the last mesh call"""
+        ms = [C.c_float(0.0) for _ in range(3)]
+        self.check(self.lib.svr_mesh_last_ms(*[C.byref(m) for m in ms]))
+        return tuple(float(m.value) for m in ms)
+
     # ---- exact volume filters (svr_volume_*): median / min / max and binomial smoothing of the raw voxels ----
     def volume_rank(self, vox, op: int, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
         """svr_volume_rank: the median (FILTER_MEDIAN), minimum (FILTER_MIN) or maximum (FILTER_MAX) of every voxel's window under the
@@ -867,6 +941,22 @@ def region_label_scan_levels(shape) -> int:
     while n > LABEL_SCAN_BLOCK:
         n, levels = (n + LABEL_SCAN_BLOCK - 1) // LABEL_SCAN_BLOCK, levels + 1
     return levels
+
+
+def mesh_positions(lib, vertices, spacing=(1.0, 1.0, 1.0), volume=None) -> np.ndarray:
+    """svr_mesh_positions: float32 [nv, 3] positions of mesh vertices (int32 [nv, 3], 1/256 voxel on the padded grid) -- millimetres,
+    (u / 256 - 0.5) * spacing, or with `volume` (a cudaVolume) the world coordinates of the sampler's mapping.  Host code of the library:
+    no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    v = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1, 3)
+    out = np.zeros((len(v), 3), dtype=np.float32)
+    sp = (C.c_double * 3)(*[float(t) for t in spacing])
+    rc = lib.svr_mesh_positions(v.ctypes.data_as(C.c_void_p), len(v), sp, C.byref(volume) if volume is not None else None, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        msg = lib.svr_last_error().decode()
+        lib.svr_clear_error()
+        raise SvrError(f"svr_mesh_positions failed ({rc}): {msg}")
+    return out
 
 
 def distance_weights(spacing, shape, lib=None):
@@ -1349,6 +1439,42 @@ class Canvas:
             self.dev.free(buf)
             if owned is not None:
                 self.dev.free(owned)
+
+    # ---- extension: surface meshes of regions and isosurfaces (svr_mesh_*; io.write_stl / write_ply) ----
+    def _set_surface(self, mesh):
+        self.surfaceVertices, self.surfaceTriangles, self.surfaceInfo = mesh
+        return self.surfaceInfo
+
+    def ExtractRegionSurface(self, mask, relax: int = 0) -> abi.MeshInfo:
+        """The surface of a region of the loaded volume (a bool array [nz][ny][nx] or the device pointer of its bit mask) after `relax`
+        relaxation steps; the canvas keeps the mesh for SaveSurface / SurfaceMeasure.  Returns the svr_mesh_info."""
+        if not self.ready:
+            raise SvrError("a surface needs a loaded volume")
+        nx, ny, nz = self.volumeDim
+        return self._set_surface(self.dev.mesh_region(mask, relax, shape=(nz, ny, nx)))
+
+    def ExtractIsoSurface(self, vox, level: int, relax: int = 0) -> abi.MeshInfo:
+        """The isosurface {v >= level} of the raw u16 voxels of the loaded volume (a host array [nz][ny][nx] or a device pointer)."""
+        if not self.ready:
+            raise SvrError("a surface needs a loaded volume")
+        nx, ny, nz = self.volumeDim
+        return self._set_surface(self.dev.mesh_isosurface(vox, level, relax, shape=(nz, ny, nx)))
+
+    def SaveSurface(self, filename: str):
+        """Writes the extracted surface in world coordinates: binary STL, or binary PLY for a name that ends in .ply."""
+        from .io import write_ply, write_stl
+        if getattr(self, "surfaceInfo", None) is None:
+            raise SvrError("SaveSurface before ExtractRegionSurface / ExtractIsoSurface")
+        xyz = mesh_positions(self.lib, self.surfaceVertices, volume=self.deviceVolume)
+        (write_ply if str(filename).lower().endswith(".ply") else write_stl)(self.dev, filename, xyz, self.surfaceTriangles)
+
+    def SurfaceMeasure(self):
+        """(volume, area) of the extracted surface in the volume's units (mm^3, mm^2): the enclosed volume is exact up to its last rounding."""
+        if getattr(self, "surfaceInfo", None) is None:
+            raise SvrError("SurfaceMeasure before ExtractRegionSurface / ExtractIsoSurface")
+        sp = [float(self.deviceVolume.spacing.x), float(self.deviceVolume.spacing.y), float(self.deviceVolume.spacing.z)]
+        vol6, area = self.dev.mesh_measure(self.surfaceVertices, self.surfaceTriangles, [t / 256.0 for t in sp])
+        return vol6 / (6.0 * 256.0 ** 3) * sp[0] * sp[1] * sp[2], area
 
     # ---- extension: denoised preview of the first frames after a restart ----
     def SetDenoisePreview(self, frames: int, params: Optional[abi.DenoiseParams] = None):

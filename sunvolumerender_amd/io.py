@@ -217,3 +217,19 @@ def tga_encode(dev, img: np.ndarray) -> bytes:
 def save_tga(dev, filename: str, img: np.ndarray):
     a = np.ascontiguousarray(img, dtype=np.uint8)
     dev.check(dev.lib.svr_tga_write(str(filename).encode(), a.shape[1], a.shape[0], a.ctypes.data_as(C.c_void_p)))
+
+
+def _write_mesh(dev, fn, filename: str, xyz: np.ndarray, triangles: np.ndarray):
+    v = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    dev.check(fn(str(filename).encode(), v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t)))
+
+
+def write_stl(dev, filename: str, xyz: np.ndarray, triangles: np.ndarray):
+    """svr_stl_write: binary STL of float32 positions [nv, 3] (host.mesh_positions) and uint32 triangles [nt, 3]."""
+    _write_mesh(dev, dev.lib.svr_stl_write, filename, xyz, triangles)
+
+
+def write_ply(dev, filename: str, xyz: np.ndarray, triangles: np.ndarray):
+    """svr_ply_write: binary little-endian PLY of the same arrays; it keeps the shared vertices."""
+    _write_mesh(dev, dev.lib.svr_ply_write, filename, xyz, triangles)
