@@ -154,7 +154,7 @@ void svr_clear_error(void);
 #define SVR_LAYOUT_CELL 4            /* the same bricks with 16-byte elements: the 8 voxels of a trilinear cell -- one 16-byte load per fetch, one
                                      * sector instead of four; 8 x the memory of the u16 volume (2.2 GB for 512^3, 17 GB for 1024^3); 32-bit element
                                      * index, 64-bit byte offsets.  What AUTO picks FIRST (then PAIR, then BRICK, then LINEAR: the next one when
-                                     * the addressing limits or hipErrorOutOfMemory rule one out; csrc/svr_api.hip, create_volume_texture) */
+                                     * the addressing limits or hipErrorOutOfMemory rule one out; csrc/svr_api_texture.hip, create_volume_texture) */
 uint64_t svr_create_volume_texture(const uint16_t* voxels, int nx, int ny, int nz,
                                    int src_is_device, int layout);
 /* gui/transferfunction.cpp:30-44 (1D float4 array, clamp / linear / normalized coords). */

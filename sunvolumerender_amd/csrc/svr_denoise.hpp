@@ -1,4 +1,4 @@
-// svr_denoise.hpp -- launch interface of the denoised preview (svr_denoise.hip) for the C-ABI layer (svr_api.hip).
+// svr_denoise.hpp -- launch interface of the denoised preview (svr_denoise.hip) for the C-ABI layer (svr_api_converge.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "svr_scene.hpp"

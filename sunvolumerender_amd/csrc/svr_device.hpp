@@ -403,7 +403,7 @@ SVR_DEV int nearest_light(const DevScene& s, v3 orig, v3 dir, float& tHit)
     float t = SVR_FLT_MAX;
     int id = -1;
     for (uint32_t i = 0; i < s.num_lights; ++i) {
-        // (lights no camera ray can reach -- outside the view frustum, lens included: svr_api.hip -- cannot change the result)
+        // (lights no camera ray can reach -- outside the view frustum, lens included: svr_api_scene.hip -- cannot change the result)
         if (!((s.primary_light_mask >> i) & 1u)) continue;
         if (disk_intersect(s.lights[i], orig, dir, t) && (t < tNear)) {
             tNear = t;

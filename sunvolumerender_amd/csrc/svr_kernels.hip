@@ -528,7 +528,7 @@ hipError_t launch_pathtrace(const DevScene& s, const DevWork& w, const LaunchCfg
     });
 }
 
-// The resolve of ONE frame over the WHOLE image -- what a render_pathtracer call does when its frame was traced ahead (svr_api.hip) -- beside
+// The resolve of ONE frame over the WHOLE image -- what a render_pathtracer call does when its frame was traced ahead (svr_api_trace.hip) -- beside
 // a persistent trace kernel that holds every CU: the queue builds of the tile kernel leave 32 VGPRs per SIMD free, so a resolve wave is
 // resident only if it needs <= 32 registers, and then there is ONE of it per SIMD (k_resolve, 18 registers, one pixel per lane: 12 + 12
 // bytes in flight per lane, 150 us per frame measured inside a trace launch).  The running mean does not care about channels, so it runs

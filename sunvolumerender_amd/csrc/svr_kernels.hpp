@@ -1,4 +1,4 @@
-// svr_kernels.hpp -- launch interface between the C-ABI layer (svr_api.hip) and the
+// svr_kernels.hpp -- launch interface between the C-ABI layer (svr_api.hip, svr_api_*.hip) and the
 // gfx950 kernels (svr_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,11 +48,11 @@ struct DrainShape {
 constexpr uint32_t QUEUE_TASKS_MAX = QUEUE_TASKS_D1 > QUEUE_TASKS ? QUEUE_TASKS_D1 : QUEUE_TASKS;
 constexpr uint32_t QUEUE_CAP_MAX = QUEUE_CAP_D1 > QUEUE_CAP ? QUEUE_CAP_D1 : QUEUE_CAP;
 constexpr uint32_t TILE_WAVES = 16;
-// the allocation (svr_api.hip, ensure_record_queues) holds the largest form; every kernel strides its waves' slices by its own shape
+// the allocation (svr_api_trace.hip, ensure_record_queues) holds the largest form; every kernel strides its waves' slices by its own shape
 constexpr size_t QUEUE_WORDS_PER_BLOCK = (size_t)REC_WORDS * QUEUE_CAP_MAX * TILE_WAVES;
 constexpr size_t PEND_FLOATS_PER_BLOCK = (size_t)QUEUE_TASKS_MAX * 3 * 64 * TILE_WAVES;
 static_assert(QUEUE_TASKS <= QUEUE_TASKS_LIMIT && QUEUE_TASKS_D1 <= QUEUE_TASKS_LIMIT, "a pending task's index has 6 bits in a record's id");
-// AUTO rule of the queue builds (svr_api.hip, plan_launch): tasks per wave from which they pay = 4 drains of the base 32 tasks
+// AUTO rule of the queue builds (svr_api_trace.hip, plan_launch): tasks per wave from which they pay = 4 drains of the base 32 tasks
 constexpr uint32_t QUEUE_AUTO_TASKS_PER_WAVE = 128;
 // Bound classes (svr_accel.hip, k_bound_class): 4 bits per half-resolution macro-cell = smallest class c whose threshold
 // BOUND_THR(c) is >= (largest transfer-function alpha any fetch in the cell can return) x invSigmaMax.

@@ -42,7 +42,7 @@ enum { PH_TICKET = PH_N + 1, PH_LOOP, PH_FIRST, PH_END_ALL };
 // ... and what the shared whole-ray march did for the tasks (svr_walk.hpp, MarchDid): marched for the pair, reused, refused, marched for the pixel alone
 enum { PROF_SHADOW_WALKS = 2 * PH_END_ALL, PROF_RECORDS, PROF_MARCH };
 constexpr uint32_t PROF_WORDS = 2 * PH_END_ALL + 6;
-static_assert(PROF_WORDS <= 32u, "the debug words behind the counters (svr_api.hip, DEBUG_WORDS)");
+static_assert(PROF_WORDS <= 32u, "the debug words behind the counters (svr_api_state.hpp, DEBUG_WORDS)");
 #ifdef SVR_TEST_HOOKS
 #define SVR_PROF 1
 struct ProfScope {

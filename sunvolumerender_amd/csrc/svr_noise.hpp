@@ -1,4 +1,4 @@
-// svr_noise.hpp -- launch interface of the noise estimate of progressive renders (svr_noise.hip) for the C-ABI layer (svr_api.hip).
+// svr_noise.hpp -- launch interface of the noise estimate of progressive renders (svr_noise.hip) for the C-ABI layer (svr_api_converge.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

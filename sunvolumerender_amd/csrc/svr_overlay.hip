@@ -234,7 +234,7 @@ int check_source(const char* who, const svr_volume* volume, int nx, int ny, int 
     return 0;
 }
 
-// The geometry of a slice call: the checks svr_render_slice_stack (svr_api.hip) makes on center, u, v, thickness, step, count and spacing,
+// The geometry of a slice call: the checks svr_render_slice_stack (svr_api_views.hip) makes on center, u, v, thickness, step, count and spacing,
 // in its order, and its FRAME and BOX.  mode, flags and the window are not looked at.
 int check_slice(const char* who, const svr_volume& vol, uint32_t w, uint32_t h, const svr_slice_params* p, uint32_t count, float spacing, svr::OvSlice& sl)
 {

@@ -270,7 +270,7 @@ SVR_DEV void fold_pending_groups(const DevScene& s, const DevWork& w, const floa
     }
 }
 
-// Launches that do NOT fold (frames traced ahead of the calls that ask for them, svr_api.hip: k_resolve / k_mean_flat fold one scratch slot
+// Launches that do NOT fold (frames traced ahead of the calls that ask for them, svr_api_trace.hip: k_resolve / k_mean_flat fold one scratch slot
 // per call): the radiance of the path with id = (pending task << 6 | lane) of this wave goes straight to lbuf[frame slot][pixel].
 // tasks: the wave's pending task numbers (LDS).
 SVR_DEV void direct_put(const DevScene& s, const DevWork& w, const uint32_t* tasks, uint32_t id, v3 L)

@@ -164,7 +164,7 @@ constexpr uint32_t PEND_TASKS = 4;
 constexpr uint32_t PEND_ROW = 65;
 // QUEUE builds keep the radiance of the last TASKS tasks in a per-wave buffer in global memory instead (rows of 64
 // floats; written and read back once by the same wave), and up to CAP path records per wave.  TASKS and CAP are the
-// build's DrainShape (svr_kernels.hpp, shared with the allocation in svr_api.hip): 64 tasks and 1024 records in the skipping
+// build's DrainShape (svr_kernels.hpp, shared with the allocation in svr_api_trace.hip): 64 tasks and 1024 records in the skipping
 // traceDepth-1 builds without pooled walks, 32 and 1024 in every other build
 static_assert(TILE_WAVES == SVR_TILE_THREADS / 64, "svr_kernels.hpp sizes the queues for 16 waves per block");
 struct LdsPend {
@@ -603,7 +603,7 @@ static hipError_t launch_tile_t(const DevScene& s, const DevWork& w, const Launc
     // index of the task order, so a ticket of MARCH_BLOCK x fgroups tasks is a pair's pixels with all their groups, in one wave, in frame order -- the
     // fold needs that, and the kept march (its tag has no frame group) then serves 2 x fgroups tasks.  Any unit that is a multiple of fgroups is exact;
     // another one would hand the groups of a pixel to different waves, and tickets that own tile rows (row_order) are single tasks: both are refused, as
-    // is every other build, and the host cuts such calls into launches of 64 frames (svr_api.hip, fold_group_frames)
+    // is every other build, and the host cuts such calls into launches of 64 frames (svr_api_trace.hip, fold_group_frames)
     const bool wide_form = !SVR_TILE_LIST && queue && skip && d1 && !cfg.pool_primary && w2.frames_log2 == 6u && s.cam_pinhole && s.ray_skip;
     const uint32_t fgroups = (w.nframes + 63u) >> 6;
     if (many_groups && !(wide_form && !w.row_order)) return hipErrorInvalidValue;

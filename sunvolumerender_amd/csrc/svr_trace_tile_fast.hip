@@ -9,7 +9,7 @@
 #undef svr
 
 namespace svr_fast {
-// type-erased entry for svr_api.hip (its DevScene / DevWork / LaunchCfg are the layout-identical types of namespace svr)
+// type-erased entry for svr_api_trace.hip (its DevScene / DevWork / LaunchCfg are the layout-identical types of namespace svr)
 hipError_t launch_trace_tile_raw(const void* scene, const void* work, const void* cfg, hipStream_t st)
 {
     return launch_trace_tile(*static_cast<const DevScene*>(scene), *static_cast<const DevWork*>(work), *static_cast<const LaunchCfg*>(cfg), st);

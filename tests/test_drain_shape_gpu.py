@@ -133,7 +133,7 @@ def test_two_pixels_per_task_dead_frame_lanes(hip_dev):
 
 
 def test_direct_form_many_tasks(hip_dev):
-    """(3) the DIRECT form at the shape of (1).  Only frames traced AHEAD of per-frame calls run it (svr_api.hip, render_ahead: batches of
+    """(3) the DIRECT form at the shape of (1).  Only frames traced AHEAD of per-frame calls run it (svr_api_trace.hip, render_ahead: batches of
     16 frames and more, production build), so the calls are canvas.paint(): the batches are 1, 2, 4, 8 (straight-line), 16, 32 (DIRECT, four
     and two pixels per task, 20 and 40 tasks per wave), then 64 frames from frame 63 and from frame 127 (DIRECT,
     one pixel per task, 80 tasks per wave on average: full drains of 64 tasks, their records popped into the scratch slots, then partial

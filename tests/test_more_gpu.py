@@ -511,7 +511,7 @@ def test_fast_bound_table_bounds_every_fetch(hip_dev, name):
 
 def test_fast_bound_lookup_far_camera_falls_back(hip_dev):
     """The look-up's table covers one voxel of rounding error between its fma and the reference's float chain, which holds while the camera is
-    within 2^21 / (16 N) volume extents (svr_api.hip, ensure_mask); beyond, the kernel takes the exact cell again.  A camera 4 000 extents
+    within 2^21 / (16 N) volume extents (svr_api_scene.hip, ensure_mask); beyond, the kernel takes the exact cell again.  A camera 4 000 extents
     away looking at the volume through a very long lens: the oracle's image, and the executed fetches of the switch off."""
     base = scenes.make_scene("tiny_head_noisy", trace_depth=1)
     ext = max(host.volume_size(base.dim, base.spacing))

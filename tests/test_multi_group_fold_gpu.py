@@ -1,5 +1,5 @@
 """Folding launches of several groups of 64 frames (SVR_OPT_GROUP_FRAMES = 128 / 256; csrc/svr_trace_tile.hip launch_tile_t, csrc/svr_tile_tasks.hpp
-fold_pending_groups, csrc/svr_api.hip fold_group_frames): in the skipping traceDepth-1 queue builds without pooled walks a call of 128 frames and more is
+fold_pending_groups, csrc/svr_api_trace.hip fold_group_frames): in the skipping traceDepth-1 queue builds without pooled walks a call of 128 frames and more is
 ONE launch per 128 / 256 frames.  A ticket is a pixel pair x all its frame groups, the running mean of a pixel is replayed in frame order across its groups
 (chained where they are pending together, through the accumulator where a drain falls between them), and the kept whole-ray march of a pair -- its
 tag no longer names a frame group -- serves every group.  Scheduling only: image and accumulator are the oracle's bit for bit in the production and
