@@ -40,8 +40,14 @@
 // ExtractRegionSurface, SaveSurface: surface nets in world coordinates; -relax N smooths it by N = 0 .. 64 constrained relaxation
 // steps); -mesh-iso RAW FILE.stl|.ply writes the isosurface {raw value >= RAW} of the (filtered) voxels, with or without a region.  Each
 // prints "mesh: V vertices, T triangles, volume ... mm^3, area ... mm^2", the region's line first.
+// -crop X0 Y0 Z0 X1 Y1 Z1 (an inclusive voxel box, cut to the volume) and -resample MM [nearest|linear|area|auto] (the same spacing MM on
+// every axis, in the units of the file's spacing; auto = linear where the grid gets finer, area where it gets coarser) change the grid
+// right after the load, in command-line order (Canvas::CropVolume, ResampleVolume): everything after works on the new grid, drawn where
+// it lay in the loaded volume.  -save-volume F writes the (filtered) voxels, -save-mask F the final region as u8 0 / 1, -save-parts F
+// its connected parts (-conn) as a u32 label map, and -save-crop VOL MASK MARGIN the region's bounding box grown by MARGIN voxels, voxels
+// and mask, as MetaImage files (.mhd + .raw, or .mha).  Each prints one line with the dimensions, the spacing and the time.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -54,7 +60,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-median E N | -smooth SIGMA]... [-show-filtered] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -80,6 +86,10 @@ int main(int argc, char** argv)
     bool showFiltered = false;                                      // -show-filtered
     std::string meshFile, meshIsoFile;                              // -mesh FILE: the surface of the final region; -mesh-iso RAW FILE: the raw isosurface
     int meshRelax = -1, meshIsoLevel = 0;                           // -relax N (with -mesh): 0 .. SVR_MESH_MAX_RELAX relaxation steps
+    struct GridStep { bool crop; int32_t lo[3], hi[3]; double mm; int mode; };   // -crop X0 Y0 Z0 X1 Y1 Z1 or -resample MM [mode]
+    std::vector<GridStep> gridSteps;                                // applied right after the load, in command-line order
+    std::string saveVolumeFile, saveMaskFile, savePartsFile, saveCropVolume, saveCropMask;   // -save-volume / -save-mask / -save-parts F, -save-crop VOL MASK MARGIN
+    int saveCropMargin = 0;
     const auto meshName = [](const char* f) {                       // an export writes .stl or .ply
         const size_t n = strlen(f);
         return n > 4 && (!strcmp(f + n - 4, ".stl") || !strcmp(f + n - 4, ".ply"));
@@ -272,6 +282,49 @@ int main(int argc, char** argv)
             meshIsoFile = argv[i + 2];
             i += 2;
         }
+        else if (!strcmp(argv[i], "-crop")) {
+            GridStep g = {true, {0, 0, 0}, {0, 0, 0}, 0.0, SVR_RESAMPLE_NEAREST};
+            bool ok = i + 6 < argc;
+            for (int k = 0; ok && k < 6; ++k) {
+                char* end = nullptr;
+                const long v = strtol(argv[i + 1 + k], &end, 10);
+                ok = end != argv[i + 1 + k] && *end == '\0' && v >= -0x7fffffffL && v <= 0x7fffffffL;
+                (k < 3 ? g.lo[k] : g.hi[k - 3]) = (int32_t)v;
+            }
+            if (!ok) { fprintf(stderr, "-crop needs an inclusive voxel box X0 Y0 Z0 X1 Y1 Z1\n"); return 2; }
+            gridSteps.push_back(g);
+            i += 6;
+        }
+        else if (!strcmp(argv[i], "-resample")) {
+            char* end = nullptr;
+            const double mm = i + 1 < argc ? strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(mm > 0.0) || !std::isfinite(mm)) {
+                fprintf(stderr, "-resample needs a spacing MM > 0 in the units of the file's spacing (got %s)\n", i + 1 < argc ? argv[i + 1] : "nothing");
+                return 2;
+            }
+            GridStep g = {false, {0, 0, 0}, {0, 0, 0}, mm, SVR_RESAMPLE_AUTO};
+            ++i;
+            const char* m = i + 1 < argc ? argv[i + 1] : "";
+            const int mode = !strcmp(m, "nearest") ? SVR_RESAMPLE_NEAREST : !strcmp(m, "linear") ? SVR_RESAMPLE_LINEAR : !strcmp(m, "area") ? SVR_RESAMPLE_AREA
+                           : !strcmp(m, "auto") ? SVR_RESAMPLE_AUTO : -1;
+            if (mode >= 0) { g.mode = mode; ++i; }
+            gridSteps.push_back(g);
+        }
+        else if (!strcmp(argv[i], "-save-volume") || !strcmp(argv[i], "-save-mask") || !strcmp(argv[i], "-save-parts")) {
+            if (i + 1 >= argc || argv[i + 1][0] == '-') { fprintf(stderr, "%s needs a file name (.mhd or .mha)\n", argv[i]); return 2; }
+            (argv[i][6] == 'v' ? saveVolumeFile : argv[i][6] == 'm' ? saveMaskFile : savePartsFile) = argv[i + 1];
+            ++i;
+        }
+        else if (!strcmp(argv[i], "-save-crop")) {
+            char* end = nullptr;
+            const long v = i + 3 < argc ? strtol(argv[i + 3], &end, 10) : -1;
+            if (i + 3 >= argc || end == argv[i + 3] || *end != '\0' || v < 0 || v > 0x7fffffffL) {
+                fprintf(stderr, "-save-crop needs two file names, of the voxels and of the mask, and a margin in voxels >= 0\n");
+                return 2;
+            }
+            saveCropVolume = argv[i + 1]; saveCropMask = argv[i + 2]; saveCropMargin = (int)v;
+            i += 3;
+        }
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -292,6 +345,10 @@ int main(int argc, char** argv)
     if (!meshFile.empty() && !grow && !threshold) { fprintf(stderr, "-mesh exports the surface of a region: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (meshRelax >= 0 && meshFile.empty()) { fprintf(stderr, "-relax needs -mesh FILE\n"); return 2; }
     if (showFiltered && filterSteps.empty()) { fprintf(stderr, "-show-filtered needs -median E N or -smooth SIGMA\n"); return 2; }
+    if ((!saveMaskFile.empty() || !savePartsFile.empty() || !saveCropVolume.empty()) && !grow && !threshold) {
+        fprintf(stderr, "-save-mask, -save-parts and -save-crop write a region: they need -grow X Y LO HI or -threshold LO HI\n");
+        return 2;
+    }
     if (svr_init(0)) return 1;
     {
         Canvas canvas(W, H);
@@ -313,12 +370,31 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
-        canvas.volumeReader->KeepVoxels(grow || threshold || !filterSteps.empty() || !meshIsoFile.empty());  // the region and filter calls work on the plain voxels
+        canvas.volumeReader->KeepVoxels(grow || threshold || !filterSteps.empty() || !meshIsoFile.empty() || !gridSteps.empty() ||
+                                        !saveVolumeFile.empty());    // the region, filter, grid and save calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         printf("%s: %d x %d x %d, range %.0f..%.0f, max gradient magnitude %.0f, %zu histogram bins\n", volume.c_str(),
                canvas.volumeReader->dim[0], canvas.volumeReader->dim[1], canvas.volumeReader->dim[2], canvas.volumeReader->range[0],
                canvas.volumeReader->range[1], canvas.volumeReader->maxMagnitude, canvas.volumeReader->histogram.size());
+        for (const GridStep& g : gridSteps) {
+            // the grid everything after works on
+            const double target[3] = {g.mm, g.mm, g.mm};
+            if ((g.crop ? canvas.CropVolume(g.lo, g.hi) : canvas.ResampleVolume(target, g.mode)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            float ms = 0.f;
+            svr_volume_resample_last_ms(&ms);
+            const int* d = canvas.volumeReader->dim;
+            const char* modes[] = {"nearest", "linear", "area", "auto"};
+            if (g.crop) printf("crop %d %d %d .. %d %d %d: ", g.lo[0], g.lo[1], g.lo[2], g.hi[0], g.hi[1], g.hi[2]);
+            else printf("resample %g %s: ", g.mm, modes[g.mode]);
+            printf("%d x %d x %d, spacing %.9g %.9g %.9g, %.3f ms\n", d[0], d[1], d[2], canvas.Volume().spacing.x, canvas.Volume().spacing.y, canvas.Volume().spacing.z, ms);
+        }
+        // a file that a -save-* step wrote: its dimensions, the spacing and the time, write included
+        const auto saved = [&](const char* what, const std::string& file, const int32_t d[3], const std::chrono::steady_clock::time_point& t0) {
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            printf("%s -> %s: %d x %d x %d, spacing %.9g %.9g %.9g, %.3f ms\n", what, file.c_str(), d[0], d[1], d[2], canvas.Volume().spacing.x, canvas.Volume().spacing.y,
+                   canvas.Volume().spacing.z, ms);
+        };
 
         // the "add light" dialog's defaults (mainwindow.cpp:229-238): a disk above the volume, facing down
         cudaAreaLight light;
@@ -353,6 +429,11 @@ int main(int argc, char** argv)
             }
         }
         if (showFiltered && canvas.ShowFiltered() != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+        if (!saveVolumeFile.empty()) {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (canvas.SaveVolume(saveVolumeFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            saved("save-volume", saveVolumeFile, canvas.volumeReader->dim, t0);
+        }
 
         // an extracted surface goes to its file in world coordinates, with one line of counts and measures in the spacing's units
         const auto exportSurface = [&](const std::string& file) {
@@ -492,6 +573,26 @@ int main(int argc, char** argv)
                 else printf("largest inscribed ball: radius %g at voxel %d %d %d\n", radius, at[0], at[1], at[2]);
             }
             if (!meshFile.empty() && (canvas.ExtractRegionSurface((uint32_t)(meshRelax < 0 ? 0 : meshRelax)) != 0 || !exportSurface(meshFile))) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            if (!saveMaskFile.empty()) {
+                const auto t0 = std::chrono::steady_clock::now();
+                if (canvas.SaveRegion(saveMaskFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                saved("save-mask", saveMaskFile, canvas.volumeReader->dim, t0);
+            }
+            if (!savePartsFile.empty()) {
+                const auto t0 = std::chrono::steady_clock::now();
+                uint32_t parts = 0u;
+                if (canvas.LabelRegion(growConn, &parts) != 0 || canvas.SaveRegionParts(savePartsFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                printf("save-parts conn %d: %u parts\n", growConn, parts);
+                saved("save-parts", savePartsFile, canvas.volumeReader->dim, t0);
+            }
+            if (!saveCropVolume.empty()) {
+                const auto t0 = std::chrono::steady_clock::now();
+                int32_t d[3] = {0, 0, 0};
+                const int rc = canvas.SaveRegionCrop(saveCropVolume, saveCropMask, saveCropMargin, d);
+                if (rc < 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (rc == SVR_REGION_STATUS_EMPTY) printf("save-crop: the region is empty; nothing is written\n");
+                else saved("save-crop", saveCropVolume + " " + saveCropMask, d, t0);
+            }
             if (overlay) {
                 // the volume is drawn as it was loaded, and the region is laid over the picture
                 if (overlayParts) {

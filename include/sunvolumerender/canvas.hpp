@@ -38,6 +38,7 @@ public:
     void Read(std::string filename, int layout = SVR_LAYOUT_AUTO)
     {
         ClearDevice();
+        layoutUsed = layout;
         histogram.assign(65536, 0u);
         svr_volume_info info;
         if ((keepVoxels ? ReadKeeping(filename, layout, &info) : svr_load_mhd(filename.c_str(), layout, &loaded, &info, histogram.data(), (uint32_t)histogram.size())) != 0) {
@@ -74,6 +75,28 @@ public:
     void KeepVoxels(bool keep) { keepVoxels = keep; }
     const uint16_t* DeviceVoxels() const { return voxels; }     // null unless KeepVoxels(true) was set before Read
 
+    // extension: change the grid of the kept voxels (KeepVoxels(true)) after Read and before CreateDeviceVolume (svr_volume_resample;
+    // include/svr_abi.h, "crop and resample").  dim, spacing, the texture and the box change -- the result is drawn where it lay inside
+    // the loaded volume's box (svr_resample_grid_place) -- while maxMagnitude, range and histogram stay those of the loaded file.
+    // Crop: the inclusive voxel box (x, y, z), cut to the volume
+    int Crop(const int32_t box_min[3], const int32_t box_max[3])
+    {
+        if (!have || !voxels) return -4;
+        svr_resample_grid grid;
+        if (int rc = svr_resample_grid_box(dim, box_min, box_max, &grid)) return rc;
+        return Regrid(grid, SVR_RESAMPLE_NEAREST);
+    }
+    // Resample: to target_spacing (x, y, z; the units of the file's spacing) under SVR_RESAMPLE_NEAREST / _LINEAR / _AREA / _AUTO; the
+    // spacing applied is that of svr_resample_grid_spacing
+    int Resample(const double target_spacing[3], int mode = SVR_RESAMPLE_AUTO)
+    {
+        if (!have || !voxels) return -4;
+        const double sp[3] = {loaded.spacing.x, loaded.spacing.y, loaded.spacing.z};
+        svr_resample_grid grid;
+        if (int rc = svr_resample_grid_spacing(dim, sp, nullptr, nullptr, target_spacing, &grid, nullptr)) return rc;
+        return Regrid(grid, mode);
+    }
+
     std::vector<uint32_t> histogram;
     int dim[3] = {0, 0, 0};
     double range[2] = {0, 0};
@@ -87,6 +110,30 @@ private:
         voxels = nullptr;
         loaded = svr_volume();
         have = false;
+    }
+    // the kept voxels on `grid`: a new device volume and texture replace the old ones; on failure everything stays as it was
+    int Regrid(const svr_resample_grid& grid, int mode)
+    {
+        const int32_t n[3] = {(int32_t)grid.axis[0].count, (int32_t)grid.axis[1].count, (int32_t)grid.axis[2].count};
+        svr_volume placed;
+        int rc = svr_resample_grid_place(&loaded, dim, &grid, &placed);
+        if (rc != 0) return rc;
+        uint16_t* out = (uint16_t*)svr_device_malloc((size_t)n[0] * n[1] * n[2] * sizeof(uint16_t));
+        if (!out) return -4;
+        rc = svr_volume_resample(voxels, dim, 1, &grid, mode, out);
+        if (rc == 0) {
+            placed.tex = svr_create_volume_texture(out, n[0], n[1], n[2], 1, layoutUsed);
+            if (!placed.tex) rc = svr_last_error_code() ? svr_last_error_code() : -4;
+        }
+        svr_device_synchronize();
+        if (rc != 0) { svr_device_free(out); return rc; }
+        svr_destroy_texture(loaded.tex);
+        svr_device_free(voxels);
+        voxels = out;
+        loaded = placed;
+        for (int a = 0; a < 3; ++a) dim[a] = n[a];
+        spacing = glm::vec3(loaded.spacing.x, loaded.spacing.y, loaded.spacing.z);
+        return 0;
     }
     // svr_load_mhd in its parts, so that the preprocessed u16 volume stays: header, elements, GPU preprocessing, texture from the device
     // buffer; the svr_volume fields as svr_load_mhd fills them (VolumeReader.cpp:174-185, cuda_bbox.h)
@@ -121,6 +168,7 @@ private:
     svr_volume loaded = svr_volume();
     bool have = false;
     bool keepVoxels = false;
+    int layoutUsed = SVR_LAYOUT_AUTO;                          // Read's layout: Crop and Resample build their texture the same way
     uint16_t* voxels = nullptr;                                // the preprocessed volume (device), with KeepVoxels
 };
 
@@ -282,6 +330,11 @@ public:
         ready = true;
         ReStartRender();
     }
+
+    // extension: VolumeReader::Crop / Resample on the loaded volume (KeepVoxels(true) before LoadVolume); the Canvas then draws and
+    // segments the new grid.  A region, a filtered copy and a shown region are dropped: they belonged to the old grid
+    int CropVolume(const int32_t box_min[3], const int32_t box_max[3]) { return ready ? AdoptVolume(volumeReader->Crop(box_min, box_max)) : -4; }
+    int ResampleVolume(const double target_spacing[3], int mode = SVR_RESAMPLE_AUTO) { return ready ? AdoptVolume(volumeReader->Resample(target_spacing, mode)) : -4; }
 
     void ReStartRender() { renderParams.frameNo = 0; }                          // canvas.h:43-47
 
@@ -824,6 +877,69 @@ public:
     bool HasRegion() const { return haveRegion; }
     const uint32_t* RegionMask() const { return haveRegion ? regionMask : nullptr; }   // device; svr_region_mask_words words
 
+    // extension: what the region methods read and made, as MetaImage files (svr_mhd_write, include/svr_io.h; a name ending in .mha gives
+    // one file, any other a header and a .raw).  ElementSpacing is the drawn volume's, Offset the world position of the centre of voxel
+    // (0, 0, 0) in the Canvas's box.  The Canvas's own state and dimensions do not change.
+    // SaveVolume: the voxels the region methods read (the filtered copy when there is one), u16
+    int SaveVolume(const std::string& filename)
+    {
+        if (!ready || !SegVoxels()) return -4;
+        const int* dim = volumeReader->dim;
+        return SaveDeviceArray(filename, SegVoxels(), SVR_ELEM_U16, sizeof(uint16_t), dim, deviceVolume);
+    }
+    // SaveRegion: the region's mask as u8, 1 inside and 0 outside (svr_region_mask_expand); svr_region_threshold with the window 1 .. 65535
+    // on the loaded file gives the mask back
+    int SaveRegion(const std::string& filename)
+    {
+        if (!ready || !haveRegion) return -4;
+        const int* dim = volumeReader->dim;
+        return SaveMask(filename, regionMask, dim, deviceVolume);
+    }
+    // SaveRegionParts: LabelRegion's label map as u32
+    int SaveRegionParts(const std::string& filename)
+    {
+        if (!ready || !haveRegion || !haveLabels) return -4;
+        const int* dim = volumeReader->dim;
+        return SaveDeviceArray(filename, regionLabels, SVR_ELEM_U32, sizeof(uint32_t), dim, deviceVolume);
+    }
+    // SaveRegionCrop: the region's bounding box grown by margin_voxels on every side and cut to the volume: the voxels and the mask,
+    // cropped on the GPU (svr_volume_resample, svr_region_resample), with the Offset of where the box lies.  crop_dims (may be null) gets
+    // the box's dimensions.  An empty region has no box: SVR_REGION_STATUS_EMPTY is returned and nothing is written
+    int SaveRegionCrop(const std::string& volume_file, const std::string& mask_file, int margin_voxels, int32_t crop_dims[3] = nullptr)
+    {
+        if (!ready || !SegVoxels() || !haveRegion) return -4;
+        if (margin_voxels < 0) return -3;
+        const int* dim = volumeReader->dim;
+        svr_region_stats st;
+        int rc = svr_region_stats_of(SegVoxels(), dim[0], dim[1], dim[2], 1, regionMask, &st);
+        if (rc != 0) return rc;
+        if (st.status == SVR_REGION_STATUS_EMPTY) return SVR_REGION_STATUS_EMPTY;
+        int32_t lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = st.bbox_min[a] > margin_voxels ? st.bbox_min[a] - margin_voxels : 0;
+            hi[a] = st.bbox_max[a] < dim[a] - margin_voxels ? st.bbox_max[a] + margin_voxels : dim[a] - 1;
+        }
+        svr_resample_grid grid;
+        svr_volume placed;
+        rc = svr_resample_grid_box(dim, lo, hi, &grid);
+        if (rc == 0) rc = svr_resample_grid_place(&deviceVolume, dim, &grid, &placed);
+        if (rc != 0) return rc;
+        const int n[3] = {(int)grid.axis[0].count, (int)grid.axis[1].count, (int)grid.axis[2].count};
+        const size_t voxels = (size_t)n[0] * n[1] * n[2];
+        uint16_t* vol = (uint16_t*)svr_device_malloc(voxels * sizeof(uint16_t));
+        uint32_t* mask = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(n[0], n[1], n[2]) * sizeof(uint32_t));
+        rc = vol && mask ? 0 : -4;
+        if (rc == 0) rc = svr_volume_resample(SegVoxels(), dim, 1, &grid, SVR_RESAMPLE_NEAREST, vol);
+        if (rc == 0) rc = svr_region_resample(regionMask, dim, &grid, mask);
+        if (rc == 0) rc = SaveDeviceArray(volume_file, vol, SVR_ELEM_U16, sizeof(uint16_t), n, placed);
+        if (rc == 0) rc = SaveMask(mask_file, mask, n, placed);
+        svr_device_synchronize();
+        if (vol) svr_device_free(vol);
+        if (mask) svr_device_free(mask);
+        if (rc == 0 && crop_dims) for (int a = 0; a < 3; ++a) crop_dims[a] = n[a];
+        return rc;
+    }
+
     bool SaveImage(const std::string& filename)
     {
         std::vector<uint8_t> host((size_t)WIDTH * HEIGHT * 4);
@@ -856,6 +972,18 @@ private:
         maxSpan *= 1.5f;
         eyeDist = maxSpan / (2 * tan((fov * 0.5f) * 0.01745329251994329576923690768489f));
     }
+    // after VolumeReader::Crop / Resample returned rc: the reader's new texture, box and spacing, and a camera that sees all of it
+    int AdoptVolume(int rc)
+    {
+        if (rc != 0) return rc;
+        ClearRegion();
+        volumeReader->CreateDeviceVolume(&deviceVolume);               // (the clips and the density scale stay)
+        setup_volume(deviceVolume);
+        ZoomToExtent();
+        UpdateCamera();
+        ReStartRender();
+        return 0;
+    }
     // the voxels that are segmented: the filtered copy when there is one, else the loaded ones (null unless KeepVoxels(true) was set)
     const uint16_t* SegVoxels() const { return filtered ? filtered : volumeReader->DeviceVoxels(); }
     // run a filter from SegVoxels() into a fresh buffer; on success that buffer becomes the filtered copy
@@ -872,6 +1000,28 @@ private:
         if (filtered) svr_device_free(filtered);
         filtered = out;
         return 0;
+    }
+    // a device array of n[0] x n[1] x n[2] elements to a MetaImage file with the spacing and the position of `vol`
+    static int SaveDeviceArray(const std::string& filename, const void* device, int elem_type, size_t elem_size, const int n[3], const svr_volume& vol)
+    {
+        std::vector<uint8_t> host((size_t)n[0] * n[1] * n[2] * elem_size);
+        if (int rc = svr_memcpy_d2h(host.data(), device, host.size())) return rc;
+        const int32_t dims[3] = {n[0], n[1], n[2]};
+        const double sp[3] = {vol.spacing.x, vol.spacing.y, vol.spacing.z};
+        const double off[3] = {vol.bbox.vmin.x + 0.5 * sp[0], vol.bbox.vmin.y + 0.5 * sp[1], vol.bbox.vmin.z + 0.5 * sp[2]};
+        return svr_mhd_write(filename.c_str(), host.data(), elem_type, dims, sp, off, 0);
+    }
+    // a device bit mask as u8 0 / 1
+    static int SaveMask(const std::string& filename, const uint32_t* mask, const int n[3], const svr_volume& vol)
+    {
+        uint8_t* bytes = (uint8_t*)svr_device_malloc((size_t)n[0] * n[1] * n[2]);
+        if (!bytes) return -4;
+        const int32_t dims[3] = {n[0], n[1], n[2]};
+        int rc = svr_region_mask_expand(mask, dims, 1, bytes);
+        if (rc == 0) rc = SaveDeviceArray(filename, bytes, SVR_ELEM_U8, 1, n, vol);
+        svr_device_synchronize();
+        svr_device_free(bytes);
+        return rc;
     }
     // a counting call, then an extraction into device arrays of the counted sizes, copied to the host
     template <typename Call>

@@ -1118,6 +1118,82 @@ int svr_mesh_positions(const int32_t* vertices_host, uint64_t nv, const double s
  * did not run).  Pointers may be NULL */
 int svr_mesh_last_ms(float* classify_ms, float* emit_ms, float* relax_ms);
 
+/* ---- crop and resample volumes, masks and label maps; paste a mask back (csrc/svr_resample.hip) ----
+ * Every other volume operation works on the grid the file came in.  These calls change the grid: a crop to a box (cheaper steps on a
+ * region of interest), a resampling to another spacing (isotropic voxels for the voxel-unit elements of svr_region_morph and
+ * svr_volume_rank) or to other dimensions (a preview-sized copy), and the way back for a mask made on a crop.  Integers only; every
+ * result is defined bit for bit and does not depend on scheduling.  Dimensions are const int32_t dims[3] = (x, y, z).
+ *
+ * THE GRID: per axis an svr_axis_map in Q16 source EDGE coordinates -- source voxel i covers [i << 16, (i + 1) << 16).  Output cell j
+ *   covers [a, a + step) with a = origin + j * step (int64).  A crop is step 65536 and origin = b0 << 16.
+ * RESAMPLING runs per axis in the order x, y, z on u16 volumes, one rounding per axis (as svr_volume_smooth); the border replicates:
+ *   clamp(i) = min(max(i, 0), n - 1).  With c = a + (step >> 1) and arithmetic shifts:
+ *     SVR_RESAMPLE_NEAREST  out = v[clamp(c >> 16)]: the source voxel whose cell holds the centre of the output cell.
+ *     SVR_RESAMPLE_LINEAR   t = c - 32768, i = t >> 16, f = t & 65535: out = (v[clamp(i)] (65536 - f) + v[clamp(i + 1)] f + 32768) >> 16.
+ *     SVR_RESAMPLE_AREA     out = (2 S + step) / (2 step), S = sum_i v[clamp(i)] ov_i over i = a >> 16 .. (a + step - 1) >> 16, where
+ *                           ov_i = min(a + step, (i + 1) << 16) - max(a, i << 16) is the overlap of the cell with voxel i (they sum to step).
+ *     SVR_RESAMPLE_AUTO     per axis LINEAR where step <= 65536 (the grid is as fine or finer), AREA where it is coarser.
+ *   An axis with step 65536 and an origin that is a multiple of 65536 is a shifted copy under every mode and costs no pass of its own.
+ * GRID HELPERS (plain host code; null -4, dimensions <= 0 or more than 2^31 voxels -6, everything else -3).  A box is inclusive and is
+ *   cut to the volume as the region calls do; NULL box pointers mean the whole volume.
+ *     _grid_box      a crop: origin = b0 << 16, step = 65536, count = b1 - b0 + 1.
+ *     _grid_spacing  per axis step = llround(65536 target / source), refused outside the step limits; origin = b0 << 16; count =
+ *                    max(1, ((b1 - b0 + 1) * 65536 + (step >> 1)) / step); spacing_out (may be NULL) = source * step / 65536, the spacing
+ *                    actually applied.  The first cell's lower edge is the box's lower face: the result fills the same physical box up
+ *                    to the rounding of count.
+ *     _grid_dims     target dimensions: step = ((b1 - b0 + 1) * 65536 + out_dim / 2) / out_dim, origin = b0 << 16, count = out_dim.
+ *     _grid_place    *out = *src with bbox (vmin, vmax, invSize), spacing and invSpacing replaced, so that the result is drawn where it
+ *                    lay inside the source volume's box: vmin + origin / 65536 * spacing and vmin + (origin + count * step) / 65536 *
+ *                    spacing per axis, in double, rounded to float; spacing * step / 65536.  tex is copied unchanged (the caller
+ *                    replaces it); invMaxMagnitude, densityScale, gradientFactor and the clips are copied, so a crop shades as the
+ *                    full volume does -- and a RESAMPLED volume keeps the source's gradient normalisation, although its gradients are
+ *                    taken over other distances.
+ * svr_volume_resample: voxels is host memory, or device memory with src_is_device; out holds count_x * count_y * count_z u16.  The
+ *   library allocates and frees at most two intermediate volumes; a call that used one, or that uploaded a host source, synchronises
+ *   before it returns.  A one-kernel call (a crop, NEAREST, or one resampled axis) on a device source is asynchronous on the library's stream.
+ * svr_region_resample: NEAREST on bit masks in the layout of svr_region_grow -- the mask of the NEAREST-resampled 0 / 1 volume.  Input
+ *   padding bits are ignored, output padding bits are 0.
+ * svr_region_label_resample: NEAREST on uint32 maps: label maps and zone maps on any grid.  A squared-distance map may be CROPPED with
+ *   it; a resampled distance is not a distance on the new grid.
+ * svr_region_paste: the inverse of a crop.  The sub-mask lies at offset_xyz inside the full mask; inside that box the full mask takes
+ *   the sub-mask's bits (SVR_PASTE_REPLACE), gains them (SVR_MASK_OR) or loses them (SVR_MASK_ANDNOT); bits outside the box keep their
+ *   value, also in the words the box's x faces cut through.  A sub-volume that does not fit at the offset is refused (-3).
+ * svr_region_mask_expand: one byte per voxel, `value` (1 .. 255) inside the mask and 0 outside: what a mask is saved from
+ *   (svr_mhd_write).  The way back: svr_region_threshold with the window 1 .. 65535 on the loaded file.
+ * Refused before the device is touched, with nothing written: a null pointer (-4); source or output dimensions <= 0 or more than 2^31
+ *   voxels (-6); (-3) a step outside SVR_RESAMPLE_MIN_STEP .. _MAX_STEP, count == 0, an axis whose cells [origin, origin + count * step)
+ *   do not meet the source extent [0, n << 16), |origin| >= 2^47, an unknown mode, op or value, an `out` that overlaps an input. */
+#define SVR_RESAMPLE_NEAREST 0
+#define SVR_RESAMPLE_LINEAR  1
+#define SVR_RESAMPLE_AREA    2
+#define SVR_RESAMPLE_AUTO    3
+#define SVR_RESAMPLE_MIN_STEP 1024u      /* 1 / 64 voxel */
+#define SVR_RESAMPLE_MAX_STEP 4194304u   /* 64 voxels */
+#define SVR_PASTE_REPLACE 0              /* the other ops of svr_region_paste are SVR_MASK_OR and SVR_MASK_ANDNOT */
+
+typedef struct svr_axis_map {        /* 16 bytes */
+    int64_t  origin;                 /* lower edge of output cell 0, in source edge coordinates, Q16 */
+    uint32_t step;                   /* width of an output cell, Q16 */
+    uint32_t count;                  /* output voxels on this axis, >= 1 */
+} svr_axis_map;
+typedef struct svr_resample_grid { svr_axis_map axis[3]; } svr_resample_grid;   /* x, y, z; 48 bytes */
+
+int svr_resample_grid_box(const int32_t src_dims[3], const int32_t box_min[3], const int32_t box_max[3], svr_resample_grid* grid);
+int svr_resample_grid_spacing(const int32_t src_dims[3], const double src_spacing[3], const int32_t* box_min_or_null,
+                              const int32_t* box_max_or_null, const double target_spacing[3], svr_resample_grid* grid, double* spacing_out);
+int svr_resample_grid_dims(const int32_t src_dims[3], const int32_t* box_min_or_null, const int32_t* box_max_or_null,
+                           const int32_t out_dims[3], svr_resample_grid* grid);
+int svr_resample_grid_place(const svr_volume* src, const int32_t src_dims[3], const svr_resample_grid* grid, svr_volume* out);
+int svr_volume_resample(const uint16_t* voxels, const int32_t src_dims[3], int src_is_device, const svr_resample_grid* grid, int mode,
+                        uint16_t* out_u16_device);
+int svr_region_resample(const uint32_t* in_mask_device, const int32_t src_dims[3], const svr_resample_grid* grid, uint32_t* out_mask_device);
+int svr_region_label_resample(const uint32_t* in_u32_device, const int32_t src_dims[3], const svr_resample_grid* grid, uint32_t* out_u32_device);
+int svr_region_paste(const uint32_t* sub_mask_device, const int32_t sub_dims[3], uint32_t* full_mask_device, const int32_t full_dims[3],
+                     const int32_t offset_xyz[3], int op);
+int svr_region_mask_expand(const uint32_t* mask_device, const int32_t dims[3], int value, uint8_t* out_u8_device);
+/* HIP-event time of the device work of the last svr_volume_resample / svr_region_resample / _label_resample / _paste / _mask_expand */
+int svr_volume_resample_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

@@ -58,6 +58,19 @@ int svr_mhd_read_header(const char* path, svr_mhd_header* out);
  * dim[0]*dim[1]*dim[2]*elem_size bytes (host memory) */
 int svr_mhd_read_elements(const svr_mhd_header* header, void* dst, size_t dst_bytes);
 
+/* Writes a volume, a mask (svr_region_mask_expand), a label map or a distance map as a MetaImage.  elems: host memory, x fastest, dim[0] *
+ * dim[1] * dim[2] elements of elem_type (any svr_elem_type).  A path ending in ".mha" gives one file with ElementDataFile = LOCAL; any
+ * other path gives the header and, next to it, <stem>.raw -- or <stem>.zraw (zlib) with CompressedData = True and CompressedDataSize
+ * when `compress` is set (a .mha is compressed the same way).  Keys, in this order: ObjectType, NDims = 3, BinaryData,
+ * BinaryDataByteOrderMSB = False, CompressedData, [CompressedDataSize,] TransformMatrix (identity), Offset, CenterOfRotation,
+ * ElementSpacing, DimSize, ElementType, ElementDataFile.  Doubles are printed with %.17g, so they read back exactly.  Offset is the
+ * MetaImage convention's: the position of the centre of voxel (0, 0, 0).  svr_mhd_read_header and svr_load_mhd IGNORE Offset, as the
+ * reference does, and centre every volume at the origin; other readers place the file by it.
+ * Refuses a null argument (-4); an unknown element type, dimensions <= 0 or above 2^31 voxels, a spacing that is not positive and
+ * finite, an offset that is not finite (-3); reports I/O failures like svr_tga_write (-20). */
+int svr_mhd_write(const char* path, const void* elems, int elem_type, const int32_t dim[3], const double spacing[3], const double offset[3],
+                  int compress);
+
 /* VolumeReader::Read after the file is in memory (VolumeReader.cpp:41-76), on the GPU:
  * cast to short -> scalar range -> rescale to full-range u16 -> histogram -> max gradient magnitude.
  *   elems            nx*ny*nz elements of elem_type, x fastest; host pointer, or device pointer if elems_on_device

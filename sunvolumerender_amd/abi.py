@@ -339,6 +339,29 @@ MESH_MAX_DIM = 8388606
 MESH_ERR_CAPACITY = -11
 
 
+class AxisMap(C.Structure):  # svr_axis_map: Q16 source edge coordinates
+    _fields_ = [("origin", C.c_int64), ("step", C.c_uint32), ("count", C.c_uint32)]
+
+
+class ResampleGrid(C.Structure):  # svr_resample_grid: x, y, z
+    _fields_ = [("axis", AxisMap * 3)]
+
+    def as_tuples(self):
+        """((origin, step, count) of x, of y, of z)"""
+        return tuple((int(m.origin), int(m.step), int(m.count)) for m in self.axis)
+
+    @property
+    def shape(self):
+        """(nz, ny, nx) of the output"""
+        return (int(self.axis[2].count), int(self.axis[1].count), int(self.axis[0].count))
+
+
+svr_axis_map, svr_resample_grid = AxisMap, ResampleGrid
+RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA, RESAMPLE_AUTO = 0, 1, 2, 3
+RESAMPLE_MIN_STEP, RESAMPLE_MAX_STEP = 1024, 4194304
+PASTE_REPLACE = 0
+
+
 EXPECTED_SIZES = {
     vec3: 12,
     cudaBBox: 36,
@@ -365,6 +388,8 @@ EXPECTED_SIZES = {
     OverlayStyle: 24,
     MeshParams: 8,
     MeshInfo: 56,
+    AxisMap: 16,
+    ResampleGrid: 48,
 }
 for _t, _n in EXPECTED_SIZES.items():
     assert C.sizeof(_t) == _n, (_t, C.sizeof(_t), _n)
@@ -557,6 +582,17 @@ PROTOTYPES = {
     "svr_mesh_measure": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _P(C.c_double), _P(C.c_int64), _P(C.c_double)]),
     "svr_mesh_positions": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_double), _P(cudaVolume), C.c_void_p]),
     "svr_mesh_last_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "svr_resample_grid_box": (C.c_int, [_P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(ResampleGrid)]),
+    "svr_resample_grid_spacing": (C.c_int, [_P(C.c_int32), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_double), _P(ResampleGrid),
+                                            _P(C.c_double)]),
+    "svr_resample_grid_dims": (C.c_int, [_P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(ResampleGrid)]),
+    "svr_resample_grid_place": (C.c_int, [_P(cudaVolume), _P(C.c_int32), _P(ResampleGrid), _P(cudaVolume)]),
+    "svr_volume_resample": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(ResampleGrid), C.c_int, C.c_void_p]),
+    "svr_region_resample": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(ResampleGrid), C.c_void_p]),
+    "svr_region_label_resample": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(ResampleGrid), C.c_void_p]),
+    "svr_region_paste": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_void_p, _P(C.c_int32), _P(C.c_int32), C.c_int]),
+    "svr_region_mask_expand": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p]),
+    "svr_volume_resample_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_get_counters": (C.c_int, [_P(Counters)]),
     "svr_reset_counters": (C.c_int, []),
     "svr_get_kernel_time": (C.c_int, [_P(C.c_double), _P(C.c_uint64)]),
@@ -575,6 +611,7 @@ PROTOTYPES = {
     "svr_tf_load": (C.c_int, [C.c_char_p, C.c_void_p, _P(C.c_int), C.c_void_p, _P(C.c_int)]),
     "svr_hdr_load": (C.c_int, [C.c_char_p, _P(C.c_int), _P(C.c_int), C.c_void_p, C.c_size_t]),
     "svr_load_env_map": (C.c_int, [C.c_char_p, _P(cudaEnvironmentLight)]),
+    "svr_mhd_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, _P(C.c_int32), _P(C.c_double), _P(C.c_double), C.c_int]),
     "svr_tga_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p]),
     "svr_tga_encode": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "svr_stl_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),

@@ -415,6 +415,66 @@ int svr_internal_mhd_load(const char* path, svr_mhd_header* h, std::vector<uint8
     return svr_mhd_read_elements(h, elems->data(), elems->size());
 }
 
+// The MetaImage writer.  Offset is written as the MetaImage convention has it, the position of the centre of voxel (0, 0, 0); this
+// library's own reader ignores it (parse_mhd above) and centres every volume, so a file written here loads centred like any other.
+int svr_mhd_write(const char* path, const void* elems, int elem_type, const int32_t dim[3], const double spacing[3], const double offset[3], int compress)
+{
+    const char* who = "svr_mhd_write";
+    if (!path || !elems || !dim || !spacing || !offset) return failf(-4, "%s: null argument", who);
+    const char* type_name = nullptr;
+    size_t elem_size = 0;
+    for (const ElemName& en : kElems)
+        if (en.type == elem_type && !type_name) { type_name = en.name; elem_size = (size_t)en.size; }
+    if (!type_name) return failf(-3, "%s: unknown element type %d", who, elem_type);
+    if (dim[0] <= 0 || dim[1] <= 0 || dim[2] <= 0 || (uint64_t)dim[0] * (uint64_t)dim[1] * (uint64_t)dim[2] > (1ull << 31))
+        return failf(-3, "%s: bad dimensions %d x %d x %d", who, (int)dim[0], (int)dim[1], (int)dim[2]);
+    for (int a = 0; a < 3; ++a)
+        if (!(spacing[a] > 0.0) || !std::isfinite(spacing[a]) || !std::isfinite(offset[a]))
+            return failf(-3, "%s: the spacing must be positive and finite and the offset finite", who);
+    const size_t bytes = (size_t)dim[0] * (size_t)dim[1] * (size_t)dim[2] * elem_size;
+    const std::string p(path);
+    const bool local = p.size() >= 4 && p.compare(p.size() - 4, 4, ".mha") == 0;
+    // the element file next to the header: <stem>.raw / <stem>.zraw, named in the header without its directory
+    const size_t slash = p.find_last_of('/'), dot = p.find_last_of('.');
+    const std::string stem = (dot != std::string::npos && (slash == std::string::npos || dot > slash + 1)) ? p.substr(0, dot) : p;
+    const std::string data_path = stem + (compress ? ".zraw" : ".raw");
+    const std::string data_name = slash == std::string::npos ? data_path : data_path.substr(slash + 1);
+
+    std::vector<uint8_t> packed;
+    const uint8_t* data = (const uint8_t*)elems;
+    size_t data_bytes = bytes;
+    if (compress) {
+        uLongf len = compressBound((uLong)bytes);
+        packed.resize((size_t)len);
+        const int z = compress2(packed.data(), &len, data, (uLong)bytes, Z_DEFAULT_COMPRESSION);
+        if (z != Z_OK) return failf(-20, "%s: zlib could not compress %zu bytes (zlib %d)", who, bytes, z);
+        data = packed.data();
+        data_bytes = (size_t)len;
+    }
+    char head[1024];
+    int n = snprintf(head, sizeof head,
+                     "ObjectType = Image\nNDims = 3\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = %s\n", compress ? "True" : "False");
+    if (compress) n += snprintf(head + n, sizeof head - (size_t)n, "CompressedDataSize = %zu\n", data_bytes);
+    n += snprintf(head + n, sizeof head - (size_t)n,
+                  "TransformMatrix = 1 0 0 0 1 0 0 0 1\nOffset = %.17g %.17g %.17g\nCenterOfRotation = 0 0 0\nElementSpacing = %.17g %.17g %.17g\n"
+                  "DimSize = %d %d %d\nElementType = %s\nElementDataFile = ",
+                  offset[0], offset[1], offset[2], spacing[0], spacing[1], spacing[2], (int)dim[0], (int)dim[1], (int)dim[2], type_name);
+    const std::string header = std::string(head, (size_t)n) + (local ? std::string("LOCAL") : data_name) + "\n";
+
+    FILE* f = fopen(path, "wb");
+    if (!f) return failf(-20, "unable to open %s for writing (%s)", path, strerror(errno));
+    bool ok = fwrite(header.data(), 1, header.size(), f) == header.size();
+    if (ok && local) ok = fwrite(data, 1, data_bytes, f) == data_bytes;
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) return failf(-20, "short write to %s", path);
+    if (local) return 0;
+    f = fopen(data_path.c_str(), "wb");
+    if (!f) return failf(-20, "unable to open %s for writing (%s)", data_path.c_str(), strerror(errno));
+    ok = fwrite(data, 1, data_bytes, f) == data_bytes;
+    ok = (fclose(f) == 0) && ok;
+    return ok ? 0 : failf(-20, "short write to %s", data_path.c_str());
+}
+
 int svr_tf_build_table(const double* opacity_nodes, int n_opacity, const double* color_nodes, int n_color,
                        int table_size, float* table_rgba, float* max_opacity)
 {

@@ -1,6 +1,6 @@
 // svr_mask.hpp -- the bit-mask layout of the region calls (svr_region_*; the contract is in include/svr_abi.h, the design in DESIGN.md
 // 8h) and the helpers that every file working on it needs: the words of a row, the lanes of a word, the launch grids.  Included by
-// svr_region_grow.hpp (svr_region.hip, svr_morph.hip), svr_label.hip, svr_distance.hip and svr_geodesic.hip.
+// svr_region_grow.hpp (svr_region.hip, svr_morph.hip), svr_label.hip, svr_distance.hip, svr_geodesic.hip and svr_resample.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -920,6 +920,122 @@ class Device:
         self.check(self.lib.svr_volume_filter_last_ms(C.byref(ms)))
         return float(ms.value)
 
+    # ---- crop and resample (svr_resample_grid_* / svr_volume_resample / svr_region_resample / _label_resample / _paste / _mask_expand) ----
+    def resample_grid_box(self, shape, box) -> abi.ResampleGrid:
+        return resample_grid_box(shape, box, self.lib)
+
+    def resample_grid_spacing(self, shape, src_spacing, target_spacing, box=None):
+        return resample_grid_spacing(shape, src_spacing, target_spacing, box, self.lib)
+
+    def resample_grid_dims(self, shape, out_shape, box=None) -> abi.ResampleGrid:
+        return resample_grid_dims(shape, out_shape, box, self.lib)
+
+    def resample_grid_place(self, volume: cudaVolume, shape, grid) -> cudaVolume:
+        return resample_grid_place(volume, shape, grid, self.lib)
+
+    def volume_resample(self, vox, grid, mode: int = abi.RESAMPLE_AUTO, shape=None, out_ptr: Optional[int] = None):
+        """svr_volume_resample: the volume on `grid` (a ResampleGrid, or ((origin, step, count) of x, y, z)) under RESAMPLE_NEAREST /
+        _LINEAR / _AREA / _AUTO.  vox is a host [nz][ny][nx] u16 array, or a device pointer with shape=(nz, ny, nx).  Returns a u16 array
+        of grid.shape; with out_ptr (a device buffer of that many u16 that does not overlap a device `vox`) the result stays on the
+        device and out_ptr is returned."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        g, dims = resample_grid(grid), (C.c_int32 * 3)(nx, ny, nz)
+        return self._volume_filter(g.shape, out_ptr, lambda out: self.lib.svr_volume_resample(src, dims, on_dev, C.byref(g), int(mode), C.c_void_p(out)))
+
+    def volume_crop(self, vox, box, shape=None, out_ptr: Optional[int] = None):
+        """volume_resample on the grid of a box ((x0, y0, z0), (x1, y1, z1)), inclusive, cut to the volume.  Returns (result, grid)."""
+        shape = vox.shape if isinstance(vox, np.ndarray) else shape
+        g = self.resample_grid_box(shape, box)
+        return self.volume_resample(vox, g, abi.RESAMPLE_NEAREST, shape, out_ptr), g
+
+    def region_resample(self, mask, grid, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_resample: NEAREST on a mask (a bool array [nz][ny][nx], or a device pointer with shape=).  Returns the bool array of
+        grid.shape; out_ptr: a device buffer of region_mask_words(grid.shape) uint32 that receives the bit mask."""
+        if isinstance(mask, np.ndarray):
+            shape = mask.shape
+        if shape is None:
+            raise ValueError("a device mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = (int(n) for n in shape)
+        g, dims = resample_grid(grid), (C.c_int32 * 3)(nx, ny, nz)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        words = region_mask_words(g.shape)
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(words, 1))
+        try:
+            self.check(self.lib.svr_region_resample(C.c_void_p(buf), dims, C.byref(g), C.c_void_p(out)))
+            return region_mask_unpack(self.to_host(out, (words,), np.uint32), g.shape)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_label_resample(self, labels, grid, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_label_resample: NEAREST on a uint32 map (labels, zones; a squared-distance map only for crops).  Returns the uint32
+        array of grid.shape, or out_ptr itself when a device buffer of that many uint32 is given."""
+        buf, (nz, ny, nx), owned = self._region_labels(labels, shape)
+        g, dims = resample_grid(grid), (C.c_int32 * 3)(nx, ny, nz)
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(int(np.prod(g.shape)), 1))
+        try:
+            self.check(self.lib.svr_region_label_resample(C.c_void_p(buf), dims, C.byref(g), C.c_void_p(out)))
+            if out_ptr is not None:
+                self.synchronize()
+                return out_ptr
+            return self.to_host(out, g.shape, np.uint32)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def region_paste(self, sub, full, offset, op: int = abi.PASTE_REPLACE, sub_shape=None, full_shape=None):
+        """svr_region_paste: the sub-mask put back at offset (x, y, z) of the full mask with PASTE_REPLACE, MASK_OR or MASK_ANDNOT.  Masks
+        are bool arrays, or device pointers with their shapes.  A device `full` is changed in place and returned; a host `full` is left
+        alone and the pasted bool array is returned."""
+        sub_shape = sub.shape if isinstance(sub, np.ndarray) else tuple(int(n) for n in sub_shape)
+        full_shape = full.shape if isinstance(full, np.ndarray) else tuple(int(n) for n in full_shape)
+        sbuf, sowned = self._region_mask(sub, sub_shape)
+        fbuf, fowned = self._region_mask(full, full_shape)
+        try:
+            self.check(self.lib.svr_region_paste(C.c_void_p(sbuf), (C.c_int32 * 3)(*sub_shape[::-1]), C.c_void_p(fbuf), (C.c_int32 * 3)(*full_shape[::-1]),
+                                                 (C.c_int32 * 3)(*[int(t) for t in offset]), int(op)))
+            if not fowned:
+                self.synchronize()
+                return full
+            return region_mask_unpack(self.to_host(fbuf, (region_mask_words(full_shape),), np.uint32), full_shape)
+        finally:
+            if sowned:
+                self.free(sbuf)
+            if fowned:
+                self.free(fbuf)
+
+    def region_mask_expand(self, mask, value: int = 1, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_mask_expand: one byte per voxel, `value` (1 .. 255) inside the mask and 0 outside -- what io.mhd_write saves a mask
+        from.  Returns the u8 array [nz][ny][nx], or out_ptr itself when a device buffer of nx * ny * nz bytes is given."""
+        if isinstance(mask, np.ndarray):
+            shape = mask.shape
+        if shape is None:
+            raise ValueError("a device mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = (int(n) for n in shape)
+        buf, owned = self._region_mask(mask, (nz, ny, nx))
+        out = out_ptr if out_ptr is not None else self.malloc(max(nx * ny * nz, 4))
+        try:
+            self.check(self.lib.svr_region_mask_expand(C.c_void_p(buf), (C.c_int32 * 3)(nx, ny, nz), int(value), C.c_void_p(out)))
+            if out_ptr is not None:
+                self.synchronize()
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint8)
+        finally:
+            if owned:
+                self.free(buf)
+            if out_ptr is None:
+                self.free(out)
+
+    def volume_resample_last_ms(self) -> float:
+        """HIP-event time of the device work of the last volume_resample / region_resample / _label_resample / _paste / _mask_expand."""
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_volume_resample_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
         """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
         m = abi.RegionMeasurement()
@@ -1004,6 +1120,72 @@ def smooth_radii(spacing, sigma, lib=None):
         lib.svr_clear_error()
         raise SvrError(f"svr_volume_smooth_radii failed ({rc}): {msg}")
     return (int(r[0]), int(r[1]), int(r[2])), (float(so[0]), float(so[1]), float(so[2]))
+
+
+def resample_grid(grid) -> abi.ResampleGrid:
+    """A ResampleGrid from ((origin, step, count) of x, of y, of z); a ResampleGrid is returned as it is."""
+    if isinstance(grid, abi.ResampleGrid):
+        return grid
+    g = abi.ResampleGrid()
+    for a in range(3):
+        g.axis[a].origin, g.axis[a].step, g.axis[a].count = (int(t) for t in grid[a])
+    return g
+
+
+def _grid_call(lib, name, rc):
+    if rc != 0:
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise SvrError(f"{name} failed ({rc}): {msg}")
+
+
+def _grid_box_args(shape, box):
+    nz, ny, nx = (int(n) for n in shape)
+    b0 = b1 = None
+    if box is not None:
+        b0, b1 = (C.c_int32 * 3)(*[int(t) for t in box[0]]), (C.c_int32 * 3)(*[int(t) for t in box[1]])
+    return (C.c_int32 * 3)(nx, ny, nz), b0, b1
+
+
+def resample_grid_box(shape, box, lib=None) -> abi.ResampleGrid:
+    """svr_resample_grid_box: the grid of a crop of a [nz][ny][nx] volume to box = ((x0, y0, z0), (x1, y1, z1)), inclusive, cut to the
+    volume.  The grid helpers are host code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    dims, b0, b1 = _grid_box_args(shape, box)
+    g = abi.ResampleGrid()
+    _grid_call(lib, "svr_resample_grid_box", lib.svr_resample_grid_box(dims, b0, b1, C.byref(g)))
+    return g
+
+
+def resample_grid_spacing(shape, src_spacing, target_spacing, box=None, lib=None):
+    """svr_resample_grid_spacing: (grid, spacing applied) for resampling a [nz][ny][nx] volume (or a box of it) from src_spacing to
+    target_spacing, both (x, y, z); a scalar target means isotropic."""
+    lib = lib if lib is not None else abi.load()
+    dims, b0, b1 = _grid_box_args(shape, box)
+    target = [float(target_spacing)] * 3 if np.isscalar(target_spacing) else [float(t) for t in target_spacing]
+    g, out = abi.ResampleGrid(), (C.c_double * 3)()
+    _grid_call(lib, "svr_resample_grid_spacing", lib.svr_resample_grid_spacing(dims, (C.c_double * 3)(*[float(t) for t in src_spacing]), b0, b1,
+                                                                                (C.c_double * 3)(*target), C.byref(g), out))
+    return g, (float(out[0]), float(out[1]), float(out[2]))
+
+
+def resample_grid_dims(shape, out_shape, box=None, lib=None) -> abi.ResampleGrid:
+    """svr_resample_grid_dims: the grid that maps a [nz][ny][nx] volume (or a box of it) onto out_shape = (nz', ny', nx')."""
+    lib = lib if lib is not None else abi.load()
+    dims, b0, b1 = _grid_box_args(shape, box)
+    g = abi.ResampleGrid()
+    _grid_call(lib, "svr_resample_grid_dims", lib.svr_resample_grid_dims(dims, b0, b1, (C.c_int32 * 3)(*[int(n) for n in out_shape][::-1]), C.byref(g)))
+    return g
+
+
+def resample_grid_place(volume: cudaVolume, shape, grid, lib=None) -> cudaVolume:
+    """svr_resample_grid_place: a copy of `volume` (the cudaVolume of the [nz][ny][nx] source) whose box and spacing are those of the
+    resampled volume, where it lay inside the source's box.  tex is copied: the caller replaces it."""
+    lib = lib if lib is not None else abi.load()
+    dims, _, _ = _grid_box_args(shape, None)
+    g, out = resample_grid(grid), cudaVolume()
+    _grid_call(lib, "svr_resample_grid_place", lib.svr_resample_grid_place(C.byref(volume), dims, C.byref(g), C.byref(out)))
+    return out
 
 
 def region_mask_words(shape) -> int:

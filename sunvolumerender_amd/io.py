@@ -219,6 +219,46 @@ def save_tga(dev, filename: str, img: np.ndarray):
     dev.check(dev.lib.svr_tga_write(str(filename).encode(), a.shape[1], a.shape[0], a.ctypes.data_as(C.c_void_p)))
 
 
+ELEM_DTYPES = {abi.ELEM_I8: np.int8, abi.ELEM_U8: np.uint8, abi.ELEM_I16: np.int16, abi.ELEM_U16: np.uint16, abi.ELEM_I32: np.int32,
+               abi.ELEM_U32: np.uint32, abi.ELEM_F32: np.float32, abi.ELEM_F64: np.float64}
+
+
+def _io_check(lib, rc: int, what: str):
+    if rc != 0:
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise RuntimeError(f"{what} failed ({rc}): {msg}")
+
+
+def mhd_write(filename: str, arr: np.ndarray, spacing=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0), compress: bool = False, lib=None):
+    """svr_mhd_write: a [nz][ny][nx] array of one of the eight MetaImage element types (a bool array is written as u8 0 / 1) as
+    `filename` -- one file for .mha, else the header plus <stem>.raw or, compressed, <stem>.zraw.  spacing and offset are (x, y, z);
+    offset is the position of the centre of voxel (0, 0, 0).  Host code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    a = np.ascontiguousarray(arr)
+    if a.dtype == np.bool_:
+        a = a.astype(np.uint8)
+    if a.ndim != 3:
+        raise ValueError("the array must be [nz][ny][nx]")
+    types = [t for t, d in ELEM_DTYPES.items() if np.dtype(d) == a.dtype]
+    if not types:
+        raise ValueError(f"MetaImage has no element type for {a.dtype}")
+    dim = (C.c_int32 * 3)(a.shape[2], a.shape[1], a.shape[0])
+    sp, off = (C.c_double * 3)(*[float(t) for t in spacing]), (C.c_double * 3)(*[float(t) for t in offset])
+    _io_check(lib, lib.svr_mhd_write(str(filename).encode(), a.ctypes.data_as(C.c_void_p), types[0], dim, sp, off, int(bool(compress))), "svr_mhd_write")
+
+
+def mhd_read(filename: str, lib=None):
+    """svr_mhd_read_header + svr_mhd_read_elements: (the [nz][ny][nx] array in the file's element type, the spacing (x, y, z)).  Host
+    code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    h = abi.MhdHeader()
+    _io_check(lib, lib.svr_mhd_read_header(str(filename).encode(), C.byref(h)), "svr_mhd_read_header")
+    out = np.zeros((int(h.dim[2]), int(h.dim[1]), int(h.dim[0])), dtype=ELEM_DTYPES[int(h.elem_type)])
+    _io_check(lib, lib.svr_mhd_read_elements(C.byref(h), out.ctypes.data_as(C.c_void_p), out.nbytes), "svr_mhd_read_elements")
+    return out, tuple(float(s) for s in h.spacing)
+
+
 def _write_mesh(dev, fn, filename: str, xyz: np.ndarray, triangles: np.ndarray):
     v = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
     t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
