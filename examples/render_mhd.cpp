@@ -40,6 +40,12 @@
 // ExtractRegionSurface, SaveSurface: surface nets in world coordinates; -relax N smooths it by N = 0 .. 64 constrained relaxation
 // steps); -mesh-iso RAW FILE.stl|.ply writes the isosurface {raw value >= RAW} of the (filtered) voxels, with or without a region.  Each
 // prints "mesh: V vertices, T triangles, volume ... mm^3, area ... mm^2", the region's line first.
+// -seed X Y CLASS [RADIUS] (repeatable) and -growcut [GAIN SHIFT] are grow-from-seeds (Canvas::AddSeed, GrowFromSeeds: svr_region_growcut):
+// every -seed picks at pixel (X, Y) like -grow and paints a stroke of class CLASS = 1, 2, ... -- the ball of RADIUS in the units of the
+// spacing, twice the smallest spacing by default -- and -growcut gives every voxel of the region made by -grow / -threshold, or without
+// one of the whole volume, to the class whose strokes reach it over the path that crosses the least contrast (a move costs 1 + GAIN *
+// (|difference of the raw values| >> SHIFT), 1 and 0 by default).  -overlay then tints every class in its own colour and -save-parts
+// writes the class map; -keep-class C makes class C the region, for the clean-up steps, -keep / -remove, -mesh and -save-mask.
 // -crop X0 Y0 Z0 X1 Y1 Z1 (an inclusive voxel box, cut to the volume) and -resample MM [nearest|linear|area|auto] (the same spacing MM on
 // every axis, in the units of the file's spacing; auto = linear where the grid gets finer, area where it gets coarser) change the grid
 // right after the load, in command-line order (Canvas::CropVolume, ResampleVolume): everything after works on the new grid, drawn where
@@ -47,7 +53,7 @@
 // its connected parts (-conn) as a u32 label map, and -save-crop VOL MASK MARGIN the region's bounding box grown by MARGIN voxels, voxels
 // and mask, as MetaImage files (.mhd + .raw, or .mha).  Each prints one line with the dimensions, the spacing and the time.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -60,7 +66,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -72,6 +78,10 @@ int main(int argc, char** argv)
     float slicePos = 0.5f, slabThickness = 0.f;
     std::vector<uint32_t> picks;                                    // -pick: (x, y) pairs
     svr_hit_params hitParams = {SVR_HIT_OPACITY, 0.5f, 0.5f};
+    struct SeedStroke { int x, y, cls; double radius; };            // -seed X Y CLASS [RADIUS]: radius < 0 = twice the smallest spacing
+    std::vector<SeedStroke> seeds;
+    bool growcut = false;                                           // -growcut [GAIN SHIFT]: grow the strokes' classes; -keep-class C: one of them becomes the region
+    int growGain = 1, growShift = 0, keepClass = 0;                 // (the gain and shift of svr_region_growcut_params_default)
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
     bool threshold = false;                                         // -threshold: the whole window growLo .. growHi, no pick
@@ -234,6 +244,30 @@ int main(int argc, char** argv)
             grow = true;
             i += 4;
         }
+        else if (!strcmp(argv[i], "-seed") && i + 3 < argc) {
+            SeedStroke s = {atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]), -1.0};
+            if (s.x < 0 || s.y < 0 || s.cls < 1 || s.cls > (int)Canvas::SEED_MAX_CLASS) { fprintf(stderr, "-seed needs a pixel X Y >= 0 and a class 1 .. %u (got %s %s %s)\n", Canvas::SEED_MAX_CLASS, argv[i + 1], argv[i + 2], argv[i + 3]); return 2; }
+            i += 3;
+            char* end = nullptr;
+            if (i + 1 < argc && argv[i + 1][0] != '-' && (s.radius = strtod(argv[i + 1], &end), end != argv[i + 1] && !*end)) {
+                if (!(s.radius >= 0.0) || !std::isfinite(s.radius)) { fprintf(stderr, "-seed: the brush radius must be >= 0, in the units of the spacing (got %s)\n", argv[i + 1]); return 2; }
+                ++i;
+            }
+            else s.radius = -1.0;
+            seeds.push_back(s);
+        }
+        else if (!strcmp(argv[i], "-growcut")) {
+            growcut = true;
+            if (i + 2 < argc && argv[i + 1][0] != '-' && argv[i + 2][0] != '-') {
+                growGain = atoi(argv[i + 1]); growShift = atoi(argv[i + 2]);
+                if (growGain < 0 || growGain > 65535 || growShift < 0 || growShift > 15) { fprintf(stderr, "-growcut needs GAIN 0 .. 65535 and SHIFT 0 .. 15 (got %s %s)\n", argv[i + 1], argv[i + 2]); return 2; }
+                i += 2;
+            }
+        }
+        else if (!strcmp(argv[i], "-keep-class") && i + 1 < argc) {
+            keepClass = atoi(argv[++i]);
+            if (keepClass < 1 || keepClass > (int)Canvas::SEED_MAX_CLASS) { fprintf(stderr, "-keep-class needs a class 1 .. %u (got %s)\n", Canvas::SEED_MAX_CLASS, argv[i]); return 2; }
+        }
         else if (!strcmp(argv[i], "-conn") && i + 1 < argc) {
             growConn = atoi(argv[++i]);
             if (growConn != 6 && growConn != 18 && growConn != 26) { fprintf(stderr, "-conn needs 6, 18 or 26 (got %s)\n", argv[i]); return 2; }
@@ -330,22 +364,26 @@ int main(int argc, char** argv)
     }
     if ((slabMode || stack) && sliceAxis < 0) { fprintf(stderr, "-slab and -stack need -slice\n"); return 2; }
     if (grow && threshold) { fprintf(stderr, "-grow and -threshold exclude each other\n"); return 2; }
-    if (!cleanSteps.empty() && !grow && !threshold) {
+    if (growcut && seeds.empty()) { fprintf(stderr, "-growcut needs strokes: -seed X Y CLASS [RADIUS], at least one\n"); return 2; }
+    if (!seeds.empty() && !growcut) { fprintf(stderr, "-seed needs -growcut [GAIN SHIFT]\n"); return 2; }
+    if (keepClass && !growcut) { fprintf(stderr, "-keep-class needs -growcut [GAIN SHIFT]\n"); return 2; }
+    const bool anyRegion = grow || threshold || growcut;           // something makes a region: the steps after it have one to work on
+    if (!cleanSteps.empty() && !anyRegion) {
         if (cleanSteps[0].op <= -3) fprintf(stderr, "%s needs -grow X Y LO HI or -threshold LO HI\n", cleanSteps[0].name);
         else fprintf(stderr, "%s needs -grow X Y LO HI\n", cleanSteps[0].name);
         return 2;
     }
-    if (thickness && !grow && !threshold) { fprintf(stderr, "-thickness needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
-    if (threshold)
+    if (thickness && !anyRegion) { fprintf(stderr, "-thickness needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if (!grow)
         for (const CleanStep& c : cleanSteps)
             if (c.op == -1) { fprintf(stderr, "-detach starts from the picked voxel: it needs -grow X Y LO HI, not -threshold\n"); return 2; }
-    if ((overlay || overlayParts) && !grow && !threshold) { fprintf(stderr, "-overlay needs a region: -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if ((overlay || overlayParts) && !anyRegion) { fprintf(stderr, "-overlay needs a region: -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (overlayParts && !overlay) { fprintf(stderr, "-overlay-parts needs -overlay FILL EDGE\n"); return 2; }
     if (overlay && sliceAxis < 0 && !raycast && !(project && proj.mode != SVR_PROJ_MEAN)) { fprintf(stderr, "-overlay tints a slice or a picture with one hit per pixel: it needs -slice, -stack, -raycast, -mip or -iso L\n"); return 2; }
-    if (!meshFile.empty() && !grow && !threshold) { fprintf(stderr, "-mesh exports the surface of a region: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if (!meshFile.empty() && !anyRegion) { fprintf(stderr, "-mesh exports the surface of a region: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (meshRelax >= 0 && meshFile.empty()) { fprintf(stderr, "-relax needs -mesh FILE\n"); return 2; }
     if (showFiltered && filterSteps.empty()) { fprintf(stderr, "-show-filtered needs -median E N or -smooth SIGMA\n"); return 2; }
-    if ((!saveMaskFile.empty() || !savePartsFile.empty() || !saveCropVolume.empty()) && !grow && !threshold) {
+    if ((!saveMaskFile.empty() || !savePartsFile.empty() || !saveCropVolume.empty()) && !anyRegion) {
         fprintf(stderr, "-save-mask, -save-parts and -save-crop write a region: they need -grow X Y LO HI or -threshold LO HI\n");
         return 2;
     }
@@ -370,7 +408,7 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
-        canvas.volumeReader->KeepVoxels(grow || threshold || !filterSteps.empty() || !meshIsoFile.empty() || !gridSteps.empty() ||
+        canvas.volumeReader->KeepVoxels(anyRegion || !filterSteps.empty() || !meshIsoFile.empty() || !gridSteps.empty() ||
                                         !saveVolumeFile.empty());    // the region, filter, grid and save calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
@@ -466,32 +504,63 @@ int main(int argc, char** argv)
             return 0;
         }
 
-        if (grow || threshold) {
+        if (anyRegion) {
             // pick, segment, measure; what follows renders the kept (or the remaining) volume
             svr_hit hit = svr_hit();
-            if (grow && canvas.Pick((uint32_t)growX, (uint32_t)growY, &hit, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-            if (grow && hit.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-grow: %s at pixel %d %d\n", hit.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", growX, growY); return 1; }
-            svr_region_stats st;
-            if ((grow ? canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) : canvas.ThresholdRegion((uint32_t)growLo, (uint32_t)growHi, &st)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            svr_region_stats st = svr_region_stats();
             const double sp[3] = {canvas.Volume().spacing.x, canvas.Volume().spacing.y, canvas.Volume().spacing.z};
-            svr_region_measurement m;
-            if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-            if (threshold) {
-                uint32_t parts = 0u;
-                if (canvas.CountRegionParts(growConn, &parts) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-                if (st.status == SVR_REGION_STATUS_EMPTY)
-                    printf("threshold window %d..%d: no voxel lies in the window; the region is empty\n", growLo, growHi);
+            svr_region_measurement m = svr_region_measurement();
+            if (grow || threshold) {
+                if (grow && canvas.Pick((uint32_t)growX, (uint32_t)growY, &hit, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (grow && hit.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-grow: %s at pixel %d %d\n", hit.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", growX, growY); return 1; }
+                if ((grow ? canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) : canvas.ThresholdRegion((uint32_t)growLo, (uint32_t)growHi, &st)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (threshold) {
+                    uint32_t parts = 0u;
+                    if (canvas.CountRegionParts(growConn, &parts) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    if (st.status == SVR_REGION_STATUS_EMPTY)
+                        printf("threshold window %d..%d: no voxel lies in the window; the region is empty\n", growLo, growHi);
+                    else
+                        printf("threshold window %d..%d conn %d: %u parts, %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
+                               growLo, growHi, growConn, parts, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                               st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+                }
+                else if (st.status == SVR_REGION_STATUS_EMPTY)
+                    printf("grow %d %d window %d..%d: the picked voxel (value %g) is outside the window; the region is empty\n", growX, growY, growLo, growHi, hit.value);
                 else
-                    printf("threshold window %d..%d conn %d: %u parts, %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
-                           growLo, growHi, growConn, parts, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
-                           st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+                    printf("grow %d %d window %d..%d conn %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %u sweeps\n",
+                           growX, growY, growLo, growHi, growConn, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                           st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
             }
-            else if (st.status == SVR_REGION_STATUS_EMPTY)
-                printf("grow %d %d window %d..%d: the picked voxel (value %g) is outside the window; the region is empty\n", growX, growY, growLo, growHi, hit.value);
-            else
-                printf("grow %d %d window %d..%d conn %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %u sweeps\n",
-                       growX, growY, growLo, growHi, growConn, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
-                       st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
+            if (growcut) {
+                // strokes of classes on picked voxels, grown over the region made above or, without one, over the whole volume
+                const double brush = 2.0 * std::fmin(sp[0], std::fmin(sp[1], sp[2]));
+                for (const SeedStroke& s : seeds) {
+                    svr_hit sh = svr_hit();
+                    if (canvas.Pick((uint32_t)s.x, (uint32_t)s.y, &sh, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    if (sh.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-seed: %s at pixel %d %d\n", sh.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", s.x, s.y); return 1; }
+                    if (canvas.AddSeed(sh, (uint32_t)s.cls, s.radius < 0.0 ? brush : s.radius) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                }
+                svr_growcut_params gp;
+                svr_region_growcut_params_default(&gp, 26);
+                gp.contrast_gain = (uint32_t)growGain; gp.contrast_shift = (uint32_t)growShift;
+                uint32_t found = 0u;
+                const int rc = canvas.GrowFromSeeds(&gp, grow || threshold, &found);
+                if (rc != 0 && rc != SVR_REGION_ERR_RANGE) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                float ms = 0.f;
+                svr_region_growcut_last_ms(&ms);
+                printf("growcut gain %d shift %d, %zu strokes%s: %u classes own voxels; %.2f ms%s\n", growGain, growShift, seeds.size(),
+                       grow || threshold ? " inside the region" : "", found, ms, rc ? "; COSTS SATURATED: raise SHIFT or lower GAIN" : "");
+                if (keepClass) {
+                    if (canvas.KeepSeedClass((uint32_t)keepClass, &st) != 0 || svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    if (st.status == SVR_REGION_STATUS_EMPTY)
+                        printf("keep-class %d: the region is empty\n", keepClass);
+                    else
+                        printf("keep-class %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n", keepClass,
+                               (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1], st.bbox_min[2],
+                               st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+                }
+            }
             if (!cleanSteps.empty()) {
                 std::string done;
                 bool plainSteps = false;                           // a step other than -largest / -minsize / -ball-* / -split: those print their own lines
@@ -581,8 +650,10 @@ int main(int argc, char** argv)
             if (!savePartsFile.empty()) {
                 const auto t0 = std::chrono::steady_clock::now();
                 uint32_t parts = 0u;
-                if (canvas.LabelRegion(growConn, &parts) != 0 || canvas.SaveRegionParts(savePartsFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
-                printf("save-parts conn %d: %u parts\n", growConn, parts);
+                const bool classes = canvas.RegionLabels() && growcut && !keepClass && cleanSteps.empty();   // the class map of -growcut is still the region's
+                if ((!classes && canvas.LabelRegion(growConn, &parts) != 0) || canvas.SaveRegionParts(savePartsFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (classes) printf("save-parts: the classes of -growcut\n");
+                else printf("save-parts conn %d: %u parts\n", growConn, parts);
                 saved("save-parts", savePartsFile, canvas.volumeReader->dim, t0);
             }
             if (!saveCropVolume.empty()) {

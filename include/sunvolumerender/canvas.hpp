@@ -764,6 +764,110 @@ public:
         *length = d == SVR_GEO_NONE ? 0.0 : (double)d * unit;
         return d == SVR_GEO_NONE ? SVR_REGION_STATUS_EMPTY : SVR_REGION_STATUS_OK;
     }
+    // Grow from seeds (svr_region_growcut / _label_paint; include/svr_abi.h, "grow from seeds"): strokes of class 1, 2, ... on the picture,
+    // then every voxel goes to the class whose strokes reach it over the path that crosses the least image contrast.
+    // AddSeed: a stroke of class cls (1 .. SEED_MAX_CLASS) around the voxel of a pick (a FOUND record of Pick / HitMap): the ball of
+    // brush_radius (>= 0, finite, in the spacing's units; 0 = the voxel alone) painted on the Canvas's marker map.  The first class
+    // painted on a voxel stays.  The region, if there is one, stays as it is
+    static constexpr uint32_t SEED_MAX_CLASS = 255u;
+    int AddSeed(const svr_hit& hit, uint32_t cls, double brush_radius)
+    {
+        if (!ready || !SegVoxels() || hit.status != SVR_HIT_STATUS_FOUND) return -4;
+        if (cls == 0u || cls > SEED_MAX_CLASS || !(brush_radius >= 0.0) || !std::isfinite(brush_radius)) return -3;
+        const int* dim = volumeReader->dim;
+        const int32_t dims[3] = {dim[0], dim[1], dim[2]};
+        int32_t seed[3];
+        if (int rc = svr_region_seed_from_world(&deviceVolume, dim[0], dim[1], dim[2], &hit.position, seed)) return rc;
+        uint32_t w[3];
+        double unit = 0.0;
+        if (int rc = RegionDistanceUnits(w, &unit)) return rc;
+        const size_t n = (size_t)dim[0] * dim[1] * dim[2], words = (size_t)svr_region_mask_words(dim[0], dim[1], dim[2]);
+        if (!seedMarkers) {
+            seedMarkers = (uint32_t*)svr_device_malloc(n * sizeof(uint32_t));
+            if (!seedMarkers) return -4;
+            seedMaxClass = 0u;
+            if (int rc = svr_memset_device(seedMarkers, 0, n * sizeof(uint32_t))) { ClearSeeds(); return rc; }
+        }
+        uint32_t* masks = (uint32_t*)svr_device_malloc(2 * words * sizeof(uint32_t));      // the pick's voxel, and the ball around it
+        if (!masks) return -4;
+        const uint32_t bit = 1u << (seed[0] & 31);
+        const size_t word = ((size_t)seed[2] * dim[1] + seed[1]) * ((size_t)(dim[0] + 31) / 32) + (size_t)(seed[0] >> 5);
+        int rc = svr_memset_device(masks, 0, words * sizeof(uint32_t));
+        if (rc == 0) rc = svr_memcpy_h2d(masks + word, &bit, sizeof bit);
+        if (rc == 0) rc = svr_region_ball(masks, dim[0], dim[1], dim[2], SVR_MORPH_DILATE, w, LengthToR2(brush_radius, unit), masks + words);
+        if (rc == 0) rc = svr_region_label_paint(seedMarkers, dims, masks + words, cls, 1);
+        svr_device_free(masks);                                                           // (waits for the paint, which is asynchronous)
+        if (rc == 0 && cls > seedMaxClass) seedMaxClass = cls;
+        return rc;
+    }
+    void ClearSeeds()
+    {
+        if (seedMarkers) svr_device_free(seedMarkers);
+        seedMarkers = nullptr;
+        seedMaxClass = 0u;
+    }
+    // GrowFromSeeds: the classes of the strokes grown over the current region (inside_region) or over the whole volume.  params null =
+    // svr_region_growcut_params_default(26).  *classes_found (may be null) = the classes that own at least one voxel.  The class map
+    // becomes the region's labels -- OverlayRegionOnSlice, OverlayRegion and SaveRegionParts then show and save the classes -- and, grown
+    // over the whole volume, the region becomes every voxel that got a class.  The strokes stay, for more of them and another run.
+    // SVR_REGION_ERR_RANGE (costs reached the cap: raise contrast_shift) leaves the flagged result in place and is returned
+    int GrowFromSeeds(const svr_growcut_params* params, bool inside_region, uint32_t* classes_found)
+    {
+        if (!ready || !SegVoxels() || !seedMarkers || (inside_region && !haveRegion)) return -4;
+        const int* dim = volumeReader->dim;
+        const int32_t dims[3] = {dim[0], dim[1], dim[2]};
+        svr_growcut_params p;
+        if (params) p = *params;
+        else svr_region_growcut_params_default(&p, 26);
+        const size_t n = (size_t)dim[0] * dim[1] * dim[2];
+        if (!regionLabels) regionLabels = (uint32_t*)svr_device_malloc(n * sizeof(uint32_t));
+        if (!regionMask) regionMask = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
+        if (!regionLabels || !regionMask) return -4;
+        haveLabels = false;
+        const int grown = svr_region_growcut(SegVoxels(), dims, 1, seedMarkers, inside_region ? regionMask : nullptr, &p, nullptr, regionLabels, nullptr);
+        if (grown != 0 && grown != SVR_REGION_ERR_RANGE) return grown;
+        const uint32_t count = seedMaxClass;
+        std::vector<uint8_t> keep(count + 1u, 1);
+        std::vector<svr_region_component> table(count);
+        char* d = (char*)svr_device_malloc(count * sizeof(svr_region_component) + keep.size());
+        if (!d) return -4;
+        int rc = svr_region_label_table(regionLabels, nullptr, dim[0], dim[1], dim[2], 1, count, (svr_region_component*)d);
+        if (rc == 0) rc = svr_memcpy_d2h(table.data(), d, count * sizeof(svr_region_component));
+        if (rc == 0 && !inside_region) {                                                  // the region: every voxel that got a class
+            uint8_t* keep_device = (uint8_t*)(d + count * sizeof(svr_region_component));
+            rc = svr_memcpy_h2d(keep_device, keep.data(), keep.size());
+            if (rc == 0) rc = svr_region_select(regionLabels, dim[0], dim[1], dim[2], count, keep_device, regionMask);
+            if (rc == 0) rc = svr_device_synchronize();
+            haveRegion = rc == 0;
+            haveSeed = false;
+        }
+        svr_device_free(d);
+        if (rc != 0) return rc;
+        haveLabels = true;
+        labelClasses = count;
+        if (classes_found) {
+            *classes_found = 0u;
+            for (const svr_region_component& c : table) *classes_found += c.voxels ? 1u : 0u;
+        }
+        return grown;
+    }
+    // KeepSeedClass: the voxels of class cls of the last GrowFromSeeds become the region, like MorphRegion's result: ShowRegion,
+    // ExtractRegionSurface and SaveRegion follow.  The class map goes with the region it belonged to
+    int KeepSeedClass(uint32_t cls, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask() || !haveLabels || labelClasses == 0u) return -4;
+        if (cls == 0u || cls > labelClasses) return -3;
+        const int* dim = volumeReader->dim;
+        std::vector<uint8_t> keep(labelClasses + 1u, 0);
+        keep[cls] = 1;
+        uint8_t* keep_device = (uint8_t*)svr_device_malloc(keep.size());
+        if (!keep_device) return -4;
+        int rc = svr_memcpy_h2d(keep_device, keep.data(), keep.size());
+        if (rc == 0) rc = svr_region_select(regionLabels, dim[0], dim[1], dim[2], labelClasses, keep_device, regionWork);
+        svr_device_free(keep_device);                                                     // (waits for the select)
+        if (rc == 0) labelClasses = 0u;
+        return ReplaceRegion(rc, stats);
+    }
     // extension: the region as an overlay on what is drawn (svr_overlay_slice, svr_render_hits + svr_hit_ids + svr_overlay_ids;
     // include/svr_abi.h, "overlays").  The region itself stays as it is.
     // LabelRegion: numbers the connected components of the region 1 .. *count (connectivity 6, 18 or 26) and keeps the labels next to the
@@ -776,6 +880,7 @@ public:
         if (!regionLabels) return -4;
         const int rc = svr_region_label(regionMask, dim[0], dim[1], dim[2], connectivity, regionLabels, count);
         haveLabels = rc == 0;
+        labelClasses = 0u;                             // (parts, not the classes of GrowFromSeeds)
         return rc;
     }
     // OverlayRegionOnSlice: tints the slice image in img -- what RENDER_MODE_SLICE drew for `params` -- by the region: the labels when
@@ -1055,6 +1160,8 @@ private:
         if (regionWork) svr_device_free(regionWork);
         if (regionLabels) svr_device_free(regionLabels);
         regionTex = 0; regionMask = nullptr; regionWork = nullptr; regionLabels = nullptr; haveRegion = false; haveSeed = false; haveLabels = false;
+        labelClasses = 0u;
+        ClearSeeds();                                  // (the strokes were voxels of the volume that goes)
     }
     // a device u16 volume of the loaded dimensions becomes the texture every renderer draws (ShowRegion, ShowRegionDistance)
     int ShowVoxels(const uint16_t* shown)
@@ -1142,6 +1249,9 @@ private:
     uint32_t* regionWork = nullptr;                // the other mask buffer of the clean-up calls
     uint32_t* regionLabels = nullptr;              // LabelRegion's parts of the region (device, uint32 per voxel); freed with regionMask
     bool haveLabels = false;                       // false once anything replaces the region
+    uint32_t labelClasses = 0u;                    // > 0: the labels are the classes 1 .. labelClasses of GrowFromSeeds
+    uint32_t* seedMarkers = nullptr;               // AddSeed's marker map (device, uint32 per voxel): 0 = no stroke, else the class
+    uint32_t seedMaxClass = 0u;                    // the largest class painted on it
     int32_t regionSeed[3] = {0, 0, 0};             // GrowRegion's seed voxel and connectivity, for DetachRegion
     int regionConnectivity = 6;
     bool haveSeed = false;                         // false after ThresholdRegion: the region then comes from no pick

@@ -982,6 +982,63 @@ int svr_region_zone_cut(const uint32_t* zones_device, int nx, int ny, int nz, in
  * svr_region_seed_labels / svr_region_zone_cut, whichever came last (waits for it) */
 int svr_region_geodesic_last_ms(float* ms);
 
+/* ---- grow from seeds: multi-label segmentation by image-weighted shortest paths (csrc/svr_growcut.hip) ----
+ * The user marks a few voxels of every class (1 = the object, 2 = the background, ...); every voxel of the domain then goes to the class
+ * whose markers reach it over the path that crosses the least image contrast: Fast GrowCut (Zhu et al.), the shortest-path form of
+ * GrowCut.  Masks, label, cost and zone arrays are as in the geodesic section; dimensions are const int32_t dims[3] = (x, y, z).
+ * Integers only; every result is exact and unique, whatever order the GPU works in.
+ * THE COST OF A MOVE between allowed neighbours u, v of class c (the classes and `step_weights` of the geodesic section; 0 forbids a
+ *   class):  cost(u, v) = step_weights[c] + contrast_gain * (|I(u) - I(v)| >> contrast_shift),  I the raw u16 voxel as in svr_volume_rank.
+ *   It is symmetric and at least 1.  contrast_gain lies in 0 .. 65535, contrast_shift in 0 .. 15, and a call is refused when
+ *   wmax + contrast_gain * (65535 >> contrast_shift) > 0x7FFFFFFF: dist(u) + cost then stays below 2^33 and 64-bit arithmetic needs no
+ *   further check.
+ * THE RESULT, with sat(x) = min(x, SVR_GROWCUT_CAP): key(v) = (cost, zone) is the lexicographic minimum, over all walks inside the domain
+ *   from a source to v, of (sat(cost of the walk), label of its source).  Sources are the voxels of the domain with a non-zero marker
+ *   label; their key is (0, label).  Outside the domain and where no source reaches, cost is SVR_GEO_NONE and zone 0.  A NULL domain means
+ *   the whole volume.  Either output may be NULL, not both; zones_device may be marker_labels_device itself.  With no source at all every
+ *   cost is SVR_GEO_NONE, every zone 0, and the return is 0.  With contrast_gain = 0 the result is svr_region_geodesic's, bit for bit.
+ *   voxels is host memory, or device memory with src_is_device; a host source is uploaded once.  Workspace 8 bytes per voxel; the call
+ *   synchronises the stream.  *info_or_null receives the sweeps launched, the voxels of the domain that no source reaches, and the
+ *   voxels whose cost is the cap.
+ * SATURATION: the a-priori bound of the geodesic call, wmax (voxels - 1) <= 0xFFFFFFFE, is NOT applied here -- it would allow 31 per move
+ *   at 512^3.  The device adds with saturation at SVR_GROWCUT_CAP instead.  Since sat(sat(a) + w) = sat(a + w), saturating after every
+ *   move equals saturating a walk's sum, so every key ever stored is the (sat(cost), label) of a real walk, and the state in which no
+ *   voxel can fall is the minimum over walks above: one solution, reached in any order from "all NONE" (DESIGN.md 8q).  If info->saturated
+ *   is non-zero the call returns SVR_REGION_ERR_RANGE and the error text says to raise contrast_shift or lower contrast_gain; the outputs
+ *   then hold the saturated solution above -- defined, but flagged: on the plateau cost = CAP the zone is the smallest label that reaches
+ *   it at all.
+ * SWEEPS: params->max_sweeps = 0 means svr_region_geodesic_default_max_sweeps of the dimensions; at the cap the call returns
+ *   SVR_REGION_ERR_SWEEPS as svr_region_geodesic does (outputs are upper bounds and NOT valid; info->sweeps holds the launches).
+ * PARAMS DEFAULT (plain host code): weight 1 on the classes of connectivity 6 / 18 / 26 and 0 on the others, gain 1, shift 0, max_sweeps 0.
+ * SEED CLASSES: zero-fills labels_device and gives the voxel of seed i (HOST arrays of (x, y, z) and of classes) the label classes[i]; of
+ *   several seeds on one voxel the lowest i wins.  Asynchronous.
+ * LABEL PAINT: writes `label` (non-zero) on every voxel whose mask bit is set, or only where the current label is 0 when only_unlabelled
+ *   is set; padding bits are ignored.  This is how a brush stroke becomes a marker: a seed mask dilated by svr_region_ball, or any mask
+ *   the chain made.  Asynchronous.
+ * REFUSED, before the device is touched and with nothing written: a null pointer where one is required, or both outputs NULL (-4); a
+ *   dimension <= 0 or more than 2^31 voxels (-6); (-3) all seven weights 0, a gain above 65535, a shift above 15, the move-cost bound, a
+ *   connectivity other than 6 / 18 / 26, a class or label of 0, nseeds == 0 or > SVR_REGION_MAX_SEEDS, a seed outside the volume, an
+ *   output that overlaps an input other than zones over marker labels, labels that overlap the mask. */
+typedef struct svr_growcut_params {
+    uint32_t step_weights[7];   /* per move class x, y, z, xy, xz, yz, xyz as in svr_region_geodesic; 0 forbids the class */
+    uint32_t contrast_gain;     /* 0 .. 65535 */
+    uint32_t contrast_shift;    /* 0 .. 15 */
+    uint32_t max_sweeps;        /* 0 = svr_region_geodesic_default_max_sweeps of the dims */
+} svr_growcut_params;           /* 40 bytes */
+typedef struct svr_growcut_info { uint32_t sweeps; uint64_t unreached; uint64_t saturated; } svr_growcut_info;   /* 24 bytes */
+#define SVR_GROWCUT_CAP 0xFFFFFFFEu
+#define SVR_REGION_ERR_RANGE (-12)   /* costs reached SVR_GROWCUT_CAP: the outputs hold the saturated solution */
+
+int svr_region_growcut_params_default(svr_growcut_params* p, int connectivity);
+int svr_region_growcut(const uint16_t* voxels, const int32_t dims[3], int src_is_device,
+                       const uint32_t* marker_labels_device, const uint32_t* domain_mask_device_or_null,
+                       const svr_growcut_params* params,
+                       uint32_t* cost_device_or_null, uint32_t* zones_device_or_null, svr_growcut_info* info_or_null);
+int svr_region_seed_classes(const int32_t* seeds_xyz, const uint32_t* classes, uint32_t nseeds, const int32_t dims[3], uint32_t* labels_device);
+int svr_region_label_paint(uint32_t* labels_device, const int32_t dims[3], const uint32_t* mask_device, uint32_t label, int only_unlabelled);
+/* HIP-event time of the device work of the last svr_region_growcut / _seed_classes / _label_paint, whichever came last (waits for it) */
+int svr_region_growcut_last_ms(float* ms);
+
 /* ---- overlays: region masks and label maps on slices and 3D views (csrc/svr_overlay.hip) ----
  * Per-pixel region ids, outlines, and a blend onto the RGBA8 images that svr_render_slice, svr_render_slice_stack, render_raycasting and
  * svr_render_projection write.  Integers only, but for the sample points of a slice, which are the float32 points of the slice section;

@@ -302,6 +302,22 @@ GEO_NONE = 0xFFFFFFFF
 GEO_TILE = (32, 8, 8)     # the relaxation tile of csrc/svr_geodesic.hip in voxels (x, y, z)
 
 
+class GrowcutParams(C.Structure):  # svr_growcut_params
+    _fields_ = [("step_weights", C.c_uint32 * 7), ("contrast_gain", C.c_uint32), ("contrast_shift", C.c_uint32), ("max_sweeps", C.c_uint32)]
+
+
+class GrowcutInfo(C.Structure):  # svr_growcut_info
+    _fields_ = [("sweeps", C.c_uint32), ("unreached", C.c_uint64), ("saturated", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+svr_growcut_params, svr_growcut_info = GrowcutParams, GrowcutInfo
+GROWCUT_CAP = 0xFFFFFFFE
+REGION_ERR_RANGE = -12
+
+
 class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
     _fields_ = [("mask_device", C.c_void_p), ("labels_device", C.c_void_p)]
 
@@ -566,6 +582,11 @@ PROTOTYPES = {
                                    _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "svr_region_zone_cut": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "svr_region_geodesic_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_region_growcut_params_default": (C.c_int, [_P(GrowcutParams), C.c_int]),
+    "svr_region_growcut": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, _P(GrowcutParams), C.c_void_p, C.c_void_p, _P(GrowcutInfo)]),
+    "svr_region_seed_classes": (C.c_int, [_P(C.c_int32), _P(C.c_uint32), C.c_uint32, _P(C.c_int32), C.c_void_p]),
+    "svr_region_label_paint": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_void_p, C.c_uint32, C.c_int]),
+    "svr_region_growcut_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
     "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
     "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,

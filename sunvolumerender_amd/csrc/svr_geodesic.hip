@@ -32,6 +32,7 @@
 
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
+#include "svr_geo_keys.hpp"         // GeoWeights, move_class, the whole-pair accesses lds_get / lds_put / key_get / key_put
 #include "svr_mask.hpp"             // RegionDims, lane_at, half_ballot, the grids
 #include "svr_sweep.hpp"
 #include "svr_volume_host.hpp"
@@ -46,21 +47,7 @@ static_assert(GEO_THREADS == 256 && GX == 32, "the lane mapping assumes a tile o
 constexpr uint64_t KEY_NONE = ~0ull;
 constexpr int LANE_THREADS = MASK_THREADS;               // the one-lane-per-voxel kernels
 
-// w[c]: the weight of move class c (x, y, z, xy, xz, yz, xyz); reach bit c: a tile in a direction of class c can see this tile's keys
-struct GeoWeights { uint32_t w[7]; uint32_t reach; };
 struct GeoSeeds { uint32_t n; uint32_t at[SVR_REGION_MAX_SEEDS]; };   // at[i] = the voxel of seed i, or ~0 if a lower seed has it
-
-// the class of a move or direction from the coordinates it changes
-__host__ __device__ constexpr int move_class(int dx, int dy, int dz)
-{
-    const int m = (dx != 0 ? 1 : 0) | (dy != 0 ? 2 : 0) | (dz != 0 ? 4 : 0);
-    return m == 1 ? 0 : m == 2 ? 1 : m == 4 ? 2 : m == 3 ? 3 : m == 5 ? 4 : m == 6 ? 5 : 6;
-}
-
-__device__ inline uint64_t lds_get(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void lds_put(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline uint64_t key_get(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void key_put(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(LANE_THREADS) void k_geo_init(const uint32_t* labels, const uint32_t* __restrict__ mask, RegionDims d, size_t words, int nty,
                                                            uint64_t* __restrict__ keys, uint32_t* __restrict__ dirty)
@@ -234,12 +221,7 @@ int check_step_weights(const char* who, const uint32_t* weights_or_null, int con
     if (!step_weights_fit(w64, nx, ny, nz))
         return failf(-3, "%s: the longest path of %d x %d x %d under step weights %u, %u, %u, %u, %u, %u, %u would overflow 32 bits", who, nx, ny, nz, out->w[0],
                      out->w[1], out->w[2], out->w[3], out->w[4], out->w[5], out->w[6]);
-    // a tile in a direction that changes the coordinates S sees this tile through the moves that change at least S
-    static const int bits[7] = {1, 2, 4, 3, 5, 6, 7};
-    out->reach = 0u;
-    for (int dir = 0; dir < 7; ++dir)
-        for (int c = 0; c < 7; ++c)
-            if (out->w[c] && (bits[c] & bits[dir]) == bits[dir]) out->reach |= 1u << dir;
+    out->reach = geo_reach(out->w);
     return 0;
 }
 

@@ -744,6 +744,106 @@ class Device:
         self.check(self.lib.svr_region_geodesic_last_ms(C.byref(ms)))
         return float(ms.value)
 
+    # ---- grow from seeds (svr_region_growcut / _seed_classes / _label_paint) ----
+    def growcut_params(self, step_weights=None, connectivity: int = 26, gain: int = 1, shift: int = 0, max_sweeps: int = 0) -> abi.GrowcutParams:
+        """svr_region_growcut_params_default of the connectivity with the weights (if given), gain, shift and cap replaced."""
+        p = abi.GrowcutParams()
+        self.check(self.lib.svr_region_growcut_params_default(C.byref(p), int(connectivity)))
+        if step_weights is not None:
+            for c in range(7):
+                p.step_weights[c] = int(step_weights[c])
+        p.contrast_gain, p.contrast_shift, p.max_sweeps = int(gain), int(shift), int(max_sweeps)
+        return p
+
+    def region_growcut(self, vox, labels, domain=None, shape=None, step_weights=None, connectivity: int = 26, gain: int = 1, shift: int = 0,
+                       max_sweeps: int = 0, want_cost: bool = True, want_zones: bool = True, cost_ptr: Optional[int] = None,
+                       zones_ptr: Optional[int] = None):
+        """svr_region_growcut: (cost, zones, info).  Every voxel of `domain` (a bool array [nz][ny][nx] or a device pointer; None = the
+        whole volume) gets the class of the marker (non-zero entries of `labels`, a uint32 array or a device pointer) that reaches it
+        over the cheapest path, a move costing step_weights[class] + gain * (|I(u) - I(v)| >> shift) on the raw voxels of `vox` (a host
+        u16 array, or a device pointer with shape=).  step_weights None = 1 on the move classes of `connectivity`.  GEO_NONE / 0 where no
+        marker reaches.  An output that is not wanted is None; with cost_ptr / zones_ptr (device buffers of 4 nx ny nz bytes; zones_ptr
+        may be the labels' own pointer) the result stays on the device and the pointer is returned.  info is the svr_growcut_info.  A
+        failure raises SvrError with .code and .info set; for REGION_ERR_RANGE (costs reached GROWCUT_CAP) .cost and .zones hold the
+        saturated solution as well."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        lbuf, lshape, lowned = self._region_labels(labels, (nz, ny, nx))
+        if tuple(lshape) != (nz, ny, nx):
+            raise ValueError("the volume and the labels differ in shape")
+        mbuf, mowned = (None, False) if domain is None else self._region_mask(domain, (nz, ny, nx))
+        p = self.growcut_params(step_weights, connectivity, gain, shift, max_sweeps)
+        dims = (C.c_int32 * 3)(nx, ny, nz)
+        nbytes = 4 * max(nx * ny * nz, 1)
+        cout = cost_ptr if cost_ptr is not None else (self.malloc(nbytes) if want_cost else None)
+        zout = zones_ptr if zones_ptr is not None else (self.malloc(nbytes) if want_zones else None)
+        info = abi.GrowcutInfo()
+
+        def results():
+            cost = cost_ptr if cost_ptr is not None else (self.to_host(cout, (nz, ny, nx), np.uint32) if cout is not None else None)
+            zones = zones_ptr if zones_ptr is not None else (self.to_host(zout, (nz, ny, nx), np.uint32) if zout is not None else None)
+            return cost, zones
+        try:
+            rc = self.lib.svr_region_growcut(src, dims, on_dev, C.c_void_p(lbuf), None if mbuf is None else C.c_void_p(mbuf), C.byref(p),
+                                             None if cout is None else C.c_void_p(cout), None if zout is None else C.c_void_p(zout), C.byref(info))
+            try:
+                self.check(rc)
+            except SvrError as e:
+                e.code, e.info = int(rc), info
+                if rc == abi.REGION_ERR_RANGE:
+                    e.cost, e.zones = results()
+                raise
+            return results() + (info,)
+        finally:
+            if lowned:
+                self.free(lbuf)
+            if mowned:
+                self.free(mbuf)
+            if cost_ptr is None and cout is not None:
+                self.free(cout)
+            if zones_ptr is None and zout is not None:
+                self.free(zout)
+
+    def region_seed_classes(self, seeds, classes, shape, out_ptr: Optional[int] = None):
+        """svr_region_seed_classes: a zero uint32 array [nz][ny][nx] with classes[i] on the voxel (x, y, z) of seed i (the lowest i of
+        several on a voxel).  Returns the array, or out_ptr itself when a device buffer of 4 nx ny nz bytes is given."""
+        nz, ny, nx = (int(n) for n in shape)
+        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        cls = np.ascontiguousarray(classes, dtype=np.uint32).reshape(-1)
+        if len(cls) != len(xyz):
+            raise ValueError("one class per seed")
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
+        try:
+            self.check(self.lib.svr_region_seed_classes(xyz.ctypes.data_as(C.POINTER(C.c_int32)), cls.ctypes.data_as(C.POINTER(C.c_uint32)), len(xyz),
+                                                        (C.c_int32 * 3)(nx, ny, nz), C.c_void_p(out)))
+            self.synchronize()
+            if out_ptr is not None:
+                return out_ptr
+            return self.to_host(out, (nz, ny, nx), np.uint32)
+        finally:
+            if out_ptr is None:
+                self.free(out)
+
+    def region_label_paint(self, labels, mask, label: int, only_unlabelled: bool = False, shape=None):
+        """svr_region_label_paint: `label` on every voxel of `mask` (a bool array or a device pointer), or only where the label is still 0.
+        labels: a uint32 array [nz][ny][nx] (the painted copy is returned) or a device pointer with shape= (painted in place and
+        returned)."""
+        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, shape)
+        mbuf, mowned = self._region_mask(mask, (nz, ny, nx))
+        try:
+            self.check(self.lib.svr_region_label_paint(C.c_void_p(lbuf), (C.c_int32 * 3)(nx, ny, nz), C.c_void_p(mbuf), int(label), int(bool(only_unlabelled))))
+            self.synchronize()
+            return self.to_host(lbuf, (nz, ny, nx), np.uint32) if lowned else lbuf
+        finally:
+            if lowned:
+                self.free(lbuf)
+            if mowned:
+                self.free(mbuf)
+
+    def region_growcut_last_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_region_growcut_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
     def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
         """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
