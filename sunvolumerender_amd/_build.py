@@ -24,7 +24,7 @@ CONTRACT_FLAGS = {"-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-r
 # (full -ffast-math, and hardware exp / sin / cos in place of the polynomial versions, cost 50-60 spilled VGPRs in this kernel
 # and made it 38 % SLOWER; the walk's logarithm + reciprocal division + contraction keep the register allocation)
 FAST_FLAGS = ["-ffp-contract=fast", "-freciprocal-math", "-fno-signed-zeros"]
-HIP_HEADERS = ["svr_trace_tile.hip", "svr_trace_lm.hip", "svr_trace_env.hip", "svr_math.hpp", "svr_scene.hpp", "svr_device.hpp", "svr_kernels.hpp", "svr_kernel_common.hpp", "svr_walk.hpp", "svr_lanes.hpp", "svr_tile_tasks.hpp", "svr_primary.hpp", "svr_denoise.hpp", "svr_noise.hpp", "svr_project.hpp", "svr_slice.hpp", "svr_chain.hpp", "svr_hits.hpp", "svr_march.hpp", "svr_path.hpp", "svr_region_grow.hpp", "svr_rank_select.hpp", "svr_sweep.hpp", "svr_mask.hpp", "svr_volume_host.hpp", "svr_scan.hpp", "svr_api_state.hpp", "svr_geo_keys.hpp"]
+HIP_HEADERS = ["svr_trace_tile.hip", "svr_trace_lm.hip", "svr_trace_env.hip", "svr_math.hpp", "svr_scene.hpp", "svr_device.hpp", "svr_kernels.hpp", "svr_kernel_common.hpp", "svr_walk.hpp", "svr_lanes.hpp", "svr_tile_tasks.hpp", "svr_primary.hpp", "svr_denoise.hpp", "svr_noise.hpp", "svr_project.hpp", "svr_slice.hpp", "svr_chain.hpp", "svr_hits.hpp", "svr_march.hpp", "svr_path.hpp", "svr_region_grow.hpp", "svr_rank_select.hpp", "svr_sweep.hpp", "svr_mask.hpp", "svr_volume_host.hpp", "svr_scan.hpp", "svr_api_state.hpp", "svr_geo_relax.hpp"]
 
 HIPCC_FLAGS = [
     "-O3",

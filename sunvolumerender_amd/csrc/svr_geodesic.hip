@@ -1,170 +1,18 @@
 // svr_geodesic.hip -- geodesic distances and influence zones inside region masks, and the splitting of a region at its necks that they
 // make possible (svr_region_geodesic, _seed_labels, _geodesic_weights, _split, _zone_cut; the contract is in include/svr_abi.h, the design
-// in DESIGN.md 8m).  Integers only, on the mask layout of svr_mask.hpp.
-//
-// Every voxel has one packed key (dist << 32) | zone in a workspace of 8 bytes per voxel; ~0 = "outside the domain or not reached".  A
-// source has (0, label); every other voxel of the domain wants the lexicographic minimum over its allowed neighbours u of
-// (dist(u) + w(u -> v), zone(u)) -- a plain unsigned 64-bit minimum of key(u) + (w << 32).  That system has one solution (induction on
-// dist: weights are >= 1), and relaxing voxels in ANY order from ~0 reaches it: a key only falls, every key ever stored is the (cost,
-// source label) of a real path, so it never falls below the solution, and a state in which no voxel can fall is the solution.
-//   k_geo_init    one lane per voxel: the key from the label and the domain bit; a source marks its tile dirty.
-//   k_geo_relax   one block per dirty tile of 32 x 8 x 8 voxels (a tile is one mask word wide).  The keys of the tile and of a halo of one
-//     voxel go to LDS (34 x 10 x 10 x 8 B = 27200 B: rows of consecutive 8-byte words, which ds_read_b64 serves a half-wave at a time
-//     without bank conflicts); a thread owns the column (lx, ly, 0 .. 7) and holds its eight domain bits in a register.  The block relaxes
-//     its own voxels in place until an iteration lowers none, stores the voxels that fell, and marks the neighbour tiles that see a face
-//     layer with a fallen voxel dirty for the next sweep -- the dirty-map protocol of svr_region_grow.hpp and the host loop of svr_sweep.hpp.
-//   k_geo_finish  one lane per voxel: splits the keys into dist and zones and counts the unreached voxels of the domain.
-//   k_geo_seeds, k_zone_cut: one lane per seed / per voxel.
-// ONE WRITER, WHOLE PAIRS: a key in global memory is written by its tile's block alone, and every access to a key that another thread
-//   may write -- halo loads and result stores in global memory, all LDS traffic of the relaxation -- is ONE aligned 64-bit atomic access
-//   (relaxed; agent scope in global memory, workgroup scope in LDS), so a reader gets distance and zone from the same write.  A stale
-//   key only delays a voxel (its tile is marked dirty by whoever lowers the key later); a torn one could pair a new distance with an
-//   old, smaller label and would never be repaired.
-// NO OVERFLOW: the host refuses wmax (voxels - 1) > 0xFFFFFFFE; a stored key is the cost of a simple path, so key + (w << 32) wraps only
-//   for the key ~0, which the comparison `candidate > key` filters out.
-// TERMINATION: no lane or block waits for another.  The relaxation of a tile works on a halo that is fixed in LDS, and an iteration
-//   relaxes every voxel from values no worse than a Jacobi step would see, so it is over after at most one iteration per voxel of the
-//   tile (Bellman-Ford); the loop is also counted against that number.
+// in DESIGN.md 8m).  The keys, the relaxation under PlainCost and its host driver are in svr_geo_relax.hpp; here are the step weights
+// and their overflow bound, the default sweep cap, the split and k_zone_cut (one lane per voxel).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
 #include "../../include/svr_abi.h"
 #include "svr_internal.hpp"
-#include "svr_geo_keys.hpp"         // GeoWeights, move_class, the whole-pair accesses lds_get / lds_put / key_get / key_put
-#include "svr_mask.hpp"             // RegionDims, lane_at, half_ballot, the grids
-#include "svr_sweep.hpp"
-#include "svr_volume_host.hpp"
+#include "svr_geo_relax.hpp"        // PlainCost, geo_run, place_seeds, check_geo_outputs, classes_of; the mask layout and the host scaffolding
 
 using svr::failf;
 
 namespace {
-
-constexpr int GX = 32, GY = 8, GZ = 8;                   // tile in voxels; GX = one mask word
-constexpr int GEO_THREADS = GX * GY;                     // one thread per column of GZ voxels
-static_assert(GEO_THREADS == 256 && GX == 32, "the lane mapping assumes a tile one mask word wide and 256 threads");
-constexpr uint64_t KEY_NONE = ~0ull;
-constexpr int LANE_THREADS = MASK_THREADS;               // the one-lane-per-voxel kernels
-
-struct GeoSeeds { uint32_t n; uint32_t at[SVR_REGION_MAX_SEEDS]; };   // at[i] = the voxel of seed i, or ~0 if a lower seed has it
-
-__global__ __launch_bounds__(LANE_THREADS) void k_geo_init(const uint32_t* labels, const uint32_t* __restrict__ mask, RegionDims d, size_t words, int nty,
-                                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ dirty)
-{
-    const LaneAt a = lane_at(d, words);
-    if (!a.inside) return;
-    const uint32_t lab = labels[a.v];
-    const bool source = lab != 0u && ((mask[a.i] >> a.bit) & 1u);
-    keys[a.v] = source ? (uint64_t)lab : KEY_NONE;
-    if (source) dirty[((size_t)(a.z / GZ) * nty + a.y / GY) * d.wx + a.x / GX] = 1u;
-}
-
-__global__ __launch_bounds__(GEO_THREADS) void k_geo_relax(uint64_t* keys, const uint32_t* __restrict__ mask, RegionDims d, GeoWeights gw, int nty, int ntz,
-                                                           uint32_t* dirty_cur, uint32_t* dirty_next, uint32_t* added)
-{
-    const size_t tile = blockIdx.x;
-    if (!dirty_cur[tile]) return;
-    __shared__ uint64_t K[GZ + 2][GY + 2][GX + 2];
-    __shared__ uint32_t s_flags;
-    const int tid = threadIdx.x;
-    const int ntx = d.wx;
-    const int tx = (int)(tile % ntx), ty = (int)((tile / ntx) % nty), tz = (int)(tile / ((size_t)ntx * nty));
-    for (int i = tid; i < (GZ + 2) * (GY + 2) * (GX + 2); i += GEO_THREADS) {
-        const int hx = i % (GX + 2), hy = (i / (GX + 2)) % (GY + 2), hz = i / ((GX + 2) * (GY + 2));
-        const int gx = tx * GX + hx - 1, gy = ty * GY + hy - 1, gz = tz * GZ + hz - 1;
-        uint64_t k = KEY_NONE;
-        if (gx >= 0 && gx < d.nx && gy >= 0 && gy < d.ny && gz >= 0 && gz < d.nz) k = key_get(&keys[((size_t)gz * d.ny + gy) * d.nx + gx]);
-        K[hz][hy][hx] = k;
-    }
-    const int lx = tid % GX, ly = tid / GX;
-    const int gx = tx * GX + lx, gy = ty * GY + ly;
-    uint32_t dom = 0u;                                   // bit lz: voxel (lx, ly, lz) of the tile is in the domain
-    if (gx < d.nx && gy < d.ny)
-        for (int lz = 0; lz < GZ; ++lz) {
-            const int gz = tz * GZ + lz;
-            if (gz < d.nz) dom |= ((mask[((size_t)gz * d.ny + gy) * d.wx + tx] >> lx) & 1u) << lz;
-        }
-    if (tid == 0) s_flags = 0u;
-    __syncthreads();
-    if (tid == 0) dirty_cur[tile] = 0u;                  // (every thread has read the flag: this buffer is the sweep after next's)
-    uint32_t fell = 0u;                                  // bit lz: this thread lowered voxel (lx, ly, lz)
-    for (int it = 0; it <= GX * GY * GZ; ++it) {
-        int changed = 0;
-#pragma unroll 1
-        for (int lz = 0; lz < GZ; ++lz) {
-            if (!((dom >> lz) & 1u)) continue;
-            uint64_t* const own = &K[lz + 1][ly + 1][lx + 1];
-            const uint64_t k0 = lds_get(own);
-            uint64_t best = k0;
-#pragma unroll
-            for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-                for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        if (dx == 0 && dy == 0 && dz == 0) continue;
-                        const uint32_t w = gw.w[move_class(dx, dy, dz)];
-                        if (w == 0u) continue;
-                        const uint64_t u = lds_get(own + (dz * (GY + 2) + dy) * (GX + 2) + dx);
-                        const uint64_t c = u + ((uint64_t)w << 32);                  // wraps only for u = ~0 (see the head of the file)
-                        if (c > u && c < best) best = c;
-                    }
-            if (best < k0) {
-                lds_put(own, best);
-                fell |= 1u << lz;
-                changed = 1;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
-    if (fell) {
-        uint32_t f = 64u;
-        if (lx == 0) f |= 1u;
-        if (lx == GX - 1) f |= 2u;
-        if (ly == 0) f |= 4u;
-        if (ly == GY - 1) f |= 8u;
-        if (fell & 1u) f |= 16u;
-        if (fell >> (GZ - 1)) f |= 32u;
-        for (int lz = 0; lz < GZ; ++lz)
-            if ((fell >> lz) & 1u) key_put(&keys[((size_t)(tz * GZ + lz) * d.ny + gy) * d.nx + gx], K[lz + 1][ly + 1][lx + 1]);
-        atomicOr(&s_flags, f);
-    }
-    __syncthreads();
-    const uint32_t flags = s_flags;
-    if (tid == 0 && (flags & 64u)) atomicAdd(added, 1u);
-    if (tid < 27) {
-        // the neighbour tile in direction (dx, dy, dz) sees the layers of this tile that lie on all the faces the direction names
-        const int dx = tid % 3 - 1, dy = (tid / 3) % 3 - 1, dz = tid / 9 - 1;
-        if ((dx == 0 && dy == 0 && dz == 0) || !((gw.reach >> move_class(dx, dy, dz)) & 1u)) return;
-        const uint32_t need = (dx < 0 ? 1u : dx > 0 ? 2u : 0u) | (dy < 0 ? 4u : dy > 0 ? 8u : 0u) | (dz < 0 ? 16u : dz > 0 ? 32u : 0u);
-        const int ax = tx + dx, ay = ty + dy, az = tz + dz;
-        if ((flags & need) == need && ax >= 0 && ax < ntx && ay >= 0 && ay < nty && az >= 0 && az < ntz)
-            dirty_next[((size_t)az * nty + ay) * ntx + ax] = 1u;
-    }
-}
-
-__global__ __launch_bounds__(LANE_THREADS) void k_geo_finish(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ mask, RegionDims d, size_t words,
-                                                             uint32_t* dist, uint32_t* zones, uint32_t* unreached)
-{
-    const LaneAt a = lane_at(d, words);
-    bool lost = false;
-    if (a.inside) {
-        const uint64_t k = keys[a.v];
-        const uint32_t dd = (uint32_t)(k >> 32);
-        if (dist) dist[a.v] = dd;
-        if (zones) zones[a.v] = dd == SVR_GEO_NONE ? 0u : (uint32_t)k;
-        lost = dd == SVR_GEO_NONE && ((mask[a.i] >> a.bit) & 1u);
-    }
-    const unsigned long long b = __ballot(lost);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(unreached, (uint32_t)__popcll(b));
-}
-
-__global__ void k_geo_seeds(GeoSeeds s, uint32_t* __restrict__ labels)
-{
-    const uint32_t i = threadIdx.x;
-    if (i < s.n && s.at[i] != 0xFFFFFFFFu) labels[s.at[i]] = i + 1u;
-}
 
 template <int CONN>
 __global__ __launch_bounds__(LANE_THREADS) void k_zone_cut(const uint32_t* __restrict__ zones, RegionDims d, size_t words, uint32_t* __restrict__ out)
@@ -195,8 +43,6 @@ __global__ __launch_bounds__(LANE_THREADS) void k_zone_cut(const uint32_t* __res
 
 // ---------------- host side ----------------
 constexpr uint32_t CHAMFER[7] = {3u, 3u, 3u, 4u, 4u, 4u, 5u};
-
-int classes_of(int connectivity) { return connectivity == 6 ? 3 : connectivity == 18 ? 6 : 7; }
 
 // wmax (voxels - 1) <= 0xFFFFFFFE: the cost of the longest simple path fits (voxels <= 2^31, wmax < 2^32: the product is below 2^63)
 bool step_weights_fit(const uint64_t w[7], int nx, int ny, int nz)
@@ -229,43 +75,17 @@ uint64_t geo_tiles(int nx, int ny, int nz) { return (uint64_t)((nx + GX - 1) / G
 
 CallEvents g_events;                                     // around the device work of the last call of this file (svr_region_geodesic_last_ms)
 
-// the checked core of svr_region_geodesic and of the zones step of svr_region_split.  *unreached (may be NULL) = the voxels of the
-// domain that no source reaches.  Synchronises the stream.
-int geodesic_run(const char* who, const uint32_t* labels, const uint32_t* mask, const RegionDims& d, const GeoWeights& gw, uint32_t max_sweeps, uint32_t* dist,
+// geo_run under PlainCost.  *sweeps_out and *unreached (either may be NULL) are written when the sweeps ran; the count of capped voxels
+// is ignored: a geodesic distance may be 0xFFFFFFFE.
+int geodesic_run(const char* who, const uint32_t* labels, const uint32_t* mask, const RegionDims& d, const PlainCost& cost, uint32_t max_sweeps, uint32_t* dist,
                  uint32_t* zones, uint32_t* unreached, uint32_t* sweeps_out)
 {
-    if (svr::ensure_ready()) return svr_last_error_code();
-    hipStream_t st = svr::current_stream();
-    const size_t n = (size_t)d.nx * d.ny * d.nz, words = mask_words(d);
-    const int nty = (d.ny + GY - 1) / GY, ntz = (d.nz + GZ - 1) / GZ;
-    const size_t tiles = (size_t)d.wx * nty * ntz;
-    const uint32_t cap = max_sweeps ? max_sweeps : svr_region_geodesic_default_max_sweeps(d.nx, d.ny, d.nz);
-    DeviceBuffer buf;                                    // the keys, then the two dirty maps, the batch counters and the unreached count
-    const size_t small = 2 * tiles + SVR_REGION_BATCH + 1;
-    SVR_HIP_TRY(buf.alloc(n * sizeof(uint64_t) + small * sizeof(uint32_t)));
-    uint64_t* const keys = buf.as<uint64_t>();
-    uint32_t* const dirty = (uint32_t*)(keys + n);
-    uint32_t* const added = dirty + 2 * tiles;
-    uint32_t* const lost = added + SVR_REGION_BATCH;
-    CallTimer timer(g_events, st);                       // (the launches, not the allocation)
-    SVR_HIP_TRY(hipMemsetAsync(dirty, 0, small * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_geo_init, lane_grid(words), dim3(LANE_THREADS), 0, st, labels, mask, d, words, nty, keys, dirty);
-    SVR_HIP_TRY(hipGetLastError());
-    uint32_t sweeps = 0u;
-    bool done = false;
-    SVR_HIP_TRY(sweep_to_fixpoint(st, tiles, dirty, added, cap, &sweeps, &done, [&](uint32_t* cur, uint32_t* next, uint32_t* add) {
-        hipLaunchKernelGGL(k_geo_relax, dim3((uint32_t)tiles), dim3(GEO_THREADS), 0, st, keys, mask, d, gw, nty, ntz, cur, next, add);
-    }));
-    hipLaunchKernelGGL(k_geo_finish, lane_grid(words), dim3(LANE_THREADS), 0, st, keys, mask, d, words, dist, zones, lost);
-    SVR_HIP_TRY(hipGetLastError());
-    timer.stop();
-    uint32_t lost_host = 0u;
-    SVR_HIP_TRY(hipMemcpyAsync(&lost_host, lost, sizeof lost_host, hipMemcpyDeviceToHost, st));
-    SVR_HIP_TRY(hipStreamSynchronize(st));               // (buf is freed on return)
-    if (sweeps_out) *sweeps_out = sweeps;
-    if (unreached) *unreached = lost_host;
-    if (!done) return failf(SVR_REGION_ERR_SWEEPS, "%s: keys were still falling after %u sweeps; the outputs are upper bounds, not the map", who, sweeps);
-    return 0;
+    GeoResult res;
+    const int e = geo_run(who, g_events, cost, nullptr, labels, mask, d, max_sweeps, dist, zones, &res);
+    if (e && e != SVR_REGION_ERR_SWEEPS) return e;
+    if (sweeps_out) *sweeps_out = res.sweeps;
+    if (unreached) *unreached = res.unreached;
+    return e;
 }
 
 } // namespace
@@ -287,19 +107,13 @@ int svr_region_geodesic(const uint32_t* marker_labels_device, const uint32_t* do
     if (!marker_labels_device || !domain_mask_device) return failf(-4, "%s: null argument", who);
     if (!dist_device_or_null && !zones_device_or_null) return failf(-4, "%s: both outputs are null", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
-    GeoWeights gw;
-    if (int e = check_step_weights(who, step_weights_or_null, 26, nx, ny, nz, &gw)) return e;
+    PlainCost cost;
+    if (int e = check_step_weights(who, step_weights_or_null, 26, nx, ny, nz, &cost.gw)) return e;
     const RegionDims d = make_dims(nx, ny, nz);
-    const size_t map_bytes = (size_t)nx * ny * nz * sizeof(uint32_t), mask_bytes = mask_words(d) * sizeof(uint32_t);
-    uint32_t* const outs[2] = {dist_device_or_null, zones_device_or_null};
-    for (int i = 0; i < 2; ++i) {
-        if (!outs[i]) continue;
-        const bool alias = i == 1 && outs[i] == marker_labels_device;                 // zones in place over the labels
-        if (overlap(outs[i], map_bytes, domain_mask_device, mask_bytes) || (!alias && overlap(outs[i], map_bytes, marker_labels_device, map_bytes)))
-            return failf(-3, "%s: an output must not overlap an input (only zones may be the marker labels themselves)", who);
-    }
-    if (outs[0] && outs[1] && overlap(outs[0], map_bytes, outs[1], map_bytes)) return failf(-3, "%s: the two outputs must not overlap", who);
-    return geodesic_run(who, marker_labels_device, domain_mask_device, d, gw, max_sweeps, dist_device_or_null, zones_device_or_null, nullptr, sweeps_out);
+    if (int e = check_geo_outputs(who, marker_labels_device, (size_t)nx * ny * nz * sizeof(uint32_t), domain_mask_device, mask_words(d) * sizeof(uint32_t), nullptr, 0,
+                                  dist_device_or_null, zones_device_or_null))
+        return e;
+    return geodesic_run(who, marker_labels_device, domain_mask_device, d, cost, max_sweeps, dist_device_or_null, zones_device_or_null, nullptr, sweeps_out);
 }
 
 int svr_region_seed_labels(const int32_t* seeds_xyz, uint32_t nseeds, int nx, int ny, int nz, uint32_t* labels_device)
@@ -308,24 +122,7 @@ int svr_region_seed_labels(const int32_t* seeds_xyz, uint32_t nseeds, int nx, in
     if (!seeds_xyz || !labels_device) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (int e = check_seeds(who, seeds_xyz, nseeds, nx, ny, nz)) return e;
-    GeoSeeds seeds;
-    memset(&seeds, 0, sizeof seeds);
-    seeds.n = nseeds;
-    uint32_t at[SVR_REGION_MAX_SEEDS];
-    for (uint32_t i = 0; i < nseeds; ++i) {
-        const int32_t x = seeds_xyz[3u * i], y = seeds_xyz[3u * i + 1u], z = seeds_xyz[3u * i + 2u];
-        at[i] = (uint32_t)(((size_t)z * ny + y) * nx + x);                // below 2^31
-        seeds.at[i] = at[i];
-        for (uint32_t j = 0; j < i; ++j)
-            if (at[j] == at[i]) seeds.at[i] = 0xFFFFFFFFu;                // the lowest seed on a voxel wins
-    }
-    if (svr::ensure_ready()) return svr_last_error_code();
-    hipStream_t st = svr::current_stream();
-    CallTimer timer(g_events, st);
-    SVR_HIP_TRY(hipMemsetAsync(labels_device, 0, (size_t)nx * ny * nz * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_geo_seeds, dim3(1), dim3(SVR_REGION_MAX_SEEDS), 0, st, seeds, labels_device);
-    SVR_HIP_TRY(hipGetLastError());
-    return 0;
+    return place_seeds(who, g_events, seeds_xyz, nullptr, nseeds, nx, ny, nz, labels_device);     // the class of seed i is i + 1
 }
 
 int svr_region_geodesic_weights(const double spacing[3], int connectivity, int nx, int ny, int nz, uint32_t weights[7], double* unit_out)
@@ -368,8 +165,8 @@ int svr_region_split(const uint32_t* in_mask_device, int nx, int ny, int nz, con
     if (!in_mask_device || !zones_device || !count_out || !unreached_out) return failf(-4, "%s: null argument", who);
     if (int e = check_dims(who, nx, ny, nz)) return e;
     if (int e = check_connectivity(who, "connectivity", connectivity)) return e;
-    GeoWeights gw;
-    if (int e = check_step_weights(who, step_weights_or_null, connectivity, nx, ny, nz, &gw)) return e;
+    PlainCost cost;
+    if (int e = check_step_weights(who, step_weights_or_null, connectivity, nx, ny, nz, &cost.gw)) return e;
     uint32_t dw[3];
     if (int e = svr::check_distance_weights(who, dist_weights_or_null, nx, ny, nz, dw)) return e;
     const RegionDims d = make_dims(nx, ny, nz);
@@ -387,7 +184,7 @@ int svr_region_split(const uint32_t* in_mask_device, int nx, int ny, int nz, con
         SVR_HIP_TRY(hipStreamSynchronize(svr::current_stream()));                                 // (an r2 = 0 ball and the label are done with `cores`)
     }
     uint32_t lost = 0u;
-    const int e = geodesic_run(who, zones_device, in_mask_device, d, gw, max_sweeps, nullptr, zones_device, &lost, sweeps_out);
+    const int e = geodesic_run(who, zones_device, in_mask_device, d, cost, max_sweeps, nullptr, zones_device, &lost, sweeps_out);
     if (e) return e;
     *count_out = count;
     *unreached_out = lost;

@@ -1,6 +1,7 @@
 // svr_mask.hpp -- the bit-mask layout of the region calls (svr_region_*; the contract is in include/svr_abi.h, the design in DESIGN.md
 // 8h) and the helpers that every file working on it needs: the words of a row, the lanes of a word, the launch grids.  Included by
-// svr_region_grow.hpp (svr_region.hip, svr_morph.hip), svr_label.hip, svr_distance.hip, svr_geodesic.hip, svr_growcut.hip and svr_resample.hip.
+// svr_region_grow.hpp (svr_region.hip, svr_morph.hip), svr_label.hip, svr_distance.hip, svr_geo_relax.hpp (svr_geodesic.hip, svr_growcut.hip)
+// and svr_resample.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -30,7 +31,7 @@ __device__ inline uint32_t half_ballot(bool p)
 
 // A lane of the one-lane-per-voxel kernels, 32 lanes per mask word: lane t is bit `bit` of word i (word gw of row `row`), voxel v =
 // (x, y, z).  word_ok: the word exists (the lanes past the last word take word 0's coordinates); inside: the voxel exists.  A kernel
-// pays for the fields it reads.  (svr_distance.hip, svr_geodesic.hip and svr_growcut.hip use it; svr_label.hip keeps its own form, see there.)
+// pays for the fields it reads.  (svr_distance.hip, svr_geo_relax.hpp and its two files use it; svr_label.hip keeps its own form, see there.)
 struct LaneAt { size_t i, v, row; int bit, gw, x, y, z; bool word_ok, inside; };
 __device__ inline LaneAt lane_at(size_t t, const RegionDims& d, size_t words)
 {

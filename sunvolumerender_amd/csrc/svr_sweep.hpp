@@ -1,5 +1,5 @@
 // svr_sweep.hpp -- the host loop that launches sweeps of a tile kernel until one of them changes nothing, shared by the grow kernel of
-// svr_region_grow.hpp (svr_region.hip, svr_morph.hip) and the relaxations of svr_geodesic.hip and svr_growcut.hip.  The dirty-map protocol of the kernels is
+// svr_region_grow.hpp (svr_region.hip, svr_morph.hip) and the relaxation of svr_geo_relax.hpp (svr_geodesic.hip, svr_growcut.hip).  The dirty-map protocol of the kernels is
 // described at the head of svr_region.hip.
 #pragma once
 #include <hip/hip_runtime.h>

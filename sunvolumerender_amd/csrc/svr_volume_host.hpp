@@ -1,5 +1,6 @@
 // svr_volume_host.hpp -- the host scaffolding of the volume-op entry points (svr_region.hip, svr_morph.hip, svr_label.hip,
-// svr_distance.hip, svr_filter.hip, svr_geodesic.hip, svr_growcut.hip, svr_resample.hip): the argument checks they share, device memory that frees itself, and the event
+// svr_distance.hip, svr_filter.hip, svr_resample.hip, and through svr_geo_relax.hpp svr_geodesic.hip and svr_growcut.hip): the argument checks they share,
+// device memory that frees itself, and the event
 // pair behind each family's svr_*_last_ms.  Host only.  An entry point checks in the order null (-4), dimensions (-6), the rest (-3),
 // then svr::ensure_ready(); after that it owns what it allocates through DeviceBuffer / DeviceVoxels and leaves through SVR_HIP_TRY.
 #pragma once

@@ -18,7 +18,7 @@ from tests.cpp_example import build_example
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = (ROOT / "include" / "svr_abi.h").read_text()
-SOURCE = (ROOT / "sunvolumerender_amd" / "csrc" / "svr_geodesic.hip").read_text()
+SOURCE = (ROOT / "sunvolumerender_amd" / "csrc" / "svr_geo_relax.hpp").read_text()        # the tile constants
 
 
 @pytest.fixture(scope="module")

@@ -179,6 +179,58 @@ def test_flat_shapes(hip_dev, shape):
         same_pair((dist, zones), (want, np.full(shape, 0xFFFFFFFF, dtype=np.uint32)), (shape, "row"))
 
 
+# ------------------------------------------------------------------------------------------------ a source on a tile face
+# A source never falls, so its tile's block marks no neighbour tile for it: the init kernel has to wake the tile across the face.  The
+# smallest shapes at which that can go wrong: one marker on either side of the first tile face of each axis, in a domain that has no
+# other voxel on the face layer.  (shape, domain voxels or None = all, marker (z, y, x), label, the line's distances or its last four)
+_DIAGONAL = [(6 + k, 6 + k, 30 + k) for k in range(4)]
+FACE_CASES = [
+    ((1, 1, 34), None, (0, 0, 31), 5, [3, 0, 3, 6]),
+    ((1, 1, 34), None, (0, 0, 32), 5, [6, 3, 0, 3]),
+    ((1, 10, 1), None, (0, 7, 0), 5, [3, 0, 3, 6]),
+    ((1, 10, 1), None, (0, 8, 0), 5, [6, 3, 0, 3]),
+    ((10, 1, 1), None, (7, 0, 0), 5, [3, 0, 3, 6]),
+    ((10, 1, 1), None, (8, 0, 0), 5, [6, 3, 0, 3]),
+    ((10, 10, 34), _DIAGONAL, (7, 7, 31), 9, [5, 0, 5, 10]),
+    ((10, 10, 34), _DIAGONAL, (8, 8, 32), 9, [10, 5, 0, 5]),
+]
+
+
+@pytest.mark.parametrize("shape, voxels, marker, label, line", FACE_CASES, ids=[f"{c[0]}-{c[2]}".replace(" ", "") for c in FACE_CASES])
+def test_source_on_a_tile_face(hip_dev, shape, voxels, marker, label, line):
+    from tests.test_growcut_gpu import Grow                                               # (that module imports this one)
+
+    domain = np.ones(shape, dtype=bool)
+    if voxels is not None:
+        domain[:] = False
+        domain[tuple(zip(*voxels))] = True
+    labels = np.zeros(shape, dtype=np.uint32)
+    labels[marker] = label
+    want = gr.geodesic(labels, domain)
+    assert want[0][domain][-4:].tolist() == line and (want[1][domain] == label).all()     # the reference, by hand
+    with Grow(hip_dev, shape) as g:
+        lab, dom = g.put(labels), g.put(rr.pack(domain))
+        dist, zones, _ = g.geodesic(lab, dom, gr.CHAMFER, g.map(), g.map())
+        same_pair((dist, zones), want, (shape, marker))
+        cost, zones, info = g.growcut(g.put(np.full(shape, 1000, dtype=np.uint16)), lab, dom, gr.CHAMFER, 0, 0, g.map(), g.map())
+        same_pair((cost, zones), want, (shape, marker, "growcut, gain 0"))
+        assert (info.unreached, info.saturated) == (0, 0)
+
+
+def test_split_core_on_a_tile_face(hip_dev):
+    """Two cores, one of them the three voxels from the last one of the first tile on.  (With r2 = 0 every voxel of the mask is a core
+    voxel, so nothing has to cross the face: a pin, which the init kernel that marked only a source's own tile passed as well.)"""
+    shape = (1, 1, 34)
+    m = np.ones(shape, dtype=bool)
+    m[0, 0, 30] = False
+    want, want_count, want_lost = gr.split(m, 0, 6)
+    assert (want_count, want_lost) == (2, 0) and want[0, 0, 29:].tolist() == [1, 0, 2, 2, 2]
+    with Geo(hip_dev, shape) as g:
+        zones, count, lost, _ = g.split(g.put(rr.pack(m)), 0, 6, None, g.map())
+        same_map(zones, want, "split on a face")
+        assert (count, lost) == (want_count, 0)
+
+
 # ------------------------------------------------------------------------------------------------ ties
 @pytest.mark.parametrize("axis, middle", gr.TIE_CASES)
 def test_ties_go_to_the_smaller_label(hip_dev, axis, middle):
