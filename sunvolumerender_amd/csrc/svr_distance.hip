@@ -108,7 +108,7 @@ template <int MODE>
 __global__ __launch_bounds__(THREADS) void k_dist_columns(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t* __restrict__ stack, ColPass p,
                                                           uint32_t r2)
 {
-    const size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t t = lane_thread();
     const size_t wi = t >> 5;
     const int bit = (int)(t & 31u);
     const uint32_t gw = (uint32_t)(wi % p.wx);

@@ -221,7 +221,7 @@ template <int CONN>
 __global__ __launch_bounds__(THREADS) void k_label_union(const uint32_t* __restrict__ mask, uint32_t* L, RegionDims d, size_t words, uint32_t cap,
                                                          uint32_t* err)
 {
-    const size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t t = lane_thread();
     const size_t i = t >> 5;
     const int bit = (int)(t & 31u);
     if (i >= words) return;
@@ -270,7 +270,7 @@ struct LabelLane { size_t i; int bit, x; bool inside; WordAt w; size_t v; };
 __device__ inline LabelLane label_lane(const RegionDims& d, size_t words)
 {
     LabelLane a;
-    const size_t t = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t t = lane_thread();
     a.i = t >> 5;
     a.bit = (int)(t & 31u);
     const bool word_ok = a.i < words;

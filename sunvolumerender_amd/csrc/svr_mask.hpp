@@ -49,15 +49,26 @@ __device__ inline LaneAt lane_at(size_t t, const RegionDims& d, size_t words)
     a.v = a.row * (size_t)d.nx + (size_t)a.x;
     return a;
 }
-__device__ inline LaneAt lane_at(const RegionDims& d, size_t words) { return lane_at((size_t)blockIdx.x * MASK_THREADS + threadIdx.x, d, words); }
+// the thread of a lane_grid (below) in launch order: blockIdx.y counts planes of gridDim.x blocks
+__device__ inline size_t lane_thread() { return ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * MASK_THREADS + threadIdx.x; }
+__device__ inline LaneAt lane_at(const RegionDims& d, size_t words) { return lane_at(lane_thread(), d, words); }
 
 inline RegionDims make_dims(int nx, int ny, int nz) { return RegionDims{nx, ny, nz, (nx + 31) / 32}; }
 inline size_t mask_words(const RegionDims& d) { return (size_t)d.wx * d.ny * d.nz; }
 
 // The grids of MASK_THREADS threads: one thread per item (a mask word, mostly), one lane per voxel of `words` mask words.  A volume has
-// at most 2^31 voxels, so at most 2^31 items: 2^23 blocks.  A row has fewer words than voxels, so words <= 2^31 as well and the lanes
-// of the narrowest rows (nx = 1: 32 lanes per voxel) make at most 2^28 blocks: both fit the 2^31 - 1 blocks of a grid's x.
+// at most 2^31 voxels, so at most 2^31 items: 2^23 blocks.  A row has fewer words than voxels, so words <= 2^31 as well, and the lanes
+// of the narrowest rows (nx = 1: 32 lanes per voxel) make up to 2^28 blocks of 2^36 threads.  The runtime refuses a launch of more than
+// 2^32 - 1 threads along one dimension (hipErrorInvalidConfiguration: 2^27 words of rows with nx <= 32 reach exactly 2^32), so the
+// blocks past LANE_GRID_X go to planes along y: at most 2^6.  The kernels take their lane from lane_thread(); the blocks that the last
+// plane has too many find no word (word_ok, or their own test against `words`).
+constexpr uint32_t LANE_GRID_X = 1u << 22;               // 2^30 threads along x
 inline dim3 word_grid(size_t items) { return dim3((uint32_t)((items + MASK_THREADS - 1) / MASK_THREADS)); }
-inline dim3 lane_grid(size_t words) { return word_grid(words * 32); }
+inline dim3 lane_grid(size_t words)
+{
+    const size_t blocks = (words * 32 + MASK_THREADS - 1) / MASK_THREADS;
+    if (blocks <= LANE_GRID_X) return dim3((uint32_t)blocks);
+    return dim3(LANE_GRID_X, (uint32_t)((blocks + LANE_GRID_X - 1) / LANE_GRID_X));
+}
 
 } // namespace
