@@ -26,6 +26,11 @@
 // -minsize N those of at least N voxels (Canvas::KeepLargestRegion, RemoveSmallRegions; connectivity -conn): clean-up steps taken in
 // command-line order with the others, each printing the parts it found and kept and the measurements of what is left.  -detach starts
 // from the picked voxel and is therefore not available after -threshold.
+// -otsu CLASSES CLASS [SHIFT] stands where -threshold LO HI may stand: the window is class CLASS = 1 .. CLASSES (dark to bright) of the exact
+// Otsu thresholds of the histogram of raw value >> SHIFT (Canvas::OtsuRegion; CLASSES = 2, or 3 with SHIFT >= 8; SHIFT is 8 by default).
+// It prints the thresholds as raw values and the window, then goes on as -threshold with that window.  -auto-window PLO PHI sets the grey
+// window of -slice / -mip / -mean to the quantiles PLO and PHI, in per mille, of the (filtered) voxels (Canvas::AutoWindow).  After -grow,
+// -threshold or -otsu the median raw value of the region is printed with the measurements (Canvas::RegionMedian).
 // -ball-dilate L, -ball-erode L, -ball-open L and -ball-close L are clean-up steps too, by a true ball of radius L > 0 in the units of the
 // volume's spacing (Canvas::BallMorphRegion: the exact Euclidean distance map, any radius at the same cost); each prints the measurements
 // of what is left.  -thickness prints, after the last step, the largest ball inscribed in the region and its centre voxel.
@@ -53,7 +58,7 @@
 // its connected parts (-conn) as a u32 label map, and -save-crop VOL MASK MARGIN the region's bounding box grown by MARGIN voxels, voxels
 // and mask, as MetaImage files (.mhd + .raw, or .mha).  Each prints one line with the dimensions, the spacing and the time.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -66,7 +71,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-grow X Y LO HI | -threshold LO HI [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -85,6 +90,8 @@ int main(int argc, char** argv)
     bool grow = false;                                              // -grow: pixel, raw window, connectivity, what to show
     int growX = 0, growY = 0, growLo = 0, growHi = 65535, growConn = 6, growMode = SVR_REGION_KEEP;
     bool threshold = false;                                         // -threshold: the whole window growLo .. growHi, no pick
+    int otsuClasses = 0, otsuClass = 0, otsuShift = 8;              // -otsu CLASSES CLASS [SHIFT]: -threshold with the window of an Otsu class
+    int autoLo = -1, autoHi = -1;                                   // -auto-window PLO PHI: the grey window from two quantiles, per mille
     bool overlay = false;                                           // -overlay FILL EDGE: tint the picture by the region, which is not cut out of the volume
     int overlayFill = 96, overlayEdge = 255, overlayParts = 0;      // -overlay-parts CONN: label the region first, one colour per part
     struct CleanStep { const char* name; int op; uint32_t radius; double length; };   // op: SVR_MORPH_*, 0 = -fillholes, -1 = -detach, -3 = -largest, -4 = -minsize (radius: K or N), -5 = -split (length: L), -10 - SVR_MORPH_* = -ball-* (length: L)
@@ -179,7 +186,35 @@ int main(int argc, char** argv)
         }
         else if (!strcmp(argv[i], "-show-filtered")) showFiltered = true;
         else if (!strcmp(argv[i], "-thickness")) thickness = true;
+        else if (!strcmp(argv[i], "-otsu")) {
+            char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr;
+            const long k = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : 0, c = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : 0;
+            if (i + 2 >= argc || e0 == argv[i + 1] || *e0 != '\0' || e1 == argv[i + 2] || *e1 != '\0' || (k != 2 && k != 3) || c < 1 || c > k) {
+                fprintf(stderr, "-otsu needs CLASSES = 2 or 3 and CLASS = 1 .. CLASSES (got %s %s)\n", i + 1 < argc ? argv[i + 1] : "nothing", i + 2 < argc ? argv[i + 2] : "nothing");
+                return 2;
+            }
+            otsuClasses = (int)k; otsuClass = (int)c;
+            i += 2;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {
+                const long sh = strtol(argv[i + 1], &e2, 10);
+                if (*e2 != '\0' || sh > 15 || (k == 3 && sh < 8)) { fprintf(stderr, "-otsu: SHIFT is 0 .. 15, and at least 8 with three classes (got %s)\n", argv[i + 1]); return 2; }
+                otsuShift = (int)sh;
+                ++i;
+            }
+            threshold = true;
+        }
+        else if (!strcmp(argv[i], "-auto-window")) {
+            char *e0 = nullptr, *e1 = nullptr;
+            const long lo = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : 0, hi = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : 0;
+            if (i + 2 >= argc || e0 == argv[i + 1] || *e0 != '\0' || e1 == argv[i + 2] || *e1 != '\0' || lo < 0 || hi > 1000 || lo > hi) {
+                fprintf(stderr, "-auto-window needs two quantiles in per mille, 0 <= PLO <= PHI <= 1000 (got %s %s)\n", i + 1 < argc ? argv[i + 1] : "nothing", i + 2 < argc ? argv[i + 2] : "nothing");
+                return 2;
+            }
+            autoLo = (int)lo; autoHi = (int)hi;
+            i += 2;
+        }
         else if (!strcmp(argv[i], "-threshold")) {
+            if (otsuClasses) { fprintf(stderr, "-threshold and -otsu exclude each other\n"); return 2; }
             char *e0 = nullptr, *e1 = nullptr;
             const long lo = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : 0, hi = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : 0;
             if (i + 2 >= argc || e0 == argv[i + 1] || *e0 != '\0' || e1 == argv[i + 2] || *e1 != '\0' || lo < 0 || hi > 65535 || lo > hi) {
@@ -363,7 +398,8 @@ int main(int argc, char** argv)
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if ((slabMode || stack) && sliceAxis < 0) { fprintf(stderr, "-slab and -stack need -slice\n"); return 2; }
-    if (grow && threshold) { fprintf(stderr, "-grow and -threshold exclude each other\n"); return 2; }
+    if (grow && threshold) { fprintf(stderr, "-grow and -threshold / -otsu exclude each other\n"); return 2; }
+    if (autoLo >= 0 && sliceAxis < 0 && !(project && proj.mode != SVR_PROJ_ISO)) { fprintf(stderr, "-auto-window sets the grey window of -slice, -mip or -mean\n"); return 2; }
     if (growcut && seeds.empty()) { fprintf(stderr, "-growcut needs strokes: -seed X Y CLASS [RADIUS], at least one\n"); return 2; }
     if (!seeds.empty() && !growcut) { fprintf(stderr, "-seed needs -growcut [GAIN SHIFT]\n"); return 2; }
     if (keepClass && !growcut) { fprintf(stderr, "-keep-class needs -growcut [GAIN SHIFT]\n"); return 2; }
@@ -408,7 +444,7 @@ int main(int argc, char** argv)
         const cudaTextureObject_t tfTex = tf.Update();                // (argument evaluation order is unspecified)
         canvas.SetTransferFunction(tfTex, tf.GetMaxOpacityValue());
 
-        canvas.volumeReader->KeepVoxels(anyRegion || !filterSteps.empty() || !meshIsoFile.empty() || !gridSteps.empty() ||
+        canvas.volumeReader->KeepVoxels(anyRegion || autoLo >= 0 || !filterSteps.empty() || !meshIsoFile.empty() || !gridSteps.empty() ||
                                         !saveVolumeFile.empty());    // the region, filter, grid and save calls work on the plain voxels
         canvas.LoadVolume(volume);
         if (!canvas.volumeReader->IsLoaded()) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
@@ -467,6 +503,15 @@ int main(int argc, char** argv)
             }
         }
         if (showFiltered && canvas.ShowFiltered() != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+        if (autoLo >= 0) {
+            // the grey window of the slice or projection from two quantiles of the voxels
+            uint32_t raw[2] = {0u, 0u};
+            if (canvas.AutoWindow((uint32_t)autoLo, (uint32_t)autoHi, 1000u, &proj.window_lo, &proj.window_hi, false, raw) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            float ms = 0.f;
+            svr_volume_histogram_last_ms(&ms);
+            printf("auto-window %d %d: raw %u..%u, window %.9g %.9g; %.3f ms\n", autoLo, autoHi, raw[0], raw[1], proj.window_lo, proj.window_hi, ms);
+            canvas.SetProjection(proj);
+        }
         if (!saveVolumeFile.empty()) {
             const auto t0 = std::chrono::steady_clock::now();
             if (canvas.SaveVolume(saveVolumeFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
@@ -513,7 +558,14 @@ int main(int argc, char** argv)
             if (grow || threshold) {
                 if (grow && canvas.Pick((uint32_t)growX, (uint32_t)growY, &hit, hitParams) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 if (grow && hit.status != SVR_HIT_STATUS_FOUND) { fprintf(stderr, "-grow: %s at pixel %d %d\n", hit.status == SVR_HIT_STATUS_MISS ? "the ray misses the volume" : "no hit along the ray", growX, growY); return 1; }
-                if ((grow ? canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) : canvas.ThresholdRegion((uint32_t)growLo, (uint32_t)growHi, &st)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if (otsuClasses) {
+                    uint32_t thr[2] = {0u, 0u}, win[2] = {0u, 0u};
+                    if (canvas.OtsuRegion((uint32_t)otsuClasses, (uint32_t)otsuClass, (uint32_t)otsuShift, &st, thr, win) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    growLo = (int)win[0]; growHi = (int)win[1];
+                    if (otsuClasses == 2) printf("otsu 2 classes shift %d: threshold %u; class %d window %d..%d\n", otsuShift, thr[0], otsuClass, growLo, growHi);
+                    else printf("otsu 3 classes shift %d: thresholds %u %u; class %d window %d..%d\n", otsuShift, thr[0], thr[1], otsuClass, growLo, growHi);
+                }
+                else if ((grow ? canvas.GrowRegion(hit, (uint32_t)growLo, (uint32_t)growHi, growConn, &st) : canvas.ThresholdRegion((uint32_t)growLo, (uint32_t)growHi, &st)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 if (svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 if (threshold) {
                     uint32_t parts = 0u;
@@ -531,6 +583,11 @@ int main(int argc, char** argv)
                     printf("grow %d %d window %d..%d conn %d: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %u sweeps\n",
                            growX, growY, growLo, growHi, growConn, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
                            st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, st.sweeps);
+                if (st.status != SVR_REGION_STATUS_EMPTY) {
+                    uint32_t median = 0u;
+                    if (canvas.RegionMedian(&median) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                    printf("median: raw %u\n", median);
+                }
             }
             if (growcut) {
                 // strokes of classes on picked voxels, grown over the region made above or, without one, over the whole volume

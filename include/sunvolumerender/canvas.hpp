@@ -652,6 +652,76 @@ public:
         svr_device_free(labels);
         return rc;
     }
+    // Histograms of the segmented voxels (svr_volume_histogram, svr_histogram_*; include/svr_abi.h, "histograms of the u16 voxels"): of
+    // the filtered copy when there is one, of the whole volume or, with insideRegion, of the voxels of the current region.
+    // VolumeHistogram: counts = the 65536 >> shift bins of raw value >> shift
+    int VolumeHistogram(uint32_t shift, std::vector<uint32_t>& counts, bool insideRegion = false)
+    {
+        const uint16_t* vox = SegVoxels();
+        if (!ready || !vox || (insideRegion && !haveRegion)) return -4;
+        svr_histogram_params p;
+        svr_histogram_params_default(&p);
+        p.shift = shift;
+        uint32_t first = 0u, last = 0u;
+        if (const int rc = svr_histogram_bin_range(&p, 0u, &first, &last)) return rc;            // (refuses a shift above 15)
+        const uint32_t bins = svr_histogram_bins(&p);
+        uint32_t* d = (uint32_t*)svr_device_malloc((size_t)bins * sizeof(uint32_t));
+        if (!d) return -4;
+        int rc = svr_volume_histogram(vox, volumeReader->dim, 1, insideRegion ? regionMask : nullptr, &p, d);
+        counts.assign(bins, 0u);
+        if (rc == 0) rc = svr_memcpy_d2h(counts.data(), d, (size_t)bins * sizeof(uint32_t));     // (waits for the stream)
+        svr_device_free(d);
+        return rc;
+    }
+    // OtsuRegion: the current region becomes class classIndex (1 .. classes, from dark to bright) of the exact Otsu thresholds of the
+    // histogram at `shift` (classes = 2, or 3 with shift >= 8), through svr_histogram_bin_range and ThresholdRegion.  thresholds_raw
+    // (classes - 1 values: the last raw value of each lower class) and window_raw (the class's lo, hi) are optional outputs
+    int OtsuRegion(uint32_t classes, uint32_t classIndex, uint32_t shift, svr_region_stats* stats = nullptr, uint32_t* thresholds_raw = nullptr,
+                   uint32_t* window_raw = nullptr)
+    {
+        if (classIndex < 1u || classIndex > classes) return -3;
+        std::vector<uint32_t> counts;
+        if (const int rc = VolumeHistogram(shift, counts)) return rc;
+        uint32_t t[2] = {0u, 0u};
+        if (const int rc = svr_histogram_otsu(counts.data(), (uint32_t)counts.size(), classes, t, nullptr)) return rc;
+        svr_histogram_params p;
+        svr_histogram_params_default(&p);
+        p.shift = shift;
+        const uint32_t firstBin = classIndex == 1u ? 0u : t[classIndex - 2u] + 1u;
+        const uint32_t lastBin = classIndex == classes ? (uint32_t)counts.size() - 1u : t[classIndex - 1u];
+        uint32_t lo = 0u, hi = 0u, skip = 0u;
+        if (const int rc = svr_histogram_bin_range(&p, firstBin, &lo, &skip)) return rc;
+        if (const int rc = svr_histogram_bin_range(&p, lastBin, &skip, &hi)) return rc;
+        for (uint32_t k = 0; thresholds_raw && k + 1u < classes; ++k)
+            if (const int rc = svr_histogram_bin_range(&p, t[k], &skip, &thresholds_raw[k])) return rc;
+        if (window_raw) { window_raw[0] = lo; window_raw[1] = hi; }
+        return ThresholdRegion(lo, hi, stats);
+    }
+    // AutoWindow: the quantiles numLo / den and numHi / den of the raw values (svr_histogram_quantile) as the grey window of slices and
+    // projections, raw / 65535 x densityScale; a window of one value is opened by one raw step.  window_raw (optional): the two raw values
+    int AutoWindow(uint32_t numLo, uint32_t numHi, uint32_t den, float* lo, float* hi, bool insideRegion = false, uint32_t* window_raw = nullptr)
+    {
+        if (!lo || !hi) return -4;
+        if (numLo > numHi) return -3;
+        std::vector<uint32_t> counts;
+        if (const int rc = VolumeHistogram(0u, counts, insideRegion)) return rc;
+        uint32_t a = 0u, b = 0u;
+        if (const int rc = svr_histogram_quantile(counts.data(), (uint32_t)counts.size(), numLo, den, &a)) return rc;
+        if (const int rc = svr_histogram_quantile(counts.data(), (uint32_t)counts.size(), numHi, den, &b)) return rc;
+        if (window_raw) { window_raw[0] = a; window_raw[1] = b; }
+        if (a == b) { if (b < 65535u) ++b; else --a; }
+        *lo = (float)a / 65535.f * deviceVolume.densityScale;
+        *hi = (float)b / 65535.f * deviceVolume.densityScale;
+        return 0;
+    }
+    // RegionMedian: *raw = the median raw value of the region's voxels (the quantile 1 / 2); SVR_HISTOGRAM_STATUS_EMPTY for an empty region
+    int RegionMedian(uint32_t* raw)
+    {
+        if (!raw) return -4;
+        std::vector<uint32_t> counts;
+        if (const int rc = VolumeHistogram(0u, counts, true)) return rc;
+        return svr_histogram_quantile(counts.data(), (uint32_t)counts.size(), 1u, 2u, raw);
+    }
     // Surface meshes (svr_mesh_region / _isosurface / _positions / _measure, svr_stl_write / svr_ply_write; include/svr_abi.h, "surface
     // meshes of region masks and isosurfaces").  ExtractRegionSurface: the closed surface of the current region after `relax` (0 ..
     // SVR_MESH_MAX_RELAX) constrained relaxation steps; ExtractIsoSurface: the surface {raw value >= level} of the segmented voxels.  The

@@ -1039,6 +1039,64 @@ int svr_region_label_paint(uint32_t* labels_device, const int32_t dims[3], const
 /* HIP-event time of the device work of the last svr_region_growcut / _seed_classes / _label_paint, whichever came last (waits for it) */
 int svr_region_growcut_last_ms(float* ms);
 
+/* ---- histograms of the u16 voxels: whole volume, inside a mask, per label; exact Otsu and quantiles (csrc/svr_histogram.hip;
+ *      DESIGN.md 8r) ----
+ * The histogram of the voxels the chain works on (after svr_volume_rank / _smooth / _resample), optionally inside a region mask (the
+ * layout of the region section; padding bits are ignored, whatever they hold) or per part of a label array (any uint32 per voxel: the
+ * components of svr_region_label, the zones of svr_region_split, the classes of svr_region_growcut).  Dimensions are const int32_t
+ * dims[3] = (x, y, z).  Integers only; every result is exact and unique, whatever order the GPU works in.  The calls are stateless,
+ * run on the library's stream and touch no scene, option or accumulator.
+ * PARAMS: a voxel of value v counts iff it lies in the inclusive box (cut to the volume) and lo <= v <= hi; its bin is (v - lo) >> shift.
+ *   There are svr_histogram_bins = ((hi - lo) >> shift) + 1 bins (at most 65536); the last may be narrower than 1 << shift.  Voxels
+ *   outside the window are not counted (they are not clamped into the end bins).  params == NULL means the defaults: 0 .. 65535,
+ *   shift 0, the whole volume.  svr_histogram_bin_range gives the raw values of a bin, lo + (bin << shift) .. min(hi, lo + ((bin + 1) <<
+ *   shift) - 1): the window that svr_region_threshold takes.
+ * VOLUME HISTOGRAM: counts_device[b], svr_histogram_bins entries, = the number of voxels in the box whose mask bit is set (every voxel
+ *   with a NULL mask) and whose value falls in bin b.  A count fits in uint32 because a volume has at most 2^31 voxels.  The output is
+ *   overwritten, not accumulated.  voxels is host memory, or device memory with src_is_device; a host source is uploaded once and the
+ *   call then synchronises the stream; with a device source the call is asynchronous.
+ * LABEL HISTOGRAM: counts_device is [count + 1][bins]; row l counts the voxels whose label is l, row 0 the background; labels above
+ *   `count` are ignored as in svr_region_label_table.  count == 0 is allowed and gives the background row alone.  (count + 1) * bins
+ *   may not exceed SVR_HISTOGRAM_MAX_CELLS.
+ * REFUSED, before the device is touched: a null pointer (-4); a dimension <= 0 or more than 2^31 voxels (-6); (-3) lo > hi, hi > 65535,
+ *   shift > 15, a box that is inverted or has no voxel of the volume in it, more than SVR_HISTOGRAM_MAX_CELLS cells, a counts_device
+ *   that overlaps an input.
+ * ANALYSIS of a HOST histogram is plain host code: no device, any uint32 counts (a row of the label table, a caller's own).  `bins`
+ *   >= 1; indices below are bin indices.  With N = the total count, N == 0 returns SVR_HISTOGRAM_STATUS_EMPTY with the outputs 0
+ *   (a status, not an error: svr_last_error_code is unchanged); bins == 0 or a null pointer is refused (-3 / -4).
+ *   MOMENTS: n = sum c[b], sum = sum b c[b], sum_sq = sum b^2 c[b], added in 128 bits; a histogram of a volume (N <= 2^31, bins
+ *     <= 65536) stays below 2^63, and a caller's counts whose sums do not fit 64 bits are refused (-3).
+ *   QUANTILE (den > 0, num <= den, else -3): with C(b) the count through bin b, the smallest b with C(b) > 0 and den * C(b) >= num * N,
+ *     compared in 128 bits.  num = 0 gives the first occupied bin, num = den the last; for 0 < q <= 1 this is numpy's
+ *     percentile(method="inverted_cdf").
+ *   OTSU: classes = 2, or 3 with bins <= 256 (anything else -3; coarsen with `shift`).  thresholds_out receives classes - 1 values
+ *     t_1 < ... , each in 0 .. bins - 2: the LAST bins of the lower classes (class j spans t_{j-1} + 1 .. t_j, t_0 = -1, the last class
+ *     ends at bins - 1).  Chosen is the tuple that maximises sum_j S_j^2 / N_j (N_j the count of class j, S_j = sum b c[b] over it, an
+ *     empty class contributes 0), which has the maximiser of the between-class variance; the comparison is exact (256-bit cross
+ *     products), and ties go to the lexicographically smallest tuple.  bins < classes (no such tuple) is -3.  *eta_out (may be NULL)
+ *     = between-class variance / total variance as a double (0 when the total variance is 0): informative only. */
+#define SVR_HISTOGRAM_MAX_CELLS 16777216u     /* (count + 1) * bins of svr_region_label_histogram: 64 MB of counters */
+#define SVR_HISTOGRAM_STATUS_EMPTY 1
+typedef struct svr_histogram_params {   /* 4-byte members only, 36 bytes */
+    uint32_t lo, hi;                    /* inclusive raw-value window; voxels outside it are not counted */
+    uint32_t shift;                     /* 0 .. 15: bin(v) = (v - lo) >> shift */
+    int32_t  box_min[3], box_max[3];    /* inclusive voxel box, intersected with the volume */
+} svr_histogram_params;
+int      svr_histogram_params_default(svr_histogram_params* p);      /* 0 .. 65535, shift 0, 0 .. INT32_MAX */
+uint32_t svr_histogram_bins(const svr_histogram_params* p);          /* ((hi - lo) >> shift) + 1; 0 for invalid params */
+int      svr_histogram_bin_range(const svr_histogram_params* p, uint32_t bin, uint32_t* v_lo, uint32_t* v_hi);
+
+int svr_volume_histogram(const uint16_t* voxels, const int32_t dims[3], int src_is_device, const uint32_t* mask_device_or_null,
+                         const svr_histogram_params* params_or_null, uint32_t* counts_device);
+int svr_region_label_histogram(const uint32_t* labels_device, const uint16_t* voxels, const int32_t dims[3], int src_is_device,
+                               uint32_t count, const svr_histogram_params* params_or_null, uint32_t* counts_device);
+/* HIP-event time of the device work of the last svr_volume_histogram / svr_region_label_histogram (waits for it) */
+int svr_volume_histogram_last_ms(float* ms);
+
+int svr_histogram_moments(const uint32_t* counts, uint32_t bins, uint64_t* n, uint64_t* sum, uint64_t* sum_sq);
+int svr_histogram_quantile(const uint32_t* counts, uint32_t bins, uint32_t num, uint32_t den, uint32_t* bin_out);
+int svr_histogram_otsu(const uint32_t* counts, uint32_t bins, uint32_t classes, uint32_t* thresholds_out, double* eta_out);
+
 /* ---- overlays: region masks and label maps on slices and 3D views (csrc/svr_overlay.hip) ----
  * Per-pixel region ids, outlines, and a blend onto the RGBA8 images that svr_render_slice, svr_render_slice_stack, render_raycasting and
  * svr_render_projection write.  Integers only, but for the sample points of a slice, which are the float32 points of the slice section;

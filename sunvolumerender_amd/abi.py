@@ -318,6 +318,15 @@ GROWCUT_CAP = 0xFFFFFFFE
 REGION_ERR_RANGE = -12
 
 
+class HistogramParams(C.Structure):  # svr_histogram_params
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32), ("shift", C.c_uint32), ("box_min", C.c_int32 * 3), ("box_max", C.c_int32 * 3)]
+
+
+svr_histogram_params = HistogramParams
+HISTOGRAM_MAX_CELLS = 1 << 24
+HISTOGRAM_STATUS_EMPTY = 1
+
+
 class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
     _fields_ = [("mask_device", C.c_void_p), ("labels_device", C.c_void_p)]
 
@@ -587,6 +596,15 @@ PROTOTYPES = {
     "svr_region_seed_classes": (C.c_int, [_P(C.c_int32), _P(C.c_uint32), C.c_uint32, _P(C.c_int32), C.c_void_p]),
     "svr_region_label_paint": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_void_p, C.c_uint32, C.c_int]),
     "svr_region_growcut_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_histogram_params_default": (C.c_int, [_P(HistogramParams)]),
+    "svr_histogram_bins": (C.c_uint32, [_P(HistogramParams)]),
+    "svr_histogram_bin_range": (C.c_int, [_P(HistogramParams), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    "svr_volume_histogram": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, C.c_void_p, _P(HistogramParams), C.c_void_p]),
+    "svr_region_label_histogram": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_int, C.c_uint32, _P(HistogramParams), C.c_void_p]),
+    "svr_volume_histogram_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_histogram_moments": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "svr_histogram_quantile": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
+    "svr_histogram_otsu": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_double)]),
     "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
     "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
     "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,

@@ -844,6 +844,66 @@ class Device:
         self.check(self.lib.svr_region_growcut_last_ms(C.byref(ms)))
         return float(ms.value)
 
+    # ---- histograms of the u16 voxels (svr_volume_histogram, svr_region_label_histogram); the analysis is in the module functions ----
+    def histogram_params(self, lo: int = 0, hi: int = 65535, shift: int = 0, box=None) -> abi.HistogramParams:
+        """svr_histogram_params_default with the window, shift and box ((x0, y0, z0), (x1, y1, z1), inclusive) replaced."""
+        return histogram_params(lo, hi, shift, box, self.lib)
+
+    def _histogram_out(self, cells, out_ptr, call):
+        out = out_ptr if out_ptr is not None else self.malloc(4 * max(cells, 1))
+        try:
+            call(C.c_void_p(out))
+            self.synchronize()
+            return self.to_host(out, (cells,), np.uint32)
+        finally:
+            if out_ptr is None:
+                self.free(out)
+
+    def volume_histogram(self, vox, mask=None, lo: int = 0, hi: int = 65535, shift: int = 0, box=None, shape=None,
+                         out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_volume_histogram: np.uint32[bins], bins = ((hi - lo) >> shift) + 1: the voxels of `box` (inclusive, cut to the volume; None
+        = all) whose mask bit is set (mask: a bool array [nz][ny][nx], a device pointer to the bit mask, or None = every voxel) and whose
+        value v lies in lo .. hi, counted in bin (v - lo) >> shift.  vox is a host [nz][ny][nx] u16 array, or a device pointer with
+        shape=(nz, ny, nx).  out_ptr: a device buffer of 4 * bins bytes that receives the counts."""
+        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
+        p = self.histogram_params(lo, hi, shift, box)
+        bins = int(self.lib.svr_histogram_bins(C.byref(p)))
+        mbuf, mowned = (None, False) if mask is None else self._region_mask(mask, (nz, ny, nx))
+        dims = (C.c_int32 * 3)(nx, ny, nz)
+        try:
+            return self._histogram_out(bins, out_ptr, lambda out: self.check(self.lib.svr_volume_histogram(
+                src, dims, on_dev, None if mbuf is None else C.c_void_p(mbuf), C.byref(p), out)))
+        finally:
+            if mowned:
+                self.free(mbuf)
+
+    def region_label_histogram(self, labels, vox, count: int, lo: int = 0, hi: int = 65535, shift: int = 0, box=None, shape=None,
+                               out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_label_histogram: np.uint32[count + 1, bins]; row l is the histogram of the voxels whose label is l (row 0: the
+        background; labels above count are ignored).  labels: a uint32 array [nz][ny][nx] or a device pointer with shape=; vox, the
+        window, shift and box as in volume_histogram.  out_ptr: a device buffer of 4 * (count + 1) * bins bytes."""
+        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, shape)
+        try:
+            src, vshape, on_dev, _keep = self._region_source(vox, (nz, ny, nx))
+            if tuple(vshape) != (nz, ny, nx):
+                raise ValueError("the volume and the labels differ in shape")
+            p = self.histogram_params(lo, hi, shift, box)
+            bins = int(self.lib.svr_histogram_bins(C.byref(p)))
+            dims = (C.c_int32 * 3)(nx, ny, nz)
+            cells = (int(count) + 1) * bins
+            if bins == 0 or cells > abi.HISTOGRAM_MAX_CELLS:
+                cells = 0                                         # the library refuses the call: a token buffer is enough to hear it
+            return self._histogram_out(cells, out_ptr, lambda out: self.check(self.lib.svr_region_label_histogram(
+                C.c_void_p(lbuf), src, dims, on_dev, int(count), C.byref(p), out))).reshape(int(count) + 1, bins)
+        finally:
+            if lowned:
+                self.free(lbuf)
+
+    def volume_histogram_last_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self.check(self.lib.svr_volume_histogram_last_ms(C.byref(ms)))
+        return float(ms.value)
+
     # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
     def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
         """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
@@ -1220,6 +1280,80 @@ def smooth_radii(spacing, sigma, lib=None):
         lib.svr_clear_error()
         raise SvrError(f"svr_volume_smooth_radii failed ({rc}): {msg}")
     return (int(r[0]), int(r[1]), int(r[2])), (float(so[0]), float(so[1]), float(so[2]))
+
+
+def _histogram_call(lib, name, rc):
+    """Raises on an error code; returns True when the histogram was empty (SVR_HISTOGRAM_STATUS_EMPTY)."""
+    if rc not in (0, abi.HISTOGRAM_STATUS_EMPTY):
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise SvrError(f"{name} failed ({rc}): {msg}")
+    return rc == abi.HISTOGRAM_STATUS_EMPTY
+
+
+def _histogram_counts(counts):
+    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    return c, c.ctypes.data_as(C.c_void_p) if len(c) else None
+
+
+def histogram_params(lo: int = 0, hi: int = 65535, shift: int = 0, box=None, lib=None) -> abi.HistogramParams:
+    """svr_histogram_params_default with the window, shift and box ((x0, y0, z0), (x1, y1, z1), inclusive) replaced.  The histogram
+    helpers below are host code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    p = abi.HistogramParams()
+    _histogram_call(lib, "svr_histogram_params_default", lib.svr_histogram_params_default(C.byref(p)))
+    p.lo, p.hi, p.shift = int(lo), int(hi), int(shift)
+    if box is not None:
+        for a in range(3):
+            p.box_min[a], p.box_max[a] = int(box[0][a]), int(box[1][a])
+    return p
+
+
+def histogram_bins(lo: int = 0, hi: int = 65535, shift: int = 0, lib=None) -> int:
+    """svr_histogram_bins: ((hi - lo) >> shift) + 1, or 0 for an invalid window or shift."""
+    lib = lib if lib is not None else abi.load()
+    p = histogram_params(lo, hi, shift, None, lib)
+    return int(lib.svr_histogram_bins(C.byref(p)))
+
+
+def histogram_bin_range(bin: int, lo: int = 0, hi: int = 65535, shift: int = 0, lib=None):
+    """svr_histogram_bin_range: (v_lo, v_hi), the raw values of a bin -- the window for region_threshold."""
+    lib = lib if lib is not None else abi.load()
+    p = histogram_params(lo, hi, shift, None, lib)
+    a, b = C.c_uint32(0), C.c_uint32(0)
+    _histogram_call(lib, "svr_histogram_bin_range", lib.svr_histogram_bin_range(C.byref(p), int(bin), C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def histogram_moments(counts, lib=None):
+    """svr_histogram_moments: (n, sum, sum_sq) of the bin indices of a uint32 histogram; (0, 0, 0) when it is empty."""
+    lib = lib if lib is not None else abi.load()
+    c, ptr = _histogram_counts(counts)
+    n, s, q = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _histogram_call(lib, "svr_histogram_moments", lib.svr_histogram_moments(ptr, len(c), C.byref(n), C.byref(s), C.byref(q)))
+    return int(n.value), int(s.value), int(q.value)
+
+
+def histogram_quantile(counts, num: int, den: int, lib=None):
+    """svr_histogram_quantile: the smallest bin b with C(b) > 0 and den * C(b) >= num * N (numpy's inverted_cdf for 0 < num / den <= 1;
+    num = 0: the first occupied bin); None when the histogram is empty."""
+    lib = lib if lib is not None else abi.load()
+    c, ptr = _histogram_counts(counts)
+    b = C.c_uint32(0)
+    empty = _histogram_call(lib, "svr_histogram_quantile", lib.svr_histogram_quantile(ptr, len(c), int(num), int(den), C.byref(b)))
+    return None if empty else int(b.value)
+
+
+def histogram_otsu(counts, classes: int = 2, lib=None):
+    """svr_histogram_otsu: (thresholds, eta): the classes - 1 exact Otsu thresholds (the last bins of the lower classes; ties go to the
+    lexicographically smallest tuple) and between-class / total variance; (None, 0.0) when the histogram is empty."""
+    lib = lib if lib is not None else abi.load()
+    c, ptr = _histogram_counts(counts)
+    t, eta = (C.c_uint32 * 2)(), C.c_double(0.0)
+    empty = _histogram_call(lib, "svr_histogram_otsu", lib.svr_histogram_otsu(ptr, len(c), int(classes), t, C.byref(eta)))
+    if empty:
+        return None, 0.0
+    return tuple(int(t[k]) for k in range(int(classes) - 1)), float(eta.value)
 
 
 def resample_grid(grid) -> abi.ResampleGrid:
