@@ -11,6 +11,9 @@ so tests and the benchmark read like the reference's own host code:
   Canvas (LoadVolume, setters, paintGL, ReStartRender)  gui/canvas.cpp:8-117, gui/canvas.h:43-175
 
 All arithmetic that the reference does in `float` is done in numpy float32 here.
+
+The volume operations (regions, masks, labels, distances, filters, meshes, resampling, histograms, overlays) are in volume_ops.py:
+Device inherits their methods from volume_ops.VolumeOps, and their module functions are names of this module as well.
 """
 from __future__ import annotations
 
@@ -170,8 +173,25 @@ class SvrError(RuntimeError):
     pass
 
 
-class Device:
-    """Thin RAII-style wrapper over the svr_* helper entry points (non-fatal error mode)."""
+def _host_call(lib, name, rc, ok=(0,)):
+    """The return value of a call into the library's host code, or SvrError with the library's message for a value outside `ok`."""
+    if rc not in ok:
+        msg = lib.svr_last_error().decode("utf-8", "replace")
+        lib.svr_clear_error()
+        raise SvrError(f"{name} failed ({rc}): {msg}")
+    return rc
+
+
+# The volume operations live in volume_ops.py, which takes SvrError, _host_call and _to_vec3 from here: the import follows them.  Every
+# public name of it stays a name of this module.
+from .volume_ops import (COMPONENT_DTYPE, LABEL_SCAN_BLOCK, VolumeOps as _VolumeOps, distance_weights, geodesic_weights, histogram_bin_range,  # noqa: E402,F401
+                         histogram_bins, histogram_moments, histogram_otsu, histogram_params, histogram_quantile, mesh_positions,
+                         region_label_scan_levels, region_mask_pack, region_mask_unpack, region_mask_words, region_seed_from_world,
+                         resample_grid, resample_grid_box, resample_grid_dims, resample_grid_place, resample_grid_spacing, smooth_radii)
+
+
+class Device(_VolumeOps):
+    """Thin RAII-style wrapper over the svr_* helper entry points (non-fatal error mode); the volume operations are volume_ops.VolumeOps."""
 
     def __init__(self, device: int = 0, fatal_errors: bool = False):
         self.lib = abi.load()
@@ -280,1191 +300,12 @@ class Device:
         self.check(self.lib.svr_get_noise_estimate(C.byref(est), C.c_void_p(tile_ptr) if tile_ptr else None))
         return est
 
-    # ---- seeded region growing (svr_region_*): pick, segment, measure, show ----
-    def _region_source(self, vox, shape):
-        """(pointer argument, (nz, ny, nx), src_is_device, keep-alive) of a host u16 array or a device pointer with `shape`."""
-        if isinstance(vox, np.ndarray):
-            a = np.ascontiguousarray(vox, dtype=np.uint16)
-            if a.ndim != 3:
-                raise ValueError("the volume must be [nz][ny][nx]")
-            return a.ctypes.data_as(C.c_void_p), a.shape, 0, a
-        if shape is None:
-            raise ValueError("a device volume needs shape=(nz, ny, nx)")
-        return C.c_void_p(int(vox)), tuple(int(n) for n in shape), 1, None
-
-    def region_params(self, lo: int = 0, hi: int = 65535, connectivity: int = 6, box=None, max_sweeps: int = 0) -> abi.RegionParams:
-        """svr_region_params_default with the window, connectivity, box ((x0, y0, z0), (x1, y1, z1), inclusive) and cap replaced."""
-        p = abi.RegionParams()
-        self.check(self.lib.svr_region_params_default(C.byref(p)))
-        p.lo, p.hi, p.connectivity, p.max_sweeps = int(lo), int(hi), int(connectivity), int(max_sweeps)
-        if box is not None:
-            for a in range(3):
-                p.box_min[a], p.box_max[a] = int(box[0][a]), int(box[1][a])
-        return p
-
-    def region_grow(self, vox, seeds, lo: int, hi: int, connectivity: int = 6, box=None, max_sweeps: int = 0, shape=None,
-                    mask_ptr: Optional[int] = None):
-        """svr_region_grow: the connected component(s) of {lo <= v <= hi} (inside `box`) around the seed voxels (x, y, z).  vox is a
-        host [nz][ny][nx] u16 array, or a device pointer with shape=(nz, ny, nx).  Returns (mask, stats): the region as a bool array
-        [nz][ny][nx] and the svr_region_stats.  mask_ptr: a device buffer of region_mask_words(shape) uint32 that receives the bit mask
-        (else a temporary one is used)."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
-        p = self.region_params(lo, hi, connectivity, box, max_sweeps)
-        words = region_mask_words((nz, ny, nx))
-        buf = mask_ptr if mask_ptr is not None else self.malloc(4 * max(words, 1))
-        st = abi.RegionStats()
-        try:
-            self.check(self.lib.svr_region_grow(src, nx, ny, nz, on_dev, xyz.ctypes.data_as(C.POINTER(C.c_int32)), len(xyz), C.byref(p),
-                                                C.c_void_p(buf), C.byref(st)))
-            mask = region_mask_unpack(self.to_host(buf, (words,), np.uint32), (nz, ny, nx))
-        finally:
-            if mask_ptr is None:
-                self.free(buf)
-        return mask, st
-
-    def region_stats_of(self, vox, mask, shape=None) -> abi.RegionStats:
-        """svr_region_stats_of: the statistics of any mask (a bool array [nz][ny][nx], or a device pointer to the bit mask)."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        st = abi.RegionStats()
-        try:
-            self.check(self.lib.svr_region_stats_of(src, nx, ny, nz, on_dev, C.c_void_p(buf), C.byref(st)))
-        finally:
-            if owned:
-                self.free(buf)
-        return st
-
-    def region_apply(self, vox, mask, mode: int = abi.REGION_KEEP, fill: int = 0, shape=None, out_ptr: Optional[int] = None):
-        """svr_region_apply: the volume with the voxels outside (REGION_KEEP) or inside (REGION_REMOVE) the region set to `fill`.
-        Returns a u16 array [nz][ny][nx]; with out_ptr (a device buffer of nx * ny * nz u16, which may be a device `vox` itself) the
-        result stays on the device and out_ptr is returned."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        out = out_ptr if out_ptr is not None else self.malloc(2 * nx * ny * nz)
-        try:
-            self.check(self.lib.svr_region_apply(src, nx, ny, nz, on_dev, C.c_void_p(buf), int(mode), int(fill), C.c_void_p(out)))
-            if out_ptr is not None:
-                self.synchronize()
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint16)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def _region_mask(self, mask, shape):
-        """(device pointer, owned) of a bool array (uploaded as the bit mask) or of a device pointer."""
-        if isinstance(mask, np.ndarray):
-            words = region_mask_pack(mask.reshape(shape))
-            buf = self.malloc(4 * max(len(words), 1))
-            self.to_device(buf, words)
-            return buf, True
-        return int(mask), False
-
-    # ---- operations on region masks (svr_region_morph / _combine / _reconstruct / _fill_holes / _detach) ----
-    def _mask_call(self, masks, shape, out_ptr, call):
-        """Runs call(device pointers of `masks` (None stays None), shape, out) and returns the result mask as a bool array [nz][ny][nx].
-        masks: bool arrays [nz][ny][nx] (uploaded) or device pointers with shape=(nz, ny, nx); out_ptr: a device buffer of
-        region_mask_words(shape) uint32 that receives the bit mask (else a temporary one is used)."""
-        arrays = [m for m in masks if isinstance(m, np.ndarray)]
-        if arrays:
-            shape = arrays[0].shape
-        if shape is None:
-            raise ValueError("device masks need shape=(nz, ny, nx)")
-        shape = tuple(int(n) for n in shape)
-        if len(shape) != 3:
-            raise ValueError("a mask must be [nz][ny][nx]")
-        bufs = [None if m is None else self._region_mask(m, shape) for m in masks]
-        words = region_mask_words(shape)
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(words, 1))
-        try:
-            extra = call([None if b is None else C.c_void_p(b[0]) for b in bufs], shape, C.c_void_p(out))
-            mask = region_mask_unpack(self.to_host(out, (words,), np.uint32), shape)
-        finally:
-            for b in bufs:
-                if b is not None and b[1]:
-                    self.free(b[0])
-            if out_ptr is None:
-                self.free(out)
-        return mask if extra is None else (mask, extra)
-
-    def region_morph(self, mask, op: int, element: int = 6, radius: int = 1, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_morph: MORPH_DILATE / _ERODE / _OPEN / _CLOSE of a mask by the unit element 6 / 18 / 26 applied `radius` times."""
-        def call(p, s, out):
-            self.check(self.lib.svr_region_morph(p[0], s[2], s[1], s[0], int(op), int(element), int(radius), out))
-        return self._mask_call([mask], shape, out_ptr, call)
-
-    def region_combine(self, a, b, op: int, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_combine: MASK_AND / _OR / _ANDNOT (a & ~b) / _XOR of two masks, or MASK_NOT of a (b = None).  out_ptr may be a or b."""
-        def call(p, s, out):
-            self.check(self.lib.svr_region_combine(p[0], p[1], s[2], s[1], s[0], int(op), out))
-        return self._mask_call([a, b], shape, out_ptr, call)
-
-    def region_reconstruct(self, marker, cand, connectivity: int = 6, max_sweeps: int = 0, shape=None, out_ptr: Optional[int] = None):
-        """svr_region_reconstruct: the components of `cand` that hold a voxel of marker & cand.  Returns (mask, sweeps)."""
-        def call(p, s, out):
-            sweeps = C.c_uint32(0)
-            self.check(self.lib.svr_region_reconstruct(p[0], p[1], s[2], s[1], s[0], int(connectivity), int(max_sweeps), out, C.byref(sweeps)))
-            return int(sweeps.value)
-        return self._mask_call([marker, cand], shape, out_ptr, call)
-
-    def region_fill_holes(self, mask, background_connectivity: int = 6, max_sweeps: int = 0, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_fill_holes: the mask and every background voxel that cannot reach a face of the volume."""
-        def call(p, s, out):
-            self.check(self.lib.svr_region_fill_holes(p[0], s[2], s[1], s[0], int(background_connectivity), int(max_sweeps), out))
-        return self._mask_call([mask], shape, out_ptr, call)
-
-    def region_detach(self, mask, seeds, element: int = 6, radius: int = 1, connectivity: int = 6, max_sweeps: int = 0, shape=None,
-                      out_ptr: Optional[int] = None):
-        """svr_region_detach: the part of a grown region around the seed voxels (x, y, z) that survives an opening by `element` applied
-        `radius` times -- what hangs on it by thinner connections is cut off.  Returns (mask, status): REGION_STATUS_OK or _EMPTY."""
-        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
-
-        def call(p, s, out):
-            status = C.c_int32(0)
-            self.check(self.lib.svr_region_detach(p[0], s[2], s[1], s[0], xyz.ctypes.data_as(C.POINTER(C.c_int32)), len(xyz), int(element),
-                                                  int(radius), int(connectivity), int(max_sweeps), out, C.byref(status)))
-            return int(status.value)
-        return self._mask_call([mask], shape, out_ptr, call)
-
-    # ---- connected components of region masks (svr_region_threshold / _label / _label_table / _select / _select_by_size) ----
-    def region_threshold(self, vox, lo: int, hi: int, box=None, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_threshold: the mask {voxel in `box` : lo <= v <= hi} of a host [nz][ny][nx] u16 array or a device pointer with
-        shape=(nz, ny, nx); box = ((x0, y0, z0), (x1, y1, z1)), inclusive, or None for the whole volume.  Returns the bool array."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        b0 = b1 = None
-        if box is not None:
-            b0, b1 = (C.c_int32 * 3)(*[int(t) for t in box[0]]), (C.c_int32 * 3)(*[int(t) for t in box[1]])
-
-        def call(p, s, out):
-            self.check(self.lib.svr_region_threshold(src, nx, ny, nz, on_dev, int(lo), int(hi), b0, b1, out))
-        return self._mask_call([], (nz, ny, nx), out_ptr, call)
-
-    def _region_labels(self, labels, shape):
-        """(device pointer, (nz, ny, nx), owned) of a uint32 label array [nz][ny][nx] (uploaded) or of a device pointer with `shape`."""
-        if isinstance(labels, np.ndarray):
-            a = np.ascontiguousarray(labels, dtype=np.uint32)
-            if a.ndim != 3:
-                raise ValueError("the labels must be [nz][ny][nx]")
-            buf = self.malloc(max(a.nbytes, 4))
-            self.to_device(buf, a)
-            return buf, a.shape, True
-        if shape is None:
-            raise ValueError("device labels need shape=(nz, ny, nx)")
-        return int(labels), tuple(int(n) for n in shape), False
-
-    def region_label(self, mask, connectivity: int = 6, shape=None, out_ptr: Optional[int] = None):
-        """svr_region_label: the connected components of a mask (a bool array [nz][ny][nx], or a device pointer with shape=) under
-        connectivity 6 / 18 / 26, numbered 1 .. K by their first voxel.  Returns (labels, K): a uint32 array [nz][ny][nx], or out_ptr
-        itself when a device buffer of 4 nx ny nz bytes is given."""
-        if isinstance(mask, np.ndarray):
-            shape = mask.shape
-        if shape is None:
-            raise ValueError("a device mask needs shape=(nz, ny, nx)")
-        nz, ny, nx = (int(n) for n in shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
-        k = C.c_uint32(0)
-        try:
-            self.check(self.lib.svr_region_label(C.c_void_p(buf), nx, ny, nz, int(connectivity), C.c_void_p(out), C.byref(k)))
-            if out_ptr is not None:
-                return out_ptr, int(k.value)
-            return self.to_host(out, (nz, ny, nx), np.uint32), int(k.value)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_label_table(self, labels, count: int, vox=None, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_label_table: the svr_region_component of the labels 1 .. count as a numpy structured array (COMPONENT_DTYPE),
-        indexed by label - 1.  labels: a uint32 array [nz][ny][nx] or a device pointer with shape=; vox (optional, for `sum`): a host
-        u16 array or a device pointer of the same shape.  out_ptr: a device buffer of 40 * count bytes that receives the table."""
-        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, shape)
-        src, on_dev = None, 0
-        if vox is not None:
-            src, vshape, on_dev, _keep = self._region_source(vox, (nz, ny, nx))
-            if tuple(vshape) != (nz, ny, nx):
-                raise ValueError("the volume and the labels differ in shape")
-        out = out_ptr if out_ptr is not None else self.malloc(40 * max(int(count), 1))
-        try:
-            self.check(self.lib.svr_region_label_table(C.c_void_p(lbuf), src, nx, ny, nz, on_dev, int(count), C.c_void_p(out)))
-            self.synchronize()
-            return self.to_host(out, (int(count),), COMPONENT_DTYPE)
-        finally:
-            if lowned:
-                self.free(lbuf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_select(self, labels, count: int, keep, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_select: the mask of the voxels whose label has a non-zero entry in keep (count + 1 entries, indexed by label; entry
-        0 is ignored)."""
-        lbuf, lshape, lowned = self._region_labels(labels, shape)
-        k = np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1)
-        if len(k) != int(count) + 1:
-            raise ValueError("keep must have count + 1 entries")
-        kbuf = self.malloc(len(k))
-        self.to_device(kbuf, k)
-
-        def call(p, s, out):
-            self.check(self.lib.svr_region_select(C.c_void_p(lbuf), s[2], s[1], s[0], int(count), C.c_void_p(kbuf), out))
-        try:
-            return self._mask_call([], lshape, out_ptr, call)
-        finally:
-            self.free(kbuf)
-            if lowned:
-                self.free(lbuf)
-
-    def region_select_by_size(self, labels, count: int, table=None, min_voxels: int = 0, largest_k: int = 0, shape=None,
-                              out_ptr: Optional[int] = None):
-        """svr_region_select_by_size: the components with at least min_voxels voxels among the largest_k largest (0 = no limit; ties go
-        to the lower label).  table: the structured array of region_label_table, a device pointer to it, or None (it is computed).
-        Returns (mask, kept)."""
-        lbuf, lshape, lowned = self._region_labels(labels, shape)
-        tbuf, towned = None, True
-        try:
-            if table is None:
-                tbuf = self.malloc(40 * max(int(count), 1))
-                self.region_label_table(lbuf, count, shape=lshape, out_ptr=tbuf)
-            elif isinstance(table, np.ndarray):
-                t = np.ascontiguousarray(table, dtype=COMPONENT_DTYPE)
-                tbuf = self.malloc(max(t.nbytes, 40))
-                self.to_device(tbuf, t)
-            else:
-                tbuf, towned = int(table), False
-
-            def call(p, s, out):
-                kept = C.c_uint32(0)
-                self.check(self.lib.svr_region_select_by_size(C.c_void_p(lbuf), s[2], s[1], s[0], int(count), C.c_void_p(tbuf), int(min_voxels),
-                                                              int(largest_k), out, C.byref(kept)))
-                return int(kept.value)
-            return self._mask_call([], lshape, out_ptr, call)
-        finally:
-            if towned and tbuf is not None:
-                self.free(tbuf)
-            if lowned:
-                self.free(lbuf)
-
-    def region_label_last_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_region_label_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    # ---- exact Euclidean distance maps and ball morphology (svr_region_distance / _distance_select / _ball / _distance_max / _distance_volume) ----
-    @staticmethod
-    def _weights(weights):
-        return None if weights is None else (C.c_uint32 * 3)(*[int(t) for t in weights])
-
-    def _region_map(self, d2, shape):
-        """(device pointer, (nz, ny, nx), owned) of a uint32 map [nz][ny][nx] (uploaded) or of a device pointer with `shape`."""
-        return self._region_labels(d2, shape)
-
-    def region_distance(self, mask, shape=None, weights=None, target: int = abi.DIST_TO_SET, out_ptr: Optional[int] = None):
-        """svr_region_distance: the exact squared distance, under the integer weights (wx, wy, wz) (None = 1, 1, 1), of every voxel to the
-        nearest set voxel (DIST_TO_SET) or to the nearest unset voxel of the volume (DIST_TO_UNSET); DIST_NONE everywhere when there is
-        none.  mask: a bool array [nz][ny][nx], or a device pointer with shape=.  Returns a uint32 array [nz][ny][nx], or out_ptr itself
-        when a device buffer of 4 nx ny nz bytes is given."""
-        if isinstance(mask, np.ndarray):
-            shape = mask.shape
-        if shape is None:
-            raise ValueError("a device mask needs shape=(nz, ny, nx)")
-        nz, ny, nx = (int(n) for n in shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
-        try:
-            self.check(self.lib.svr_region_distance(C.c_void_p(buf), nx, ny, nz, self._weights(weights), int(target), C.c_void_p(out)))
-            if out_ptr is not None:
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint32)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_distance_select(self, d2, lo2: int, hi2: int, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_distance_select: the mask of the voxels with lo2 <= d2 <= hi2.  d2: a uint32 array [nz][ny][nx] or a device pointer
-        with shape=."""
-        dbuf, dshape, downed = self._region_map(d2, shape)
-
-        def call(p, s, out):
-            self.check(self.lib.svr_region_distance_select(C.c_void_p(dbuf), s[2], s[1], s[0], int(lo2), int(hi2), out))
-        try:
-            return self._mask_call([], dshape, out_ptr, call)
-        finally:
-            if downed:
-                self.free(dbuf)
-
-    def region_ball(self, mask, op: int, r2: int, weights=None, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_ball: MORPH_DILATE / _ERODE / _OPEN / _CLOSE of a mask by the ball {offset : weighted d^2 <= r2}."""
-        def call(p, s, out):
-            self.check(self.lib.svr_region_ball(p[0], s[2], s[1], s[0], int(op), self._weights(weights), int(r2), out))
-        return self._mask_call([mask], shape, out_ptr, call)
-
-    def region_distance_max(self, d2, mask=None, shape=None):
-        """svr_region_distance_max: (max_d2, first_index, status) over the voxels of `mask` (a bool array or a device pointer; None = all
-        voxels): the largest value other than DIST_NONE and the smallest linear voxel index that attains it; status REGION_STATUS_EMPTY
-        when there is no such voxel."""
-        dbuf, (nz, ny, nx), downed = self._region_map(d2, shape)
-        mbuf, mowned = (None, False) if mask is None else self._region_mask(mask, (nz, ny, nx))
-        m, first, status = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
-        try:
-            self.check(self.lib.svr_region_distance_max(C.c_void_p(dbuf), C.c_void_p(mbuf) if mbuf is not None else None, nx, ny, nz, C.byref(m),
-                                                        C.byref(first), C.byref(status)))
-        finally:
-            if downed:
-                self.free(dbuf)
-            if mowned:
-                self.free(mbuf)
-        return int(m.value), int(first.value), int(status.value)
-
-    def region_distance_volume(self, d2, scale: int = 1, shape=None, out_ptr: Optional[int] = None):
-        """svr_region_distance_volume: min(65535, isqrt(d2 scale^2)) as a u16 array [nz][ny][nx] (DIST_NONE gives 65535); with out_ptr (a
-        device buffer of nx * ny * nz u16) the result stays on the device and out_ptr is returned."""
-        dbuf, (nz, ny, nx), downed = self._region_map(d2, shape)
-        out = out_ptr if out_ptr is not None else self.malloc(2 * max(nx * ny * nz, 1))
-        try:
-            self.check(self.lib.svr_region_distance_volume(C.c_void_p(dbuf), nx, ny, nz, int(scale), C.c_void_p(out)))
-            self.synchronize()
-            if out_ptr is not None:
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint16)
-        finally:
-            if downed:
-                self.free(dbuf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_distance_last_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_region_distance_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    def region_distance_pass_ms(self):
-        """(rows, y, z) HIP-event times of the passes of the last transform."""
-        ms = [C.c_float(0.0) for _ in range(3)]
-        self.check(self.lib.svr_region_distance_pass_ms(*[C.byref(t) for t in ms]))
-        return tuple(float(t.value) for t in ms)
-
-    # ---- geodesic distances, influence zones and splitting (svr_region_geodesic / _seed_labels / _split / _zone_cut) ----
-    @staticmethod
-    def _step_weights(weights):
-        return None if weights is None else (C.c_uint32 * 7)(*[int(t) for t in weights])
-
-    def region_geodesic(self, labels, domain, shape=None, step_weights=None, max_sweeps: int = 0, want_dist: bool = True, want_zones: bool = True,
-                        dist_ptr: Optional[int] = None, zones_ptr: Optional[int] = None):
-        """svr_region_geodesic: (dist, zones, sweeps) inside `domain` (a bool array [nz][ny][nx], or a device pointer with shape=) from the
-        voxels whose entry in `labels` (a uint32 array or a device pointer) is non-zero: the cost of the cheapest path of moves with the
-        seven step weights (x, y, z, xy, xz, yz, xyz; 0 forbids a class; None = 3, 3, 3, 4, 4, 4, 5) and the smallest label that attains it.
-        GEO_NONE / 0 where no marker reaches.  An output that is not wanted is None; with dist_ptr / zones_ptr (device buffers of
-        4 nx ny nz bytes; zones_ptr may be the labels' own pointer) the result stays on the device and the pointer is returned."""
-        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, domain.shape if isinstance(domain, np.ndarray) else shape)
-        mbuf, mowned = self._region_mask(domain, (nz, ny, nx))
-        nbytes = 4 * max(nx * ny * nz, 1)
-        dout = dist_ptr if dist_ptr is not None else (self.malloc(nbytes) if want_dist else None)
-        zout = zones_ptr if zones_ptr is not None else (self.malloc(nbytes) if want_zones else None)
-        sweeps = C.c_uint32(0)
-        try:
-            self.check(self.lib.svr_region_geodesic(C.c_void_p(lbuf), C.c_void_p(mbuf), nx, ny, nz, self._step_weights(step_weights), int(max_sweeps),
-                                                    None if dout is None else C.c_void_p(dout), None if zout is None else C.c_void_p(zout),
-                                                    C.byref(sweeps)))
-            dist = dist_ptr if dist_ptr is not None else (self.to_host(dout, (nz, ny, nx), np.uint32) if dout is not None else None)
-            zones = zones_ptr if zones_ptr is not None else (self.to_host(zout, (nz, ny, nx), np.uint32) if zout is not None else None)
-            return dist, zones, int(sweeps.value)
-        finally:
-            if lowned:
-                self.free(lbuf)
-            if mowned:
-                self.free(mbuf)
-            if dist_ptr is None and dout is not None:
-                self.free(dout)
-            if zones_ptr is None and zout is not None:
-                self.free(zout)
-
-    def region_seed_labels(self, seeds, shape, out_ptr: Optional[int] = None):
-        """svr_region_seed_labels: a zero uint32 array [nz][ny][nx] with the label i + 1 on the voxel (x, y, z) of seed i (the lowest i of
-        several on a voxel).  Returns the array, or out_ptr itself when a device buffer of 4 nx ny nz bytes is given."""
-        nz, ny, nx = (int(n) for n in shape)
-        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
-        try:
-            self.check(self.lib.svr_region_seed_labels(xyz.ctypes.data_as(C.POINTER(C.c_int32)), len(xyz), nx, ny, nz, C.c_void_p(out)))
-            self.synchronize()
-            if out_ptr is not None:
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint32)
-        finally:
-            if out_ptr is None:
-                self.free(out)
-
-    def region_split(self, mask, r2: int, connectivity: int = 26, dist_weights=None, step_weights=None, max_sweeps: int = 0, shape=None,
-                     out_ptr: Optional[int] = None):
-        """svr_region_split: erodes the mask by the ball of squared radius r2 (dist_weights as in region_ball), labels the cores under
-        `connectivity` and gives every voxel of the mask to the core that is nearest inside the mask (step_weights as in
-        region_geodesic; None = the chamfer weights of the connectivity).  Returns (zones, count, unreached, sweeps): a uint32 array
-        [nz][ny][nx] (or out_ptr itself), the number of cores, the voxels of the mask that no core reaches, the sweeps launched."""
-        if isinstance(mask, np.ndarray):
-            shape = mask.shape
-        if shape is None:
-            raise ValueError("a device mask needs shape=(nz, ny, nx)")
-        nz, ny, nx = (int(n) for n in shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
-        count, lost, sweeps = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-        try:
-            self.check(self.lib.svr_region_split(C.c_void_p(buf), nx, ny, nz, self._weights(dist_weights), int(r2), int(connectivity),
-                                                 self._step_weights(step_weights), int(max_sweeps), C.c_void_p(out), C.byref(count), C.byref(lost),
-                                                 C.byref(sweeps)))
-            zones = out_ptr if out_ptr is not None else self.to_host(out, (nz, ny, nx), np.uint32)
-            return zones, int(count.value), int(lost.value), int(sweeps.value)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_zone_cut(self, zones, connectivity: int = 26, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_zone_cut: the mask of the voxels with a zone and no connectivity-neighbour in a smaller non-zero zone: the zones with a
-        cut of one voxel between them.  zones: a uint32 array [nz][ny][nx] or a device pointer with shape=."""
-        zbuf, zshape, zowned = self._region_labels(zones, shape)
-
-        def call(p, s, out):
-            self.check(self.lib.svr_region_zone_cut(C.c_void_p(zbuf), s[2], s[1], s[0], int(connectivity), out))
-        try:
-            return self._mask_call([], zshape, out_ptr, call)
-        finally:
-            if zowned:
-                self.free(zbuf)
-
-    def region_geodesic_last_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_region_geodesic_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    # ---- grow from seeds (svr_region_growcut / _seed_classes / _label_paint) ----
-    def growcut_params(self, step_weights=None, connectivity: int = 26, gain: int = 1, shift: int = 0, max_sweeps: int = 0) -> abi.GrowcutParams:
-        """svr_region_growcut_params_default of the connectivity with the weights (if given), gain, shift and cap replaced."""
-        p = abi.GrowcutParams()
-        self.check(self.lib.svr_region_growcut_params_default(C.byref(p), int(connectivity)))
-        if step_weights is not None:
-            for c in range(7):
-                p.step_weights[c] = int(step_weights[c])
-        p.contrast_gain, p.contrast_shift, p.max_sweeps = int(gain), int(shift), int(max_sweeps)
-        return p
-
-    def region_growcut(self, vox, labels, domain=None, shape=None, step_weights=None, connectivity: int = 26, gain: int = 1, shift: int = 0,
-                       max_sweeps: int = 0, want_cost: bool = True, want_zones: bool = True, cost_ptr: Optional[int] = None,
-                       zones_ptr: Optional[int] = None):
-        """svr_region_growcut: (cost, zones, info).  Every voxel of `domain` (a bool array [nz][ny][nx] or a device pointer; None = the
-        whole volume) gets the class of the marker (non-zero entries of `labels`, a uint32 array or a device pointer) that reaches it
-        over the cheapest path, a move costing step_weights[class] + gain * (|I(u) - I(v)| >> shift) on the raw voxels of `vox` (a host
-        u16 array, or a device pointer with shape=).  step_weights None = 1 on the move classes of `connectivity`.  GEO_NONE / 0 where no
-        marker reaches.  An output that is not wanted is None; with cost_ptr / zones_ptr (device buffers of 4 nx ny nz bytes; zones_ptr
-        may be the labels' own pointer) the result stays on the device and the pointer is returned.  info is the svr_growcut_info.  A
-        failure raises SvrError with .code and .info set; for REGION_ERR_RANGE (costs reached GROWCUT_CAP) .cost and .zones hold the
-        saturated solution as well."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        lbuf, lshape, lowned = self._region_labels(labels, (nz, ny, nx))
-        if tuple(lshape) != (nz, ny, nx):
-            raise ValueError("the volume and the labels differ in shape")
-        mbuf, mowned = (None, False) if domain is None else self._region_mask(domain, (nz, ny, nx))
-        p = self.growcut_params(step_weights, connectivity, gain, shift, max_sweeps)
-        dims = (C.c_int32 * 3)(nx, ny, nz)
-        nbytes = 4 * max(nx * ny * nz, 1)
-        cout = cost_ptr if cost_ptr is not None else (self.malloc(nbytes) if want_cost else None)
-        zout = zones_ptr if zones_ptr is not None else (self.malloc(nbytes) if want_zones else None)
-        info = abi.GrowcutInfo()
-
-        def results():
-            cost = cost_ptr if cost_ptr is not None else (self.to_host(cout, (nz, ny, nx), np.uint32) if cout is not None else None)
-            zones = zones_ptr if zones_ptr is not None else (self.to_host(zout, (nz, ny, nx), np.uint32) if zout is not None else None)
-            return cost, zones
-        try:
-            rc = self.lib.svr_region_growcut(src, dims, on_dev, C.c_void_p(lbuf), None if mbuf is None else C.c_void_p(mbuf), C.byref(p),
-                                             None if cout is None else C.c_void_p(cout), None if zout is None else C.c_void_p(zout), C.byref(info))
-            try:
-                self.check(rc)
-            except SvrError as e:
-                e.code, e.info = int(rc), info
-                if rc == abi.REGION_ERR_RANGE:
-                    e.cost, e.zones = results()
-                raise
-            return results() + (info,)
-        finally:
-            if lowned:
-                self.free(lbuf)
-            if mowned:
-                self.free(mbuf)
-            if cost_ptr is None and cout is not None:
-                self.free(cout)
-            if zones_ptr is None and zout is not None:
-                self.free(zout)
-
-    def region_seed_classes(self, seeds, classes, shape, out_ptr: Optional[int] = None):
-        """svr_region_seed_classes: a zero uint32 array [nz][ny][nx] with classes[i] on the voxel (x, y, z) of seed i (the lowest i of
-        several on a voxel).  Returns the array, or out_ptr itself when a device buffer of 4 nx ny nz bytes is given."""
-        nz, ny, nx = (int(n) for n in shape)
-        xyz = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
-        cls = np.ascontiguousarray(classes, dtype=np.uint32).reshape(-1)
-        if len(cls) != len(xyz):
-            raise ValueError("one class per seed")
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(nx * ny * nz, 1))
-        try:
-            self.check(self.lib.svr_region_seed_classes(xyz.ctypes.data_as(C.POINTER(C.c_int32)), cls.ctypes.data_as(C.POINTER(C.c_uint32)), len(xyz),
-                                                        (C.c_int32 * 3)(nx, ny, nz), C.c_void_p(out)))
-            self.synchronize()
-            if out_ptr is not None:
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint32)
-        finally:
-            if out_ptr is None:
-                self.free(out)
-
-    def region_label_paint(self, labels, mask, label: int, only_unlabelled: bool = False, shape=None):
-        """svr_region_label_paint: `label` on every voxel of `mask` (a bool array or a device pointer), or only where the label is still 0.
-        labels: a uint32 array [nz][ny][nx] (the painted copy is returned) or a device pointer with shape= (painted in place and
-        returned)."""
-        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, shape)
-        mbuf, mowned = self._region_mask(mask, (nz, ny, nx))
-        try:
-            self.check(self.lib.svr_region_label_paint(C.c_void_p(lbuf), (C.c_int32 * 3)(nx, ny, nz), C.c_void_p(mbuf), int(label), int(bool(only_unlabelled))))
-            self.synchronize()
-            return self.to_host(lbuf, (nz, ny, nx), np.uint32) if lowned else lbuf
-        finally:
-            if lowned:
-                self.free(lbuf)
-            if mowned:
-                self.free(mbuf)
-
-    def region_growcut_last_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_region_growcut_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    # ---- histograms of the u16 voxels (svr_volume_histogram, svr_region_label_histogram); the analysis is in the module functions ----
-    def histogram_params(self, lo: int = 0, hi: int = 65535, shift: int = 0, box=None) -> abi.HistogramParams:
-        """svr_histogram_params_default with the window, shift and box ((x0, y0, z0), (x1, y1, z1), inclusive) replaced."""
-        return histogram_params(lo, hi, shift, box, self.lib)
-
-    def _histogram_out(self, cells, out_ptr, call):
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(cells, 1))
-        try:
-            call(C.c_void_p(out))
-            self.synchronize()
-            return self.to_host(out, (cells,), np.uint32)
-        finally:
-            if out_ptr is None:
-                self.free(out)
-
-    def volume_histogram(self, vox, mask=None, lo: int = 0, hi: int = 65535, shift: int = 0, box=None, shape=None,
-                         out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_volume_histogram: np.uint32[bins], bins = ((hi - lo) >> shift) + 1: the voxels of `box` (inclusive, cut to the volume; None
-        = all) whose mask bit is set (mask: a bool array [nz][ny][nx], a device pointer to the bit mask, or None = every voxel) and whose
-        value v lies in lo .. hi, counted in bin (v - lo) >> shift.  vox is a host [nz][ny][nx] u16 array, or a device pointer with
-        shape=(nz, ny, nx).  out_ptr: a device buffer of 4 * bins bytes that receives the counts."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        p = self.histogram_params(lo, hi, shift, box)
-        bins = int(self.lib.svr_histogram_bins(C.byref(p)))
-        mbuf, mowned = (None, False) if mask is None else self._region_mask(mask, (nz, ny, nx))
-        dims = (C.c_int32 * 3)(nx, ny, nz)
-        try:
-            return self._histogram_out(bins, out_ptr, lambda out: self.check(self.lib.svr_volume_histogram(
-                src, dims, on_dev, None if mbuf is None else C.c_void_p(mbuf), C.byref(p), out)))
-        finally:
-            if mowned:
-                self.free(mbuf)
-
-    def region_label_histogram(self, labels, vox, count: int, lo: int = 0, hi: int = 65535, shift: int = 0, box=None, shape=None,
-                               out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_label_histogram: np.uint32[count + 1, bins]; row l is the histogram of the voxels whose label is l (row 0: the
-        background; labels above count are ignored).  labels: a uint32 array [nz][ny][nx] or a device pointer with shape=; vox, the
-        window, shift and box as in volume_histogram.  out_ptr: a device buffer of 4 * (count + 1) * bins bytes."""
-        lbuf, (nz, ny, nx), lowned = self._region_labels(labels, shape)
-        try:
-            src, vshape, on_dev, _keep = self._region_source(vox, (nz, ny, nx))
-            if tuple(vshape) != (nz, ny, nx):
-                raise ValueError("the volume and the labels differ in shape")
-            p = self.histogram_params(lo, hi, shift, box)
-            bins = int(self.lib.svr_histogram_bins(C.byref(p)))
-            dims = (C.c_int32 * 3)(nx, ny, nz)
-            cells = (int(count) + 1) * bins
-            if bins == 0 or cells > abi.HISTOGRAM_MAX_CELLS:
-                cells = 0                                         # the library refuses the call: a token buffer is enough to hear it
-            return self._histogram_out(cells, out_ptr, lambda out: self.check(self.lib.svr_region_label_histogram(
-                C.c_void_p(lbuf), src, dims, on_dev, int(count), C.byref(p), out))).reshape(int(count) + 1, bins)
-        finally:
-            if lowned:
-                self.free(lbuf)
-
-    def volume_histogram_last_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_volume_histogram_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
-    def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
-        """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
-        to abi.OVERLAY_MAX_PALETTE RGBA8 entries as uint32 (r in the low byte) or as rows (r, g, b, a); the style keeps the array alive."""
-        st = abi.OverlayStyle()
-        self.check(self.lib.svr_overlay_style_default(C.byref(st)))
-        if fill_alpha is not None:
-            st.fill_alpha = int(fill_alpha)
-        if edge_alpha is not None:
-            st.edge_alpha = int(edge_alpha)
-        if palette is not None:
-            pal = np.asarray(palette)
-            if pal.ndim == 2:
-                pal = np.ascontiguousarray(pal, dtype=np.uint8).view("<u4").reshape(-1)
-            st._palette = np.ascontiguousarray(pal, dtype=np.uint32)
-            st.palette = st._palette.ctypes.data_as(C.POINTER(C.c_uint32))
-            st.palette_count = len(st._palette)
-        return st
-
-    def overlay_palette_default(self, n: int = abi.OVERLAY_DEFAULT_PALETTE) -> np.ndarray:
-        out = np.zeros(int(n), dtype=np.uint32)
-        self.check(self.lib.svr_overlay_palette_default(out.ctypes.data_as(C.POINTER(C.c_uint32)), int(n)))
-        return out
-
-    @staticmethod
-    def _overlay_source(mask: Optional[int], labels: Optional[int]) -> abi.OverlaySource:
-        return abi.OverlaySource(C.c_void_p(int(mask)) if mask else None, C.c_void_p(int(labels)) if labels else None)
-
-    def slice_ids(self, ids: int, volume: cudaVolume, shape, w: int, h: int, params: abi.SliceParams, mask: Optional[int] = None,
-                  labels: Optional[int] = None, count: int = 1, spacing: float = 0.0):
-        """svr_slice_ids: the region id of every owned pixel of `count` slices into the device buffer ids (count x h x w uint32).  mask /
-        labels: the device pointer of a bit mask or of a uint32 label array of the (nz, ny, nx) = shape volume; exactly one is given."""
-        nz, ny, nx = (int(n) for n in shape)
-        src = self._overlay_source(mask, labels)
-        self.check(self.lib.svr_slice_ids(C.c_void_p(int(ids)), C.byref(volume), nx, ny, nz, int(w), int(h), C.byref(params), int(count),
-                                          C.c_float(float(spacing)), C.byref(src)))
-
-    def hit_ids(self, ids: int, hits: int, w: int, h: int, volume: cudaVolume, shape, mask: Optional[int] = None, labels: Optional[int] = None):
-        """svr_hit_ids: the region id of every record of a full w x h hit map (svr_render_hits) into the device buffer ids."""
-        nz, ny, nx = (int(n) for n in shape)
-        src = self._overlay_source(mask, labels)
-        self.check(self.lib.svr_hit_ids(C.c_void_p(int(ids)), C.c_void_p(int(hits)), int(w), int(h), C.byref(volume), nx, ny, nz, C.byref(src)))
-
-    def overlay_ids(self, imgs: int, ids: int, w: int, h: int, count: int = 1, style: Optional[abi.OverlayStyle] = None):
-        """svr_overlay_ids: tints `count` RGBA8 images of w x h in place by their id images: fill inside a part, outline at its edge."""
-        st = style if style is not None else self.overlay_style()
-        self.check(self.lib.svr_overlay_ids(C.c_void_p(int(imgs)), C.c_void_p(int(ids)), int(w), int(h), int(count), C.byref(st)))
-
-    def overlay_slice(self, imgs: int, volume: cudaVolume, shape, w: int, h: int, params: abi.SliceParams, mask: Optional[int] = None,
-                      labels: Optional[int] = None, style: Optional[abi.OverlayStyle] = None, count: int = 1, spacing: float = 0.0):
-        """svr_overlay_slice: slice_ids followed by overlay_ids in one kernel, over the owned pixels of the slice images at imgs."""
-        nz, ny, nx = (int(n) for n in shape)
-        src = self._overlay_source(mask, labels)
-        st = style if style is not None else self.overlay_style()
-        self.check(self.lib.svr_overlay_slice(C.c_void_p(int(imgs)), C.byref(volume), nx, ny, nz, int(w), int(h), C.byref(params), int(count),
-                                              C.c_float(float(spacing)), C.byref(src), C.byref(st)))
-
-    def overlay_last_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_overlay_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    # ---- surface meshes by surface nets (svr_mesh_isosurface / _region / _measure / _positions) ----
-    def mesh_params(self, level: Optional[int] = None, relax: int = 0) -> abi.MeshParams:
-        p = abi.MeshParams()
-        self.check(self.lib.svr_mesh_params_default(C.byref(p)))
-        if level is not None:
-            p.level = int(level)
-        p.relax = int(relax)
-        return p
-
-    def _mesh_extract(self, call):
-        """A counting call, then an extraction call into buffers of the counted size.  call(vertices pointer, vertex capacity, triangles
-        pointer, triangle capacity, info) runs the C function.  Returns (vertices int32 [nv, 3], triangles uint32 [nt, 3], info)."""
-        info = abi.MeshInfo()
-        self.check(call(None, 0, None, 0, info))
-        nv, nt = int(info.vertices), int(info.triangles)
-        if nv == 0:
-            return np.zeros((0, 3), np.int32), np.zeros((0, 3), np.uint32), info
-        buf = self.malloc(12 * (nv + max(nt, 1)))
-        try:
-            self.check(call(C.c_void_p(buf), nv, C.c_void_p(buf + 12 * nv), nt, info))
-            return self.to_host(buf, (nv, 3), np.int32), self.to_host(buf + 12 * nv, (nt, 3), np.uint32), info
-        finally:
-            self.free(buf)
-
-    def mesh_isosurface(self, vox, level: int, relax: int = 0, shape=None):
-        """svr_mesh_isosurface: the surface-nets mesh of {v >= level} of a host [nz][ny][nx] u16 array or a device pointer with
-        shape=(nz, ny, nx), after `relax` constrained relaxation steps.  Returns (vertices, triangles, info): int32 [nv, 3] in units of
-        1/256 voxel on the padded grid (sample x sits at 256 (x + 1)), uint32 [nt, 3], and the svr_mesh_info."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        p = self.mesh_params(level, relax)
-        return self._mesh_extract(lambda v, nv, t, nt, info: self.lib.svr_mesh_isosurface(src, nx, ny, nz, on_dev, C.byref(p), v, nv, t, nt, C.byref(info)))
-
-    def mesh_region(self, mask, relax: int = 0, shape=None):
-        """svr_mesh_region: the same for a region mask (a bool array [nz][ny][nx], or a device pointer to the bit mask with shape=)."""
-        if isinstance(mask, np.ndarray):
-            shape = mask.shape
-        if shape is None:
-            raise ValueError("a device mask needs shape=(nz, ny, nx)")
-        nz, ny, nx = (int(n) for n in shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        p = self.mesh_params(None, relax)
-        try:
-            return self._mesh_extract(lambda v, nv, t, nt, info: self.lib.svr_mesh_region(C.c_void_p(buf), nx, ny, nz, C.byref(p), v, nv, t, nt, C.byref(info)))
-        finally:
-            if owned:
-                self.free(buf)
-
-    def mesh_measure(self, vertices, triangles, scale=(1.0 / 256, 1.0 / 256, 1.0 / 256)):
-        """svr_mesh_measure of host arrays (uploaded): (volume6, area) -- the exact integer 6 * 256^3 * (enclosed volume in voxels) and the
-        surface area under the per-axis scale (spacing / 256)."""
-        v = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1, 3)
-        t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
-        s = (C.c_double * 3)(*[float(x) for x in scale])
-        vol, area = C.c_int64(0), C.c_double(0.0)
-        buf = self.malloc(max(v.nbytes, 4) + max(t.nbytes, 4))
-        try:
-            if len(v):
-                self.to_device(buf, v)
-            if len(t):
-                self.to_device(buf + max(v.nbytes, 4), t)
-            self.check(self.lib.svr_mesh_measure(C.c_void_p(buf), len(v), C.c_void_p(buf + max(v.nbytes, 4)), len(t), s, C.byref(vol), C.byref(area)))
-        finally:
-            self.free(buf)
-        return int(vol.value), float(area.value)
-
-    def mesh_positions(self, vertices, spacing=(1.0, 1.0, 1.0), volume: Optional[cudaVolume] = None) -> np.ndarray:
-        return mesh_positions(self.lib, vertices, spacing, volume)
-
-    def mesh_last_ms(self):
-        """(classify, emit, relax) HIP-event milliseconds of the last mesh call"""
-        ms = [C.c_float(0.0) for _ in range(3)]
-        self.check(self.lib.svr_mesh_last_ms(*[C.byref(m) for m in ms]))
-        return tuple(float(m.value) for m in ms)
-
-    # ---- exact volume filters (svr_volume_*): median / min / max and binomial smoothing of the raw voxels ----
-    def volume_rank(self, vox, op: int, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
-        """svr_volume_rank: the median (FILTER_MEDIAN), minimum (FILTER_MIN) or maximum (FILTER_MAX) of every voxel's window under the
-        unit element 6 / 18 / 26 with a replicated border, applied `iterations` times.  vox is a host [nz][ny][nx] u16 array, or a device
-        pointer with shape=(nz, ny, nx).  Returns a u16 array [nz][ny][nx]; with out_ptr (a device buffer of nx * ny * nz u16 that does
-        not overlap a device `vox`) the result stays on the device and out_ptr is returned."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        return self._volume_filter((nz, ny, nx), out_ptr, lambda out: self.lib.svr_volume_rank(
-            src, nx, ny, nz, on_dev, int(op), int(element), int(iterations), C.c_void_p(out)))
-
-    def volume_median(self, vox, element: int = 6, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
-        """volume_rank with FILTER_MEDIAN."""
-        return self.volume_rank(vox, abi.FILTER_MEDIAN, element, iterations, shape, out_ptr)
-
-    def volume_smooth(self, vox, radii, shape=None, out_ptr: Optional[int] = None):
-        """svr_volume_smooth: separable binomial smoothing with the per-axis radii (rx, ry, rz), each 0 .. SMOOTH_MAX_RADIUS, one
-        rounding per axis, a replicated border.  vox, the return value and out_ptr as in volume_rank."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        r = (C.c_uint32 * 3)(*[int(t) for t in radii])
-        return self._volume_filter((nz, ny, nx), out_ptr, lambda out: self.lib.svr_volume_smooth(src, nx, ny, nz, on_dev, r, C.c_void_p(out)))
-
-    def _volume_filter(self, shape, out_ptr, call):
-        nz, ny, nx = shape
-        out = out_ptr if out_ptr is not None else self.malloc(2 * max(nx * ny * nz, 1))
-        try:
-            self.check(call(out))
-            self.synchronize()
-            if out_ptr is not None:
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint16)
-        finally:
-            if out_ptr is None:
-                self.free(out)
-
-    def volume_filter_last_ms(self) -> float:
-        """HIP-event time of the device work of the last volume_rank / volume_smooth call."""
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_volume_filter_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    # ---- crop and resample (svr_resample_grid_* / svr_volume_resample / svr_region_resample / _label_resample / _paste / _mask_expand) ----
-    def resample_grid_box(self, shape, box) -> abi.ResampleGrid:
-        return resample_grid_box(shape, box, self.lib)
-
-    def resample_grid_spacing(self, shape, src_spacing, target_spacing, box=None):
-        return resample_grid_spacing(shape, src_spacing, target_spacing, box, self.lib)
-
-    def resample_grid_dims(self, shape, out_shape, box=None) -> abi.ResampleGrid:
-        return resample_grid_dims(shape, out_shape, box, self.lib)
-
-    def resample_grid_place(self, volume: cudaVolume, shape, grid) -> cudaVolume:
-        return resample_grid_place(volume, shape, grid, self.lib)
-
-    def volume_resample(self, vox, grid, mode: int = abi.RESAMPLE_AUTO, shape=None, out_ptr: Optional[int] = None):
-        """svr_volume_resample: the volume on `grid` (a ResampleGrid, or ((origin, step, count) of x, y, z)) under RESAMPLE_NEAREST /
-        _LINEAR / _AREA / _AUTO.  vox is a host [nz][ny][nx] u16 array, or a device pointer with shape=(nz, ny, nx).  Returns a u16 array
-        of grid.shape; with out_ptr (a device buffer of that many u16 that does not overlap a device `vox`) the result stays on the
-        device and out_ptr is returned."""
-        src, (nz, ny, nx), on_dev, _keep = self._region_source(vox, shape)
-        g, dims = resample_grid(grid), (C.c_int32 * 3)(nx, ny, nz)
-        return self._volume_filter(g.shape, out_ptr, lambda out: self.lib.svr_volume_resample(src, dims, on_dev, C.byref(g), int(mode), C.c_void_p(out)))
-
-    def volume_crop(self, vox, box, shape=None, out_ptr: Optional[int] = None):
-        """volume_resample on the grid of a box ((x0, y0, z0), (x1, y1, z1)), inclusive, cut to the volume.  Returns (result, grid)."""
-        shape = vox.shape if isinstance(vox, np.ndarray) else shape
-        g = self.resample_grid_box(shape, box)
-        return self.volume_resample(vox, g, abi.RESAMPLE_NEAREST, shape, out_ptr), g
-
-    def region_resample(self, mask, grid, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
-        """svr_region_resample: NEAREST on a mask (a bool array [nz][ny][nx], or a device pointer with shape=).  Returns the bool array of
-        grid.shape; out_ptr: a device buffer of region_mask_words(grid.shape) uint32 that receives the bit mask."""
-        if isinstance(mask, np.ndarray):
-            shape = mask.shape
-        if shape is None:
-            raise ValueError("a device mask needs shape=(nz, ny, nx)")
-        nz, ny, nx = (int(n) for n in shape)
-        g, dims = resample_grid(grid), (C.c_int32 * 3)(nx, ny, nz)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        words = region_mask_words(g.shape)
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(words, 1))
-        try:
-            self.check(self.lib.svr_region_resample(C.c_void_p(buf), dims, C.byref(g), C.c_void_p(out)))
-            return region_mask_unpack(self.to_host(out, (words,), np.uint32), g.shape)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_label_resample(self, labels, grid, shape=None, out_ptr: Optional[int] = None):
-        """svr_region_label_resample: NEAREST on a uint32 map (labels, zones; a squared-distance map only for crops).  Returns the uint32
-        array of grid.shape, or out_ptr itself when a device buffer of that many uint32 is given."""
-        buf, (nz, ny, nx), owned = self._region_labels(labels, shape)
-        g, dims = resample_grid(grid), (C.c_int32 * 3)(nx, ny, nz)
-        out = out_ptr if out_ptr is not None else self.malloc(4 * max(int(np.prod(g.shape)), 1))
-        try:
-            self.check(self.lib.svr_region_label_resample(C.c_void_p(buf), dims, C.byref(g), C.c_void_p(out)))
-            if out_ptr is not None:
-                self.synchronize()
-                return out_ptr
-            return self.to_host(out, g.shape, np.uint32)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def region_paste(self, sub, full, offset, op: int = abi.PASTE_REPLACE, sub_shape=None, full_shape=None):
-        """svr_region_paste: the sub-mask put back at offset (x, y, z) of the full mask with PASTE_REPLACE, MASK_OR or MASK_ANDNOT.  Masks
-        are bool arrays, or device pointers with their shapes.  A device `full` is changed in place and returned; a host `full` is left
-        alone and the pasted bool array is returned."""
-        sub_shape = sub.shape if isinstance(sub, np.ndarray) else tuple(int(n) for n in sub_shape)
-        full_shape = full.shape if isinstance(full, np.ndarray) else tuple(int(n) for n in full_shape)
-        sbuf, sowned = self._region_mask(sub, sub_shape)
-        fbuf, fowned = self._region_mask(full, full_shape)
-        try:
-            self.check(self.lib.svr_region_paste(C.c_void_p(sbuf), (C.c_int32 * 3)(*sub_shape[::-1]), C.c_void_p(fbuf), (C.c_int32 * 3)(*full_shape[::-1]),
-                                                 (C.c_int32 * 3)(*[int(t) for t in offset]), int(op)))
-            if not fowned:
-                self.synchronize()
-                return full
-            return region_mask_unpack(self.to_host(fbuf, (region_mask_words(full_shape),), np.uint32), full_shape)
-        finally:
-            if sowned:
-                self.free(sbuf)
-            if fowned:
-                self.free(fbuf)
-
-    def region_mask_expand(self, mask, value: int = 1, shape=None, out_ptr: Optional[int] = None):
-        """svr_region_mask_expand: one byte per voxel, `value` (1 .. 255) inside the mask and 0 outside -- what io.mhd_write saves a mask
-        from.  Returns the u8 array [nz][ny][nx], or out_ptr itself when a device buffer of nx * ny * nz bytes is given."""
-        if isinstance(mask, np.ndarray):
-            shape = mask.shape
-        if shape is None:
-            raise ValueError("a device mask needs shape=(nz, ny, nx)")
-        nz, ny, nx = (int(n) for n in shape)
-        buf, owned = self._region_mask(mask, (nz, ny, nx))
-        out = out_ptr if out_ptr is not None else self.malloc(max(nx * ny * nz, 4))
-        try:
-            self.check(self.lib.svr_region_mask_expand(C.c_void_p(buf), (C.c_int32 * 3)(nx, ny, nz), int(value), C.c_void_p(out)))
-            if out_ptr is not None:
-                self.synchronize()
-                return out_ptr
-            return self.to_host(out, (nz, ny, nx), np.uint8)
-        finally:
-            if owned:
-                self.free(buf)
-            if out_ptr is None:
-                self.free(out)
-
-    def volume_resample_last_ms(self) -> float:
-        """HIP-event time of the device work of the last volume_resample / region_resample / _label_resample / _paste / _mask_expand."""
-        ms = C.c_float(0.0)
-        self.check(self.lib.svr_volume_resample_last_ms(C.byref(ms)))
-        return float(ms.value)
-
-    def region_measure(self, stats: abi.RegionStats, spacing=(1.0, 1.0, 1.0)) -> abi.RegionMeasurement:
-        """svr_region_measure: volume, mean, standard deviation, centroid (voxel indices) and surface area from the integer statistics."""
-        m = abi.RegionMeasurement()
-        sp = (C.c_double * 3)(*[float(t) for t in spacing])
-        self.check(self.lib.svr_region_measure(C.byref(stats), sp, C.byref(m)))
-        return m
-
-
-# svr_region_component as a numpy record (40 bytes); LABEL_SCAN_BLOCK mirrors SVR_LABEL_SCAN_BLOCK of csrc/svr_label.hip
-COMPONENT_DTYPE = np.dtype([("voxels", "<u4"), ("first", "<u4"), ("bbox_min", "<i4", (3,)), ("bbox_max", "<i4", (3,)), ("sum", "<u8")])
-assert COMPONENT_DTYPE.itemsize == 40
-LABEL_SCAN_BLOCK = abi.LABEL_SCAN_BLOCK
-
-
-def region_label_scan_levels(shape) -> int:
-    """The levels of svr_region_label's renumbering scan for a [nz][ny][nx] volume: 1 while one block covers the mask words, 2 up to
-    a block of blocks, and so on."""
-    n, levels = region_mask_words(shape), 1
-    while n > LABEL_SCAN_BLOCK:
-        n, levels = (n + LABEL_SCAN_BLOCK - 1) // LABEL_SCAN_BLOCK, levels + 1
-    return levels
-
-
-def mesh_positions(lib, vertices, spacing=(1.0, 1.0, 1.0), volume=None) -> np.ndarray:
-    """svr_mesh_positions: float32 [nv, 3] positions of mesh vertices (int32 [nv, 3], 1/256 voxel on the padded grid) -- millimetres,
-    (u / 256 - 0.5) * spacing, or with `volume` (a cudaVolume) the world coordinates of the sampler's mapping.  Host code of the library:
-    no device is needed."""
-    lib = lib if lib is not None else abi.load()
-    v = np.ascontiguousarray(vertices, dtype=np.int32).reshape(-1, 3)
-    out = np.zeros((len(v), 3), dtype=np.float32)
-    sp = (C.c_double * 3)(*[float(t) for t in spacing])
-    rc = lib.svr_mesh_positions(v.ctypes.data_as(C.c_void_p), len(v), sp, C.byref(volume) if volume is not None else None, out.ctypes.data_as(C.c_void_p))
-    if rc != 0:
-        msg = lib.svr_last_error().decode()
-        lib.svr_clear_error()
-        raise SvrError(f"svr_mesh_positions failed ({rc}): {msg}")
-    return out
-
-
-def distance_weights(spacing, shape, lib=None):
-    """svr_region_distance_weights: ((wx, wy, wz), unit) for a spacing (sx, sy, sz) and a [nz][ny][nx] shape: the integer weights of the
-    squared distance in units of `unit` = min(spacing) / 2^k.  A length L is r2 = floor((L / unit)^2); a map value d2 means sqrt(d2) unit.
-    Host code of the library: no device is needed."""
-    lib = lib if lib is not None else abi.load()
-    nz, ny, nx = (int(n) for n in shape)
-    sp = (C.c_double * 3)(*[float(t) for t in spacing])
-    w, unit = (C.c_uint32 * 3)(), C.c_double(0.0)
-    rc = lib.svr_region_distance_weights(sp, nx, ny, nz, w, C.byref(unit))
-    if rc != 0:
-        msg = lib.svr_last_error().decode()
-        lib.svr_clear_error()
-        raise SvrError(f"svr_region_distance_weights failed ({rc}): {msg}")
-    return (int(w[0]), int(w[1]), int(w[2])), float(unit.value)
-
-
-def geodesic_weights(spacing, connectivity, shape, lib=None):
-    """svr_region_geodesic_weights: ((w_x, w_y, w_z, w_xy, w_xz, w_yz, w_xyz), unit) for a spacing (sx, sy, sz), a connectivity 6 / 18 / 26
-    and a [nz][ny][nx] shape: the Euclidean lengths of the moves in units of `unit` = min(spacing) / 2^k, rounded, 0 for the classes
-    beyond the connectivity.  A geodesic map value d means about d unit.  Host code of the library: no device is needed."""
-    lib = lib if lib is not None else abi.load()
-    nz, ny, nx = (int(n) for n in shape)
-    sp = (C.c_double * 3)(*[float(t) for t in spacing])
-    w, unit = (C.c_uint32 * 7)(), C.c_double(0.0)
-    rc = lib.svr_region_geodesic_weights(sp, int(connectivity), nx, ny, nz, w, C.byref(unit))
-    if rc != 0:
-        msg = lib.svr_last_error().decode()
-        lib.svr_clear_error()
-        raise SvrError(f"svr_region_geodesic_weights failed ({rc}): {msg}")
-    return tuple(int(t) for t in w), float(unit.value)
-
-
-def smooth_radii(spacing, sigma, lib=None):
-    """svr_volume_smooth_radii: ((rx, ry, rz), (sx, sy, sz)) for a spacing and a sigma in the spacing's units: the binomial radii
-    llround(2 (sigma / spacing[a])^2) and the sigma each one applies, sqrt(r / 2) spacing[a].  Host code of the library: no device is
-    needed."""
-    lib = lib if lib is not None else abi.load()
-    sp = (C.c_double * 3)(*[float(t) for t in spacing])
-    r, so = (C.c_uint32 * 3)(), (C.c_double * 3)()
-    rc = lib.svr_volume_smooth_radii(sp, float(sigma), r, so)
-    if rc != 0:
-        msg = lib.svr_last_error().decode()
-        lib.svr_clear_error()
-        raise SvrError(f"svr_volume_smooth_radii failed ({rc}): {msg}")
-    return (int(r[0]), int(r[1]), int(r[2])), (float(so[0]), float(so[1]), float(so[2]))
-
-
-def _histogram_call(lib, name, rc):
-    """Raises on an error code; returns True when the histogram was empty (SVR_HISTOGRAM_STATUS_EMPTY)."""
-    if rc not in (0, abi.HISTOGRAM_STATUS_EMPTY):
-        msg = lib.svr_last_error().decode("utf-8", "replace")
-        lib.svr_clear_error()
-        raise SvrError(f"{name} failed ({rc}): {msg}")
-    return rc == abi.HISTOGRAM_STATUS_EMPTY
-
-
-def _histogram_counts(counts):
-    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
-    return c, c.ctypes.data_as(C.c_void_p) if len(c) else None
-
-
-def histogram_params(lo: int = 0, hi: int = 65535, shift: int = 0, box=None, lib=None) -> abi.HistogramParams:
-    """svr_histogram_params_default with the window, shift and box ((x0, y0, z0), (x1, y1, z1), inclusive) replaced.  The histogram
-    helpers below are host code of the library: no device is needed."""
-    lib = lib if lib is not None else abi.load()
-    p = abi.HistogramParams()
-    _histogram_call(lib, "svr_histogram_params_default", lib.svr_histogram_params_default(C.byref(p)))
-    p.lo, p.hi, p.shift = int(lo), int(hi), int(shift)
-    if box is not None:
-        for a in range(3):
-            p.box_min[a], p.box_max[a] = int(box[0][a]), int(box[1][a])
-    return p
-
-
-def histogram_bins(lo: int = 0, hi: int = 65535, shift: int = 0, lib=None) -> int:
-    """svr_histogram_bins: ((hi - lo) >> shift) + 1, or 0 for an invalid window or shift."""
-    lib = lib if lib is not None else abi.load()
-    p = histogram_params(lo, hi, shift, None, lib)
-    return int(lib.svr_histogram_bins(C.byref(p)))
-
-
-def histogram_bin_range(bin: int, lo: int = 0, hi: int = 65535, shift: int = 0, lib=None):
-    """svr_histogram_bin_range: (v_lo, v_hi), the raw values of a bin -- the window for region_threshold."""
-    lib = lib if lib is not None else abi.load()
-    p = histogram_params(lo, hi, shift, None, lib)
-    a, b = C.c_uint32(0), C.c_uint32(0)
-    _histogram_call(lib, "svr_histogram_bin_range", lib.svr_histogram_bin_range(C.byref(p), int(bin), C.byref(a), C.byref(b)))
-    return int(a.value), int(b.value)
-
-
-def histogram_moments(counts, lib=None):
-    """svr_histogram_moments: (n, sum, sum_sq) of the bin indices of a uint32 histogram; (0, 0, 0) when it is empty."""
-    lib = lib if lib is not None else abi.load()
-    c, ptr = _histogram_counts(counts)
-    n, s, q = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    _histogram_call(lib, "svr_histogram_moments", lib.svr_histogram_moments(ptr, len(c), C.byref(n), C.byref(s), C.byref(q)))
-    return int(n.value), int(s.value), int(q.value)
-
-
-def histogram_quantile(counts, num: int, den: int, lib=None):
-    """svr_histogram_quantile: the smallest bin b with C(b) > 0 and den * C(b) >= num * N (numpy's inverted_cdf for 0 < num / den <= 1;
-    num = 0: the first occupied bin); None when the histogram is empty."""
-    lib = lib if lib is not None else abi.load()
-    c, ptr = _histogram_counts(counts)
-    b = C.c_uint32(0)
-    empty = _histogram_call(lib, "svr_histogram_quantile", lib.svr_histogram_quantile(ptr, len(c), int(num), int(den), C.byref(b)))
-    return None if empty else int(b.value)
-
-
-def histogram_otsu(counts, classes: int = 2, lib=None):
-    """svr_histogram_otsu: (thresholds, eta): the classes - 1 exact Otsu thresholds (the last bins of the lower classes; ties go to the
-    lexicographically smallest tuple) and between-class / total variance; (None, 0.0) when the histogram is empty."""
-    lib = lib if lib is not None else abi.load()
-    c, ptr = _histogram_counts(counts)
-    t, eta = (C.c_uint32 * 2)(), C.c_double(0.0)
-    empty = _histogram_call(lib, "svr_histogram_otsu", lib.svr_histogram_otsu(ptr, len(c), int(classes), t, C.byref(eta)))
-    if empty:
-        return None, 0.0
-    return tuple(int(t[k]) for k in range(int(classes) - 1)), float(eta.value)
-
-
-def resample_grid(grid) -> abi.ResampleGrid:
-    """A ResampleGrid from ((origin, step, count) of x, of y, of z); a ResampleGrid is returned as it is."""
-    if isinstance(grid, abi.ResampleGrid):
-        return grid
-    g = abi.ResampleGrid()
-    for a in range(3):
-        g.axis[a].origin, g.axis[a].step, g.axis[a].count = (int(t) for t in grid[a])
-    return g
-
-
-def _grid_call(lib, name, rc):
-    if rc != 0:
-        msg = lib.svr_last_error().decode("utf-8", "replace")
-        lib.svr_clear_error()
-        raise SvrError(f"{name} failed ({rc}): {msg}")
-
-
-def _grid_box_args(shape, box):
-    nz, ny, nx = (int(n) for n in shape)
-    b0 = b1 = None
-    if box is not None:
-        b0, b1 = (C.c_int32 * 3)(*[int(t) for t in box[0]]), (C.c_int32 * 3)(*[int(t) for t in box[1]])
-    return (C.c_int32 * 3)(nx, ny, nz), b0, b1
-
-
-def resample_grid_box(shape, box, lib=None) -> abi.ResampleGrid:
-    """svr_resample_grid_box: the grid of a crop of a [nz][ny][nx] volume to box = ((x0, y0, z0), (x1, y1, z1)), inclusive, cut to the
-    volume.  The grid helpers are host code of the library: no device is needed."""
-    lib = lib if lib is not None else abi.load()
-    dims, b0, b1 = _grid_box_args(shape, box)
-    g = abi.ResampleGrid()
-    _grid_call(lib, "svr_resample_grid_box", lib.svr_resample_grid_box(dims, b0, b1, C.byref(g)))
-    return g
-
-
-def resample_grid_spacing(shape, src_spacing, target_spacing, box=None, lib=None):
-    """svr_resample_grid_spacing: (grid, spacing applied) for resampling a [nz][ny][nx] volume (or a box of it) from src_spacing to
-    target_spacing, both (x, y, z); a scalar target means isotropic."""
-    lib = lib if lib is not None else abi.load()
-    dims, b0, b1 = _grid_box_args(shape, box)
-    target = [float(target_spacing)] * 3 if np.isscalar(target_spacing) else [float(t) for t in target_spacing]
-    g, out = abi.ResampleGrid(), (C.c_double * 3)()
-    _grid_call(lib, "svr_resample_grid_spacing", lib.svr_resample_grid_spacing(dims, (C.c_double * 3)(*[float(t) for t in src_spacing]), b0, b1,
-                                                                                (C.c_double * 3)(*target), C.byref(g), out))
-    return g, (float(out[0]), float(out[1]), float(out[2]))
-
-
-def resample_grid_dims(shape, out_shape, box=None, lib=None) -> abi.ResampleGrid:
-    """svr_resample_grid_dims: the grid that maps a [nz][ny][nx] volume (or a box of it) onto out_shape = (nz', ny', nx')."""
-    lib = lib if lib is not None else abi.load()
-    dims, b0, b1 = _grid_box_args(shape, box)
-    g = abi.ResampleGrid()
-    _grid_call(lib, "svr_resample_grid_dims", lib.svr_resample_grid_dims(dims, b0, b1, (C.c_int32 * 3)(*[int(n) for n in out_shape][::-1]), C.byref(g)))
-    return g
-
-
-def resample_grid_place(volume: cudaVolume, shape, grid, lib=None) -> cudaVolume:
-    """svr_resample_grid_place: a copy of `volume` (the cudaVolume of the [nz][ny][nx] source) whose box and spacing are those of the
-    resampled volume, where it lay inside the source's box.  tex is copied: the caller replaces it."""
-    lib = lib if lib is not None else abi.load()
-    dims, _, _ = _grid_box_args(shape, None)
-    g, out = resample_grid(grid), cudaVolume()
-    _grid_call(lib, "svr_resample_grid_place", lib.svr_resample_grid_place(C.byref(volume), dims, C.byref(g), C.byref(out)))
-    return out
-
-
-def region_mask_words(shape) -> int:
-    """svr_region_mask_words of a [nz][ny][nx] volume."""
-    nz, ny, nx = shape
-    return ((nx + 31) // 32) * ny * nz
-
-
-def region_mask_unpack(words: np.ndarray, shape) -> np.ndarray:
-    """The bit mask of svr_region_grow (uint32 words) as a bool array [nz][ny][nx]."""
-    nz, ny, nx = shape
-    wx = (nx + 31) // 32
-    b = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8).reshape(nz, ny, wx * 4), axis=-1, bitorder="little")
-    return b[:, :, :nx].astype(bool)
-
-
-def region_mask_pack(mask: np.ndarray) -> np.ndarray:
-    """A bool array [nz][ny][nx] as the bit mask of the region calls: uint32 words, padding bits 0."""
-    nz, ny, nx = mask.shape
-    wx = (nx + 31) // 32
-    padded = np.zeros((nz, ny, wx * 32), dtype=np.uint8)
-    padded[:, :, :nx] = mask
-    return np.ascontiguousarray(np.packbits(padded, axis=-1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32))
-
-
-def region_seed_from_world(lib, volume: cudaVolume, dim, point):
-    """svr_region_seed_from_world: the voxel (x, y, z) whose cell contains a world point (e.g. a svr_hit position); dim = (nx, ny, nz).
-    Host code of the library: no device is needed."""
-    ijk = (C.c_int32 * 3)()
-    pt = _to_vec3(point)
-    if lib.svr_region_seed_from_world(C.byref(volume), int(dim[0]), int(dim[1]), int(dim[2]), C.byref(pt), ijk) != 0:
-        msg = lib.svr_last_error().decode("utf-8", "replace")
-        lib.svr_clear_error()
-        raise SvrError(msg)
-    return (int(ijk[0]), int(ijk[1]), int(ijk[2]))
-
 
 def slice_params_axis(lib, volume: cudaVolume, axis: int, position: float, w: int, h: int) -> abi.SliceParams:
     """svr_slice_params_axis: the plane perpendicular to world axis 0 / 1 / 2 at `position` in [0, 1] across the clipped box of
     `volume`, fitted to w x h pixels.  Host code of the library: no device is needed."""
     p = abi.SliceParams()
-    if lib.svr_slice_params_axis(C.byref(p), C.byref(volume), int(axis), C.c_float(float(position)), int(w), int(h)) != 0:
-        msg = lib.svr_last_error().decode("utf-8", "replace")
-        lib.svr_clear_error()
-        raise SvrError(f"svr_slice_params_axis: {msg}")
+    _host_call(lib, "svr_slice_params_axis", lib.svr_slice_params_axis(C.byref(p), C.byref(volume), int(axis), C.c_float(float(position)), int(w), int(h)))
     return p
 
 
@@ -1473,10 +314,7 @@ def slice_params_through(lib, volume: cudaVolume, axis: int, point, w: int, h: i
     of the library: no device is needed."""
     p = abi.SliceParams()
     q = _to_vec3(point)
-    if lib.svr_slice_params_through(C.byref(p), C.byref(volume), int(axis), C.byref(q), int(w), int(h)) != 0:
-        msg = lib.svr_last_error().decode("utf-8", "replace")
-        lib.svr_clear_error()
-        raise SvrError(f"svr_slice_params_through: {msg}")
+    _host_call(lib, "svr_slice_params_through", lib.svr_slice_params_through(C.byref(p), C.byref(volume), int(axis), C.byref(q), int(w), int(h)))
     return p
 
 
@@ -1801,9 +639,9 @@ class Canvas:
             self.dev.free(buf)
 
     # ---- extension: overlays of region masks and label maps (svr_overlay_slice; svr_render_hits + svr_hit_ids + svr_overlay_ids) ----
-    def _overlay_region(self, mask, labels):
-        """(mask pointer, labels pointer, owned buffer or None, (nz, ny, nx)) of a bool mask / uint32 label array [nz][ny][nx] (uploaded)
-        or of a device pointer to either; exactly one of the two is given."""
+    def _overlay_region(self, s, mask, labels):
+        """(mask pointer, labels pointer, (nz, ny, nx)) of a bool mask / uint32 label array [nz][ny][nx] (uploaded in the staging scope
+        s) or of a device pointer to either; exactly one of the two is given."""
         if (mask is None) == (labels is None):
             raise SvrError("an overlay needs a mask or a label array, not both")
         if not self.ready:
@@ -1811,50 +649,40 @@ class Canvas:
         nx, ny, nz = self.volumeDim
         shape = (nz, ny, nx)
         if mask is not None:
-            buf, owned = self.dev._region_mask(mask, shape)
-            return buf, None, buf if owned else None, shape
-        buf, lshape, owned = self.dev._region_labels(labels, shape)
-        if tuple(lshape) != shape:
-            if owned:
-                self.dev.free(buf)
-            raise SvrError(f"the labels are {tuple(lshape)}, the volume is {shape}")
-        return None, buf, buf if owned else None, shape
+            return s.mask(mask, shape).value, None, shape
+        buf, lshape = s.map(labels, shape)
+        if lshape != shape:
+            raise SvrError(f"the labels are {lshape}, the volume is {shape}")
+        return None, buf.value, shape
 
     def paint_slice_overlay(self, params: abi.SliceParams, mask=None, labels=None, style: Optional[abi.OverlayStyle] = None, count: int = 1,
                             spacing: float = 0.0, imgs: Optional[int] = None, sync: bool = False):
         """Tints the slice (or, with imgs and count, the stack) that paint_slice / paint_slice_stack drew with the same params by a region:
         mask (a bool array [nz][ny][nx] or the device pointer of a bit mask) or labels (a uint32 array or device pointer).  Every part
         gets the colour of its id, filled with style.fill_alpha and outlined with style.edge_alpha."""
-        m, l, owned, shape = self._overlay_region(mask, labels)
-        try:
+        with self.dev._staging() as s:
+            m, l, shape = self._overlay_region(s, mask, labels)
             self.dev.overlay_slice(self.img if imgs is None else imgs, self.deviceVolume, shape, self.W, self.H, params, m, l, style, count, spacing)
-            if sync or owned is not None:
+            if sync or s.owned:                               # an uploaded region is freed on exit: the kernel is done with it first
                 self.dev.synchronize()
-        finally:
-            if owned is not None:
-                self.dev.free(owned)
 
     def paint_overlay(self, mask=None, labels=None, style: Optional[abi.OverlayStyle] = None, mode: int = abi.HIT_OPACITY, alpha: float = 0.5,
                       iso: float = 0.5, sync: bool = False):
         """Tints the 3D picture in the canvas image (paint with the ray caster, or paint_projection) by a region: every pixel whose ray
         meets what the picture shows (the hit map of `mode`, alpha, iso; see hit_map) inside a part gets that part's colour.  Pixels
         outside a row shard or render window in force have no hit record and stay as they are.  Synchronises."""
-        m, l, owned, shape = self._overlay_region(mask, labels)
-        p = abi.HitParams(int(mode), float(alpha), float(iso))
-        n = self.W * self.H
-        buf = self.dev.malloc(n * (HIT_DTYPE.itemsize + 4))
-        ids = buf + n * HIT_DTYPE.itemsize
-        try:
+        with self.dev._staging() as s:
+            m, l, shape = self._overlay_region(s, mask, labels)
+            p = abi.HitParams(int(mode), float(alpha), float(iso))
+            n = self.W * self.H
+            buf = s.alloc(n * (HIT_DTYPE.itemsize + 4))
+            ids = buf + n * HIT_DTYPE.itemsize
             self.dev.check(self.lib.svr_memset_device(C.c_void_p(buf), 0, n * HIT_DTYPE.itemsize))
             self.dev.check(self.lib.svr_render_hits(C.c_void_p(buf), C.byref(self.deviceVolume), C.byref(self.transferFunction),
                                                     C.byref(self.camera), C.c_float(self.stepSize), C.byref(p)))
             self.dev.hit_ids(ids, buf, self.W, self.H, self.deviceVolume, shape, m, l)
             self.dev.overlay_ids(self.img, ids, self.W, self.H, 1, style)
             self.dev.synchronize()
-        finally:
-            self.dev.free(buf)
-            if owned is not None:
-                self.dev.free(owned)
 
     # ---- extension: surface meshes of regions and isosurfaces (svr_mesh_*; io.write_stl / write_ply) ----
     def _set_surface(self, mesh):
