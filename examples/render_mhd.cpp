@@ -57,8 +57,11 @@
 // it lay in the loaded volume.  -save-volume F writes the (filtered) voxels, -save-mask F the final region as u8 0 / 1, -save-parts F
 // its connected parts (-conn) as a u32 label map, and -save-crop VOL MASK MARGIN the region's bounding box grown by MARGIN voxels, voxels
 // and mask, as MetaImage files (.mhd + .raw, or .mha).  Each prints one line with the dimensions, the spacing and the time.
+// -compare-mask F compares the final region with the mask in F (one byte per voxel, non-zero = set, the volume's dimensions: what
+// -save-mask wrote, or a ground truth) and prints one line: Dice, Jaccard, the Hausdorff distance, its 95 % form and the average
+// symmetric surface distance in the units of the spacing (Canvas::CompareRegionWithFile).
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -71,7 +74,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -105,6 +108,7 @@ int main(int argc, char** argv)
     int meshRelax = -1, meshIsoLevel = 0;                           // -relax N (with -mesh): 0 .. SVR_MESH_MAX_RELAX relaxation steps
     struct GridStep { bool crop; int32_t lo[3], hi[3]; double mm; int mode; };   // -crop X0 Y0 Z0 X1 Y1 Z1 or -resample MM [mode]
     std::vector<GridStep> gridSteps;                                // applied right after the load, in command-line order
+    std::string compareMaskFile;                                    // -compare-mask F: the final region against the mask in F
     std::string saveVolumeFile, saveMaskFile, savePartsFile, saveCropVolume, saveCropMask;   // -save-volume / -save-mask / -save-parts F, -save-crop VOL MASK MARGIN
     int saveCropMargin = 0;
     const auto meshName = [](const char* f) {                       // an export writes .stl or .ply
@@ -384,6 +388,10 @@ int main(int argc, char** argv)
             (argv[i][6] == 'v' ? saveVolumeFile : argv[i][6] == 'm' ? saveMaskFile : savePartsFile) = argv[i + 1];
             ++i;
         }
+        else if (!strcmp(argv[i], "-compare-mask")) {
+            if (i + 1 >= argc || argv[i + 1][0] == '-') { fprintf(stderr, "-compare-mask needs the file name of a mask (.mhd or .mha, one byte per voxel)\n"); return 2; }
+            compareMaskFile = argv[++i];
+        }
         else if (!strcmp(argv[i], "-save-crop")) {
             char* end = nullptr;
             const long v = i + 3 < argc ? strtol(argv[i + 3], &end, 10) : -1;
@@ -423,6 +431,7 @@ int main(int argc, char** argv)
         fprintf(stderr, "-save-mask, -save-parts and -save-crop write a region: they need -grow X Y LO HI or -threshold LO HI\n");
         return 2;
     }
+    if (!compareMaskFile.empty() && !anyRegion) { fprintf(stderr, "-compare-mask compares a region with the file: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (svr_init(0)) return 1;
     {
         Canvas canvas(W, H);
@@ -697,6 +706,17 @@ int main(int argc, char** argv)
                 if (rc < 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 if (rc == SVR_REGION_STATUS_EMPTY) printf("largest inscribed ball: none (the region is empty or fills the volume)\n");
                 else printf("largest inscribed ball: radius %g at voxel %d %d %d\n", radius, at[0], at[1], at[2]);
+            }
+            if (!compareMaskFile.empty()) {                             // the final region against a saved mask: overlap and surface distances
+                svr_compare_measurement m;
+                svr_region_comparison c;
+                if (canvas.CompareRegionWithFile(compareMaskFile, &m, &c) != 0) {
+                    fprintf(stderr, "-compare-mask %s: %s\n", compareMaskFile.c_str(), svr_last_error_code() ? svr_last_error() : "not a one-byte mask of the volume's dimensions");
+                    return 1;
+                }
+                printf("compare-mask: dice %.17g jaccard %.17g hd %.17g hd95 %.17g assd %.17g mm (both %llu, region only %llu, file only %llu voxels)\n", m.dice,
+                       m.jaccard, m.hausdorff, m.hausdorff_q, m.assd, (unsigned long long)c.overlap[SVR_OVERLAP_BOTH],
+                       (unsigned long long)c.overlap[SVR_OVERLAP_A_ONLY], (unsigned long long)c.overlap[SVR_OVERLAP_B_ONLY]);
             }
             if (!meshFile.empty() && (canvas.ExtractRegionSurface((uint32_t)(meshRelax < 0 ? 0 : meshRelax)) != 0 || !exportSurface(meshFile))) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
             if (!saveMaskFile.empty()) {

@@ -1052,6 +1052,81 @@ public:
     bool HasRegion() const { return haveRegion; }
     const uint32_t* RegionMask() const { return haveRegion ? regionMask : nullptr; }   // device; svr_region_mask_words words
 
+    // extension: how far the region is from another mask of the same dimensions (svr_region_compare / _compare_measure; include/svr_abi.h,
+    // "comparing segmentations").  The region is A, the other mask B; distances are in the units of the loaded volume's spacing (mm), by
+    // the weights and unit of RegionDistanceUnits.  tolerances (may be null) are ntol <= SVR_COMPARE_MAX_TOLERANCES lengths in those units
+    // for the surface Dice.  comparison (may be null) receives the integers.  The region stays as it is
+    int CompareRegion(const uint32_t* otherMaskDevice, svr_compare_measurement* out, svr_region_comparison* comparison = nullptr, int element = 6,
+                      const double* tolerances = nullptr, uint32_t ntol = 0u)
+    {
+        if (!ready || !haveRegion || !otherMaskDevice || !out) return -4;
+        if (ntol > SVR_COMPARE_MAX_TOLERANCES || (ntol && !tolerances)) return -3;
+        svr_compare_params p;
+        svr_compare_params_default(&p);
+        double unit = 0.0;
+        if (int rc = RegionDistanceUnits(p.weights, &unit)) return rc;
+        p.element = element;
+        p.ntol = ntol;
+        for (uint32_t k = 0; k < ntol; ++k) {
+            if (!(tolerances[k] >= 0.0) || !std::isfinite(tolerances[k])) return -3;
+            p.tolerances2[k] = LengthToR2(tolerances[k], unit);
+        }
+        const int* dim = volumeReader->dim;
+        svr_region_comparison c;
+        if (int rc = svr_region_compare(regionMask, otherMaskDevice, dim[0], dim[1], dim[2], &p, &c)) return rc;
+        if (comparison) *comparison = c;
+        return svr_region_compare_measure(&c, unit, out);
+    }
+    // CompareRegionWithFile: the same against a mask MetaImage of one byte per voxel as SaveRegion writes it, non-zero = set; the file
+    // must have the dimensions of the loaded volume (-3 otherwise)
+    int CompareRegionWithFile(const std::string& filename, svr_compare_measurement* out, svr_region_comparison* comparison = nullptr, int element = 6,
+                              const double* tolerances = nullptr, uint32_t ntol = 0u)
+    {
+        if (!ready || !haveRegion || !out) return -4;
+        const int* dim = volumeReader->dim;
+        svr_mhd_header h;
+        int rc = svr_mhd_read_header(filename.c_str(), &h);
+        if (rc != 0) return rc;
+        if (h.elem_size != 1 || h.dim[0] != dim[0] || h.dim[1] != dim[1] || h.dim[2] != dim[2]) return -3;
+        const size_t n = (size_t)dim[0] * dim[1] * dim[2];
+        std::vector<uint8_t> bytes(n);
+        rc = svr_mhd_read_elements(&h, bytes.data(), bytes.size());
+        if (rc != 0) return rc;
+        std::vector<uint16_t> set(n);
+        for (size_t i = 0; i < n; ++i) set[i] = bytes[i] ? 1u : 0u;
+        uint32_t* other = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
+        if (!other) return -4;
+        rc = svr_region_threshold(set.data(), dim[0], dim[1], dim[2], 0, 1u, 65535u, nullptr, nullptr, other);      // (a host source: synchronises)
+        if (rc == 0) rc = CompareRegion(other, out, comparison, element, tolerances, ntol);
+        svr_device_free(other);
+        return rc;
+    }
+    // MatchRegionParts: which part of LabelRegion's label map (counts parts) is which part of another label map of the same dimensions
+    // (otherLabelsDevice, labels 1 .. otherCount): bestOther[l - 1] = the part of the other map with the largest Jaccard index with part
+    // l, 0 for none, bestMine (may be null) the other way round (svr_region_label_overlap, svr_overlap_match).  table (may be null)
+    // receives the overlap table [count + 1][otherCount + 1]
+    int MatchRegionParts(uint32_t count, const uint32_t* otherLabelsDevice, uint32_t otherCount, std::vector<uint32_t>* bestOther,
+                         std::vector<uint32_t>* bestMine = nullptr, std::vector<uint32_t>* table = nullptr)
+    {
+        if (!ready || !haveRegion || !haveLabels || !otherLabelsDevice || !bestOther) return -4;
+        if (count == 0u || otherCount == 0u) return -3;
+        const int32_t dims[3] = {volumeReader->dim[0], volumeReader->dim[1], volumeReader->dim[2]};
+        const size_t cells = ((size_t)count + 1u) * ((size_t)otherCount + 1u);
+        if (cells > SVR_HISTOGRAM_MAX_CELLS) return -3;
+        uint32_t* d = (uint32_t*)svr_device_malloc(cells * sizeof(uint32_t));
+        if (!d) return -4;
+        std::vector<uint32_t> t(cells);
+        int rc = svr_region_label_overlap(regionLabels, count, otherLabelsDevice, otherCount, dims, d);
+        if (rc == 0) rc = svr_memcpy_d2h(t.data(), d, cells * sizeof(uint32_t));
+        svr_device_free(d);
+        if (rc != 0) return rc;
+        bestOther->assign(count, 0u);
+        if (bestMine) bestMine->assign(otherCount, 0u);
+        rc = svr_overlap_match(t.data(), count, otherCount, bestOther->data(), bestMine ? bestMine->data() : nullptr);
+        if (table) table->swap(t);
+        return rc;
+    }
+
     // extension: what the region methods read and made, as MetaImage files (svr_mhd_write, include/svr_io.h; a name ending in .mha gives
     // one file, any other a header and a .raw).  ElementSpacing is the drawn volume's, Offset the world position of the centre of voxel
     // (0, 0, 0) in the Canvas's box.  The Canvas's own state and dimensions do not change.

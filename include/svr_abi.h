@@ -1309,6 +1309,115 @@ int svr_region_mask_expand(const uint32_t* mask_device, const int32_t dims[3], i
 /* HIP-event time of the device work of the last svr_volume_resample / svr_region_resample / _label_resample / _paste / _mask_expand */
 int svr_volume_resample_last_ms(float* ms);
 
+/* ---- comparing segmentations: surfaces, overlap tables and exact surface distances (csrc/svr_compare.hip) ----
+ * Masks are DEVICE pointers in the layout of the region section; input padding bits are ignored whatever they hold (and count as unset
+ * neighbours), output padding bits are 0.  Maps and label arrays are dense uint32 [nz][ny][nx] on the device.  Dimensions are nx, ny,
+ * nz, or const int32_t dims[3] = (x, y, z).  Integers only on the device; every result is exact and unique, whatever order the GPU
+ * works in.  The calls are stateless, run on the library's stream and touch no scene, option or accumulator.
+ * SURFACE: out = the voxels of `in` that have a neighbour under the unit element 6 / 18 / 26 that is unset OR LIES OUTSIDE THE VOLUME:
+ *   in & ~binary_erosion(in, border_value=0), the convention of the usual surface-distance tools and of this library's meshes, which
+ *   are closed at the faces of the volume.  This is NOT the border rule of svr_region_morph's ERODE (there nothing outside the volume
+ *   counts as background, and a region is not eroded from a face): in & ~ERODE(in) misses the voxels that touch a face.  out may not
+ *   overlap in.  Asynchronous.
+ * OVERLAP: counts_host[4] = the voxels of the domain (every voxel when it is NULL) that are in both masks, in A only, in B only, in
+ *   neither (SVR_OVERLAP_*).  Synchronises.
+ * LABEL OVERLAP: table_device is uint32 [count_a + 1][count_b + 1]; cell la * (count_b + 1) + lb = the number of voxels with label la
+ *   in A and lb in B; row 0 and column 0 are the backgrounds.  A voxel with a label above its count is not counted.  count_a, count_b
+ *   >= 1, and the cells may not exceed SVR_HISTOGRAM_MAX_CELLS.  The table is overwritten, not accumulated.  Asynchronous.
+ * OVERLAP MATCH (plain host code, on a host copy of that table): best_b_for_a[la - 1], la = 1 .. count_a, = the label lb in 1 ..
+ *   count_b with the largest Jaccard index inter / (|la| + |lb| - inter), inter = cell (la, lb), |la| = the sum of row la and |lb| = the
+ *   sum of column lb, background cells included; fractions are compared exactly by 64-bit cross-multiplication (in 128 bits); ties go
+ *   to the lower label; 0 where no lb has inter > 0.  best_a_for_b_or_null[lb - 1] is the same the other way round.
+ * SUMMARY of a uint32 map (squared distances, geodesic distances, growcut costs) over the voxels of a mask (all voxels when NULL):
+ *   svr_distance_summary below.  tolerances2: a HOST array of ntol <= SVR_COMPARE_MAX_TOLERANCES values (NULL with ntol = 0).
+ *   Synchronises.
+ * HISTOGRAM of such a map over a mask: counts_device[(v - lo) >> shift] for the values lo <= v <= hi; bins = ((hi - lo) >> shift) + 1,
+ *   at most 65536; shift <= 31.  Values outside lo .. hi are not counted, so SVR_DIST_NONE is counted only when hi reaches it.  The
+ *   counts are overwritten, not accumulated.  Asynchronous.
+ * QUANTILE: *value_out = the smallest value v other than SVR_DIST_NONE with C(v) > 0 and den C(v) >= num N, C the cumulative count and
+ *   N the number of such values: the rule of svr_histogram_quantile on the values themselves (numpy's inverted_cdf for 0 < num / den
+ *   <= 1).  Two histogram passes: 0 .. max at the smallest shift that fits 65536 bins, then the chosen bin's values at shift 0.  With no
+ *   such value *status = SVR_REGION_STATUS_EMPTY, *value_out = 0 and the return is 0.  Synchronises.
+ * COMPARE: the overlap counts of A and B, their surfaces S(A), S(B) under params->element, and per direction the summary and the
+ *   quantile of the squared distance to the other surface: ab = svr_region_distance(S(B), weights, SVR_DIST_TO_SET) over S(A), ba the
+ *   reverse.  params == NULL means svr_compare_params_default: element 6, weights 1, 1, 1, quantile 95 / 100, no tolerances.  An empty
+ *   mask sets SVR_COMPARE_A_EMPTY / _B_EMPTY in status and the return stays 0: the directed fields of a direction FROM an empty mask are
+ *   all 0, those of a direction TO an empty mask are 0 but for none = the surface voxels of the other mask (every distance is
+ *   SVR_DIST_NONE).  Workspace at its peak: one map (4 bytes per voxel), svr_region_distance's own (8 bytes per voxel), two masks, and
+ *   256 KB of counters.  Synchronises.
+ * MEASURE (plain host code): svr_compare_measurement from a svr_region_comparison; `unit` is the length of sqrt(d2) = 1 (the unit_out
+ *   of svr_region_distance_weights, or 1 for voxel units).  With n_ab = ab.voxels, A = both + a_only, B = both + b_only:
+ *     dice = 2 both / (2 both + a_only + b_only);  jaccard = both / (both + a_only + b_only);
+ *     volume_difference = 2 (A - B) / (A + B)                                   (signed: positive when A is larger);
+ *     hausdorff_ab = unit sqrt(ab.max), hausdorff_ba likewise, hausdorff = the larger of the two;
+ *     hausdorff_q_ab = unit sqrt(quantile_ab), hausdorff_q_ba likewise, hausdorff_q = the larger of the two;
+ *     assd = unit (ab.sum_root_q8 + ba.sum_root_q8) / 256 / (n_ab + n_ba);
+ *     rms = unit sqrt((ab.sum + ba.sum) / (n_ab + n_ba));
+ *     surface_dice[k] = (ab.within[k] + ba.within[k]) / (surface[0] + surface[1]) for k < ntol, 0 for the others.
+ *   Every operand is converted to double first and the operations are made in the order written.  A value whose denominator is 0 is
+ *   NaN; a directed distance with n = 0 is NaN, and so is a symmetric one when either direction is.
+ * REFUSED, before the device is touched: a null pointer (-4); a dimension <= 0 or more than 2^31 voxels (-6); (-3) an element that is
+ *   not 6, 18 or 26, a weight of 0 or the overflow bound of svr_region_distance, lo > hi, more than 65536 bins, shift > 31, ntol > 8,
+ *   den == 0 or num > den, count_a == 0 or count_b == 0, more than SVR_HISTOGRAM_MAX_CELLS cells, an output that overlaps an input. */
+#define SVR_OVERLAP_BOTH    0
+#define SVR_OVERLAP_A_ONLY  1
+#define SVR_OVERLAP_B_ONLY  2
+#define SVR_OVERLAP_NEITHER 3
+#define SVR_COMPARE_MAX_TOLERANCES 8
+#define SVR_COMPARE_A_EMPTY 1
+#define SVR_COMPARE_B_EMPTY 2
+typedef struct svr_distance_summary {   /* 72 bytes: four uint64, then ten uint32 */
+    uint64_t voxels;                    /* the voxels of the mask whose value is not SVR_DIST_NONE */
+    uint64_t none;                      /* the voxels of the mask whose value is SVR_DIST_NONE */
+    uint64_t sum;                       /* the sum of the values (of `voxels`, as all that follows) */
+    uint64_t sum_root_q8;               /* the sum of isqrt(v 2^16) = floor(256 sqrt(v)), isqrt as in svr_region_distance_volume */
+    uint32_t max;                       /* the largest value; 0 when voxels == 0 */
+    uint32_t first_max;                 /* the smallest linear index (z ny + y) nx + x that attains it; 0 when voxels == 0 */
+    uint32_t within[SVR_COMPARE_MAX_TOLERANCES];   /* within[k] = the values <= tolerances2[k]; 0 for k >= ntol */
+} svr_distance_summary;
+typedef struct svr_compare_params {     /* 4-byte members only, 60 bytes */
+    int32_t  element;                   /* 6 / 18 / 26: the element of the surfaces */
+    uint32_t weights[3];                /* the weights (x, y, z) of the squared distance, as in svr_region_distance */
+    uint32_t q_num, q_den;              /* the quantile of the directed distances */
+    uint32_t ntol;                      /* 0 .. SVR_COMPARE_MAX_TOLERANCES */
+    uint32_t tolerances2[SVR_COMPARE_MAX_TOLERANCES];   /* squared tolerances, in the units of the map */
+} svr_compare_params;
+typedef struct svr_region_comparison {  /* 208 bytes; integers only */
+    uint64_t overlap[4];                /* SVR_OVERLAP_*: both, A only, B only, neither */
+    uint64_t surface[2];                /* the voxels of S(A), S(B) */
+    svr_distance_summary ab, ba;        /* the squared distances from S(A) to S(B), from S(B) to S(A) */
+    uint32_t quantile_ab, quantile_ba;  /* their q_num / q_den quantiles (squared); 0 when there is no value */
+    uint32_t ntol;                      /* as in the params */
+    int32_t  status;                    /* SVR_COMPARE_A_EMPTY | SVR_COMPARE_B_EMPTY */
+} svr_region_comparison;
+typedef struct svr_compare_measurement {   /* 19 doubles, 152 bytes; the formulas are above */
+    double dice, jaccard, volume_difference;
+    double hausdorff_ab, hausdorff_ba, hausdorff;
+    double hausdorff_q_ab, hausdorff_q_ba, hausdorff_q;
+    double assd, rms;
+    double surface_dice[SVR_COMPARE_MAX_TOLERANCES];
+} svr_compare_measurement;
+int svr_region_surface(const uint32_t* in_mask_device,
+                       int nx, int ny, int nz, int element, uint32_t* out_mask_device);
+int svr_region_overlap(const uint32_t* a_mask_device, const uint32_t* b_mask_device,
+                       int nx, int ny, int nz, const uint32_t* domain_mask_device_or_null, uint64_t counts_host[4]);
+int svr_region_label_overlap(const uint32_t* a_labels_device, uint32_t count_a, const uint32_t* b_labels_device, uint32_t count_b,
+                             const int32_t dims[3], uint32_t* table_device);
+int svr_overlap_match(const uint32_t* table_host, uint32_t count_a, uint32_t count_b, uint32_t* best_b_for_a, uint32_t* best_a_for_b_or_null);
+int svr_region_distance_summary(const uint32_t* map_device, const uint32_t* mask_device_or_null,
+                                int nx, int ny, int nz, const uint32_t* tolerances2_or_null, uint32_t ntol, svr_distance_summary* out_host);
+int svr_region_distance_histogram(const uint32_t* map_device, const uint32_t* mask_device_or_null, const int32_t dims[3], uint32_t lo,
+                                  uint32_t hi, uint32_t shift, uint32_t* counts_device);
+int svr_region_distance_quantile(const uint32_t* map_device, const uint32_t* mask_device_or_null, const int32_t dims[3], uint32_t num,
+                                 uint32_t den, uint32_t* value_out, int32_t* status);
+int svr_compare_params_default(svr_compare_params* p);
+int svr_region_compare(const uint32_t* a_mask_device, const uint32_t* b_mask_device,
+                       int nx, int ny, int nz, const svr_compare_params* params_or_null, svr_region_comparison* out_host);
+int svr_region_compare_measure(const svr_region_comparison* c, double unit, svr_compare_measurement* out);
+/* HIP-event time of the device work of the last of the device calls above (waits for it); for svr_region_compare it spans the two
+ * svr_region_distance runs as well */
+int svr_region_compare_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

@@ -327,6 +327,32 @@ HISTOGRAM_MAX_CELLS = 1 << 24
 HISTOGRAM_STATUS_EMPTY = 1
 
 
+class DistanceSummary(C.Structure):  # svr_distance_summary
+    _fields_ = [("voxels", C.c_uint64), ("none", C.c_uint64), ("sum", C.c_uint64), ("sum_root_q8", C.c_uint64), ("max", C.c_uint32),
+                ("first_max", C.c_uint32), ("within", C.c_uint32 * 8)]
+
+
+class CompareParams(C.Structure):  # svr_compare_params
+    _fields_ = [("element", C.c_int32), ("weights", C.c_uint32 * 3), ("q_num", C.c_uint32), ("q_den", C.c_uint32), ("ntol", C.c_uint32),
+                ("tolerances2", C.c_uint32 * 8)]
+
+
+class RegionComparison(C.Structure):  # svr_region_comparison
+    _fields_ = [("overlap", C.c_uint64 * 4), ("surface", C.c_uint64 * 2), ("ab", DistanceSummary), ("ba", DistanceSummary),
+                ("quantile_ab", C.c_uint32), ("quantile_ba", C.c_uint32), ("ntol", C.c_uint32), ("status", C.c_int32)]
+
+
+class CompareMeasurement(C.Structure):  # svr_compare_measurement
+    _fields_ = [(n, C.c_double) for n in ("dice", "jaccard", "volume_difference", "hausdorff_ab", "hausdorff_ba", "hausdorff",
+                                          "hausdorff_q_ab", "hausdorff_q_ba", "hausdorff_q", "assd", "rms")] + [("surface_dice", C.c_double * 8)]
+
+
+svr_distance_summary, svr_compare_params, svr_region_comparison, svr_compare_measurement = DistanceSummary, CompareParams, RegionComparison, CompareMeasurement
+OVERLAP_BOTH, OVERLAP_A_ONLY, OVERLAP_B_ONLY, OVERLAP_NEITHER = 0, 1, 2, 3
+COMPARE_MAX_TOLERANCES = 8
+COMPARE_A_EMPTY, COMPARE_B_EMPTY = 1, 2
+
+
 class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
     _fields_ = [("mask_device", C.c_void_p), ("labels_device", C.c_void_p)]
 
@@ -605,6 +631,17 @@ PROTOTYPES = {
     "svr_histogram_moments": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "svr_histogram_quantile": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
     "svr_histogram_otsu": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_double)]),
+    "svr_region_surface": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "svr_region_overlap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, _P(C.c_uint64)]),
+    "svr_region_label_overlap": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _P(C.c_int32), C.c_void_p]),
+    "svr_overlap_match": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    "svr_region_distance_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), C.c_uint32, _P(DistanceSummary)]),
+    "svr_region_distance_histogram": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "svr_region_distance_quantile": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int32), C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_int32)]),
+    "svr_compare_params_default": (C.c_int, [_P(CompareParams)]),
+    "svr_region_compare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(CompareParams), _P(RegionComparison)]),
+    "svr_region_compare_measure": (C.c_int, [_P(RegionComparison), C.c_double, _P(CompareMeasurement)]),
+    "svr_region_compare_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
     "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
     "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,

@@ -184,9 +184,10 @@ def _host_call(lib, name, rc, ok=(0,)):
 
 # The volume operations live in volume_ops.py, which takes SvrError, _host_call and _to_vec3 from here: the import follows them.  Every
 # public name of it stays a name of this module.
-from .volume_ops import (COMPONENT_DTYPE, LABEL_SCAN_BLOCK, VolumeOps as _VolumeOps, distance_weights, geodesic_weights, histogram_bin_range,  # noqa: E402,F401
-                         histogram_bins, histogram_moments, histogram_otsu, histogram_params, histogram_quantile, mesh_positions,
-                         region_label_scan_levels, region_mask_pack, region_mask_unpack, region_mask_words, region_seed_from_world,
+from .volume_ops import (COMPONENT_DTYPE, LABEL_SCAN_BLOCK, VolumeOps as _VolumeOps, compare_measure, compare_params, distance_weights,  # noqa: E402,F401
+                         geodesic_weights, histogram_bin_range, histogram_bins, histogram_moments, histogram_otsu, histogram_params,
+                         histogram_quantile, mesh_positions, overlap_match, region_label_scan_levels, region_mask_pack,
+                         region_mask_unpack, region_mask_words, region_seed_from_world,
                          resample_grid, resample_grid_box, resample_grid_dims, resample_grid_place, resample_grid_spacing, smooth_radii)
 
 

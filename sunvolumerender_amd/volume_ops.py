@@ -568,6 +568,90 @@ class VolumeOps:
     def volume_histogram_last_ms(self) -> float:
         return self._last_ms(self.lib.svr_volume_histogram_last_ms)
 
+    # ---- comparing segmentations (svr_region_surface / _overlap / _label_overlap / _distance_summary / _distance_histogram /
+    #      _distance_quantile / _compare); overlap_match and compare_measure are module functions ----
+    def region_surface(self, mask, element: int = 6, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_surface: the voxels of a mask (a bool array [nz][ny][nx], or a device pointer with shape=) that have a neighbour
+        under the unit element 6 / 18 / 26 that is unset or lies outside the volume.  Returns the bool array."""
+        with self._staging() as s:
+            nz, ny, nx = shape = _shape_of("mask", mask, shape)
+            buf, out = s.mask(mask, shape), s.mask_out(shape, out_ptr)
+            self.check(self.lib.svr_region_surface(buf, nx, ny, nz, int(element), C.c_void_p(out)))
+            return s.mask_result(out, shape)
+
+    def region_overlap(self, a, b, domain=None, shape=None):
+        """svr_region_overlap: (both, a_only, b_only, neither), the voxels of `domain` (None = all) by their membership in the masks a
+        and b (bool arrays [nz][ny][nx], or device pointers with shape=)."""
+        with self._staging() as s:
+            nz, ny, nx = shape = _shape_of("mask", (a, b, domain), shape)
+            abuf, bbuf, dbuf = s.mask(a, shape), s.mask(b, shape), s.mask(domain, shape)
+            counts = (C.c_uint64 * 4)()
+            self.check(self.lib.svr_region_overlap(abuf, bbuf, nx, ny, nz, dbuf, counts))
+            return tuple(int(c) for c in counts)
+
+    def region_label_overlap(self, a, count_a: int, b, count_b: int, shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_label_overlap: np.uint32[count_a + 1, count_b + 1]; cell (la, lb) counts the voxels with label la in a and lb in b
+        (uint32 arrays [nz][ny][nx], or device pointers with shape=); row 0 and column 0 are the backgrounds, labels above their count are
+        not counted.  out_ptr: a device buffer of 4 * (count_a + 1) * (count_b + 1) bytes that receives the table."""
+        with self._staging() as s:
+            abuf, shape = s.map(a, shape)
+            bbuf, _ = s.map(b, like=shape)
+            ra, rb = int(count_a) + 1, int(count_b) + 1
+            cells = ra * rb
+            if min(ra, rb) < 2 or cells > abi.HISTOGRAM_MAX_CELLS:
+                ra, rb, cells = 0, 0, 0                           # the library refuses the call: a token buffer is enough to hear it
+            out = s.out(4 * max(cells, 1), out_ptr)
+            self.check(self.lib.svr_region_label_overlap(abuf, int(count_a), bbuf, int(count_b), _dims(shape), C.c_void_p(out)))
+            return self.to_host(out, (cells,), np.uint32).reshape(ra, rb)
+
+    def region_distance_summary(self, d2, mask=None, tolerances2=(), shape=None) -> abi.DistanceSummary:
+        """svr_region_distance_summary: the svr_distance_summary of a uint32 map (an array [nz][ny][nx] or a device pointer with shape=)
+        over the voxels of `mask` (a bool array or a device pointer; None = all voxels); tolerances2: up to 8 values for `within`."""
+        with self._staging() as s:
+            dbuf, shape = s.map(d2, shape)
+            nz, ny, nx = shape
+            tol, out = [int(t) for t in tolerances2], abi.DistanceSummary()
+            self.check(self.lib.svr_region_distance_summary(dbuf, s.mask(mask, shape), nx, ny, nz, _u32s(tol, len(tol)) if tol else None, len(tol),
+                                                            C.byref(out)))
+            return out
+
+    def region_distance_histogram(self, d2, mask=None, lo: int = 0, hi: int = 65535, shift: int = 0, shape=None,
+                                  out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_distance_histogram: np.uint32[((hi - lo) >> shift) + 1]: the values lo .. hi of a uint32 map over the voxels of
+        `mask` (None = all), counted in bin (v - lo) >> shift.  out_ptr: a device buffer of 4 * bins bytes that receives the counts."""
+        with self._staging() as s:
+            dbuf, shape = s.map(d2, shape)
+            bins = ((int(hi) - int(lo)) >> int(shift)) + 1 if 0 <= int(lo) <= int(hi) and 0 <= int(shift) <= 31 else 0
+            if bins > 65536:
+                bins = 0                                          # the library refuses the call: a token buffer is enough to hear it
+            mbuf, out = s.mask(mask, shape), s.out(4 * max(bins, 1), out_ptr)
+            self.check(self.lib.svr_region_distance_histogram(dbuf, mbuf, _dims(shape), int(lo), int(hi), int(shift), C.c_void_p(out)))
+            return self.to_host(out, (bins,), np.uint32)
+
+    def region_distance_quantile(self, d2, num: int, den: int, mask=None, shape=None):
+        """svr_region_distance_quantile: the exact inverted_cdf quantile num / den of the values other than DIST_NONE of a uint32 map over
+        the voxels of `mask` (None = all); None when there is no such value."""
+        with self._staging() as s:
+            dbuf, shape = s.map(d2, shape)
+            value, status = C.c_uint32(0), C.c_int32(0)
+            self.check(self.lib.svr_region_distance_quantile(dbuf, s.mask(mask, shape), _dims(shape), int(num), int(den), C.byref(value), C.byref(status)))
+            return None if status.value == abi.REGION_STATUS_EMPTY else int(value.value)
+
+    def region_compare(self, a, b, element: int = 6, weights=None, quantile=(95, 100), tolerances2=(), shape=None) -> abi.RegionComparison:
+        """svr_region_compare: the svr_region_comparison of two masks (bool arrays [nz][ny][nx], or device pointers with shape=): overlap
+        counts, surface sizes under `element`, and per direction the summary and the `quantile` = (num, den) of the squared distances
+        between the surfaces under the integer weights (wx, wy, wz) (None = 1, 1, 1).  compare_measure turns it into Dice, Hausdorff
+        and surface distances."""
+        with self._staging() as s:
+            nz, ny, nx = shape = _shape_of("mask", (a, b), shape)
+            abuf, bbuf = s.mask(a, shape), s.mask(b, shape)
+            p, out = compare_params(element, weights, quantile, tolerances2, self.lib), abi.RegionComparison()
+            self.check(self.lib.svr_region_compare(abuf, bbuf, nx, ny, nz, C.byref(p), C.byref(out)))
+            return out
+
+    def region_compare_last_ms(self) -> float:
+        return self._last_ms(self.lib.svr_region_compare_last_ms)
+
     # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
     def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
         """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
@@ -929,6 +1013,48 @@ def histogram_otsu(counts, classes: int = 2, lib=None):
     if empty:
         return None, 0.0
     return tuple(int(t[k]) for k in range(int(classes) - 1)), float(eta.value)
+
+
+def compare_params(element: int = 6, weights=None, quantile=(95, 100), tolerances2=(), lib=None) -> abi.CompareParams:
+    """svr_compare_params_default with the element, weights (None = 1, 1, 1), quantile (num, den) and squared tolerances replaced.  The
+    comparison helpers below are host code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    p = abi.CompareParams()
+    _host_call(lib, "svr_compare_params_default", lib.svr_compare_params_default(C.byref(p)))
+    p.element, p.q_num, p.q_den = int(element), int(quantile[0]), int(quantile[1])
+    if weights is not None:
+        for a in range(3):
+            p.weights[a] = int(weights[a])
+    tol = [int(t) for t in tolerances2]
+    p.ntol = len(tol)                                         # (more than 8: the library refuses the call)
+    for k, t in enumerate(tol[:abi.COMPARE_MAX_TOLERANCES]):
+        p.tolerances2[k] = t
+    return p
+
+
+def overlap_match(table, lib=None):
+    """svr_overlap_match: (best_b_for_a, best_a_for_b) of a label overlap table np.uint32[count_a + 1, count_b + 1]: for each label 1 ..
+    count of one map the non-background label of the other with the largest Jaccard index (sizes from the row and column sums; ties go to
+    the lower label), 0 where nothing overlaps.  Two uint32 arrays, indexed by label - 1."""
+    lib = lib if lib is not None else abi.load()
+    t = np.ascontiguousarray(table, dtype=np.uint32)
+    if t.ndim != 2:
+        raise ValueError("the table must be [count_a + 1][count_b + 1]")
+    ca, cb = t.shape[0] - 1, t.shape[1] - 1
+    best_b, best_a = np.zeros(max(ca, 1), np.uint32), np.zeros(max(cb, 1), np.uint32)
+    _host_call(lib, "svr_overlap_match", lib.svr_overlap_match(t.ctypes.data_as(C.c_void_p), ca, cb, best_b.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                               best_a.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return best_b[:ca], best_a[:cb]
+
+
+def compare_measure(comparison: abi.RegionComparison, unit: float = 1.0, lib=None) -> abi.CompareMeasurement:
+    """svr_region_compare_measure: Dice, Jaccard, volume difference, directed / symmetric / quantile Hausdorff distances, ASSD, RMS and
+    surface Dice (the formulas are in include/svr_abi.h) from the integers of region_compare; `unit` is the length of sqrt(d2) = 1, e.g.
+    the unit of distance_weights.  NaN where a denominator is 0."""
+    lib = lib if lib is not None else abi.load()
+    m = abi.CompareMeasurement()
+    _host_call(lib, "svr_region_compare_measure", lib.svr_region_compare_measure(C.byref(comparison), float(unit), C.byref(m)))
+    return m
 
 
 def resample_grid(grid) -> abi.ResampleGrid:
