@@ -60,8 +60,14 @@
 // -compare-mask F compares the final region with the mask in F (one byte per voxel, non-zero = set, the volume's dimensions: what
 // -save-mask wrote, or a ground truth) and prints one line: Dice, Jaccard, the Hausdorff distance, its 95 % form and the average
 // symmetric surface distance in the units of the spacing (Canvas::CompareRegionWithFile).
+// -scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...] cuts the region with a closed line drawn on the picture that is rendered, through its
+// camera: two points are the corners of an inclusive pixel rectangle, three or more the vertices of a polygon in pixels; `inside` removes
+// the voxels seen inside it, `outside` those seen outside (Canvas::ScissorRegion).  -scissor-slice x|y|z POS inside|outside|fill T X0 Y0 ...
+// does the same on the slice picture of that axis and position, within the slab of thickness T around the plane (T = 0: the whole
+// depth); `fill` adds the voxels instead (Canvas::ScissorRegionOnSlice, PaintRegionOnSlice).  Both come after the clean-up steps, in
+// command-line order, and print the region they leave.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -74,7 +80,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -109,6 +115,8 @@ int main(int argc, char** argv)
     struct GridStep { bool crop; int32_t lo[3], hi[3]; double mm; int mode; };   // -crop X0 Y0 Z0 X1 Y1 Z1 or -resample MM [mode]
     std::vector<GridStep> gridSteps;                                // applied right after the load, in command-line order
     std::string compareMaskFile;                                    // -compare-mask F: the final region against the mask in F
+    struct ScissorStep { int axis; float pos; int op; float thickness; std::vector<double> polygon; };   // -scissor (axis -1) / -scissor-slice, in order
+    std::vector<ScissorStep> scissorSteps;
     std::string saveVolumeFile, saveMaskFile, savePartsFile, saveCropVolume, saveCropMask;   // -save-volume / -save-mask / -save-parts F, -save-crop VOL MASK MARGIN
     int saveCropMargin = 0;
     const auto meshName = [](const char* f) {                       // an export writes .stl or .ply
@@ -392,6 +400,59 @@ int main(int argc, char** argv)
             if (i + 1 >= argc || argv[i + 1][0] == '-') { fprintf(stderr, "-compare-mask needs the file name of a mask (.mhd or .mha, one byte per voxel)\n"); return 2; }
             compareMaskFile = argv[++i];
         }
+        else if (!strcmp(argv[i], "-scissor") || !strcmp(argv[i], "-scissor-slice")) {
+            const bool onSlice = argv[i][8] != '\0';
+            const char* const name = argv[i];
+            ScissorStep sc = {-1, 0.5f, 0, 0.f, {}};
+            bool ok = true;
+            if (onSlice) {
+                ok = i + 2 < argc;
+                if (ok) {
+                    const char* a = argv[i + 1];
+                    sc.axis = (!strcmp(a, "x") || !strcmp(a, "0")) ? 0 : (!strcmp(a, "y") || !strcmp(a, "1")) ? 1 : (!strcmp(a, "z") || !strcmp(a, "2")) ? 2 : -1;
+                    sc.pos = (float)atof(argv[i + 2]);
+                    ok = sc.axis >= 0 && sc.pos >= 0.f && sc.pos <= 1.f;
+                    i += 2;
+                }
+            }
+            ok = ok && i + 1 < argc;
+            if (ok) {
+                const char* o = argv[++i];
+                sc.op = !strcmp(o, "inside") ? SVR_SCISSOR_ERASE_INSIDE : !strcmp(o, "outside") ? SVR_SCISSOR_ERASE_OUTSIDE : (onSlice && !strcmp(o, "fill")) ? SVR_SCISSOR_FILL_INSIDE : 0;
+                ok = sc.op != 0;
+            }
+            if (ok && onSlice) {
+                char* end = nullptr;
+                sc.thickness = i + 1 < argc ? strtof(argv[i + 1], &end) : -1.f;
+                ok = i + 1 < argc && end != argv[i + 1] && *end == '\0' && sc.thickness >= 0.f && std::isfinite(sc.thickness);
+                ++i;
+            }
+            while (ok && i + 1 < argc) {                            // the coordinates: every following argument that is a number
+                char* end = nullptr;
+                const double v = strtod(argv[i + 1], &end);
+                if (end == argv[i + 1] || *end != '\0') break;
+                sc.polygon.push_back(v);
+                ++i;
+            }
+            if (!ok || sc.polygon.size() < 4 || sc.polygon.size() % 2 != 0) {
+                fprintf(stderr, "%s needs %sinside|outside%s and the points X0 Y0 X1 Y1 [X2 Y2 ...] in pixels: two corners of a rectangle, or three or more vertices\n", name,
+                        onSlice ? "an axis x, y or z, a position in [0, 1], " : "", onSlice ? "|fill, a slab thickness >= 0" : "");
+                return 2;
+            }
+            if (sc.polygon.size() == 4) {                           // two corners: the inclusive pixel rectangle
+                int32_t q[8];
+                const double x0 = std::fmin(sc.polygon[0], sc.polygon[2]), x1 = std::fmax(sc.polygon[0], sc.polygon[2]);
+                const double y0 = std::fmin(sc.polygon[1], sc.polygon[3]), y1 = std::fmax(sc.polygon[1], sc.polygon[3]);
+                if (!(std::fabs(x0) < 4e4 && std::fabs(x1) < 4e4 && std::fabs(y0) < 4e4 && std::fabs(y1) < 4e4) ||
+                    svr_stencil_rect((int32_t)std::floor(x0), (int32_t)std::floor(y0), (int32_t)std::floor(x1), (int32_t)std::floor(y1), q) != 0) {
+                    fprintf(stderr, "%s: the rectangle lies beyond the coordinate limit\n", name);
+                    return 2;
+                }
+                sc.polygon.clear();
+                for (int k = 0; k < 8; ++k) sc.polygon.push_back(q[k] / 256.0);
+            }
+            scissorSteps.push_back(sc);
+        }
         else if (!strcmp(argv[i], "-save-crop")) {
             char* end = nullptr;
             const long v = i + 3 < argc ? strtol(argv[i + 3], &end, 10) : -1;
@@ -431,6 +492,7 @@ int main(int argc, char** argv)
         fprintf(stderr, "-save-mask, -save-parts and -save-crop write a region: they need -grow X Y LO HI or -threshold LO HI\n");
         return 2;
     }
+    if (!scissorSteps.empty() && !anyRegion) { fprintf(stderr, "-scissor and -scissor-slice cut a region: they need -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (!compareMaskFile.empty() && !anyRegion) { fprintf(stderr, "-compare-mask compares a region with the file: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (svr_init(0)) return 1;
     {
@@ -698,6 +760,28 @@ int main(int argc, char** argv)
                     printf("cleaned (%s, element %d): %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g\n",
                            done.c_str(), cleanElement, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
                            st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
+            }
+            for (const ScissorStep& sc : scissorSteps) {                // cut or paint with a closed line on the picture, or on a slice picture
+                int rc;
+                if (sc.axis < 0) rc = canvas.ScissorRegion(sc.polygon, sc.op, &st);
+                else {
+                    svr_slice_params sp2;
+                    rc = svr_slice_params_axis(&sp2, &canvas.Volume(), sc.axis, sc.pos, (uint32_t)W, (uint32_t)H);
+                    if (rc == 0) rc = canvas.ScissorRegionOnSlice(sp2, (uint32_t)W, (uint32_t)H, sc.polygon, sc.op, sc.thickness, &st);
+                }
+                if (rc == 0) rc = svr_region_measure(&st, sp, &m);
+                if (rc != 0) { fprintf(stderr, "-scissor: %s\n", svr_last_error_code() ? svr_last_error() : "not a polygon the scissors take"); return 1; }
+                float ms = 0.f;
+                svr_region_scissor_last_ms(&ms);
+                const char* const what = sc.op == SVR_SCISSOR_ERASE_INSIDE ? "inside" : sc.op == SVR_SCISSOR_ERASE_OUTSIDE ? "outside" : "fill";
+                char view[64] = "";
+                if (sc.axis >= 0) snprintf(view, sizeof view, "-slice %c %g thickness %g", "xyz"[sc.axis], sc.pos, sc.thickness);
+                if (st.status == SVR_REGION_STATUS_EMPTY)
+                    printf("scissor%s %s, %zu vertices: the region is empty; %.3f ms\n", view, what, sc.polygon.size() / 2, ms);
+                else
+                    printf("scissor%s %s, %zu vertices: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %.3f ms\n", view, what,
+                           sc.polygon.size() / 2, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
+                           st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, ms);
             }
             if (thickness) {
                 double radius = 0.0;

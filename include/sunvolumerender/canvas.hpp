@@ -1052,6 +1052,29 @@ public:
     bool HasRegion() const { return haveRegion; }
     const uint32_t* RegionMask() const { return haveRegion ? regionMask : nullptr; }   // device; svr_region_mask_words words
 
+    // extension: scissors (svr_stencil_polygon, svr_region_scissor_camera / _slice; include/svr_abi.h, "scissors").  polygon: the (x, y)
+    // pairs of a closed line drawn on the picture, in pixels (the centre of pixel (px, py) is (px + 0.5, py + 0.5)), converted to 1/256
+    // pixel by rounding to nearest; op: SVR_SCISSOR_ERASE_INSIDE / _ERASE_OUTSIDE / _FILL_INSIDE.  The region mask is changed in place;
+    // *stats (may be null) gets the statistics of the new mask.  With no region yet, SVR_SCISSOR_FILL_INSIDE starts one from nothing.
+    // ScissorRegion: through the canvas's camera, on the WIDTH x HEIGHT picture.  The projection takes the camera's frame u, v, w to be
+    // orthonormal: a camera set up with an `up` that is not perpendicular to the view direction has shorter u and v, and cuts elsewhere
+    int ScissorRegion(const std::vector<double>& polygon, int op, svr_region_stats* stats = nullptr)
+    {
+        return Scissor(nullptr, (uint32_t)WIDTH, (uint32_t)HEIGHT, polygon, op, 0.f, stats);
+    }
+    // ScissorRegionOnSlice: through slice 0 of `params` on a w x h slice picture, within the slab of `thickness` (world units) around the
+    // plane; thickness <= 0 means the whole depth.  PaintRegionOnSlice adds the prism to the region
+    int ScissorRegionOnSlice(const svr_slice_params& params, uint32_t w, uint32_t h, const std::vector<double>& polygon, int op, float thickness,
+                             svr_region_stats* stats = nullptr)
+    {
+        return Scissor(&params, w, h, polygon, op, thickness, stats);
+    }
+    int PaintRegionOnSlice(const svr_slice_params& params, uint32_t w, uint32_t h, const std::vector<double>& polygon, float thickness,
+                           svr_region_stats* stats = nullptr)
+    {
+        return Scissor(&params, w, h, polygon, SVR_SCISSOR_FILL_INSIDE, thickness, stats);
+    }
+
     // extension: how far the region is from another mask of the same dimensions (svr_region_compare / _compare_measure; include/svr_abi.h,
     // "comparing segmentations").  The region is A, the other mask B; distances are in the units of the loaded volume's spacing (mm), by
     // the weights and unit of RegionDistanceUnits.  tolerances (may be null) are ntol <= SVR_COMPARE_MAX_TOLERANCES lengths in those units
@@ -1332,6 +1355,41 @@ private:
     {
         const double q = length / unit, r2 = std::floor(q * q);
         return r2 >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)r2;
+    }
+    // the scissor calls of the public section: slice == nullptr means the canvas's camera
+    int Scissor(const svr_slice_params* slice, uint32_t w, uint32_t h, const std::vector<double>& polygon, int op, float thickness, svr_region_stats* stats)
+    {
+        const uint16_t* vox = SegVoxels();
+        if (!ready || !vox) return -4;
+        if (op != SVR_SCISSOR_ERASE_INSIDE && op != SVR_SCISSOR_ERASE_OUTSIDE && op != SVR_SCISSOR_FILL_INSIDE) return -3;
+        if (!haveRegion && op != SVR_SCISSOR_FILL_INSIDE) return -4;
+        if (polygon.size() < 6 || polygon.size() % 2 != 0 || polygon.size() / 2 > SVR_STENCIL_MAX_VERTICES || w == 0u || h == 0u) return -3;
+        std::vector<int32_t> q8(polygon.size());
+        for (size_t i = 0; i < polygon.size(); ++i) {
+            const double v = std::nearbyint(polygon[i] * 256.0);
+            if (!(std::fabs(v) <= (double)SVR_STENCIL_MAX_COORD)) return -3;
+            q8[i] = (int32_t)v;
+        }
+        const int* dim = volumeReader->dim;
+        if (!regionMask) regionMask = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words(dim[0], dim[1], dim[2]) * sizeof(uint32_t));
+        if (!regionMask) return -4;
+        uint32_t* stencil = (uint32_t*)svr_device_malloc((size_t)svr_region_mask_words((int)w, (int)h, 1) * sizeof(uint32_t));
+        if (!stencil) return -4;
+        const uint32_t count = (uint32_t)(polygon.size() / 2);
+        svr_scissor_params p;
+        svr_scissor_params_default(&p);
+        p.op = haveRegion ? op : SVR_SCISSOR_SELECT;                  // (filling nothing: the prism itself)
+        if (slice && thickness > 0.f) { p.depth_lo = -0.5f * thickness; p.depth_hi = 0.5f * thickness; }
+        int rc = svr_stencil_polygon(q8.data(), &count, 1u, w, h, stencil);
+        if (rc == 0)
+            rc = slice ? svr_region_scissor_slice(regionMask, dim[0], dim[1], dim[2], &deviceVolume, slice, w, h, stencil, &p, regionMask)
+                       : svr_region_scissor_camera(regionMask, dim[0], dim[1], dim[2], &deviceVolume, &camera, stencil, &p, regionMask);
+        if (rc == 0) rc = svr_device_synchronize();                // the stencil is freed below
+        svr_device_free(stencil);
+        if (rc != 0) return rc;
+        if (!haveRegion) { haveRegion = true; haveSeed = false; }
+        haveLabels = false;                                        // (they were the parts of the mask that went)
+        return stats ? svr_region_stats_of(vox, dim[0], dim[1], dim[2], 1, regionMask, stats) : 0;
     }
     // the second mask buffer, into which the clean-up calls write (their `out` must not overlap their input)
     bool WorkMask()

@@ -1418,6 +1418,79 @@ int svr_region_compare_measure(const svr_region_comparison* c, double unit, svr_
  * svr_region_distance runs as well */
 int svr_region_compare_last_ms(float* ms);
 
+/* ---- scissors: cut and paint region masks with a polygon drawn on a view (csrc/svr_scissor.hip) ----
+ * The direction the views lack: from a voxel to the pixel it is seen at.  A polygon drawn on the picture is filled on the pixel grid (a
+ * STENCIL), and every voxel whose centre is seen inside the fill (the PRISM) is selected, removed from, kept in or added to a mask.
+ * STENCIL LAYOUT: the stencil of a w x h image is the region mask of a w x h x 1 volume in the layout of the region section: uint32
+ *   [h][ceil(w / 32)], pixel (x, y) is bit x & 31 of word y * wx + (x >> 5), padding bits 0 on output.  svr_region_combine,
+ *   svr_region_morph and svr_region_stats_of therefore work on stencils with nx = w, ny = h, nz = 1; dilating a stencil is the width of
+ *   a brush.
+ * POLYGON: vertices_xy_q8 is a HOST array of (x, y) pairs in 1/256 pixel; the centre of pixel (px, py) is (256 px + 128, 256 py + 128).
+ *   contour_counts[k] is the number of vertices of contour k, the contours follow one another in the array and each is closed
+ *   implicitly.  The edge set E is the union of all contours' edges, so a second contour inside the first is a hole.
+ * FILL RULE: even-odd with the half-open crossing rule, exact in int64.  For pixel centre c and edge (a, b) the edge COUNTS iff
+ *   (a.y > c.y) != (b.y > c.y) and c lies strictly to the left of the edge's crossing of the line y = c.y:
+ *   cross = (b.x - a.x)(c.y - a.y) - (b.y - a.y)(c.x - a.x), with cross > 0 when b.y > a.y and cross < 0 otherwise.  The pixel is set
+ *   iff an odd number of edges count.  Horizontal edges never count.  Polygons that share an edge tile the plane: no pixel is in both
+ *   and none in neither.
+ * LIMITS: every coordinate satisfies |v| <= 2^23 (SVR_STENCIL_MAX_COORD), so every product stays below 2^49 (a pixel outside the
+ *   polygon's bounding box is unset without looking at an edge); at most SVR_STENCIL_MAX_VERTICES vertices in total; each contour has at
+ *   least 3; ncontours >= 1; w, h >= 1 and w h <= 2^31.  svr_stencil_polygon is asynchronous on the library's stream; the vertex list is
+ *   read before the call returns.  svr_stencil_rect (plain host code) writes the four vertices of the inclusive pixel rectangle x0 ..
+ *   x1, y0 .. y1 -- its corners lie on pixel corners: (256 x0, 256 y0), (256 (x1 + 1), 256 y0), (256 (x1 + 1), 256 (y1 + 1)),
+ *   (256 x0, 256 (y1 + 1)); it refuses x1 < x0, y1 < y0 and a corner beyond the coordinate limit.
+ * PROJECTION: the pixel and the depth at which a view sees a world point P.  Everything is float32 without contraction, with correctly
+ *   rounded division; dot(p, q) = (p.x q.x + p.y q.y) + p.z q.z.
+ *   CAMERA: the inverse of the pinhole centre ray of the projection section (wm1 = (float)imageW - 1, hm1 = (float)imageH - 1).
+ *     d = P - pos per component, a = dot(d, u), b = dot(d, v), c = -dot(d, w), depth = c.  If c > 0 is false (behind the pinhole, or
+ *     NaN) the point is seen at no pixel.  Otherwise s = ((a / (c * (aspectRatio * tanFovxOverTwo)) + 1) * 0.5f) * wm1 and
+ *     r = ((b / (c * tanFovxOverTwo) + 1) * 0.5f) * hm1, every operation rounded.  The frame u, v, w is TAKEN to be orthonormal, as the
+ *     reference's camera makes it; the calls do not check it.
+ *   SLICE: the inverse of the PLANE POINT of the slice section for slice 0 of the params on a w x h image.  d = P - center,
+ *     a = dot(d, u) / dot(u, u), b = dot(d, v) / dot(v, v), s = a + 0.5f * (float)w, r = b + 0.5f * (float)h, depth = dot(d, n) with n
+ *     the FRAME normal of the slice section.  The inverse is exact when u and v are perpendicular, which every svr_slice_params_axis /
+ *     _through result satisfies; thickness, step, mode, flags and the window are not looked at.
+ *   PIXEL: (floor(s), floor(r)) if 0 <= s < (float)W and 0 <= r < (float)H (comparisons of floats), otherwise none.
+ *   svr_scissor_project_camera / _slice are plain host code that runs the very function the kernel runs: 0 with the pixel in xy, 1
+ *   with xy = (-1, -1) when the point is seen at no pixel; *depth is written in both cases.
+ * VOXEL CENTRE: per axis tc = ((float)i + 0.5f) / (float)n and P = bbox.vmin + (bbox.vmax - bbox.vmin) * tc, every operation rounded,
+ *   on the UNCLIPPED box: the mapping that svr_region_seed_from_world inverts.
+ * PRISM: voxel (i, j, k) is in the prism iff its centre is seen at a pixel, that pixel's stencil bit is set, and depth_lo <= depth <=
+ *   depth_hi (closed, on the float depth itself).  The stencil is that of the camera's imageW x imageH, or of the slice call's w x h.
+ *   Depth is a world distance along the view axis: in a slice view depth -t/2 .. t/2 is a slab of thickness t around the plane.
+ * OP: SVR_SCISSOR_SELECT out = prism (in may be NULL and is not read); _ERASE_INSIDE out = in & ~prism; _ERASE_OUTSIDE out = in & prism;
+ *   _FILL_INSIDE out = in | prism.  out may be in.  Input padding bits are ignored, output padding bits are 0.  Asynchronous.
+ * REFUSED, before the device is touched: a null pointer, except `in` with SELECT (-4); a dimension <= 0 or more than 2^31 voxels (-6);
+ *   (-3) an unknown op, flags != 0, a NaN depth bound, depth_lo > depth_hi, a non-finite bbox.vmin / vmax, camera frame or position, an
+ *   imageW or imageH of 0 or more than 2^31 pixels, a tanFovxOverTwo or aspectRatio that is not finite and > 0; for a slice: w or h of
+ *   0 or more than 2^31 pixels, a non-finite member of center, u or v, a cross(u, v) whose length is 0 or not finite; for a polygon:
+ *   what LIMITS names. */
+#define SVR_STENCIL_MAX_VERTICES 4096
+#define SVR_STENCIL_MAX_COORD 8388608      /* 2^23 */
+#define SVR_SCISSOR_SELECT        0
+#define SVR_SCISSOR_ERASE_INSIDE  1
+#define SVR_SCISSOR_ERASE_OUTSIDE 2
+#define SVR_SCISSOR_FILL_INSIDE   3
+typedef struct svr_scissor_params {     /* 4-byte members only, 16 bytes */
+    int32_t  op;                        /* SVR_SCISSOR_* */
+    float    depth_lo, depth_hi;        /* the closed depth interval of the prism */
+    uint32_t flags;                     /* must be 0 */
+} svr_scissor_params;
+int svr_scissor_params_default(svr_scissor_params* p);   /* SELECT, -INF .. +INF.  Plain host code */
+int svr_stencil_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t vertices_xy_q8[8]);
+int svr_stencil_polygon(const int32_t* vertices_xy_q8, const uint32_t* contour_counts, uint32_t ncontours, uint32_t w, uint32_t h,
+                        uint32_t* stencil_device);
+int svr_scissor_project_camera(const svr_camera* camera, const svr_vec3* point, int32_t xy[2], float* depth);
+int svr_scissor_project_slice(const svr_slice_params* slice, uint32_t w, uint32_t h, const svr_vec3* point, int32_t xy[2], float* depth);
+int svr_region_scissor_camera(const uint32_t* in_mask_device_or_null,
+                              int nx, int ny, int nz, const svr_volume* volume, const svr_camera* camera,
+                              const uint32_t* stencil_device, const svr_scissor_params* p, uint32_t* out_mask_device);
+int svr_region_scissor_slice(const uint32_t* in_mask_device_or_null,
+                             int nx, int ny, int nz, const svr_volume* volume, const svr_slice_params* slice, uint32_t w, uint32_t h,
+                             const uint32_t* stencil_device, const svr_scissor_params* p, uint32_t* out_mask_device);
+/* HIP-event time of the device work of the last svr_stencil_polygon / svr_region_scissor_camera / _slice (waits for it) */
+int svr_region_scissor_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

@@ -353,6 +353,16 @@ COMPARE_MAX_TOLERANCES = 8
 COMPARE_A_EMPTY, COMPARE_B_EMPTY = 1, 2
 
 
+class ScissorParams(C.Structure):  # svr_scissor_params
+    _fields_ = [("op", C.c_int32), ("depth_lo", C.c_float), ("depth_hi", C.c_float), ("flags", C.c_uint32)]
+
+
+svr_scissor_params = ScissorParams
+SCISSOR_SELECT, SCISSOR_ERASE_INSIDE, SCISSOR_ERASE_OUTSIDE, SCISSOR_FILL_INSIDE = 0, 1, 2, 3
+STENCIL_MAX_VERTICES = 4096
+STENCIL_MAX_COORD = 1 << 23
+
+
 class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
     _fields_ = [("mask_device", C.c_void_p), ("labels_device", C.c_void_p)]
 
@@ -642,6 +652,16 @@ PROTOTYPES = {
     "svr_region_compare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(CompareParams), _P(RegionComparison)]),
     "svr_region_compare_measure": (C.c_int, [_P(RegionComparison), C.c_double, _P(CompareMeasurement)]),
     "svr_region_compare_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_scissor_params_default": (C.c_int, [_P(ScissorParams)]),
+    "svr_stencil_rect": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32)]),
+    "svr_stencil_polygon": (C.c_int, [_P(C.c_int32), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "svr_scissor_project_camera": (C.c_int, [_P(cudaCamera), _P(vec3), _P(C.c_int32), _P(C.c_float)]),
+    "svr_scissor_project_slice": (C.c_int, [_P(SliceParams), C.c_uint32, C.c_uint32, _P(vec3), _P(C.c_int32), _P(C.c_float)]),
+    "svr_region_scissor_camera": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(cudaVolume), _P(cudaCamera), C.c_void_p, _P(ScissorParams),
+                                            C.c_void_p]),
+    "svr_region_scissor_slice": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(cudaVolume), _P(SliceParams), C.c_uint32, C.c_uint32,
+                                           C.c_void_p, _P(ScissorParams), C.c_void_p]),
+    "svr_region_scissor_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
     "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
     "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,

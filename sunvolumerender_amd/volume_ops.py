@@ -652,6 +652,58 @@ class VolumeOps:
     def region_compare_last_ms(self) -> float:
         return self._last_ms(self.lib.svr_region_compare_last_ms)
 
+    # ---- scissors (svr_stencil_polygon, svr_region_scissor_camera / _slice); scissor_project_camera / _slice, stencil_rect and
+    #      scissor_params are module functions ----
+    def stencil_polygon(self, contours, w: int, h: int, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_stencil_polygon: the even-odd fill of a polygon on a w x h pixel grid.  contours: a list of (n, 2) arrays of (x, y) in
+        pixels (the centre of pixel (px, py) is (px + 0.5, py + 0.5)), each closed implicitly, converted to 1/256 pixel by round(256 v);
+        a contour inside another is a hole.  Returns the stencil words, np.uint32[h * ceil(w / 32)]: the bit mask of a [1][h][w] volume
+        (region_mask_unpack(words, (1, h, w))[0] is the image).  out_ptr: a device buffer of that many words that receives them."""
+        q8, counts = _contours_q8(contours)
+        w, h = _image_size(w, h)
+        with self._staging() as s:
+            words = region_mask_words((1, h, w))
+            out = s.out(4 * words, out_ptr)
+            self.check(self.lib.svr_stencil_polygon(q8.ctypes.data_as(C.POINTER(C.c_int32)), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(counts),
+                                                    w, h, C.c_void_p(out)))
+            return self.to_host(out, (words,), np.uint32)
+
+    def region_scissor(self, mask, stencil, volume: cudaVolume, camera=None, slice=None, w: Optional[int] = None, h: Optional[int] = None,
+                       op: int = abi.SCISSOR_SELECT, depth=(-np.inf, np.inf), shape=None, out_ptr: Optional[int] = None) -> np.ndarray:
+        """svr_region_scissor_camera / _slice: the voxels of the [nz][ny][nx] grid of `volume` (its bbox) whose centre is seen inside
+        the stencil -- through `camera` (a cudaCamera; the stencil is imageW x imageH) or through `slice` (a SliceParams on a w x h
+        image), exactly one of the two -- at a depth in the closed interval `depth`, combined with `mask` by op: SCISSOR_SELECT (mask
+        may be None, with shape=), _ERASE_INSIDE, _ERASE_OUTSIDE, _FILL_INSIDE.  mask: a bool array [nz][ny][nx] or a device pointer
+        with shape=; stencil: a bool image [h][w], the words of stencil_polygon, or a device pointer.  out_ptr may be the mask's own
+        pointer.  Returns the bool array."""
+        if (camera is None) == (slice is None):
+            raise ValueError("exactly one of camera and slice must be given")
+        if camera is not None and (w is not None or h is not None):
+            raise ValueError("w and h belong to a slice view: a camera has its imageW x imageH")
+        if slice is not None and (w is None or h is None):
+            raise ValueError("a slice view needs w= and h=")
+        w, h = _image_size(camera.imageW if camera is not None else w, camera.imageH if camera is not None else h)
+        if mask is None and int(op) != abi.SCISSOR_SELECT:
+            raise ValueError("only SCISSOR_SELECT works without a mask")
+        if mask is None and shape is None:
+            raise ValueError("SCISSOR_SELECT without a mask needs shape=(nz, ny, nx)")
+        nz, ny, nx = shape = _shape_of("mask", mask, shape) if mask is not None else _shape_of("mask", (), shape)
+        sten = _stencil_words(stencil, w, h)
+        p = scissor_params(op, depth)
+        with self._staging() as s:
+            buf = s.mask(mask, shape)
+            sbuf = C.c_void_p(s.upload(sten, 4)) if isinstance(sten, np.ndarray) else C.c_void_p(int(sten))
+            out = s.mask_out(shape, out_ptr)
+            if camera is not None:
+                rc = self.lib.svr_region_scissor_camera(buf, nx, ny, nz, C.byref(volume), C.byref(camera), sbuf, C.byref(p), C.c_void_p(out))
+            else:
+                rc = self.lib.svr_region_scissor_slice(buf, nx, ny, nz, C.byref(volume), C.byref(slice), w, h, sbuf, C.byref(p), C.c_void_p(out))
+            self.check(rc)
+            return s.mask_result(out, shape)
+
+    def region_scissor_last_ms(self) -> float:
+        return self._last_ms(self.lib.svr_region_scissor_last_ms)
+
     # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
     def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
         """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
@@ -1055,6 +1107,85 @@ def compare_measure(comparison: abi.RegionComparison, unit: float = 1.0, lib=Non
     m = abi.CompareMeasurement()
     _host_call(lib, "svr_region_compare_measure", lib.svr_region_compare_measure(C.byref(comparison), float(unit), C.byref(m)))
     return m
+
+
+def _image_size(w, h):
+    w, h = int(w), int(h)
+    if w < 1 or h < 1 or w * h > 1 << 31:
+        raise ValueError(f"an image of {w} x {h} pixels: w and h must be at least 1 and w * h at most 2^31")
+    return w, h
+
+
+def _contours_q8(contours):
+    """(int32 (x, y) pairs in 1/256 pixel, uint32 vertex counts) of a list of (n, 2) pixel arrays; ValueError for what the library refuses"""
+    if isinstance(contours, np.ndarray) and contours.ndim == 2:
+        contours = [contours]
+    if len(contours) == 0:
+        raise ValueError("a polygon needs at least one contour")
+    parts = []
+    for k, c in enumerate(contours):
+        a = np.asarray(c, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 3:
+            raise ValueError(f"contour {k} must be an (n, 2) array of (x, y) with n >= 3")
+        if not np.isfinite(a).all():
+            raise ValueError(f"contour {k} holds a coordinate that is not finite")
+        q = np.rint(a * 256.0)
+        if np.abs(q).max() > abi.STENCIL_MAX_COORD:
+            raise ValueError(f"contour {k} holds a coordinate beyond 2^23 / 256 = 32768 pixels")
+        parts.append(q.astype(np.int32))
+    counts = np.array([len(q) for q in parts], dtype=np.uint32)
+    if int(counts.sum()) > abi.STENCIL_MAX_VERTICES:
+        raise ValueError(f"more than {abi.STENCIL_MAX_VERTICES} vertices")
+    return np.ascontiguousarray(np.concatenate(parts)), counts
+
+
+def _stencil_words(stencil, w: int, h: int):
+    """The stencil operand of a w x h image: a bool image [h][w] packed, uint32 words checked for their number, a device pointer as it is"""
+    if not isinstance(stencil, np.ndarray):
+        if stencil is None:
+            raise ValueError("a stencil is needed")
+        return int(stencil)
+    if stencil.dtype == bool:
+        if stencil.shape != (h, w):
+            raise ValueError(f"the stencil image must be [{h}][{w}] (got {list(stencil.shape)})")
+        return region_mask_pack(stencil.reshape(1, h, w))
+    words = region_mask_words((1, h, w))
+    if stencil.dtype != np.uint32 or stencil.shape != (words,):
+        raise ValueError(f"the stencil must be a bool image [{h}][{w}] or its {words} uint32 words")
+    return np.ascontiguousarray(stencil)
+
+
+def scissor_params(op: int = abi.SCISSOR_SELECT, depth=(-np.inf, np.inf)) -> abi.ScissorParams:
+    """svr_scissor_params with the op and the closed depth interval (lo, hi); flags 0"""
+    return abi.ScissorParams(int(op), float(depth[0]), float(depth[1]), 0)
+
+
+def stencil_rect(x0: int, y0: int, x1: int, y1: int, lib=None) -> np.ndarray:
+    """svr_stencil_rect: the contour, a float (4, 2) array in pixels, of the inclusive pixel rectangle x0 .. x1, y0 .. y1.  Host code of the
+    library, as the two projections below: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    q = (C.c_int32 * 8)()
+    _host_call(lib, "svr_stencil_rect", lib.svr_stencil_rect(int(x0), int(y0), int(x1), int(y1), q))
+    return np.array(list(q), dtype=np.float64).reshape(4, 2) / 256.0
+
+
+def scissor_project_camera(camera, point, lib=None):
+    """svr_scissor_project_camera: ((x, y), depth) of the pixel at which the pinhole camera sees a world point and its depth along the
+    view axis; (None, depth) when it is seen at no pixel."""
+    lib = lib if lib is not None else abi.load()
+    xy, depth, pt = (C.c_int32 * 2)(), C.c_float(0.0), _to_vec3(point)
+    rc = _host_call(lib, "svr_scissor_project_camera", lib.svr_scissor_project_camera(C.byref(camera), C.byref(pt), xy, C.byref(depth)), ok=(0, 1))
+    return ((int(xy[0]), int(xy[1])) if rc == 0 else None), float(depth.value)
+
+
+def scissor_project_slice(slice, w: int, h: int, point, lib=None):
+    """svr_scissor_project_slice: the same through the orthographic window of slice 0 of a SliceParams on a w x h image; depth is the
+    signed distance from the plane along its normal."""
+    lib = lib if lib is not None else abi.load()
+    xy, depth, pt = (C.c_int32 * 2)(), C.c_float(0.0), _to_vec3(point)
+    rc = _host_call(lib, "svr_scissor_project_slice", lib.svr_scissor_project_slice(C.byref(slice), int(w), int(h), C.byref(pt), xy, C.byref(depth)),
+                    ok=(0, 1))
+    return ((int(xy[0]), int(xy[1])) if rc == 0 else None), float(depth.value)
 
 
 def resample_grid(grid) -> abi.ResampleGrid:
