@@ -66,8 +66,12 @@
 // does the same on the slice picture of that axis and position, within the slab of thickness T around the plane (T = 0: the whole
 // depth); `fill` adds the voxels instead (Canvas::ScissorRegionOnSlice, PaintRegionOnSlice).  Both come after the clean-up steps, in
 // command-line order, and print the region they leave.
+// -fill-between x|y|z fills the slices of that axis between the slices that hold a voxel of the region, by shape-based interpolation
+// (Canvas::FillRegionBetweenSlices): what was drawn on every few slices with -scissor-slice ... fill, or thresholded in a volume that has
+// only every few slices, becomes solid.  It comes after the scissors -- so after the clean-up steps, -largest among them -- and before
+// -thickness, -mesh, -save-mask and the other outputs, and prints the keys, gaps and filled slices and the voxels before and after.
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-fill-between x|y|z] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -80,7 +84,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-fill-between x|y|z] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -117,6 +121,7 @@ int main(int argc, char** argv)
     std::string compareMaskFile;                                    // -compare-mask F: the final region against the mask in F
     struct ScissorStep { int axis; float pos; int op; float thickness; std::vector<double> polygon; };   // -scissor (axis -1) / -scissor-slice, in order
     std::vector<ScissorStep> scissorSteps;
+    int fillBetweenAxis = -1;                                       // -fill-between x|y|z
     std::string saveVolumeFile, saveMaskFile, savePartsFile, saveCropVolume, saveCropMask;   // -save-volume / -save-mask / -save-parts F, -save-crop VOL MASK MARGIN
     int saveCropMargin = 0;
     const auto meshName = [](const char* f) {                       // an export writes .stl or .ply
@@ -453,6 +458,12 @@ int main(int argc, char** argv)
             }
             scissorSteps.push_back(sc);
         }
+        else if (!strcmp(argv[i], "-fill-between")) {
+            const char* a = i + 1 < argc ? argv[i + 1] : "";
+            fillBetweenAxis = (!strcmp(a, "x") || !strcmp(a, "0")) ? 0 : (!strcmp(a, "y") || !strcmp(a, "1")) ? 1 : (!strcmp(a, "z") || !strcmp(a, "2")) ? 2 : -1;
+            if (fillBetweenAxis < 0) { fprintf(stderr, "-fill-between needs an axis x, y or z\n"); return 2; }
+            ++i;
+        }
         else if (!strcmp(argv[i], "-save-crop")) {
             char* end = nullptr;
             const long v = i + 3 < argc ? strtol(argv[i + 3], &end, 10) : -1;
@@ -493,6 +504,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (!scissorSteps.empty() && !anyRegion) { fprintf(stderr, "-scissor and -scissor-slice cut a region: they need -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if (fillBetweenAxis >= 0 && !anyRegion) { fprintf(stderr, "-fill-between fills a region: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (!compareMaskFile.empty() && !anyRegion) { fprintf(stderr, "-compare-mask compares a region with the file: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (svr_init(0)) return 1;
     {
@@ -782,6 +794,21 @@ int main(int argc, char** argv)
                     printf("scissor%s %s, %zu vertices: %llu voxels, volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %.3f ms\n", view, what,
                            sc.polygon.size() / 2, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
                            st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, ms);
+            }
+            if (fillBetweenAxis >= 0) {                                 // the slices between the drawn ones
+                svr_fill_between_info fb;
+                int rc = canvas.FillRegionBetweenSlices(fillBetweenAxis, &st, &fb);
+                if (rc == 0) rc = svr_region_measure(&st, sp, &m);
+                if (rc != 0) { fprintf(stderr, "-fill-between: %s\n", svr_last_error()); return 1; }
+                float ms = 0.f;
+                svr_region_fill_between_last_ms(&ms);
+                printf("fill-between %c: %u keys (%d .. %d), %u gaps, %u slices filled, %llu -> %llu voxels", "xyz"[fillBetweenAxis], fb.keys, (int)fb.first_key,
+                       (int)fb.last_key, fb.gaps, fb.filled_slices, (unsigned long long)fb.voxels_in, (unsigned long long)fb.voxels_out);
+                if (st.status == SVR_REGION_STATUS_EMPTY)
+                    printf("; the region is empty; %.3f ms\n", ms);
+                else
+                    printf(", volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %.3f ms\n", m.volume, m.mean, m.stddev, st.vmin, st.vmax,
+                           st.bbox_min[0], st.bbox_min[1], st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, ms);
             }
             if (thickness) {
                 double radius = 0.0;

@@ -1075,6 +1075,31 @@ public:
         return Scissor(&params, w, h, polygon, SVR_SCISSOR_FILL_INSIDE, thickness, stats);
     }
 
+    // extension: fill between slices (svr_region_slice_counts, svr_region_fill_between; include/svr_abi.h, "fill between slices").
+    // axis: 0, 1, 2 = x, y, z.  RegionSliceCounts: the set voxels of every slice of the axis -- the slices that hold a drawing.
+    // FillRegionBetweenSlices: every slice that holds a voxel of the region is a key, and the slices between consecutive keys are
+    // filled by shape-based interpolation, in-plane distances in the volume's spacing (the weights of RegionDistanceUnits) -- so a
+    // slice between two drawings is empty before the call, and to end a shape one calls svr_region_fill_between with explicit keys.  Replaces the region like MorphRegion; *info (may be null) tells the keys, gaps and filled slices
+    int RegionSliceCounts(int axis, std::vector<uint64_t>& counts)
+    {
+        if (!ready || !SegVoxels() || !haveRegion) return -4;
+        if (axis < 0 || axis > 2) return -3;
+        const int* dim = volumeReader->dim;
+        counts.assign((size_t)dim[axis], 0u);
+        return svr_region_slice_counts(regionMask, dim[0], dim[1], dim[2], axis, counts.data());
+    }
+    int FillRegionBetweenSlices(int axis, svr_region_stats* stats = nullptr, svr_fill_between_info* info = nullptr)
+    {
+        if (!WorkMask()) return -4;
+        svr_fill_between_params p;
+        svr_fill_between_params_default(&p);
+        p.axis = axis;
+        double unit = 0.0;
+        if (int rc = RegionDistanceUnits(p.weights, &unit)) return rc;
+        const int* dim = volumeReader->dim;
+        return ReplaceRegion(svr_region_fill_between(regionMask, dim[0], dim[1], dim[2], &p, regionWork, info), stats);
+    }
+
     // extension: how far the region is from another mask of the same dimensions (svr_region_compare / _compare_measure; include/svr_abi.h,
     // "comparing segmentations").  The region is A, the other mask B; distances are in the units of the loaded volume's spacing (mm), by
     // the weights and unit of RegionDistanceUnits.  tolerances (may be null) are ntol <= SVR_COMPARE_MAX_TOLERANCES lengths in those units

@@ -1491,6 +1491,89 @@ int svr_region_scissor_slice(const uint32_t* in_mask_device_or_null,
 /* HIP-event time of the device work of the last svr_stencil_polygon / svr_region_scissor_camera / _slice (waits for it) */
 int svr_region_scissor_last_ms(float* ms);
 
+/* ---- fill between slices: interpolate a region drawn on a few slices (csrc/svr_fillbetween.hip) ----
+ * A region drawn on every fifth or tenth slice of one axis (svr_region_scissor_slice with FILL_INSIDE, say) becomes a solid region: the
+ * slices between two drawn ones are filled by shape-based interpolation (Raya and Udupa), decided in integers, so the result is unique.
+ * Masks are device pointers in the layout of the region section; input padding bits are ignored, output padding bits are 0.  The calls
+ * run on the library's stream and touch no scene, option or accumulator.
+ * AXIS: 0, 1 or 2 (x, y, z), the slicing axis; slice k is the set of voxels whose coordinate on it is k, and the axis has n_axis of
+ *   them.  The two other axes are the in-plane axes u < v (by axis number), of lengths nu and nv; a planar array of a slice is
+ *   [nv][nu], u fastest.
+ * WEIGHTS: as in svr_region_distance, a host uint32[3], each >= 1, NULL = 1, 1, 1.  The weight of the slicing axis is not used: slices
+ *   are equally spaced and the interpolation is linear in the slice index.  The planar squared distance of two voxels of one slice is
+ *   wu du^2 + wv dv^2.
+ * PLANAR MAP of a slice: a uint32 per voxel of the slice -- for a set voxel the smallest planar squared distance to an unset voxel of
+ *   the same slice, for an unset voxel the smallest planar squared distance to a set voxel of the same slice, SVR_DIST_NONE where the
+ *   slice holds no voxel of the other kind.  Nothing outside the volume counts, as in svr_region_distance.  The voxel's own mask bit is
+ *   the sign.  With unit weights this is round(distance_transform_edt(s)^2) on the set voxels and round(distance_transform_edt(~s)^2)
+ *   on the unset ones, per 2D slice.
+ * FILL: given keys k_0 < k_1 < ... < k_(m-1), the output equals the input on the key slices and outside k_0 .. k_(m-1).  For a slice k
+ *   with a < k < b between consecutive keys a, b let n = b - a, t = k - a, and A, B the planar map values of the voxel's in-plane
+ *   position in slices a and b, SVR_DIST_NONE entering as the number 2^32 - 1.  The voxel is set if it is set in both keys, unset if
+ *   it is unset in both; set in a only: set iff (n - t)^2 A > t^2 B; set in b only: set iff t^2 B > (n - t)^2 A.  Equality gives
+ *   unset.  This is the sign of (n - t) s_a + t s_b for the signed distances s = +-sqrt(map), decided without a square root; both
+ *   products fit uint64 because n <= 65535 and the maps are below 2^32.  With SVR_FILL_KEEP_BETWEEN the input bits of the slices between
+ *   keys are OR-ed into the result; without it they are replaced.  Consecutive keys with n == 1 have nothing between them; a GAP is a
+ *   pair with n >= 2.  Fewer than two keys, or no gap, gives out = in with the padding cleared and the return 0.
+ *   KNOWN LIMIT of the method: the shapes of two keys that do not overlap in projection do not travel from one to the other, they fade
+ *   out and in.  Two discs of radius 6 (113 voxels) whose centres lie 20 voxels apart in the plane, drawn eight slices apart, give
+ *   the per-slice counts 113, 59, 8, 0, 0, 0, 8, 59, 113.
+ * svr_region_slice_counts: counts_host[k] = the set voxels of slice k, n_axis entries: how keys are found and how a user interface
+ *   marks the slices that hold a drawing.  Synchronises.
+ * svr_region_slice_distance: the planar maps of the listed slices, maps_device[nslices][nv][nu]; a NULL list means all n_axis slices in
+ *   order (nslices is then not looked at).  The list is a host array, in any order, repeats allowed.  The call allocates and frees its
+ *   workspace -- per voxel of the slices it works on together (all of them up to 2^26 voxels, at least one slice) 12 bytes and one bit
+ *   -- and synchronises.
+ * svr_region_fill_between: params.keys is a host array of nkeys strictly increasing slices inside the axis; NULL means every slice that
+ *   holds a set voxel (nkeys is then not looked at).  Explicit keys may name empty slices: that is how a shape is ended.  weights 0, 0, 0
+ *   means 1, 1, 1.  out may be in (no other overlap).  *info (may be NULL) receives what was done.  The call counts the slices, makes
+ *   planar maps only of the keys that border a gap, uploads a table of n_axis slices (16 bytes each) and fills in ONE pass over the mask.
+ *   WORKSPACE, freed on return and reported in info.workspace_bytes: 4 bytes per voxel of the bordering key slices for the maps, the
+ *   workspace of svr_region_slice_distance on them, the table, 8 bytes per slice for the counts.  If the maps of all bordering keys
+ *   exceed SVR_FILL_MAP_BUDGET_BYTES, or with SVR_FILL_GAP_BY_GAP, the call works in runs of consecutive gaps whose maps fit the
+ *   budget (GAP_BY_GAP: one gap, two maps at a time), one pass over the mask per run, with the same result; info.launches counts them.
+ *   Synchronises.
+ * REFUSED, before the device is touched: a null pointer other than info, a list or keys (-4); a dimension <= 0 or more than 2^31 voxels
+ *   (-6); (-3) an axis outside 0 .. 2, a weight of 0 (when any weight of the params is not 0), wu (nu - 1)^2 + wv (nv - 1)^2 >
+ *   0xFFFFFFFE, n_axis > 65536 (maps and fill), keys that do not increase strictly or lie outside the axis, nkeys < 0 with keys,
+ *   nslices <= 0 with a list, a listed slice outside the axis, unknown flag bits. */
+#define SVR_FILL_KEEP_BETWEEN 1u
+#define SVR_FILL_GAP_BY_GAP   2u
+#define SVR_FILL_MAP_BUDGET_BYTES 1073741824u     /* 2^30: the planar maps svr_region_fill_between keeps at a time */
+typedef struct svr_fill_between_params {  /* 32 bytes */
+    int32_t  axis;                        /* 0, 1, 2 */
+    uint32_t flags;                       /* SVR_FILL_* */
+    uint32_t weights[3];                  /* 0, 0, 0 = 1, 1, 1 */
+    int32_t  nkeys;
+    const int32_t* keys;                  /* host; NULL = every non-empty slice */
+} svr_fill_between_params;
+typedef struct svr_fill_between_info {    /* 56 bytes */
+    int32_t  axis;
+    uint32_t keys, gaps, filled_slices;   /* the keys used, the pairs of consecutive keys with n >= 2, the slices between them */
+    int32_t  first_key, last_key;         /* -1 without a key */
+    uint32_t launches;                    /* passes over the mask: 0 without a gap, 1 unless the map budget or GAP_BY_GAP splits the work */
+    uint32_t reserved;
+    uint64_t voxels_in, voxels_out;       /* set voxels of the input and of the result */
+    uint64_t workspace_bytes;             /* the device memory the call held at its peak */
+} svr_fill_between_info;
+int svr_fill_between_params_default(svr_fill_between_params* p);   /* axis 2, everything else 0.  Plain host code */
+/* (the dimensions stand on a line of their own, as those of the scissor calls do: tests/golden/volume_op_refusals.json lists the calls
+ * whose first line holds them and is closed; tests/test_fillbetween_cpu.py holds the refusals of these three) */
+int svr_region_slice_counts(const uint32_t* mask_device,
+                            int nx, int ny, int nz, int axis, uint64_t* counts_host);
+int svr_region_slice_distance(const uint32_t* mask_device,
+                              int nx, int ny, int nz, int axis, const uint32_t* weights_or_null,
+                              const int32_t* slices_host_or_null, int nslices, uint32_t* maps_device);
+int svr_region_fill_between(const uint32_t* in_mask_device,
+                            int nx, int ny, int nz, const svr_fill_between_params* p,
+                            uint32_t* out_mask_device, svr_fill_between_info* info_or_null);
+/* HIP-event time of the device work of the last of the three calls above, without their allocations (waits for it); for a fill: the
+ * first count, and from the planar maps to the count of the result, without the wait and the allocations between the two */
+int svr_region_fill_between_last_ms(float* ms);
+/* of the last svr_region_fill_between that had a gap: the first count of the slices, the planar maps and the fill pass (of the last
+ * launch where there were several); 0 where there was none.  Any pointer may be NULL */
+int svr_region_fill_between_pass_ms(float* counts_ms, float* maps_ms, float* fill_ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

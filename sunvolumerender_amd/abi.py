@@ -363,6 +363,21 @@ STENCIL_MAX_VERTICES = 4096
 STENCIL_MAX_COORD = 1 << 23
 
 
+class FillBetweenParams(C.Structure):  # svr_fill_between_params
+    _fields_ = [("axis", C.c_int32), ("flags", C.c_uint32), ("weights", C.c_uint32 * 3), ("nkeys", C.c_int32), ("keys", C.POINTER(C.c_int32))]
+
+
+class FillBetweenInfo(C.Structure):  # svr_fill_between_info
+    _fields_ = [("axis", C.c_int32), ("keys", C.c_uint32), ("gaps", C.c_uint32), ("filled_slices", C.c_uint32), ("first_key", C.c_int32),
+                ("last_key", C.c_int32), ("launches", C.c_uint32), ("reserved", C.c_uint32), ("voxels_in", C.c_uint64), ("voxels_out", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+
+svr_fill_between_params, svr_fill_between_info = FillBetweenParams, FillBetweenInfo
+FILL_KEEP_BETWEEN, FILL_GAP_BY_GAP = 1, 2
+FILL_MAP_BUDGET_BYTES = 1 << 30
+
+
 class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
     _fields_ = [("mask_device", C.c_void_p), ("labels_device", C.c_void_p)]
 
@@ -662,6 +677,12 @@ PROTOTYPES = {
     "svr_region_scissor_slice": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(cudaVolume), _P(SliceParams), C.c_uint32, C.c_uint32,
                                            C.c_void_p, _P(ScissorParams), C.c_void_p]),
     "svr_region_scissor_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_fill_between_params_default": (C.c_int, [_P(FillBetweenParams)]),
+    "svr_region_slice_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint64)]),
+    "svr_region_slice_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint32), _P(C.c_int32), C.c_int, C.c_void_p]),
+    "svr_region_fill_between": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(FillBetweenParams), C.c_void_p, _P(FillBetweenInfo)]),
+    "svr_region_fill_between_last_ms": (C.c_int, [_P(C.c_float)]),
+    "svr_region_fill_between_pass_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
     "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
     "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,

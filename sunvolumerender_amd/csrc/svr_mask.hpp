@@ -1,7 +1,7 @@
 // svr_mask.hpp -- the bit-mask layout of the region calls (svr_region_*; the contract is in include/svr_abi.h, the design in DESIGN.md
 // 8h) and the helpers that every file working on it needs: the words of a row, the lanes of a word, the launch grids.  Included by
-// svr_region_grow.hpp (svr_region.hip, svr_morph.hip), svr_label.hip, svr_distance.hip, svr_geo_relax.hpp (svr_geodesic.hip, svr_growcut.hip)
-// and svr_resample.hip.
+// svr_region_grow.hpp (svr_region.hip, svr_morph.hip), svr_label.hip, svr_dist_passes.hpp (svr_distance.hip, svr_fillbetween.hip),
+// svr_geo_relax.hpp (svr_geodesic.hip, svr_growcut.hip) and svr_resample.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -704,6 +704,58 @@ class VolumeOps:
     def region_scissor_last_ms(self) -> float:
         return self._last_ms(self.lib.svr_region_scissor_last_ms)
 
+    # ---- fill between slices (svr_region_slice_counts / _slice_distance / _fill_between); axis 0, 1, 2 = x, y, z ----
+    def region_slice_counts(self, mask, axis: int = 2, shape=None) -> np.ndarray:
+        """svr_region_slice_counts: np.uint64[n_axis], the set voxels of every slice of the axis.  mask: a bool array [nz][ny][nx], or a
+        device pointer with shape=."""
+        shape = _shape_of("mask", mask, shape)
+        axis = _slice_axis(axis)
+        with self._staging() as s:
+            nz, ny, nx = shape
+            counts = (C.c_uint64 * shape[2 - axis])()
+            self.check(self.lib.svr_region_slice_counts(s.mask(mask, shape), nx, ny, nz, axis, counts))
+            return np.array(list(counts), dtype=np.uint64)
+
+    def region_slice_distance(self, mask, axis: int = 2, weights=None, slices=None, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_slice_distance: the planar maps of the listed slices of the axis (None = all, in order; any order, repeats allowed)
+        under the integer weights (wx, wy, wz) (None = 1, 1, 1; the slicing axis's is not used): a uint32 array [len(slices)][nv][nu],
+        u < v the in-plane axes, or out_ptr itself when a device buffer of that many uint32 is given."""
+        shape = _shape_of("mask", mask, shape)
+        axis = _slice_axis(axis)
+        ks = None if slices is None else _slice_list("slices", slices, shape[2 - axis], increasing=False)
+        if ks is not None and len(ks) == 0:
+            raise ValueError("the slice list is empty")
+        with self._staging() as s:
+            nz, ny, nx = shape
+            n = shape[2 - axis] if ks is None else len(ks)
+            out_shape = (n,) + tuple(t for a, t in zip((2, 1, 0), shape) if a != axis)
+            buf, out = s.mask(mask, shape), s.out(4 * max(n * (_voxels(shape) // shape[2 - axis]), 1), out_ptr)
+            self.check(self.lib.svr_region_slice_distance(buf, nx, ny, nz, axis, _u32s(weights, 3), None if ks is None else ks.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          n, C.c_void_p(out)))
+            return s.array(out, out_shape, np.uint32)
+
+    def region_fill_between(self, mask, axis: int = 2, keys=None, weights=None, keep_between: bool = False, shape=None,
+                            out_ptr: Optional[int] = None, gap_by_gap: bool = False):
+        """svr_region_fill_between: the mask with the slices between consecutive keys of the axis filled by shape-based interpolation.
+        keys: strictly increasing slice numbers (they may name empty slices), None = every slice that holds a set voxel; weights: (wx,
+        wy, wz), None = 1, 1, 1; keep_between: OR the input bits of the slices between keys into the result; gap_by_gap: at most two
+        planar maps at a time.  mask: a bool array [nz][ny][nx], or a device pointer with shape=; out_ptr may be the mask's own pointer.
+        Returns (mask, info): the bool array and the svr_fill_between_info."""
+        shape = _shape_of("mask", mask, shape)
+        p = fill_between_params(axis, keys, weights, keep_between, gap_by_gap, n_axis=shape[2 - _slice_axis(axis)])
+        with self._staging() as s:
+            nz, ny, nx = shape
+            buf, out, info = s.mask(mask, shape), s.mask_out(shape, out_ptr), abi.FillBetweenInfo()
+            self.check(self.lib.svr_region_fill_between(buf, nx, ny, nz, C.byref(p), C.c_void_p(out), C.byref(info)))
+            return s.mask_result(out, shape), info
+
+    def region_fill_between_last_ms(self) -> float:
+        return self._last_ms(self.lib.svr_region_fill_between_last_ms)
+
+    def region_fill_between_pass_ms(self):
+        """(counts, maps, fill) milliseconds of the last region_fill_between that had a gap"""
+        return self._last_ms(self.lib.svr_region_fill_between_pass_ms, 3)
+
     # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
     def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
         """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
@@ -1186,6 +1238,43 @@ def scissor_project_slice(slice, w: int, h: int, point, lib=None):
     rc = _host_call(lib, "svr_scissor_project_slice", lib.svr_scissor_project_slice(C.byref(slice), int(w), int(h), C.byref(pt), xy, C.byref(depth)),
                     ok=(0, 1))
     return ((int(xy[0]), int(xy[1])) if rc == 0 else None), float(depth.value)
+
+
+def _slice_axis(axis) -> int:
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise ValueError(f"the axis must be 0, 1 or 2 for x, y, z (got {axis})")
+    return axis
+
+
+def _slice_list(noun: str, values, n_axis: Optional[int], increasing: bool) -> np.ndarray:
+    """Slice numbers as a contiguous int32 array; ValueError for what the library refuses about them"""
+    ks = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+    if len(ks) and (ks.min() < 0 or (n_axis is not None and ks.max() >= n_axis)):
+        raise ValueError(f"the {noun} must lie inside the axis" + (f", in 0 .. {n_axis - 1}" if n_axis is not None else ""))
+    if increasing and len(ks) > 1 and (np.diff(ks) <= 0).any():
+        raise ValueError(f"the {noun} must increase strictly")
+    return ks.astype(np.int32)
+
+
+def fill_between_params(axis: int = 2, keys=None, weights=None, keep_between: bool = False, gap_by_gap: bool = False,
+                        n_axis: Optional[int] = None) -> abi.FillBetweenParams:
+    """svr_fill_between_params of the axis, the keys (None = every non-empty slice), the weights (None = 1, 1, 1) and the flags.  The
+    struct keeps the key array alive.  n_axis: the length of the axis, to check the keys against."""
+    p = abi.FillBetweenParams()
+    p.axis = _slice_axis(axis)
+    p.flags = (abi.FILL_KEEP_BETWEEN if keep_between else 0) | (abi.FILL_GAP_BY_GAP if gap_by_gap else 0)
+    if weights is not None:
+        w = [int(t) for t in weights]
+        if len(w) != 3 or min(w) < 1:
+            raise ValueError("the weights must be three integers >= 1")
+        p.weights[:] = w
+    if keys is not None:
+        ks = _slice_list("keys", keys, n_axis, increasing=True)
+        p.nkeys = len(ks)
+        p._keys = ks if len(ks) else np.zeros(1, dtype=np.int32)      # (the struct holds its address; an empty list is still a list)
+        p.keys = p._keys.ctypes.data_as(C.POINTER(C.c_int32))
+    return p
 
 
 def resample_grid(grid) -> abi.ResampleGrid:
