@@ -70,8 +70,16 @@
 // (Canvas::FillRegionBetweenSlices): what was drawn on every few slices with -scissor-slice ... fill, or thresholded in a volume that has
 // only every few slices, becomes solid.  It comes after the scissors -- so after the clean-up steps, -largest among them -- and before
 // -thickness, -mesh, -save-mask and the other outputs, and prints the keys, gaps and filled slices and the voxels before and after.
+// -smooth-region median|gauss SIZE [N] smooths the ragged boundary of the region N times (1 by default) without shifting it
+// (Canvas::SmoothRegion): `median` sets a voxel iff more than half of the window of edge SIZE around it is set, `gauss` keeps the upper
+// half of the region smoothed binomially with sigma SIZE; SIZE is in the units of the spacing.  It comes after -fill-between and before
+// the outputs.  -smooth-parts SIZE [N] smooths all parts at once by the mode of the window (Canvas::SmoothRegionParts): the classes of
+// -growcut, before -keep-class picks one, or after the clean-up steps (-split among them) the parts of the region under -conn; parts
+// stay disjoint and leave no gaps, and -save-parts and -overlay then get the smoothed parts unless a later step replaces the region.
+// -density SIZE draws the local volume fraction of the region in the window of edge SIZE in place of the masked volume
+// (Canvas::ShowRegionDensity).
 //
-//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-fill-between x|y|z] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
+//   render_mhd <volume.mhd> [-tf file.tf] [-env map.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-fill-between x|y|z] [-smooth-region median|gauss SIZE [N]] [-smooth-parts SIZE [N]] [-density SIZE] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -84,7 +92,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-fill-between x|y|z] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s volume.mhd [-tf f.tf] [-env m.hdr] [-frames N] [-depth D] [-size W H] [-raycast] [-mip | -mean | -iso LEVEL] [-slice x|y|z POS] [-slab THICKNESS mip|minip|mean] [-stack N] [-window LO HI] [-tfcolor] [-pick X Y [-hit opacity A | iso L | max]] [-crop X0 Y0 Z0 X1 Y1 Z1 | -resample MM [nearest|linear|area|auto]]... [-median E N | -smooth SIGMA]... [-show-filtered] [-save-volume F] [-seed X Y CLASS [RADIUS]]... [-growcut [GAIN SHIFT]] [-keep-class C] [-auto-window PLO PHI] [-grow X Y LO HI | -threshold LO HI | -otsu CLASSES CLASS [SHIFT] [-conn 6|18|26] [-detach R | -fillholes | -open R | -close R | -dilate R | -erode R | -largest K | -minsize N | -ball-dilate L | -ball-erode L | -ball-open L | -ball-close L | -split L]... [-element 6|18|26] [-thickness] [-keep | -remove] [-overlay FILL EDGE [-overlay-parts CONN]] [-mesh FILE.stl|.ply [-relax N]] [-save-mask F] [-save-parts F] [-scissor inside|outside X0 Y0 X1 Y1 [X2 Y2 ...]]... [-scissor-slice x|y|z POS inside|outside|fill T X0 Y0 X1 Y1 [X2 Y2 ...]]... [-fill-between x|y|z] [-smooth-region median|gauss SIZE [N]] [-smooth-parts SIZE [N]] [-density SIZE] [-save-crop VOL MASK MARGIN] [-compare-mask F]] [-mesh-iso RAW FILE.stl|.ply] [-denoise-preview N] [-noise T] [-adaptive T] [-o out.tga]\n", argv[0]); return 2; }
     std::string volume = argv[1], tfFile, envFile, out = "frame.tga";
     int frames = 16, depth = 1, W = 640, H = 640;                  // common.h:8-9
     int denoisePreview = 0;
@@ -122,6 +130,24 @@ int main(int argc, char** argv)
     struct ScissorStep { int axis; float pos; int op; float thickness; std::vector<double> polygon; };   // -scissor (axis -1) / -scissor-slice, in order
     std::vector<ScissorStep> scissorSteps;
     int fillBetweenAxis = -1;                                       // -fill-between x|y|z
+    int smoothRegionOp = 0, smoothRegionN = 1, smoothPartsN = 1;    // -smooth-region median|gauss SIZE [N]; -smooth-parts SIZE [N]; -density SIZE
+    double smoothRegionSize = 0.0, smoothPartsSize = -1.0, densitySize = -1.0;
+    bool partsSmoothed = false;                                     // the canvas's label map is what -smooth-parts left
+    const auto sizeArg = [](const char* a, double* v) {             // a length >= 0
+        char* end = nullptr;
+        *v = strtod(a, &end);
+        return end != a && *end == '\0' && *v >= 0.0 && std::isfinite(*v);
+    };
+    const auto timesArg = [&](int* i, int* n) {                     // the optional [N] after a size: 1 .. 16
+        if (*i + 1 >= argc || argv[*i + 1][0] == '-') return true;
+        char* end = nullptr;
+        const long v = strtol(argv[*i + 1], &end, 10);
+        if (*end != '\0') return true;                              // (not a number: the next argument is something else)
+        if (v < 1 || v > SVR_REGION_SMOOTH_MAX_ITERATIONS) return false;
+        *n = (int)v;
+        ++*i;
+        return true;
+    };
     std::string saveVolumeFile, saveMaskFile, savePartsFile, saveCropVolume, saveCropMask;   // -save-volume / -save-mask / -save-parts F, -save-crop VOL MASK MARGIN
     int saveCropMargin = 0;
     const auto meshName = [](const char* f) {                       // an export writes .stl or .ply
@@ -464,6 +490,22 @@ int main(int argc, char** argv)
             if (fillBetweenAxis < 0) { fprintf(stderr, "-fill-between needs an axis x, y or z\n"); return 2; }
             ++i;
         }
+        else if (!strcmp(argv[i], "-smooth-region")) {
+            const char* a = i + 1 < argc ? argv[i + 1] : "";
+            smoothRegionOp = !strcmp(a, "median") ? SVR_SMOOTH_MAJORITY : !strcmp(a, "gauss") ? SVR_SMOOTH_BINOMIAL : 0;
+            if (!smoothRegionOp || i + 2 >= argc || !sizeArg(argv[i + 2], &smoothRegionSize)) { fprintf(stderr, "-smooth-region needs median or gauss and a SIZE >= 0 in the units of the spacing\n"); return 2; }
+            i += 2;
+            if (!timesArg(&i, &smoothRegionN)) { fprintf(stderr, "-smooth-region: N must lie in 1 .. %d\n", SVR_REGION_SMOOTH_MAX_ITERATIONS); return 2; }
+        }
+        else if (!strcmp(argv[i], "-smooth-parts")) {
+            if (i + 1 >= argc || !sizeArg(argv[i + 1], &smoothPartsSize)) { fprintf(stderr, "-smooth-parts needs a SIZE >= 0 in the units of the spacing\n"); return 2; }
+            ++i;
+            if (!timesArg(&i, &smoothPartsN)) { fprintf(stderr, "-smooth-parts: N must lie in 1 .. %d\n", SVR_REGION_SMOOTH_MAX_ITERATIONS); return 2; }
+        }
+        else if (!strcmp(argv[i], "-density")) {
+            if (i + 1 >= argc || !sizeArg(argv[i + 1], &densitySize)) { fprintf(stderr, "-density needs a SIZE >= 0 in the units of the spacing\n"); return 2; }
+            ++i;
+        }
         else if (!strcmp(argv[i], "-save-crop")) {
             char* end = nullptr;
             const long v = i + 3 < argc ? strtol(argv[i + 3], &end, 10) : -1;
@@ -505,6 +547,7 @@ int main(int argc, char** argv)
     }
     if (!scissorSteps.empty() && !anyRegion) { fprintf(stderr, "-scissor and -scissor-slice cut a region: they need -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (fillBetweenAxis >= 0 && !anyRegion) { fprintf(stderr, "-fill-between fills a region: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
+    if ((smoothRegionOp || smoothPartsSize >= 0.0 || densitySize >= 0.0) && !anyRegion) { fprintf(stderr, "-smooth-region, -smooth-parts and -density work on a region: they need -grow X Y LO HI, -threshold LO HI or -growcut\n"); return 2; }
     if (!compareMaskFile.empty() && !anyRegion) { fprintf(stderr, "-compare-mask compares a region with the file: it needs -grow X Y LO HI or -threshold LO HI\n"); return 2; }
     if (svr_init(0)) return 1;
     {
@@ -672,6 +715,18 @@ int main(int argc, char** argv)
                     printf("median: raw %u\n", median);
                 }
             }
+            const auto smoothParts = [&](const char* what) {          // -smooth-parts on the canvas's label map
+                uint64_t changed = 0u;
+                if (canvas.SmoothRegionParts(smoothPartsSize, (uint32_t)smoothPartsN, &changed) != 0) {
+                    fprintf(stderr, "-smooth-parts: %s\n", svr_last_error_code() ? svr_last_error() : "more than 255 parts, or none");
+                    return false;
+                }
+                float ms = 0.f;
+                svr_region_smooth_last_ms(&ms);
+                printf("smooth-parts %g x %d (%s): %llu voxels changed their part; %.3f ms\n", smoothPartsSize, smoothPartsN, what, (unsigned long long)changed, ms);
+                partsSmoothed = true;
+                return true;
+            };
             if (growcut) {
                 // strokes of classes on picked voxels, grown over the region made above or, without one, over the whole volume
                 const double brush = 2.0 * std::fmin(sp[0], std::fmin(sp[1], sp[2]));
@@ -691,7 +746,9 @@ int main(int argc, char** argv)
                 svr_region_growcut_last_ms(&ms);
                 printf("growcut gain %d shift %d, %zu strokes%s: %u classes own voxels; %.2f ms%s\n", growGain, growShift, seeds.size(),
                        grow || threshold ? " inside the region" : "", found, ms, rc ? "; COSTS SATURATED: raise SHIFT or lower GAIN" : "");
+                if (smoothPartsSize >= 0.0 && !smoothParts("the classes of -growcut")) return 1;
                 if (keepClass) {
+                    partsSmoothed = false;
                     if (canvas.KeepSeedClass((uint32_t)keepClass, &st) != 0 || svr_region_measure(&st, sp, &m) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                     if (st.status == SVR_REGION_STATUS_EMPTY)
                         printf("keep-class %d: the region is empty\n", keepClass);
@@ -773,6 +830,14 @@ int main(int argc, char** argv)
                            done.c_str(), cleanElement, (unsigned long long)st.voxels, m.volume, m.mean, m.stddev, st.vmin, st.vmax, st.bbox_min[0], st.bbox_min[1],
                            st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area);
             }
+            if (smoothPartsSize >= 0.0 && !growcut) {                   // the parts of the cleaned region, all at once
+                uint32_t parts = 0u;
+                if (canvas.LabelRegion(growConn, &parts) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                char what[64];
+                snprintf(what, sizeof what, "%u parts conn %d", parts, growConn);
+                if (!smoothParts(what)) return 1;
+            }
+            if (!scissorSteps.empty() || fillBetweenAxis >= 0 || smoothRegionOp || (growcut && !cleanSteps.empty())) partsSmoothed = false;   // (those replace the region)
             for (const ScissorStep& sc : scissorSteps) {                // cut or paint with a closed line on the picture, or on a slice picture
                 int rc;
                 if (sc.axis < 0) rc = canvas.ScissorRegion(sc.polygon, sc.op, &st);
@@ -810,6 +875,21 @@ int main(int argc, char** argv)
                     printf(", volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %.3f ms\n", m.volume, m.mean, m.stddev, st.vmin, st.vmax,
                            st.bbox_min[0], st.bbox_min[1], st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, ms);
             }
+            if (smoothRegionOp) {                                       // the ragged boundary
+                const uint64_t before = st.voxels;
+                int rc = canvas.SmoothRegion(smoothRegionOp, smoothRegionSize, (uint32_t)smoothRegionN, &st);
+                if (rc == 0) rc = svr_region_measure(&st, sp, &m);
+                if (rc != 0) { fprintf(stderr, "-smooth-region: %s\n", svr_last_error()); return 1; }
+                float ms = 0.f;
+                svr_region_smooth_last_ms(&ms);
+                printf("smooth-region %s %g x %d: %llu -> %llu voxels", smoothRegionOp == SVR_SMOOTH_MAJORITY ? "median" : "gauss", smoothRegionSize, smoothRegionN,
+                       (unsigned long long)before, (unsigned long long)st.voxels);
+                if (st.status == SVR_REGION_STATUS_EMPTY)
+                    printf("; the region is empty; %.3f ms\n", ms);
+                else
+                    printf(", volume %g, mean %.1f +- %.1f (raw %u..%u), box %d %d %d .. %d %d %d, surface %g; %.3f ms\n", m.volume, m.mean, m.stddev, st.vmin, st.vmax,
+                           st.bbox_min[0], st.bbox_min[1], st.bbox_min[2], st.bbox_max[0], st.bbox_max[1], st.bbox_max[2], m.surface_area, ms);
+            }
             if (thickness) {
                 double radius = 0.0;
                 int32_t at[3] = {-1, -1, -1};
@@ -838,9 +918,11 @@ int main(int argc, char** argv)
             if (!savePartsFile.empty()) {
                 const auto t0 = std::chrono::steady_clock::now();
                 uint32_t parts = 0u;
+                const bool smoothed = canvas.RegionLabels() && partsSmoothed;                                // what -smooth-parts left is still the region's
                 const bool classes = canvas.RegionLabels() && growcut && !keepClass && cleanSteps.empty();   // the class map of -growcut is still the region's
-                if ((!classes && canvas.LabelRegion(growConn, &parts) != 0) || canvas.SaveRegionParts(savePartsFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+                if ((!classes && !smoothed && canvas.LabelRegion(growConn, &parts) != 0) || canvas.SaveRegionParts(savePartsFile) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                 if (classes) printf("save-parts: the classes of -growcut\n");
+                else if (smoothed) printf("save-parts: the parts of -smooth-parts\n");
                 else printf("save-parts conn %d: %u parts\n", growConn, parts);
                 saved("save-parts", savePartsFile, canvas.volumeReader->dim, t0);
             }
@@ -854,13 +936,14 @@ int main(int argc, char** argv)
             }
             if (overlay) {
                 // the volume is drawn as it was loaded, and the region is laid over the picture
-                if (overlayParts) {
+                if (densitySize >= 0.0 && canvas.ShowRegionDensity(densitySize) != 0) { fprintf(stderr, "-density: %s\n", svr_last_error()); return 1; }
+                if (overlayParts && !(canvas.RegionLabels() && partsSmoothed)) {
                     uint32_t parts = 0u;
                     if (canvas.LabelRegion(overlayParts, &parts) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
                     printf("overlay parts conn %d: %u parts\n", overlayParts, parts);
                 }
             }
-            else if (canvas.ShowRegion(growMode, 0u) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
+            else if ((densitySize >= 0.0 ? canvas.ShowRegionDensity(densitySize) : canvas.ShowRegion(growMode, 0u)) != 0) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         }
         if (!meshIsoFile.empty() && (canvas.ExtractIsoSurface((uint32_t)meshIsoLevel, 0u) != 0 || !exportSurface(meshIsoFile))) { fprintf(stderr, "%s\n", svr_last_error()); return 1; }
         svr_overlay_style overlayStyle;

@@ -915,6 +915,7 @@ public:
         if (rc != 0) return rc;
         haveLabels = true;
         labelClasses = count;
+        labelCount = count;
         if (classes_found) {
             *classes_found = 0u;
             for (const svr_region_component& c : table) *classes_found += c.voxels ? 1u : 0u;
@@ -951,6 +952,7 @@ public:
         const int rc = svr_region_label(regionMask, dim[0], dim[1], dim[2], connectivity, regionLabels, count);
         haveLabels = rc == 0;
         labelClasses = 0u;                             // (parts, not the classes of GrowFromSeeds)
+        labelCount = rc == 0 ? *count : 0u;
         return rc;
     }
     // OverlayRegionOnSlice: tints the slice image in img -- what RENDER_MODE_SLICE drew for `params` -- by the region: the labels when
@@ -1098,6 +1100,69 @@ public:
         if (int rc = RegionDistanceUnits(p.weights, &unit)) return rc;
         const int* dim = volumeReader->dim;
         return ReplaceRegion(svr_region_fill_between(regionMask, dim[0], dim[1], dim[2], &p, regionWork, info), stats);
+    }
+
+    // extension: smoothing the region and its parts (svr_region_smooth / _label_smooth / _box_density; include/svr_abi.h, "smoothing
+    // region masks and label maps").  Lengths are in the units of the volume's spacing, the same on every axis, so an axis with a coarse
+    // spacing gets a smaller radius.
+    // SmoothRegion: op SVR_SMOOTH_MAJORITY -- `size` is the edge of the window, the radii those of svr_region_smooth_radii -- or
+    // SVR_SMOOTH_BINOMIAL -- `size` is the sigma, the radii those of svr_volume_smooth_radii -- applied `iterations` times.  Replaces the
+    // region like MorphRegion
+    int SmoothRegion(int op, double size, uint32_t iterations = 1, svr_region_stats* stats = nullptr)
+    {
+        if (!WorkMask()) return -4;
+        if (op != SVR_SMOOTH_MAJORITY && op != SVR_SMOOTH_BINOMIAL) return -3;
+        const int* dim = volumeReader->dim;
+        const int32_t dims[3] = {dim[0], dim[1], dim[2]};
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        uint32_t radii[3];
+        if (int rc = op == SVR_SMOOTH_MAJORITY ? svr_region_smooth_radii(sp, size, radii, nullptr) : svr_volume_smooth_radii(sp, size, radii, nullptr)) return rc;
+        int rc = svr_region_smooth(regionMask, dims, op, radii, iterations, regionWork, nullptr);
+        if (rc == 0) rc = svr_device_synchronize();
+        return ReplaceRegion(rc, stats);
+    }
+    // SmoothRegionParts: the mode filter over a window of edge `size` on the label map the canvas holds -- the parts of LabelRegion
+    // (after SplitRegion too) or the classes of GrowFromSeeds, at most SVR_LABEL_SMOOTH_MAX_COUNT of them (-3 beyond) -- all parts at
+    // once, so that they stay disjoint and leave no gaps.  The region becomes every voxel that still has a label; *changed (may be null)
+    // = the voxels whose label changed
+    int SmoothRegionParts(double size, uint32_t iterations = 1, uint64_t* changed = nullptr)
+    {
+        if (!ready || !SegVoxels() || !haveRegion || !haveLabels) return -4;
+        if (labelCount == 0u || labelCount > SVR_LABEL_SMOOTH_MAX_COUNT) return -3;
+        const int* dim = volumeReader->dim;
+        const int32_t dims[3] = {dim[0], dim[1], dim[2]};
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        uint32_t radii[3];
+        if (int rc = svr_region_smooth_radii(sp, size, radii, nullptr)) return rc;
+        const std::vector<uint8_t> keep(labelCount + 1u, 1);
+        uint32_t* smoothed = (uint32_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint32_t));
+        uint8_t* keep_device = (uint8_t*)svr_device_malloc(keep.size());
+        int rc = smoothed && keep_device ? 0 : -4;
+        if (rc == 0) rc = svr_region_label_smooth(regionLabels, dims, labelCount, radii, iterations, smoothed, changed);
+        if (rc == 0) rc = svr_memcpy_h2d(keep_device, keep.data(), keep.size());
+        if (rc == 0) rc = svr_region_select(smoothed, dim[0], dim[1], dim[2], labelCount, keep_device, regionMask);
+        if (rc == 0) rc = svr_device_synchronize();
+        if (rc == 0) std::swap(regionLabels, smoothed);
+        if (smoothed) svr_device_free(smoothed);
+        if (keep_device) svr_device_free(keep_device);
+        return rc;
+    }
+    // ShowRegionDensity: every renderer now draws the local volume fraction of the region -- the share of set voxels in the window of
+    // edge `size` around every voxel, 65535 = all of them (BV/TV of a bone mask) -- until ShowAll or the next volume
+    int ShowRegionDensity(double size)
+    {
+        if (!ready || !SegVoxels() || !haveRegion) return -4;
+        const int* dim = volumeReader->dim;
+        const int32_t dims[3] = {dim[0], dim[1], dim[2]};
+        const double sp[3] = {deviceVolume.spacing.x, deviceVolume.spacing.y, deviceVolume.spacing.z};
+        uint32_t radii[3];
+        if (int rc = svr_region_smooth_radii(sp, size, radii, nullptr)) return rc;
+        uint16_t* shown = (uint16_t*)svr_device_malloc((size_t)dim[0] * dim[1] * dim[2] * sizeof(uint16_t));
+        if (!shown) return -4;
+        int rc = svr_region_box_density(regionMask, dims, radii, shown);
+        if (rc == 0) rc = ShowVoxels(shown);
+        svr_device_free(shown);
+        return rc;
     }
 
     // extension: how far the region is from another mask of the same dimensions (svr_region_compare / _compare_measure; include/svr_abi.h,
@@ -1354,6 +1419,7 @@ private:
         if (regionLabels) svr_device_free(regionLabels);
         regionTex = 0; regionMask = nullptr; regionWork = nullptr; regionLabels = nullptr; haveRegion = false; haveSeed = false; haveLabels = false;
         labelClasses = 0u;
+        labelCount = 0u;
         ClearSeeds();                                  // (the strokes were voxels of the volume that goes)
     }
     // a device u16 volume of the loaded dimensions becomes the texture every renderer draws (ShowRegion, ShowRegionDistance)
@@ -1478,6 +1544,7 @@ private:
     uint32_t* regionLabels = nullptr;              // LabelRegion's parts of the region (device, uint32 per voxel); freed with regionMask
     bool haveLabels = false;                       // false once anything replaces the region
     uint32_t labelClasses = 0u;                    // > 0: the labels are the classes 1 .. labelClasses of GrowFromSeeds
+    uint32_t labelCount = 0u;                      // the largest label of the current label map (parts or classes): SmoothRegionParts
     uint32_t* seedMarkers = nullptr;               // AddSeed's marker map (device, uint32 per voxel): 0 = no stroke, else the class
     uint32_t seedMaxClass = 0u;                    // the largest class painted on it
     int32_t regionSeed[3] = {0, 0, 0};             // GrowRegion's seed voxel and connectivity, for DetachRegion

@@ -1574,6 +1574,64 @@ int svr_region_fill_between_last_ms(float* ms);
  * launch where there were several); 0 where there was none.  Any pointer may be NULL */
 int svr_region_fill_between_pass_ms(float* counts_ms, float* maps_ms, float* fill_ms);
 
+/* ---- smoothing region masks and label maps: box count, majority, binomial, mode (csrc/svr_smooth.hip) ----
+ * The ragged one-voxel boundary of a thresholded or grown mask is smoothed without shifting it: OPEN and CLOSE of svr_region_morph only
+ * remove or only add; the filters here treat a region and its complement alike.  Masks and label maps are device pointers in the
+ * layouts of the region section; a row's padding bits are ignored on input, whatever they hold, and are 0 on output.  Integers only:
+ * every result is defined bit for bit.  The calls run on the library's stream and touch no scene, option or accumulator.
+ * RADII: radii_xyz is a HOST array of three uint32 (x, y, z), each 0 .. SVR_REGION_SMOOTH_MAX_RADIUS.  The WINDOW of voxel (x, y, z) is
+ *   every (x + dx, y + dy, z + dz) with |dx| <= rx, |dy| <= ry, |dz| <= rz; an index outside the volume is CLAMPED per axis (numpy's pad
+ *   mode `edge`, scipy's mode='nearest', the border rule of svr_volume_rank), so a window always holds exactly N = (2rx+1)(2ry+1)(2rz+1)
+ *   values (svr_region_box_size; 0 for a NULL pointer or a radius above the cap).  Radius 0 makes the window one voxel thick on that
+ *   axis; (0, 0, 0) copies (and clears the padding).
+ * COUNT (svr_region_box_count): out[z][y][x] = the set voxels in the window, a u16 volume [nz][ny][nx] -- ready for
+ *   svr_create_volume_texture, svr_region_threshold and svr_volume_histogram: a local volume fraction (BV/TV of a bone mask).  It equals
+ *   scipy.ndimage.correlate(mask.astype(int32), ones((2rz+1, 2ry+1, 2rx+1)), mode='nearest').  With rx = ry = rz = r, count >= 1 is
+ *   svr_region_morph(DILATE, 26, r) and count == N is svr_region_morph(ERODE, 26, r): a clamped index always lies inside the window, so
+ *   the replicated border agrees with "nothing enters from outside" and with its dual.  One launch, no workspace, asynchronous.
+ *   svr_region_box_density (an addition for display) is the same call with out = floor(65535 count / N): the local volume fraction
+ *   on the full range of a u16 volume, whatever the radii.
+ * MAJORITY (svr_region_smooth, SVR_SMOOTH_MAJORITY): out is set iff 2 count > N.  N is odd, so there is no tie: the median of the binary
+ *   window, scipy.ndimage.median_filter(mask.astype(uint8), size=(2rz+1, 2ry+1, 2rx+1), mode='nearest').  It is self-dual (smoothing
+ *   the complement gives the complement); the full volume, the empty volume and every axis-aligned half-space are fixed points.
+ * BINOMIAL (svr_region_smooth, SVR_SMOOTH_BINOMIAL): out = { v : S(v) >= 32768 }, S = svr_volume_smooth(E, radii), E the u16 volume
+ *   with 65535 on the set voxels and 0 elsewhere: the binomial passes of that call with their single rounding per axis.  Radii for a
+ *   sigma come from svr_volume_smooth_radii.  NOT exactly self-dual: halves round up and 32768 is above the middle of 0 .. 65535.
+ *   The call runs svr_volume_smooth itself, once per iteration: svr_volume_filter_last_ms afterwards reports the last of those runs.
+ * MODE (svr_region_label_smooth): labels is a uint32 map [nz][ny][nx] with values 0 .. count, count <= SVR_LABEL_SMOOTH_MAX_COUNT; a
+ *   value above count is read as 0, as svr_region_select drops it.  Label 0, the background, takes part like any other.  With c_l(v)
+ *   the window voxels of label l, out(v) is the centre's own label if it attains max_l c_l(v), else the SMALLEST label that attains it.
+ *   With count == 1 this is MAJORITY of the mask labels == 1.  Parts stay disjoint and leave no gaps: that is joint smoothing.
+ * ITERATIONS: 1 .. SVR_REGION_SMOOTH_MAX_ITERATIONS; the op is applied that many times to its own output.
+ * changed_or_null: when not NULL it receives the voxels at which the final output differs from the input (for labels: from the input
+ *   as it is read, a value above count being 0).
+ * svr_region_smooth_radii (plain host code): with q = size / spacing[a], radii[a] = max(0, llround((q - 1) / 2)), the odd window
+ *   nearest to the size (q = 1, 3, 4, 5 give 0, 1, 2, 2); size_out[a] (may be NULL) = (2 radii[a] + 1) spacing[a].  Refused (-3) with
+ *   nothing written: a spacing that is not positive and finite, a size that is negative or not finite, a radius above the cap.
+ * WORKSPACE AND SYNCHRONISATION: svr_region_box_count and a MAJORITY of one iteration without `changed` are one launch: nothing is
+ *   allocated and the call is asynchronous.  MAJORITY with more iterations holds one temporary mask; BINOMIAL holds two u16 volumes (E
+ *   and S) and, with more than one radius above 0, the temporary of svr_volume_smooth; MODE holds bits(count) <= 8 bit planes of the
+ *   labels in mask layout and, with more than one iteration, one temporary label map; `changed` adds 8 bytes.  A call that allocated
+ *   or that reports `changed` synchronises the stream before it returns.
+ * REFUSED, before the device is touched and with nothing written: a null pointer other than changed_or_null (-4); a dimension <= 0 or
+ *   more than 2^31 voxels (-6); (-3) an unknown op, a radius above 8, iterations of 0 or above 16, count of 0 or above 255, an out that
+ *   overlaps an input. */
+#define SVR_SMOOTH_MAJORITY 1
+#define SVR_SMOOTH_BINOMIAL 2
+#define SVR_REGION_SMOOTH_MAX_RADIUS     8     /* = SVR_SMOOTH_MAX_RADIUS; N <= 17^3 = 4913 fits 13 bits and a u16 */
+#define SVR_REGION_SMOOTH_MAX_ITERATIONS 16
+#define SVR_LABEL_SMOOTH_MAX_COUNT       255
+uint32_t svr_region_box_size(const uint32_t radii_xyz[3]);             /* N; 0 for a radius above the cap.  Plain host code */
+int svr_region_smooth_radii(const double spacing[3], double size, uint32_t radii[3], double size_out[3]);   /* plain host code */
+int svr_region_box_count(const uint32_t* mask_device, const int32_t dims[3], const uint32_t* radii_xyz, uint16_t* out_u16_device);
+int svr_region_box_density(const uint32_t* mask_device, const int32_t dims[3], const uint32_t* radii_xyz, uint16_t* out_u16_device);
+int svr_region_smooth(const uint32_t* in_mask_device, const int32_t dims[3], int op, const uint32_t* radii_xyz, uint32_t iterations,
+                      uint32_t* out_mask_device, uint64_t* changed_or_null);
+int svr_region_label_smooth(const uint32_t* labels_device, const int32_t dims[3], uint32_t count, const uint32_t* radii_xyz,
+                            uint32_t iterations, uint32_t* out_labels_device, uint64_t* changed_or_null);
+/* HIP-event time of the device work of the last of the four device calls above, without their allocations (waits for it) */
+int svr_region_smooth_last_ms(float* ms);
+
 int svr_get_counters(svr_counters* out);              /* synchronises the launch stream */
 int svr_reset_counters(void);
 

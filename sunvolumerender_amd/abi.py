@@ -376,6 +376,8 @@ class FillBetweenInfo(C.Structure):  # svr_fill_between_info
 svr_fill_between_params, svr_fill_between_info = FillBetweenParams, FillBetweenInfo
 FILL_KEEP_BETWEEN, FILL_GAP_BY_GAP = 1, 2
 FILL_MAP_BUDGET_BYTES = 1 << 30
+SMOOTH_MAJORITY, SMOOTH_BINOMIAL = 1, 2
+REGION_SMOOTH_MAX_RADIUS, REGION_SMOOTH_MAX_ITERATIONS, LABEL_SMOOTH_MAX_COUNT = 8, 16, 255
 
 
 class OverlaySource(C.Structure):  # svr_overlay_source: exactly one device pointer is set
@@ -683,6 +685,13 @@ PROTOTYPES = {
     "svr_region_fill_between": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(FillBetweenParams), C.c_void_p, _P(FillBetweenInfo)]),
     "svr_region_fill_between_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_region_fill_between_pass_ms": (C.c_int, [_P(C.c_float), _P(C.c_float), _P(C.c_float)]),
+    "svr_region_box_size": (C.c_uint32, [_P(C.c_uint32)]),
+    "svr_region_smooth_radii": (C.c_int, [_P(C.c_double), C.c_double, _P(C.c_uint32), _P(C.c_double)]),
+    "svr_region_box_count": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_uint32), C.c_void_p]),
+    "svr_region_box_density": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_uint32), C.c_void_p]),
+    "svr_region_smooth": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int, _P(C.c_uint32), C.c_uint32, C.c_void_p, _P(C.c_uint64)]),
+    "svr_region_label_smooth": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_uint32, _P(C.c_uint32), C.c_uint32, C.c_void_p, _P(C.c_uint64)]),
+    "svr_region_smooth_last_ms": (C.c_int, [_P(C.c_float)]),
     "svr_overlay_style_default": (C.c_int, [_P(OverlayStyle)]),
     "svr_overlay_palette_default": (C.c_int, [_P(C.c_uint32), C.c_uint32]),
     "svr_slice_ids": (C.c_int, [C.c_void_p, _P(cudaVolume), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _P(SliceParams), C.c_uint32,

@@ -189,6 +189,7 @@ from .volume_ops import (COMPONENT_DTYPE, LABEL_SCAN_BLOCK, VolumeOps as _Volume
                          histogram_quantile, mesh_positions, overlap_match, region_label_scan_levels, region_mask_pack,
                          region_mask_unpack, region_mask_words, region_seed_from_world,
                          scissor_params, scissor_project_camera, scissor_project_slice, stencil_rect, fill_between_params,
+                         region_box_size, region_smooth_radii,
                          resample_grid, resample_grid_box, resample_grid_dims, resample_grid_place, resample_grid_spacing, smooth_radii)
 
 

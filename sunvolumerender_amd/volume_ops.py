@@ -756,6 +756,44 @@ class VolumeOps:
         """(counts, maps, fill) milliseconds of the last region_fill_between that had a gap"""
         return self._last_ms(self.lib.svr_region_fill_between_pass_ms, 3)
 
+    # ---- smoothing masks and label maps (svr_region_box_count / _smooth / _label_smooth); radii = (rx, ry, rz), each 0 .. 8 ----
+    def region_box_count(self, mask, radii, shape=None, out_ptr: Optional[int] = None, density: bool = False):
+        """svr_region_box_count: the set voxels in the (2rx+1) x (2ry+1) x (2rz+1) window around every voxel, the border replicated: a
+        u16 array [nz][ny][nx], or out_ptr itself when a device buffer of nx * ny * nz u16 is given.  mask: a bool array [nz][ny][nx], or
+        a device pointer with shape=.  density: svr_region_box_density, floor(65535 count / N) instead of the count."""
+        shape = _shape_of("mask", mask, shape)
+        r = _radii(radii)
+        with self._staging() as s:
+            buf, out = s.mask(mask, shape), s.out(2 * max(_voxels(shape), 1), out_ptr)
+            call = self.lib.svr_region_box_density if density else self.lib.svr_region_box_count
+            self.check(call(buf, _dims(shape), r, C.c_void_p(out)))
+            return s.array(out, shape, np.uint16)
+
+    def region_smooth(self, mask, op: int, radii, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_smooth: SMOOTH_MAJORITY (set iff more than half of the window is set: the binary median) or SMOOTH_BINOMIAL (the
+        upper half of volume_smooth of the mask at 65535) applied `iterations` times.  Returns (mask, changed): the bool array and the
+        voxels that differ from the input.  out_ptr: a device buffer of region_mask_words(shape) uint32 that is not the input."""
+        shape = _shape_of("mask", mask, shape)
+        r = _radii(radii)
+        with self._staging() as s:
+            buf, out, changed = s.mask(mask, shape), s.mask_out(shape, out_ptr), C.c_uint64(0)
+            self.check(self.lib.svr_region_smooth(buf, _dims(shape), int(op), r, int(iterations), C.c_void_p(out), C.byref(changed)))
+            return s.mask_result(out, shape), int(changed.value)
+
+    def region_label_smooth(self, labels, count: int, radii, iterations: int = 1, shape=None, out_ptr: Optional[int] = None):
+        """svr_region_label_smooth: the mode filter of a label map with values 0 .. count (count <= 255; larger values read as 0): every
+        voxel takes the most frequent label of its window, its own where that is among the most frequent, else the smallest of them.
+        Returns (labels, changed): a uint32 array [nz][ny][nx], or out_ptr itself when a device buffer of 4 nx ny nz bytes is given."""
+        r = _radii(radii)
+        with self._staging() as s:
+            lbuf, shape = s.map(labels, shape)
+            out, changed = s.out(4 * max(_voxels(shape), 1), out_ptr), C.c_uint64(0)
+            self.check(self.lib.svr_region_label_smooth(lbuf, _dims(shape), int(count), r, int(iterations), C.c_void_p(out), C.byref(changed)))
+            return s.array(out, shape, np.uint32), int(changed.value)
+
+    def region_smooth_last_ms(self) -> float:
+        return self._last_ms(self.lib.svr_region_smooth_last_ms)
+
     # ---- overlays: region masks and label maps on slices and 3D views (svr_slice_ids, svr_hit_ids, svr_overlay_ids, svr_overlay_slice) ----
     def overlay_style(self, fill_alpha: Optional[int] = None, edge_alpha: Optional[int] = None, palette=None) -> abi.OverlayStyle:
         """The library's default svr_overlay_style (fill 96, edge 255, built-in palette) with the named members replaced.  palette: up
@@ -1238,6 +1276,31 @@ def scissor_project_slice(slice, w: int, h: int, point, lib=None):
     rc = _host_call(lib, "svr_scissor_project_slice", lib.svr_scissor_project_slice(C.byref(slice), int(w), int(h), C.byref(pt), xy, C.byref(depth)),
                     ok=(0, 1))
     return ((int(xy[0]), int(xy[1])) if rc == 0 else None), float(depth.value)
+
+
+def _radii(radii):
+    r = [int(t) for t in radii]
+    if len(r) != 3 or min(r) < 0:
+        raise ValueError("the radii must be three integers >= 0 (rx, ry, rz)")
+    return (C.c_uint32 * 3)(*r)
+
+
+def region_box_size(radii, lib=None) -> int:
+    """svr_region_box_size: N = (2rx+1)(2ry+1)(2rz+1), the voxels of a smoothing window; 0 for a radius above 8.  Host code of the
+    library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    return int(lib.svr_region_box_size(_radii(radii)))
+
+
+def region_smooth_radii(spacing, size, lib=None):
+    """svr_region_smooth_radii: ((rx, ry, rz), (sx, sy, sz)) for a spacing and a window size in the spacing's units: the radii of the odd
+    window nearest to the size, max(0, llround((size / spacing[a] - 1) / 2)), and the size each one spans, (2 r + 1) spacing[a].  Host
+    code of the library: no device is needed."""
+    lib = lib if lib is not None else abi.load()
+    sp = (C.c_double * 3)(*[float(t) for t in spacing])
+    r, so = (C.c_uint32 * 3)(), (C.c_double * 3)()
+    _host_call(lib, "svr_region_smooth_radii", lib.svr_region_smooth_radii(sp, float(size), r, so))
+    return (int(r[0]), int(r[1]), int(r[2])), (float(so[0]), float(so[1]), float(so[2]))
 
 
 def _slice_axis(axis) -> int:
